@@ -5,7 +5,10 @@ per-GPU batch 32 x (128 tokens, 800 mel frames), fp32, synthetic data (BASELINE.
   python bench.py --gpus N --steps K --warmup W          (N > 1: spawns one rank per GPU itself)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, runs W warm-up and K timed steps and reports them (`value`, `ms_per_step`, the
+persistent launches' health counters); the last timed step starts from the seeded initial state again (main()).  `--dump-outputs DIR`:
+after the timed steps, what the last one computed goes to DIR/<name>.npy (dump_outputs).  `--full` adds every supplementary measurement below, each in runs of its own after the timed steps (the --no-* options
+switch single ones off again):
   `roofline`: the location-sensitive-attention step (the kernel north_star names).  In the persistent decoder launch it is a STAGE of
       every step, not a launch, so it is timed with device timestamps inside the kernel (s_memrealtime, 100 MHz) by the launch's
       profiling instantiation - a separate binary of the same source, run for one extra untimed step; mean over 256 workgroups x 801
@@ -19,6 +22,8 @@ Prints ONE JSON line on rank 0.
   `cpu_baseline`: the oracle (torch-CPU fp32 restatement of the same graph) timed on this host at the FULL workload: thread sweep on a
       short prefix, then 1 warm-up + 3 timed full train steps at the best thread count, median (falls back to a truncated sample only
       when a full step would not fit the time limit, and says so).
+  `roofline_other` / `kernel_avg_us` / `bptt_persistent` / `hoisted_contractions`: per-kernel figures of the same step (rank 0), and
+  `train_surface`: Tacotron2.Train_Step through the Feeder (tools/train_surface_bench.py; N = 1, headline batch).
 """
 import argparse
 import ctypes
@@ -106,6 +111,59 @@ def synthetic_batch(dims, B, Te, L, seed, rank, device):
     t = lambda a: torch.from_numpy(a).to(device).contiguous()
     return {"Token": t(tok), "Token_Length": t(np.full(B, Te, np.int32)), "Mel": t(mel),
             "Mel_Length": t(np.full(B, L, np.int32)), "Speaker_Embedding": t(spk)}
+
+
+DUMP_MAX_ELEMS = 7 << 19        # per step output: a larger one is written as a fixed, seeded sample of this many elements (the headline's
+                                # alignments, 801 x 32 x 128, fit whole)
+DUMP_STATE_ELEMS = 1 << 18      # sample of each parameter-sized slab (variables, gradient, Adam moments)
+# at most 5 x 14.7 MB + 4 x 1.05 MB < 64 MB at any shape (headline: 34 MB)
+
+
+def snapshot_state(eng):
+    """Device copies of everything a train step reads and an optimizer step changes (as TrainEngine.broadcast_state moves it): the variables,
+    the non-trainable slab (batch-norm moving statistics first), both Adam slots and the step counter, which keys the dropout / zoneout masks
+    and the learning rate."""
+    ps = eng.params
+    return eng.global_step, [(t, t.clone()) for t in (ps.train, ps.frozen, ps.adam_m, ps.adam_v)]
+
+
+def restore_state(eng, snap):
+    """Put a snapshot_state back, on the current stream, in front of the next step."""
+    step, pairs = snap
+    for t, saved in pairs:
+        t.copy_(saved)
+    eng.global_step = step
+    eng.params.touch()
+    eng._derived_stale = True           # the packed / folded copies of the variables are rebuilt at the next forward pass
+
+
+def _dump_sample(t, k, seed):
+    """t itself, or - when it has more than k elements - k of its elements at fixed, seeded positions (ascending), flattened."""
+    if t.numel() <= k:
+        return t
+    idx = np.sort(np.random.default_rng(seed).choice(t.numel(), size=k, replace=False))
+    return t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+
+
+def dump_outputs(eng, w, out_dir):
+    """What the last timed train step handed its caller, as DIR/<name>.npy: the loss scalars (float64: Linear, Postnet, Stop,
+    Weight_Regularization, Loss - engine.scalars), the decoder's frames before / after the postnet and its stop logits ([B, S, n_mel],
+    [B, S]), the alignments ([S, B, T_enc]), and the state the step leaves behind: the batch-norm moving statistics, and a fixed sample of
+    the updated variables, their gradient and the Adam moments (float32).  That step starts from the seeded initial state (main(): the
+    state is put back in front of it), so its inputs are the same in every run and for every --steps / --warmup, and two runs or two builds
+    can be compared file by file.  What is left between two runs is the default schedule's atomic sums (summation order, last bits)."""
+    os.makedirs(out_dir, exist_ok=True)
+    ps = eng.params
+    sc = eng.scalars(w)
+    arrays = {"loss_scalars": np.array([sc[k] for k in ("Linear_Loss", "Postnet_Loss", "Stop_Loss", "Weight_Regularization_Loss", "Loss")], np.float64)}
+    for i, (name, t) in enumerate((("mel_before_postnet", w.linear), ("mel_after_postnet", w.mel_out), ("stop_logits", w.stop),
+                                   ("alignments", w.align_hist), ("bn_moving_statistics", ps.frozen[:ps.n_moving]))):
+        arrays[name] = _dump_sample(t, DUMP_MAX_ELEMS, i)
+    for name, t in (("variables", ps.train), ("gradient", ps.grad), ("adam_m", ps.adam_m), ("adam_v", ps.adam_v)):
+        arrays[name + "_sample"] = _dump_sample(t, DUMP_STATE_ELEMS, 100)      # one index set for the four slabs
+    for name, a in arrays.items():
+        a = a.detach().float().cpu().numpy() if torch.is_tensor(a) else a
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def contraction_replay(eng, batch, w, config3):
@@ -323,9 +381,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-surface", action="store_true", help="skip the supplementary Tacotron2.Train_Step-through-the-Feeder measurement (train_surface)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, every supplementary measurement as well (module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the fp32-MFMA leg, the roofline and the per-kernel figures")
+    ap.add_argument("--no-surface", action="store_true", help="with --full: skip the supplementary Tacotron2.Train_Step-through-the-Feeder measurement (train_surface)")
     ap.add_argument("--no-overlap", action="store_true", help="gradient all-reduce behind the backward pass instead of overlapped with it (A/B switch)")
     ap.add_argument("--cpu-budget", type=float, default=0.0, help="seconds for the host baseline; 0 = the full protocol (1 warm-up + 3 timed full steps)")
     ap.add_argument("--frames", type=int, default=L_MEL, help=argparse.SUPPRESS)
@@ -338,6 +398,8 @@ def main():
     ap.add_argument("--no-gemm-tail-split", action="store_true", help=argparse.SUPPRESS)      # A/B: every GEMM tile whole (mstts_gemm_tail_split(0))
     ap.add_argument("--config3", action="store_true", help="BASELINE config 3 arithmetic (bf16 operands everywhere, fp32 master/accumulate); never the headline")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     headline_batch = args.batch == B_PER_GPU and args.tokens == T_ENC
     B_PER_GPU = args.batch
     T_ENC = args.tokens
@@ -408,14 +470,23 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    # Training on one batch is chaotic: the atomic sums of the default schedule differ in the last bits from run to run, and a few optimizer
+    # steps grow that to O(1) in the frames (two runs of one build at 10 steps).  So the LAST timed step starts from the seeded initial state
+    # again (one ~0.4 GB device copy inside the timed region): what it computes is the same in every run, whatever --steps and --warmup are.
+    start = snapshot_state(eng)
     for _ in range(args.warmup):
         eng.train_step(batch, all_reduce=reducer)
     sync()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        eng.train_step(batch, all_reduce=reducer)
+    for i in range(args.steps):
+        if i == args.steps - 1:
+            restore_state(eng, start)
+        w_last = eng.train_step(batch, all_reduce=reducer)
     sync()
     elapsed = time.perf_counter() - t0
+    del start
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, w_last, args.dump_outputs)
     per_rank_ms = [1e3 * elapsed / args.steps]
     if dist is not None:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=device)
@@ -447,7 +518,7 @@ def main():
                                               "products per fp32 product on v_mfma_f32_32x32x16_bf16 (dropped terms <= 2^-26 relative, below fp32 unit roundoff; "
                                               "error vs fp64 equal to the f32-input MFMA kernel's: tests/test_gpu_ops.py::test_gemm_split_is_fp32_accurate); "
                                               "MSTTS_GEMM_SPLIT3=0 or mstts_gemm_split3(0) selects v_mfma_f32_32x32x2_f32 everywhere")
-        if world == 1 and not args.no_roofline:
+        if args.full and world == 1 and not args.no_roofline:
             lib.call("mstts_gemm_split3", 0)
             eng.exact_f32_products = True            # ... and inside the persistent forward loop (its two on-chain products are split products otherwise)
             for _ in range(2):
@@ -498,7 +569,7 @@ def main():
                                   "non_persistent_plans": counters["non_persistent_plans"], "persist_disabled_steps": counters["persist_disabled_steps"],
                                   "collective_redos": counters["collective_redos"],
                                   "scope": "sum over all %d ranks" % world, "max_over_ranks": per_rank_max}
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         w = eng.plan(B_PER_GPU, T_ENC, L)
         S = L + 1
         lb = lib.load()
@@ -618,7 +689,7 @@ def main():
         out["step_flops_fraction_of_fp32_mfma_peak"] = (4.047e12 * L / L_MEL) / (ms_per_step * 1e-3) / 157.3e12
         out["hoisted_contractions"] = contraction_replay(eng, batch, w, args.config3)
 
-    if rank == 0 and world == 1 and headline_batch and not args.config3 and not args.no_surface and not args.no_roofline:
+    if args.full and rank == 0 and world == 1 and headline_batch and not args.config3 and not args.no_surface and not args.no_roofline:
         # Supplementary, never the headline: the reference's user trains through Tacotron2.Train() on length-bucketed batches of a different
         # shape every step (Feeder.py:111-124, MSTTS_SV.py:266-273).  50 such steps through the real Feeder and the drop-in class, beside the
         # same batches device-resident through the engine (tools/train_surface_bench.py).
@@ -631,7 +702,7 @@ def main():
         except Exception as e:          # (a supplementary leg must not cost the run its headline line)
             out["train_surface"] = {"error": "%s: %s" % (type(e).__name__, e)}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(budget_s=args.cpu_budget)
 
     if dist is not None:

@@ -12,7 +12,7 @@ build() {
 for rep in $(seq $REPS); do
   for v in "$A" "$B"; do
     build "$v"
-    echo "$v: $(python bench.py --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
+    echo "$v: $(python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(d['ms_per_step'],2), {k:round(x,2) for k,x in d['kernel_avg_us'].items()})")"
   done

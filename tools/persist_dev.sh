@@ -10,5 +10,4 @@ if [ -z "$SKIP_PARITY" ]; then
 timeout 900 python -m pytest tests/test_gpu_model.py -x -q -m gpu -k "train_step_parity and not bf16" 2>&1 | tail -15 > gpurun_out/persist_parity.log
 cat gpurun_out/persist_parity.log
 fi
-[ -n "$SKIP_BENCH" ] || timeout 600 python bench.py --steps 10 --warmup 3 ${BENCH_ARGS} 2>&1 | tail -5 > gpurun_out/persist_bench.log
-cat gpurun_out/persist_bench.log
+[ -n "$SKIP_BENCH" ] || timeout 600 python bench.py --steps 10 --warmup 3 --full ${BENCH_ARGS} 2>&1 | tail -5

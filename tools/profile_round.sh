@@ -14,8 +14,8 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python $ROOT/bench.py --steps 10 --warmup 3 > $OUT/bench_line.json 2> $OUT/bench_line.err
-python $ROOT/bench.py --steps 10 --warmup 3 --config3 --no-cpu-baseline > $OUT/bench_line_config3.json 2>> $OUT/bench_line.err
+python $ROOT/bench.py --steps 10 --warmup 3 --full > $OUT/bench_line.json 2> $OUT/bench_line.err
+python $ROOT/bench.py --steps 10 --warmup 3 --full --config3 --no-cpu-baseline > $OUT/bench_line_config3.json 2>> $OUT/bench_line.err
 python $ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-roofline --force-allreduce 2>> $OUT/bench_line.err | tail -1 > $OUT/bench_line_one_rank_rccl.json
 python $ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-roofline --force-allreduce --config3 2>> $OUT/bench_line.err | tail -1 > $OUT/bench_line_one_rank_rccl_config3.json
 python $ROOT/tools/train_surface_bench.py > $OUT/train_surface.json 2>> $OUT/bench_line.err
