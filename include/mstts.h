@@ -482,6 +482,48 @@ int mstts_wg_coupling_inv(const float* audio, const float* log_s_b, const float*
                           int64_t rows, int64_t c, int64_t c_early, mstts_stream_t s);
 int mstts_philox_normal(float* out, int64_t n, uint64_t seed, uint32_t stream_id, float sigma, mstts_stream_t s);
 
+/* ---- WaveGlow vocoder, training direction (WaveGlow/WaveGlow.py:37-85; Modules.py:9-34,135-175,210-352,373-385; Inv1x1.py:9-41).  The
+ * contractions run on mstts_gemm_f32; these are the remaining pieces, fp32, activations [rows, channels] row-major.
+ *  weight_norm_fwd : for every descriptor of the DEVICE table (one launch for all weight-normed convs of the model): per column j,
+ *                    w[r*ldw + j] = g[j] * v[r*cols + j] * rsqrt(max(sum_r v[r*cols + j]^2, 1e-5)); v is the [k*cin, cols] kernel
+ *  weight_norm_bwd : reads the effective kernel's gradient from w (same pitch) and writes dg[j] = sum dw v_hat and
+ *                    dv = g r (dw - v_hat dg) where the squared sum exceeds 1e-5, else g r dw (r = rsqrt(max(ss, 1e-5)), v_hat = v r).
+ *                    max_cols = the widest descriptor.  dv / dg are overwritten.
+ *  coupling_fwd    : o = [a0 | exp(min(log_s, 8)) * a1 + b] from y = audio . W [rows, c] and log_s_b = [log_s | b] [rows, c];
+ *                    o[:, :c_out] -> z[r*ldz + z_col + j] (an early chunk, or the last flow's whole output), o[:, c_out:] -> next
+ *                    [rows, c - c_out]; sum min(log_s, 8) added into *loss (one atomic per workgroup; loss may be NULL)
+ *  coupling_bwd    : d_o = [z[:, z_col:z_col+c_out] * inv_size | d_next]; d_y = [d_o0 | d_o1 exp(ls)], d_log_s_b = [(d_o1 a1 exp(ls) - inv_size)
+ *                    masked to log_s <= 8 | d_o1]  (inv_size = 1 / size: the audio loss's and the log-s loss's gradients)
+ *  inv1x1_logdet   : per flow f (table[2f] = element offset of W_f in params and grad, table[2f+1] = c <= 16): fp64 LU with partial
+ *                    pivoting of 1e3 W_f; *loss += (float)log(det + 1e-6) - c log(1e3) (NaN for det < 0, as TF);
+ *                    grad += grad_scale * det / (det + 1e-6) * W_f^-T
+ *  gate_bwd        : z = tanh(a[:, :C]) sigmoid(a[:, C:2C]) backward: dpre [rows, 2C] (and, when dpre2 is not NULL, the same values at
+ *                    pitch ld2 - the flow's concatenated conditioning gradient)
+ *  res_skip_bwd    : !last: d_rs [rows, 2C] = [d_x_next | d_skip], d_z = d_x_next; last: d_rs [rows, C] = d_skip, d_z = 0
+ *  overlap_add_bwd : dY[n, t, k, c] = d_up[n, t*S + k, c] where t*S + k < L, else 0 (d_up [N, L, C]: the gradient of the upsampled mel
+ *                    sliced to the audio length L <= (T-1)*S + K)
+ *  bias_fold       : out[b*width + j] = base[table[2b] + j] + base[table[2b+1] + j]   (table on the device)
+ *  adam_tf_clip    : mstts_adam_tf without weight regularisation, the gradient scaled by clip_norm / max(sqrt(sumsq_scale * sumsq[0]), clip_norm)
+ *                    with sumsq a DEVICE scalar (tf.clip_by_global_norm without a host round trip); 16-byte aligned slabs */
+typedef struct {
+    const float* v; const float* g; float* w; int64_t ldw;
+    float* dv; float* dg;
+    int64_t rows, cols;
+} mstts_wg_wn_desc;
+int mstts_wg_weight_norm_fwd(const mstts_wg_wn_desc* table, int64_t n, int64_t max_cols, mstts_stream_t s);
+int mstts_wg_weight_norm_bwd(const mstts_wg_wn_desc* table, int64_t n, int64_t max_cols, mstts_stream_t s);
+int mstts_wg_coupling_fwd(const float* y, const float* log_s_b, float* next, float* z, int64_t ldz, int64_t z_col, int64_t c_out,
+                          float* loss, int64_t rows, int64_t c, mstts_stream_t s);
+int mstts_wg_coupling_bwd(const float* y, const float* log_s_b, const float* z, int64_t ldz, int64_t z_col, int64_t c_out, const float* d_next,
+                          float inv_size, float* d_y, float* d_log_s_b, int64_t rows, int64_t c, mstts_stream_t s);
+int mstts_wg_inv1x1_logdet(const float* params, float* grad, const int64_t* table, int64_t n_flows, float grad_scale, float* loss, mstts_stream_t s);
+int mstts_wg_gate_bwd(const float* a, int64_t lda, const float* dz, float* dpre, float* dpre2, int64_t ld2, int64_t rows, int64_t C, mstts_stream_t s);
+int mstts_wg_res_skip_bwd(const float* d_x_next, const float* d_skip, float* d_rs, float* d_z, int64_t rows, int64_t C, int32_t last, mstts_stream_t s);
+int mstts_wg_overlap_add_bwd(const float* d_up, float* dY, int64_t N, int64_t T, int64_t K, int64_t S, int64_t C, int64_t L, mstts_stream_t s);
+int mstts_wg_bias_fold(const float* base, const int64_t* table, float* out, int64_t n_blocks, int64_t width, mstts_stream_t s);
+int mstts_adam_tf_clip(float* p, const float* grad, float* m, float* v, const float* sumsq, float sumsq_scale, float clip_norm,
+                       float lr_t, float beta1, float beta2, float eps, int64_t n, mstts_stream_t s);
+
 /* ---- GE2E loss of the speaker-encoder trainer, forward + backward (Speaker_Embedding/Modules.py:39-98, "Softmax" method):
  * x [N = S*P, D] = last-frame outputs of the LSTM stack, speaker-major (P consecutive rows per speaker), rows ldx apart;
  * wb = {weight, bias} of the scaled cosine similarity.  out[0] = loss, out[1] = d/d weight, out[2] = d/d bias (identically 0);

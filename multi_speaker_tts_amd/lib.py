@@ -92,6 +92,10 @@ class DecoderTrain(C.Structure):
                 ("energy_ws_floats", i64)]
 
 
+class WgWnDesc(C.Structure):
+    _fields_ = [("v", vp), ("g", vp), ("w", vp), ("ldw", i64), ("dv", vp), ("dg", vp), ("rows", i64), ("cols", i64)]
+
+
 class PersistDesc(C.Structure):
     _fields_ = [("w0pk", vp), ("w1pk", vp), ("wqpk", vp), ("xch", vp), ("ctrl", vp), ("stamps", vp), ("opk", vp), ("selftest_fail_step", i32), ("near_xcd", i32), ("pre", vp), ("b0", vp), ("recurrent_bf16", i32)]
 
@@ -212,6 +216,16 @@ SIGNATURES = {
     "mstts_wg_res_skip": (i32, [vp, vp, vp, vp, i64, i64, i32, i32, vp]),
     "mstts_wg_coupling_inv": (i32, [vp, vp, vp, vp, f32, vp, i64, i64, i64, vp]),
     "mstts_philox_normal": (i32, [vp, i64, u64, u32, f32, vp]),
+    "mstts_wg_weight_norm_fwd": (i32, [vp, i64, i64, vp]),
+    "mstts_wg_weight_norm_bwd": (i32, [vp, i64, i64, vp]),
+    "mstts_wg_coupling_fwd": (i32, [vp, vp, vp, vp, i64, i64, i64, vp, i64, i64, vp]),
+    "mstts_wg_coupling_bwd": (i32, [vp, vp, vp, i64, i64, i64, vp, f32, vp, vp, i64, i64, vp]),
+    "mstts_wg_inv1x1_logdet": (i32, [vp, vp, vp, i64, f32, vp, vp]),
+    "mstts_wg_gate_bwd": (i32, [vp, i64, vp, vp, vp, i64, i64, i64, vp]),
+    "mstts_wg_res_skip_bwd": (i32, [vp, vp, vp, vp, i64, i64, i32, vp]),
+    "mstts_wg_overlap_add_bwd": (i32, [vp, vp, i64, i64, i64, i64, i64, i64, vp]),
+    "mstts_wg_bias_fold": (i32, [vp, vp, vp, i64, i64, vp]),
+    "mstts_adam_tf_clip": (i32, [vp, vp, vp, vp, vp, f32, f32, f32, f32, f32, f32, i64, vp]),
     "mstts_lstm_seq_fwd": (i32, [P(LstmSeqFwd), vp]),
     "mstts_lstm_seq_bwd": (i32, [P(LstmSeqBwd), vp]),
     "mstts_lstm_seq_fwd_pair": (i32, [P(LstmSeqFwd), P(LstmSeqFwd), vp]),

@@ -194,11 +194,18 @@ class ParamStore:
     """Two flat fp32 slabs on the device + named views.  Offsets are multiples of 4 floats so every
     variable starts 16-byte aligned (the kernels' float4 paths rely on it)."""
 
-    def __init__(self, d: Dims, device, seed=1234, values=None, trainable_fn=None, weight_reg_fn=None):
+    def __init__(self, d: Dims, device, seed=1234, values=None, trainable_fn=None, weight_reg_fn=None, table=None):
         """trainable_fn / weight_reg_fn: name -> bool; default = the Tacotron2 trainer's sets (MSTTS_SV.py:145-159,183-190).
-        The auxiliary trainers pass their own (e.g. the `mel_to_spectrogram` scope for the Taco1 vocoder trainer)."""
+        The auxiliary trainers pass their own (e.g. the `mel_to_spectrogram` scope for the Taco1 vocoder trainer).
+        table: another model's [(name, shape[, init])] instead of variable_table(d) (the WaveGlow trainer: waveglow.variable_table);
+        its initial values then come from `values` (variables missing there start at zero)."""
         self.dims = d
-        self.table = variable_table(d)
+        if table is None:
+            self.table = variable_table(d)
+        else:
+            self.table = [(e[0], tuple(e[1]), e[2] if len(e) > 2 else "given") for e in table]
+            if values is None:
+                values = {}
         trainable_fn = trainable_fn or is_trainable
         weight_reg_fn = weight_reg_fn or in_weight_reg
         self.offset, self.shape, self.trainable = {}, {}, {}
