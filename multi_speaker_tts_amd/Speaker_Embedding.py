@@ -7,9 +7,6 @@ Batch_per_Speaker, frames, 80]} speaker-major with one random frame count from h
 """
 from __future__ import annotations
 
-import os
-import time
-
 import numpy as np
 import torch
 
@@ -17,11 +14,15 @@ from . import Hyper_Parameters as hp
 from . import Feeder as _Feeder
 from .params import Dims
 from .speaker_trainer import SpeakerTrainEngine, learning_rate
+from .training import DropIn
 
 TRAIN_KEYS = ("Global_Step", "Learning_Rate", "Loss", "Train_OP")
 
 
-class Speaker_Embedding:
+class Speaker_Embedding(DropIn):
+    HP, FILE, SCOPE = "Speaker_Embedding", "speaker_embedding.pt", "speaker_embedding"
+    COLUMNS = (("Learning rate: {:0.6f}", "Learning_Rate"), ("Loss: {:0.5f}", "Loss"))
+
     def __init__(self, is_Training=True, device="cuda", seed=1234, dims: Dims = None):
         self.is_Training = is_Training
         self.device = device
@@ -31,30 +32,9 @@ class Speaker_Embedding:
         self.inference_Tensor_Dict = {k: k for k in ("Global_Step", "Embedding")}
         self._infer = None
 
-    def _file(self):
-        return os.path.join(hp.Speaker_Embedding.Checkpoint_Path.replace("\\", "/"), "speaker_embedding.pt")
-
-    def Restore(self):
-        f = self._file()
-        if not os.path.exists(f):
-            print("There is no checkpoint.")
-            return
-        state = torch.load(f, map_location="cpu")
-        self.params.load({k: v for k, v in state.items() if k.startswith("speaker_embedding")})
-        if "__adam_m__" in state:
-            self.params.adam_m.copy_(state["__adam_m__"]); self.params.adam_v.copy_(state["__adam_v__"])
-            self.engine.wb.copy_(state["__loss_vars__"]); self.engine.wb_m.copy_(state["__loss_m__"]); self.engine.wb_v.copy_(state["__loss_v__"])
-        self.engine.global_step = int(state.get("__global_step__", 0))
-        print("Checkpoint '%s' is loaded." % f)
-
-    def Save(self):
-        f = self._file()
-        os.makedirs(os.path.dirname(f), exist_ok=True)
-        state = {k: torch.from_numpy(v) for k, v in self.params.export().items() if k.startswith("speaker_embedding")}
+    def _slots(self):
         e = self.engine
-        state.update({"__adam_m__": self.params.adam_m.cpu(), "__adam_v__": self.params.adam_v.cpu(), "__loss_vars__": e.wb.cpu(),
-                      "__loss_m__": e.wb_m.cpu(), "__loss_v__": e.wb_v.cpu(), "__global_step__": e.global_step})
-        torch.save(state, f)
+        return {**super()._slots(), "__loss_vars__": e.wb, "__loss_m__": e.wb_m, "__loss_v__": e.wb_v}
 
     def Synthetic_Pattern(self, speakers=None, per_speaker=None, seed=1234):
         """Speaker-dependent synthetic mels (a per-speaker offset pattern plus noise), so the loss has something to learn."""
@@ -69,20 +49,10 @@ class Speaker_Embedding:
 
     def Train_Step(self, pattern=None):
         pattern = pattern or self.Synthetic_Pattern()
-        dev = torch.device(self.device)
-        mel = torch.as_tensor(np.asarray(pattern["Mel"], np.float32)).to(dev).contiguous()
+        mel = self._upload(pattern["Mel"])
         step = self.engine.global_step
         w = self.engine.train_step(mel, int(pattern.get("Batch_per_Speaker", hp.Speaker_Embedding.Train.Batch_per_Speaker)))
         return {"Global_Step": step, "Learning_Rate": learning_rate(step), "Loss": float(w.out3[0]), "Train_OP": None}
-
-    def Train(self, max_steps=None, pattern_fn=None):
-        while max_steps is None or self.engine.global_step < max_steps:
-            t0 = time.time()
-            r = self.Train_Step(pattern_fn() if pattern_fn else None)
-            print("\t\t".join(["Time: {:0.3f}".format(time.time() - t0), "Global step: {}".format(r["Global_Step"]),
-                               "Learning rate: {:0.6f}".format(r["Learning_Rate"]), "Loss: {:0.5f}".format(r["Loss"])]))
-            if (r["Global_Step"] + 1) % hp.Speaker_Embedding.Train.Checkpoint_Save_Timing == 0:
-                self.Save()
 
     def Inference(self, mel_List):
         """Embeddings of whole utterances: 5 windows of 64 frames each, mean of the last-frame outputs, whole-tensor l2

@@ -14,10 +14,10 @@ import threading
 import time
 
 import numpy as np
-import torch
 
 from . import Hyper_Parameters as hp
-from .waveglow import WaveGlowEngine, WGDims, vocode
+from .training import DropIn
+from .waveglow import P_WG, WaveGlowEngine, WGDims, vocode
 from .waveglow_trainer import WaveGlowTrainEngine, learning_rate
 
 TRAIN_KEYS = ("Global_Step", "Learning_Rate", "Log_S_Loss", "Log_Det_W_Loss", "Audio_Loss", "Train_OP")
@@ -123,7 +123,11 @@ class WavFeeder:
 
 
 # ---- the trainer class ----------------------------------------------------------------------------------------------------------------
-class WaveGlow:
+class WaveGlow(DropIn):
+    HP, FILE, SCOPE = "WaveGlow", "waveglow.pt", P_WG
+    COLUMNS = (("Learning rate: {:0.5f}", "Learning_Rate"), ("Log S Loss: {:0.5f}", "Log_S_Loss"),
+               ("Log Det W Loss: {:0.5f}", "Log_Det_W_Loss"), ("Audio Loss: {:0.5f}", "Audio_Loss"))
+
     def __init__(self, device="cuda", seed=1234, dims: WGDims = None, values=None):
         self.device = device
         self.engine = WaveGlowTrainEngine(dims or WGDims.from_hp(hp), device=device, seed=seed, values=values)
@@ -131,28 +135,6 @@ class WaveGlow:
         self.feeder = None
         self.train_Tensor_Dict = {k: k for k in TRAIN_KEYS}
         self.inference_Tensor_Dict = {k: k for k in ("Global_Step", "Audio")}
-
-    def _file(self):
-        return os.path.join(hp.WaveGlow.Checkpoint_Path.replace("\\", "/"), "waveglow.pt")
-
-    def Restore(self):
-        f = self._file()
-        if not os.path.exists(f):
-            print("There is no checkpoint.")
-            return
-        state = torch.load(f, map_location="cpu")
-        self.params.load({k: v for k, v in state.items() if not k.startswith("__")})
-        if "__adam_m__" in state:
-            self.params.adam_m.copy_(state["__adam_m__"]); self.params.adam_v.copy_(state["__adam_v__"])
-        self.engine.global_step = int(state.get("__global_step__", 0))
-        print("Checkpoint '%s' is loaded." % f)
-
-    def Save(self):
-        f = self._file()
-        os.makedirs(os.path.dirname(f), exist_ok=True)
-        state = {k: torch.from_numpy(v) for k, v in self.params.export().items()}
-        state.update({"__adam_m__": self.params.adam_m.cpu(), "__adam_v__": self.params.adam_v.cpu(), "__global_step__": self.engine.global_step})
-        torch.save(state, f)
 
     def Synthetic_Pattern(self, batch_Size=None, length=None, seed=1234):
         """Audio of `length` samples (default Max_Signal_Length) and the fewest mel frames whose upsampled length covers it."""
@@ -167,10 +149,8 @@ class WaveGlow:
     def Train_Step(self, pattern=None):
         """One iteration of the reference's `while True` body (WaveGlow.py:117-129)."""
         pattern = pattern or self.Synthetic_Pattern()
-        dev = torch.device(self.device)
-        t = lambda a: torch.as_tensor(np.asarray(a, np.float32)).to(dev).contiguous()
         step = self.engine.global_step
-        w = self.engine.train_step(t(pattern["Audio"]), t(pattern["Mel"]))
+        w = self.engine.train_step(self._upload(pattern["Audio"]), self._upload(pattern["Mel"]))
         res = self.engine.scalars(w)
         res.update({"Global_Step": step, "Learning_Rate": learning_rate(step), "Train_OP": None})
         return res
@@ -179,14 +159,7 @@ class WaveGlow:
         if pattern_fn is None:
             self.feeder = self.feeder or WavFeeder(device=self.device)
             pattern_fn = self.feeder.Get_Train_Pattern
-        while max_steps is None or self.engine.global_step < max_steps:
-            t0 = time.time()
-            r = self.Train_Step(pattern_fn())
-            print("\t\t".join(["Time: {:0.3f}".format(time.time() - t0), "Global step: {}".format(r["Global_Step"]),
-                               "Learning rate: {:0.5f}".format(r["Learning_Rate"]), "Log S Loss: {:0.5f}".format(r["Log_S_Loss"]),
-                               "Log Det W Loss: {:0.5f}".format(r["Log_Det_W_Loss"]), "Audio Loss: {:0.5f}".format(r["Audio_Loss"])]))
-            if (r["Global_Step"] + 1) % hp.WaveGlow.Train.Checkpoint_Save_Timing == 0:
-                self.Save()
+        super().Train(max_steps, pattern_fn)
 
     def Inference(self, path_List, file_Prefix=None):
         """wav -> mel -> WaveGlowEngine (built from the current values) -> WAV files under hp.WaveGlow.Inference.Path/WAV (WaveGlow.py:144-205)."""

@@ -11,7 +11,6 @@ hoisted out of the time loops into large MFMA GEMMs.
 from __future__ import annotations
 
 import ctypes as C
-import math
 import os
 import warnings
 
@@ -22,8 +21,8 @@ from . import lib
 from .lib import ACT_NONE, ACT_RELU, ACT_TANH, gemm, ptr, call
 from .masks import MaskSet, step_seed
 from .params import CELL, ENC_CELL, LSA, VOC, Dims, ParamStore, bank_suffix
-
-BN_MOM, BN_EPS = 0.99, 1e-3
+from .training import (Engine, _split_k, _split_k_big, bn_train_fwd, conv_bn_bwd, conv_fwd, exponential_decay, lstm_layer_grads, lstm_seq_bwd,
+                       lstm_seq_fwd)
 
 MAX_PLANS = 64     # cached workspace sets (one per batch shape): views into ONE arena, a set owns no device memory
 
@@ -32,56 +31,7 @@ MAX_PLANS = 64     # cached workspace sets (one per batch shape): views into ONE
 def learning_rate(step):
     """MSTTS_SV.py:163-169."""
     from . import Hyper_Parameters as hp
-    lr_hp = hp.Train.Learning_Rate
-    lr = lr_hp.Initial * lr_hp.Decay_Rate ** ((step - lr_hp.Decay_Start_Step) / lr_hp.Decay_Step)
-    return min(max(lr, lr_hp.Min), lr_hp.Initial)
-
-
-def _split_k(M, N, K, n_cu=256, max_split=16):
-    """Reduction split of a weight-gradient GEMM (atomic accumulation into the gradient slab).  128x128 output tiles are
-    spread round-robin over the CUs, so a CU runs c = ceil(tiles * sk / n_cu) workgroups of K / sk each: pick the sk with the
-    least work on the busiest CU (448 tiles: sk = 4 -> 7 per CU exactly, 127 TFLOP/s, where sk = 2 leaves 3.5 -> 4 per CU,
-    107 TFLOP/s; tools/gemm_split_probe.py), with a small per-split charge for the atomics.  Long reductions (the 25 632-row
-    products) also weigh HOW MANY workgroups share a CU: one per CU is one wave per SIMD, nothing hides its load / store phases
-    (2 560 x 512 x 25 632: sk = 3 -> 240 tiles, 91 TFLOP/s; sk = 9 -> 720 tiles = 3 per CU, 117 TFLOP/s)."""
-    tiles = math.ceil(M / 128) * math.ceil(N / 128)
-    if K >= 16384:
-        ktiles, best, best_cost = K / 32.0, 1, None
-        if tiles * max_split < n_cu:             # a handful of tiles (the Taco1 convolution bank: 1..8): split until the chip is covered once
-            max_split = min(64, max(max_split, n_cu // tiles))
-        for sk in range(1, max_split + 1):
-            c = math.ceil(tiles * sk / n_cu)
-            cost = c * (ktiles / sk + 6.0) / (0.75 if c == 1 else 0.92 if c == 2 else 1.0) * (1.0 + 0.004 * sk)
-            if best_cost is None or cost < best_cost * (1.0 - 1e-9):
-                best, best_cost = sk, cost
-        return best
-    best, best_cost = 1, None
-    for sk in range(1, max_split + 1):
-        if sk > 1 and K // sk < 512:
-            break
-        cost = math.ceil(tiles * sk / n_cu) / sk + 0.004 * sk
-        if best_cost is None or cost < best_cost - 1e-9:
-            best, best_cost = sk, cost
-    return best
-
-
-def _split_k_big(M, N, K, requested, n_cu=256):
-    """Reduction split of a weight-gradient product on the 256 x 256-tile kernels (gemm_split_big_kernel / gemm_bf16_big_kernel: one workgroup
-    per CU, taken from 160 workgroups on): rounds x (K-tiles per piece + a fixed cost per piece), pieces of at least 1 024 rows.  Returns
-    `requested` (the split chosen for 128 x 128 tiles) when no split reaches those kernels."""
-    tiles = math.ceil(M / 256) * math.ceil(N / 256)
-    if M < 192 or N < 192:
-        return requested
-    best, best_cost = None, None
-    for sk in range(1, 65):
-        if sk > 1 and K // sk < 1024:
-            break
-        if tiles * sk < 160:
-            continue
-        cost = math.ceil(tiles * sk / n_cu) * (K / sk + 300.0) * (1.0 + 0.01 * sk)      # (+1 % per piece: its atomics onto the shared output)
-        if best_cost is None or cost < best_cost - 1e-9:
-            best, best_cost = sk, cost
-    return best if best is not None else requested
+    return exponential_decay(hp.Train.Learning_Rate, step)
 
 
 PERSIST_STRIKES = 2          # consecutive steps with a fallback before the persistent plans are switched off ...
@@ -158,7 +108,7 @@ class _Carver:
         return t
 
 
-class TrainEngine:
+class TrainEngine(Engine):
     def __init__(self, dims: Dims = None, device="cuda", seed=1234, rank=0, world=1, values=None,
                  update_vocoder_bn=True, use_l1=None, wr_rate=None, adam=None, recurrent_dtype=None, gemm_dtype=None, fuse_query=True,
                  arena_hint=None, deterministic=None):
@@ -286,10 +236,6 @@ class TrainEngine:
                        "w0f_b": i16((M + H) * 4 * H), "w1_b": i16(2 * H * 4 * H), "wq_b": i16(H * d.att)}
 
     # ------------------------------------------------------------------ helpers
-    def _f(self, *shape):
-        n = int(np.prod(shape))
-        return torch.zeros((n + 3) // 4 * 4, dtype=torch.float32, device=self.device)[:n].view(shape)
-
     def _gemm(self, *a, exact=False, **k):
         """Every dense / conv contraction of the step.  gemm_dtype 'bf16' (BASELINE config 3) rounds both operands to bf16 for the
         matrix cores (fp32 accumulate, fp32 master weights / activations / gradients in memory); exact=True keeps the few
@@ -311,12 +257,6 @@ class TrainEngine:
                 # dw0f, dwp_pad) or accumulates into.
                 k["split_k"], k["accumulate"] = 1, True
         return gemm(*a, bf16=bf, **k)
-
-    def P(self, name):
-        return self.params.p(name)
-
-    def G(self, name):
-        return self.params.g(name)
 
     def _ensure_fallback_packs(self):
         """Packed kernels of the launch-per-step loops (decoder cells forward / data-gradient products backward, encoder cells, the
@@ -566,50 +506,6 @@ class TrainEngine:
         w.arena_generation = self._arena.generation
         return (None if (cv.count or cv.overflow) else w), cv.off
 
-    # ------------------------------------------------------------------ conv blocks
-    def _conv_fwd(self, x, x_off, rows, T, cin, cout, K, kname, bname, out, act):
-        k, ok = self.P(kname)
-        b, ob = self.P(bname)
-        self._gemm(x, k, out, rows, cout, K * cin, cin, cout, cout, bias=b, act=act, win=(T, cin, (K - 1) // 2),
-             a_off=x_off, b_off=ok, bias_off=ob)
-
-    def _bn_fwd(self, prefix, a, y, mean, rstd, mask, keep, rows, C, ws):
-        g, og = self.P(prefix + "gamma"); b, ob = self.P(prefix + "beta")
-        mm, omm = self.P(prefix + "moving_mean"); mv, omv = self.P(prefix + "moving_variance")
-        call("mstts_bn_train_fwd", ptr(a), ptr(g, og), ptr(b, ob), ptr(mm, omm), ptr(mv, omv), ptr(y), ptr(mean), ptr(rstd),
-             ptr(mask), float(keep), BN_MOM, BN_EPS, rows, C, ptr(ws))
-
-    def _conv_block_bwd(self, dy, x_in, a, mean, rstd, mask, keep, act, prefix, rows, T, cin, cout, K, dz, dx, wgrad_stream=None):
-        """BN(+dropout)+activation+conv backward.  dy: grad of the block output; returns nothing;
-        dx (or None) receives the input gradient; parameter grads accumulate into the grad slab.
-        wgrad_stream: run the kernel's weight-gradient product (read by nothing before Adam) on that stream, behind this block's dz."""
-        g, og = self.P(prefix + "batch_normalization/gamma")
-        gg, ogg = self.G(prefix + "batch_normalization/gamma")
-        gb, ogb = self.G(prefix + "batch_normalization/beta")
-        gbias, ogbias = self.G(prefix + "conv1d/bias")
-        call("mstts_bn_train_bwd", ptr(dy), ptr(a), ptr(g, og), ptr(mean), ptr(rstd), ptr(mask), float(keep), act, ptr(dz),
-             ptr(gg, ogg), ptr(gb, ogb), ptr(gbias, ogbias), rows, cout, ptr(self._bnws))
-        gk, ogk = self.G(prefix + "conv1d/kernel")
-        pad = (K - 1) // 2
-        if wgrad_stream is not None:
-            ev = torch.cuda.Event()
-            ev.record()
-            with torch.cuda.stream(wgrad_stream):
-                wgrad_stream.wait_event(ev)
-                self._gemm(x_in, dz, gk, K * cin, cout, rows, cin, cout, cout, trans_a=True, win=(T, cin, pad),
-                     split_k=max(2, _split_k(K * cin, cout, rows)), c_off=ogk)
-        else:
-            self._gemm(x_in, dz, gk, K * cin, cout, rows, cin, cout, cout, trans_a=True, win=(T, cin, pad),
-                 split_k=max(2, _split_k(K * cin, cout, rows)), c_off=ogk)
-        if dx is not None:
-            k, ok = self.P(prefix + "conv1d/kernel")
-            key = (prefix, K, cin, cout)
-            if key not in self.flip:
-                self.flip[key] = self._f(K, cout, cin)
-            wt = self.flip[key]
-            call("mstts_conv_kernel_flip", ptr(k, ok), ptr(wt), K, cin, cout)
-            self._gemm(dz, wt, dx, rows, cin, K * cout, cout, cin, cin, win=(T, cout, K - 1 - pad))
-
     # ------------------------------------------------------------------ forward
     def forward(self, batch, w, seed=None, masks=None, _redo=False, allowed=None, overlap_vocoder=False):
         """Forward pass.  The persistent launches (encoder BiLSTM, decoder loop) are enqueued WITHOUT waiting for their control words; the
@@ -658,22 +554,16 @@ class TrainEngine:
         x, cin = w.emb, d.emb
         for i in range(d.enc_conv_n):
             pre = "encoder/conv_%d/" % i
-            self._conv_fwd(x, 0, B * Te, Te, cin, d.enc_conv_ch, d.enc_conv_k, pre + "conv1d/kernel", pre + "conv1d/bias", w.enc_a[i], ACT_RELU)
-            self._bn_fwd(pre + "batch_normalization/", w.enc_a[i], w.enc_y[i], w.enc_mean[i], w.enc_rstd[i],
+            conv_fwd(self, self._gemm, x, B * Te, Te, cin, d.enc_conv_ch, d.enc_conv_k, pre + "conv1d", w.enc_a[i], ACT_RELU)
+            bn_train_fwd(self, pre + "batch_normalization/", w.enc_a[i], w.enc_y[i], w.enc_mean[i], w.enc_rstd[i],
                          mk["enc_conv_drop_%d" % i], 1 - d.conv_drop, B * Te, d.enc_conv_ch, w.bn_ws)
             x, cin = w.enc_y[i], d.enc_conv_ch
         seqs = []
         for di, dr in enumerate(("fw", "bw")):
             k, ok = self.P(ENC_CELL % dr + "kernel"); b, ob = self.P(ENC_CELL % dr + "bias")
             self._gemm(x, k, w.enc_xw[dr], B * Te, 4 * He, cin, cin, 4 * He, 4 * He, bias=b, b_off=ok, bias_off=ob)
-            q = lib.LstmSeqFwd()
-            q.B, q.T, q.H = B, Te, He
-            q.xw = ptr(w.enc_xw[dr]); q.wh = ptr(k, ok + cin * 4 * He); q.wh_ld = 4 * He
-            q.lengths = ptr(tlen); q.reverse = di; q.zoneout = d.zoneout
-            q.zc = ptr(mk["enc_zc_" + dr]); q.zh = ptr(mk["enc_zh_" + dr])
-            q.out = ptr(w.values, di * He); q.out_sb = Te * M; q.out_st = M
-            q.c_hist = ptr(w.enc_c[dr]); q.h_hist = ptr(w.enc_h[dr]); q.acts = ptr(w.enc_acts[dr]); q.c_raw = ptr(w.enc_craw[dr])
-            q.gates_ws = ptr(w.enc_gates[dr])
+            q = lstm_seq_fwd(B, Te, He, w.enc_xw[dr], (k, ok + cin * 4 * He), tlen, di, d.zoneout, mk["enc_zc_" + dr], mk["enc_zh_" + dr],
+                             (w.values, di * He), Te * M, M, w.enc_c[dr], w.enc_h[dr], w.enc_acts[dr], w.enc_craw[dr], w.enc_gates[dr])
             if self.enc_whp is not None:                 # fused steps: packed recurrent kernel + packed h blocks
                 q.wh_p, q.h_p = ptr(self.enc_whp[dr]), ptr(w.enc_hp[dr])
             seqs.append(q)
@@ -870,8 +760,8 @@ class TrainEngine:
         for i in range(d.post_n):
             pre = "decoder/conv_%d/" % i
             cout = d.post_ch if i < d.post_n - 1 else d.n_mel
-            self._conv_fwd(x, 0, B * S, S, cin, cout, d.post_k, pre + "conv1d/kernel", pre + "conv1d/bias", w.post_a[i], ACT_TANH)
-            self._bn_fwd(pre + "batch_normalization/", w.post_a[i], w.post_y[i], w.post_mean[i], w.post_rstd[i],
+            conv_fwd(self, self._gemm, x, B * S, S, cin, cout, d.post_k, pre + "conv1d", w.post_a[i], ACT_TANH)
+            bn_train_fwd(self, pre + "batch_normalization/", w.post_a[i], w.post_y[i], w.post_mean[i], w.post_rstd[i],
                          mk["post_drop_%d" % i], 1 - d.conv_drop, B * S, cout, w.bn_ws)
             x, cin = w.post_y[i], cout
         call("mstts_add", ptr(w.linear), ptr(x), ptr(w.mel_out), B * S * d.n_mel)
@@ -908,18 +798,18 @@ class TrainEngine:
             kk, ok = self.P(VOC + "convbank_0/conv1d%s/kernel" % sfx); b, ob = self.P(VOC + "convbank_0/conv1d%s/bias" % sfx)
             self._gemm(w.mel_out, kk, w.v_tmp, rows, d.bank_ch, k * d.n_mel, d.n_mel, d.bank_ch, d.bank_ch, bias=b, act=ACT_RELU,
                  win=(S, d.n_mel, (k - 1) // 2), b_off=ok, bias_off=ob, exact=True)
-            self._bn_fwd(VOC + "convbank_0/batch_normalization%s/" % sfx, w.v_tmp, w.v_tmp2, w.v_stat, w.v_stat[d.bank_ch:], None, 1.0, rows, d.bank_ch, w.v_bn_ws)
+            bn_train_fwd(self, VOC + "convbank_0/batch_normalization%s/" % sfx, w.v_tmp, w.v_tmp2, w.v_stat, w.v_stat[d.bank_ch:], None, 1.0, rows, d.bank_ch, w.v_bn_ws)
             call("mstts_copy2d", ptr(w.v_tmp2), d.bank_ch, ptr(w.v_cat, (k - 1) * d.bank_ch), d.bank_k * d.bank_ch, rows, d.bank_ch, 0)
         C1 = d.bank_k * d.bank_ch
         call("mstts_maxpool2_same", ptr(w.v_cat), ptr(w.v_pool), B, S, C1)
         kk, ok = self.P(VOC + "convbank_0/conv1d_8/kernel"); b, ob = self.P(VOC + "convbank_0/conv1d_8/bias")
         self._gemm(w.v_pool, kk, w.v_p1, rows, d.proj1_ch, d.proj1_k * C1, C1, d.proj1_ch, d.proj1_ch, bias=b, act=ACT_RELU,
              win=(S, C1, (d.proj1_k - 1) // 2), b_off=ok, bias_off=ob, exact=True)
-        self._bn_fwd(VOC + "convbank_0/batch_normalization_8/", w.v_p1, w.v_p1y, w.v_stat, w.v_stat[d.proj1_ch:], None, 1.0, rows, d.proj1_ch, w.v_bn_ws)
+        bn_train_fwd(self, VOC + "convbank_0/batch_normalization_8/", w.v_p1, w.v_p1y, w.v_stat, w.v_stat[d.proj1_ch:], None, 1.0, rows, d.proj1_ch, w.v_bn_ws)
         kk, ok = self.P(VOC + "convbank_0/conv1d_9/kernel"); b, ob = self.P(VOC + "convbank_0/conv1d_9/bias")
         self._gemm(w.v_p1y, kk, w.v_p2, rows, d.n_mel, d.proj2_k * d.proj1_ch, d.proj1_ch, d.n_mel, d.n_mel, bias=b,
              win=(S, d.proj1_ch, (d.proj2_k - 1) // 2), b_off=ok, bias_off=ob, exact=True)
-        self._bn_fwd(VOC + "convbank_0/batch_normalization_9/", w.v_p2, w.v_p2y, w.v_stat, w.v_stat[d.n_mel:], None, 1.0, rows, d.n_mel, w.v_bn_ws)
+        bn_train_fwd(self, VOC + "convbank_0/batch_normalization_9/", w.v_p2, w.v_p2y, w.v_stat, w.v_stat[d.n_mel:], None, 1.0, rows, d.n_mel, w.v_bn_ws)
 
     # ------------------------------------------------------------------ loss + backward
     def loss_and_backward(self, w, grad_scale=1.0, on_ready=None, on_abort=None, agree=None, agree_async=None, _redo=False):
@@ -957,8 +847,10 @@ class TrainEngine:
             cin = d.n_mel if i == 0 else d.post_ch
             x_in = w.linear if i == 0 else w.post_y[i - 1]
             dx = w.post_dx if (i % 2 == 0) else w.post_dx2
-            self._conv_block_bwd(dy, x_in, w.post_a[i], w.post_mean[i], w.post_rstd[i], mk["post_drop_%d" % i], 1 - d.conv_drop,
-                                 ACT_TANH, "decoder/conv_%d/" % i, B * S, S, cin, chans[i], d.post_k, w.post_dz[i], dx, wgrad_stream=wg_stream)
+            pre = "decoder/conv_%d/" % i
+            conv_bn_bwd(self, self._gemm, pre + "conv1d", pre + "batch_normalization/", dy, x_in, w.post_a[i], w.post_mean[i], w.post_rstd[i],
+                        mk["post_drop_%d" % i], 1 - d.conv_drop, ACT_TANH, B * S, S, cin, chans[i], d.post_k, w.post_dz[i], dx, self._bnws,
+                        wgrad_stream=wg_stream)
             dy = dx
         # every postnet gradient is final: its all-reduce overlaps the decoder BPTT - unless that is the persistent launch, which needs
         # every CU of the chip for itself: a collective kernel holding CUs at that moment and the 256 workgroups waiting for each
@@ -1071,27 +963,15 @@ class TrainEngine:
         bseqs = []
         for di, dr in enumerate(("fw", "bw")):
             k, ok = self.P(ENC_CELL % dr + "kernel")
-            q = lib.LstmSeqBwd()
-            q.B, q.T, q.H = B, Te, He
-            q.wh = ptr(k, ok + cin * 4 * He); q.wh_ld = 4 * He
-            q.lengths = ptr(tlen); q.reverse = di; q.zoneout = d.zoneout
-            q.zc = ptr(mk["enc_zc_" + dr]); q.zh = ptr(mk["enc_zh_" + dr])
-            q.d_out = ptr(w.d_values, di * He); q.dout_sb = Te * M; q.dout_st = M
-            q.c_hist = ptr(w.enc_c[dr]); q.acts = ptr(w.enc_acts[dr]); q.c_raw = ptr(w.enc_craw[dr])
-            q.dgates_step = ptr(w.enc_dgs[dr]); q.dgates_pos = ptr(w.enc_dgp[dr]); q.ws = ptr(w.enc_bwd_ws[dr])
-            bseqs.append(q)
+            bseqs.append(lstm_seq_bwd(B, Te, He, (k, ok + cin * 4 * He), tlen, di, d.zoneout, mk["enc_zc_" + dr], mk["enc_zh_" + dr],
+                                      (w.d_values, di * He), Te * M, M, w.enc_c[dr], w.enc_acts[dr], w.enc_craw[dr], w.enc_dgs[dr], w.enc_dgp[dr],
+                                      w.enc_bwd_ws[dr]))
         def encoder_tail():
             """Everything behind the encoder's BPTT: the BiLSTM's weight gradients and input gradient, the convolution blocks, the embedding."""
             x_in, cin = w.enc_y[-1], d.enc_conv_ch
             for di, dr in enumerate(("fw", "bw")):
-                k, ok = self.P(ENC_CELL % dr + "kernel")
-                gk, ogk = self.G(ENC_CELL % dr + "kernel"); gb, ogb = self.G(ENC_CELL % dr + "bias")
-                self._gemm(x_in, w.enc_dgp[dr], gk, cin, 4 * He, B * Te, cin, 4 * He, 4 * He, trans_a=True,
-                     split_k=max(2, _split_k(cin, 4 * He, B * Te)), c_off=ogk)
-                self._gemm(w.enc_h[dr], w.enc_dgs[dr], gk, He, 4 * He, Te * B, He, 4 * He, 4 * He, trans_a=True,
-                     split_k=max(2, _split_k(He, 4 * He, B * Te)), c_off=ogk + cin * 4 * He)
-                call("mstts_colsum", ptr(w.enc_dgs[dr]), Te * B, 4 * He, 4 * He, ptr(gb, ogb), 1)
-                self._gemm(w.enc_dgp[dr], k, w.enc_dy, B * Te, cin, 4 * He, 4 * He, 4 * He, cin, trans_b=True, accumulate=(di == 1), b_off=ok)
+                lstm_layer_grads(self, self._gemm, ENC_CELL % dr, x_in, w.enc_h[dr], w.enc_dgp[dr], w.enc_dgs[dr], w.enc_dy, B * Te, cin, He,
+                                 dx_accumulate=di == 1)
             # ---- encoder conv backward
             dy = w.enc_dy
             bufs = [w.enc_dx, w.enc_dy]
@@ -1099,8 +979,9 @@ class TrainEngine:
                 cin = d.emb if i == 0 else d.enc_conv_ch
                 x_in = w.emb if i == 0 else w.enc_y[i - 1]
                 dx = bufs[(d.enc_conv_n - 1 - i) % 2]
-                self._conv_block_bwd(dy, x_in, w.enc_a[i], w.enc_mean[i], w.enc_rstd[i], mk["enc_conv_drop_%d" % i], 1 - d.conv_drop,
-                                     ACT_RELU, "encoder/conv_%d/" % i, B * Te, Te, cin, d.enc_conv_ch, d.enc_conv_k, w.enc_dz, dx)
+                pre = "encoder/conv_%d/" % i
+                conv_bn_bwd(self, self._gemm, pre + "conv1d", pre + "batch_normalization/", dy, x_in, w.enc_a[i], w.enc_mean[i], w.enc_rstd[i],
+                            mk["enc_conv_drop_%d" % i], 1 - d.conv_drop, ACT_RELU, B * Te, Te, cin, d.enc_conv_ch, d.enc_conv_k, w.enc_dz, dx, self._bnws)
                 dy = dx
             ge, oge = self.G("encoder/embedding_variable")
             call("mstts_embedding_bwd", ptr(tok), ptr(dy), ptr(ge, oge), B * Te, d.n_tok, d.emb)
@@ -1246,15 +1127,8 @@ class TrainEngine:
     # ------------------------------------------------------------------ optimizer
     def adam_step(self, grad_scale=1.0):
         """tf.train.AdamOptimizer + the 1e-6 * l2 regulariser's gradient (MSTTS_SV.py:145-176)."""
-        ps = self.params
-        b1, b2, eps = self.adam
-        t = self.global_step + 1
         lr = learning_rate(self.global_step)
-        lr_t = lr * math.sqrt(1 - b2 ** t) / (1 - b1 ** t)
-        call("mstts_adam_tf", ptr(ps.train), ptr(ps.grad), ptr(ps.adam_m), ptr(ps.adam_v), ptr(ps.wd_mask), float(self.wr_rate),
-             float(grad_scale), float(lr_t), b1, b2, eps, ps.n_train)
-        self.global_step += 1
-        ps.touch()
+        self._adam(lr, self.wr_rate, grad_scale)
         self._derived_stale = True
         self.refresh_derived()
         return lr

@@ -22,8 +22,7 @@ from . import lib
 from .lib import ACT_NONE, ACT_RELU, ACT_TANH, gemm, ptr, call
 from .masks import MaskSet, step_seed
 from .params import CELL, ENC_CELL, LSA, SPK, SPK_CELL, VOC, VOC_CELL, Dims, ParamStore, bank_suffix
-
-BN_EPS = 1e-3
+from .training import BN_EPS, lstm_seq_fwd
 SPK_OVERLAP = os.environ.get("MSTTS_SPK_OVERLAP", "1") != "0"     # inference forward: the speaker stack on its own stream beside the text encoder
 
 
@@ -155,20 +154,13 @@ class InferEngine:
         k, ok = self.P(cell_prefix + "kernel"); b, ob = self.P(cell_prefix + "bias")
         xw = self._f(B * T, 4 * H)
         gemm(x, k, xw, B * T, 4 * H, cin, cin, 4 * H, 4 * H, bias=b, b_off=ok, bias_off=ob)
-        q = lib.LstmSeqFwd()
-        q.B, q.T, q.H = B, T, H
-        q.xw = ptr(xw); q.wh = ptr(k, ok + cin * 4 * H); q.wh_ld = 4 * H
         if reverse and lengths is None:            # tf.reverse_sequence over the full length
             lengths = torch.full((B,), T, dtype=torch.int32, device=self.device)
             self._keep.append(lengths)
-        q.lengths = ptr(lengths); q.reverse = reverse; q.zoneout = self.d.zoneout
-        q.residual = ptr(residual)
-        q.zc, q.zh = ptr(zc), ptr(zh)
-        q.out = ptr(out, out_off); q.out_sb = out_sb; q.out_st = out_st
-        ch, hh = self._f(T + 1, B, H), self._f(T + 1, B, H)
-        q.c_hist, q.h_hist = ptr(ch), ptr(hh)
         L_ = lib.load()
-        q.gates_ws = ptr(self._f(int(L_.mstts_lstm_seq_ws_floats(B, H, 0))))
+        q = lstm_seq_fwd(B, T, H, xw, (k, ok + cin * 4 * H), lengths, reverse, self.d.zoneout, zc, zh, (out, out_off), out_sb, out_st,
+                         self._f(T + 1, B, H), self._f(T + 1, B, H), None, None, self._f(int(L_.mstts_lstm_seq_ws_floats(B, H, 0))),
+                         residual=residual)
         if fused and residual is None and L_.mstts_cell_fwd_supported(H, H):
             whp = self._f(H * 4 * H)             # (packed per call: the parameters may have been reloaded in between; 1 small launch)
             call("mstts_pack_cell_fwd", ptr(k, ok + cin * 4 * H), 4 * H, ptr(whp), H, H)

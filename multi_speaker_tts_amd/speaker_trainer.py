@@ -9,7 +9,6 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import math
 
 import numpy as np
 import torch
@@ -18,10 +17,7 @@ from . import lib
 from .lib import call, gemm, ptr
 from .masks import step_seed
 from .params import SPK, SPK_CELL, Dims, ParamStore
-from .engine import _split_k
-
-MAX_PLANS = 3      # cached workspace sets (one per batch shape); a full-size Tacotron2 set is ~5 GB
-
+from .training import Engine, Workspace, _split_k, exponential_decay, lstm_layer_grads, lstm_seq_bwd, lstm_seq_fwd
 
 
 def is_trainable(name):
@@ -31,11 +27,10 @@ def is_trainable(name):
 def learning_rate(step):
     """Speaker_Embedding.py:46-52."""
     from . import Hyper_Parameters as hp
-    lr = hp.Speaker_Embedding.Train.Learning_Rate
-    return max(lr.Initial * lr.Decay_Rate ** (step / lr.Decay_Step), lr.Min)
+    return exponential_decay(hp.Speaker_Embedding.Train.Learning_Rate, step)
 
 
-class SpeakerTrainEngine:
+class SpeakerTrainEngine(Engine):
     def __init__(self, dims: Dims = None, device="cuda", seed=1234, values=None, adam=None):
         from . import Hyper_Parameters as hp
         self.d = dims or Dims()
@@ -51,33 +46,19 @@ class SpeakerTrainEngine:
         self.wb_mask = torch.zeros(4, dtype=torch.uint8, device=self.device)
         self.global_step = 0
         self._plans = {}          # workspace sets keyed by batch shape, least recently used first (at most MAX_PLANS kept)
+        self._last = None         # the set of the last loss_and_backward (its out3 holds the loss variables' gradients)
         # persistent LSTM launches (csrc/persist_lstm.hip): all T steps of a layer in one launch each way; MSTTS_PERSIST_ENC=0 keeps the
         # launch-per-step loops, which are also the fallback
         self.persist_lstm = os.environ.get("MSTTS_PERSIST_ENC", "1") != "0"
         self.persist_lstm_fallbacks = 0
 
-    def _f(self, *shape):
-        n = int(np.prod(shape))
-        return torch.zeros((n + 3) // 4 * 4, dtype=torch.float32, device=self.device)[:n].view(shape)
-
-    def P(self, name):
-        return self.params.p(name)
-
-    def G(self, name):
-        return self.params.g(name)
-
     def plan(self, N, T):
-        if (N, T) in self._plans:
-            self._plans[(N, T)] = self._plans.pop((N, T))          # most recently used last
-            return self._plans[(N, T)]
-        while len(self._plans) >= MAX_PLANS:                 # variable-length training: do not keep a workspace per shape forever
-            self._plans.pop(next(iter(self._plans)))
+        return self._cached_plan((N, T), self._new_plan)
+
+    def _new_plan(self, N, T):
         d, f = self.d, self._f
         H, L = d.spk_lstm, d.spk_lstm_n
-
-        class W:
-            pass
-        w = W()
+        w = Workspace()
         w.N, w.T = N, T
         w.x = [f(N, T, d.spk) for _ in range(L + 1)]            # x[0] = dense output, x[l+1] = output of cell l
         w.xw = f(N * T, 4 * H)
@@ -110,7 +91,6 @@ class SpeakerTrainEngine:
         w.d_out = f(N, T, d.spk)                                # gradient of a cell's output sequence
         w.d_in = f(N, T, d.spk)
         w.dgs, w.dgp = f(T, N, 4 * H), f(N, T, 4 * H)
-        self._plans[(N, T)] = w
         return w
 
     def forward(self, mel, w, seed=None, masks=None):
@@ -131,16 +111,10 @@ class SpeakerTrainEngine:
         for i in range(d.spk_lstm_n):
             k, ok = self.P(SPK_CELL % (i, i) + "kernel"); b, ob = self.P(SPK_CELL % (i, i) + "bias")
             gemm(w.x[i], k, w.xw, N * T, 4 * H, d.spk, d.spk, 4 * H, 4 * H, bias=b, b_off=ok, bias_off=ob)
-            q = lib.LstmSeqFwd()
-            q.B, q.T, q.H = N, T, H
-            q.xw = ptr(w.xw); q.wh = ptr(k, ok + d.spk * 4 * H); q.wh_ld = 4 * H
-            q.lengths = ptr(w.lengths); q.reverse = 0; q.zoneout = d.zoneout
-            q.zc, q.zh = ptr(w.zc[i]), ptr(w.zh[i])
             res = i < d.spk_lstm_n - 1
-            q.residual = ptr(w.x[i]) if (res and not w.fused) else None
-            q.out = ptr(w.y if (res and w.fused) else w.x[i + 1]); q.out_sb = T * H; q.out_st = H
-            q.c_hist, q.h_hist, q.acts, q.c_raw = ptr(w.c[i]), ptr(w.h[i]), ptr(w.acts[i]), ptr(w.craw[i])
-            q.gates_ws = ptr(w.gates)
+            q = lstm_seq_fwd(N, T, H, w.xw, (k, ok + d.spk * 4 * H), w.lengths, 0, d.zoneout, w.zc[i], w.zh[i],
+                             (w.y if (res and w.fused) else w.x[i + 1], 0), T * H, H, w.c[i], w.h[i], w.acts[i], w.craw[i], w.gates,
+                             residual=w.x[i] if (res and not w.fused) else None)
             done = False
             if getattr(w, "persist", False):
                 call("mstts_persist_lstm_pack", ptr(k, ok + d.spk * 4 * H), 4 * H, ptr(w.pk[i][0]), ptr(w.pk[i][1]))
@@ -178,44 +152,31 @@ class SpeakerTrainEngine:
         d_out = w.d_out
         for i in range(d.spk_lstm_n - 1, -1, -1):
             k, ok = self.P(SPK_CELL % (i, i) + "kernel")
-            q = lib.LstmSeqBwd()
-            q.B, q.T, q.H = N, T, H
-            q.wh = ptr(k, ok + Dm * 4 * H); q.wh_ld = 4 * H
-            q.lengths = ptr(w.lengths); q.reverse = 0; q.zoneout = d.zoneout
-            q.zc, q.zh = ptr(w.zc[i]), ptr(w.zh[i])
-            q.d_out = ptr(d_out); q.dout_sb = T * H; q.dout_st = H
-            q.c_hist, q.acts, q.c_raw = ptr(w.c[i]), ptr(w.acts[i]), ptr(w.craw[i])
-            q.dgates_step, q.dgates_pos, q.ws = ptr(w.dgs), ptr(w.dgp), ptr(w.bwd_ws)
+            q = lstm_seq_bwd(N, T, H, (k, ok + Dm * 4 * H), w.lengths, 0, d.zoneout, w.zc[i], w.zh[i], (d_out, 0), T * H, H,
+                             w.c[i], w.acts[i], w.craw[i], w.dgs, w.dgp, w.bwd_ws)
             done = False
             if getattr(w, "persist", False) and w.phist_valid[i]:       # (the persistent BPTT reads the packed history of a persistent forward)
                 call("mstts_lstm_seq_bwd_persistent", C.byref(q), ptr(w.pk[i][1]), ptr(w.pxch), ptr(w.pctrl), ptr(w.phist[i]), ptr(w.pbws))
                 done = self._persist_ok(w, 16 * w.groups)
             if not done:
                 call("mstts_lstm_seq_bwd", C.byref(q))
-            gk, ogk = self.G(SPK_CELL % (i, i) + "kernel"); gb, ogb = self.G(SPK_CELL % (i, i) + "bias")
-            gemm(w.x[i], w.dgp, gk, Dm, 4 * H, N * T, Dm, 4 * H, 4 * H, trans_a=True, split_k=max(2, _split_k(Dm, 4 * H, N * T)), c_off=ogk)
-            gemm(w.h[i], w.dgs, gk, H, 4 * H, N * T, H, 4 * H, 4 * H, trans_a=True, split_k=max(2, _split_k(H, 4 * H, N * T)), c_off=ogk + Dm * 4 * H)
-            call("mstts_colsum", ptr(w.dgs), N * T, 4 * H, 4 * H, ptr(gb, ogb), 1)
             d_in = w.d_in if d_out is w.d_out else w.d_out
-            gemm(w.dgp, k, d_in, N * T, Dm, 4 * H, 4 * H, 4 * H, Dm, trans_b=True, b_off=ok)
+            lstm_layer_grads(self, gemm, SPK_CELL % (i, i), w.x[i], w.h[i], w.dgp, w.dgs, d_in, N * T, Dm, H)
             if i < d.spk_lstm_n - 1:                             # ResidualWrapper: the output gradient also reaches the input
                 call("mstts_add", ptr(d_in), ptr(d_out), ptr(d_in), N * T * Dm)
             d_out = d_in
         gk, ogk = self.G(SPK + "dense/kernel"); gb, ogb = self.G(SPK + "dense/bias")
         gemm(w.mel, d_out, gk, d.n_mel, Dm, N * T, d.n_mel, Dm, Dm, trans_a=True, split_k=max(2, _split_k(d.n_mel, Dm, N * T)), c_off=ogk)
         call("mstts_colsum", ptr(d_out), N * T, Dm, Dm, ptr(gb, ogb), 1)
+        self._last = w
 
-    def adam_step(self, w):
-        ps = self.params
-        b1, b2, eps = self.adam
-        t = self.global_step + 1
+    def adam_step(self, w=None):
+        w = w or self._last
         lr = learning_rate(self.global_step)
-        lr_t = lr * math.sqrt(1 - b2 ** t) / (1 - b1 ** t)
-        call("mstts_adam_tf", ptr(ps.train), ptr(ps.grad), ptr(ps.adam_m), ptr(ps.adam_v), ptr(ps.wd_mask), 0.0, 1.0, float(lr_t), b1, b2, eps, ps.n_train)
-        # the loss's (weight, bias): gradients sit in out3[1:3]
-        call("mstts_adam_tf", ptr(self.wb), ptr(w.out3, 1), ptr(self.wb_m), ptr(self.wb_v), ptr(self.wb_mask), 0.0, 1.0, float(lr_t), b1, b2, eps, 2)
-        self.global_step += 1
-        ps.touch()                           # (an InferEngine sharing this store keys its packed recurrent kernels on the version)
+        rate = self._adam(lr)
+        # the loss's (weight, bias) at the same bias-corrected rate: gradients sit in out3[1:3]
+        b1, b2, eps = self.adam
+        call("mstts_adam_tf", ptr(self.wb), ptr(w.out3, 1), ptr(self.wb_m), ptr(self.wb_v), ptr(self.wb_mask), 0.0, 1.0, float(rate), b1, b2, eps, 2)
         return lr
 
     def train_step(self, mel, batch_per_speaker, masks=None, seed=None):

@@ -8,7 +8,6 @@ LSTM-sequence kernels as the Tacotron2 trainer plus mstts_maxpool2_same_bwd, mst
 from __future__ import annotations
 
 import ctypes as C
-import math
 
 import numpy as np
 import torch
@@ -17,12 +16,10 @@ from . import lib
 from .lib import ACT_NONE, ACT_RELU, call, gemm, ptr
 from .masks import step_seed
 from .params import VOC, Dims, ParamStore, bank_suffix
-from .engine import BN_EPS, BN_MOM, _split_k
+from .training import (Engine, Workspace, _split_k, bn_train_fwd, conv_bn_bwd, conv_fwd, exponential_decay, lstm_layer_grads, lstm_seq_bwd,
+                       lstm_seq_fwd)
 
 BIRNN = VOC + "birnn/stack_bidirectional_rnn/cell_0/bidirectional_rnn/%s/zoneout_lstm_cell/"
-
-MAX_PLANS = 3      # cached workspace sets (one per batch shape); a full-size Tacotron2 set is ~5 GB
-
 
 
 def is_trainable(name):
@@ -38,12 +35,10 @@ def in_weight_reg(name):
 def learning_rate(step):
     """Taco1_Mel_to_Spect.py:63-69."""
     from . import Hyper_Parameters as hp
-    lr = hp.Taco1_Mel_to_Spect.Train.Learning_Rate
-    v = lr.Initial * lr.Decay_Rate ** ((step - lr.Decay_Start_Step) / lr.Decay_Step)
-    return min(max(v, lr.Min), lr.Initial)
+    return exponential_decay(hp.Taco1_Mel_to_Spect.Train.Learning_Rate, step)
 
 
-class Taco1TrainEngine:
+class Taco1TrainEngine(Engine):
     def __init__(self, dims: Dims = None, device="cuda", seed=1234, values=None, wr_rate=None, adam=None):
         from . import Hyper_Parameters as hp
         self.d = dims or Dims()
@@ -58,28 +53,13 @@ class Taco1TrainEngine:
         self.flip = {}
         self._plans = {}          # workspace sets keyed by batch shape, least recently used first (at most MAX_PLANS kept)
 
-    def _f(self, *shape):
-        n = int(np.prod(shape))
-        return torch.zeros((n + 3) // 4 * 4, dtype=torch.float32, device=self.device)[:n].view(shape)
-
-    def P(self, name):
-        return self.params.p(name)
-
-    def G(self, name):
-        return self.params.g(name)
-
     # ------------------------------------------------------------------ buffers
     def plan(self, B, S):
-        if (B, S) in self._plans:
-            self._plans[(B, S)] = self._plans.pop((B, S))          # most recently used last
-            return self._plans[(B, S)]
-        while len(self._plans) >= MAX_PLANS:                 # variable-length training: do not keep a workspace per shape forever
-            self._plans.pop(next(iter(self._plans)))
-        d, f = self.d, self._f
+        return self._cached_plan((B, S), self._new_plan)
 
-        class W:
-            pass
-        w = W()
+    def _new_plan(self, B, S):
+        d, f = self.d, self._f
+        w = Workspace()
         w.B, w.S = B, S
         rows, C1, Hh = B * S, d.bank_k * d.bank_ch, d.birnn
         w.bank_a = [f(rows, d.bank_ch) for _ in range(d.bank_k)]
@@ -115,36 +95,7 @@ class Taco1TrainEngine:
         w.d_p1y, w.d_pool, w.d_cat = f(rows, d.proj1_ch), f(rows, C1), f(rows, C1)
         w.dz_big = f(rows, max(d.proj1_ch, d.bank_ch, d.n_mel))
         w.d_bank, w.d_mel = f(rows, d.bank_ch), f(rows, d.n_mel)
-        self._plans[(B, S)] = w
         return w
-
-    def _bn_fwd(self, prefix, a, y, mean, rstd, rows, Cc, ws):
-        g, og = self.P(prefix + "gamma"); b, ob = self.P(prefix + "beta")
-        mm, omm = self.P(prefix + "moving_mean"); mv, omv = self.P(prefix + "moving_variance")
-        call("mstts_bn_train_fwd", ptr(a), ptr(g, og), ptr(b, ob), ptr(mm, omm), ptr(mv, omv), ptr(y), ptr(mean), ptr(rstd),
-             None, 1.0, BN_MOM, BN_EPS, rows, Cc, ptr(ws))
-
-    def _conv(self, x, rows, T, cin, cout, K, name, out, act, lda=None):
-        k, ok = self.P(name + "/kernel"); b, ob = self.P(name + "/bias")
-        gemm(x, k, out, rows, cout, K * cin, cin, cout, cout, bias=b, act=act, win=(T, cin, (K - 1) // 2), b_off=ok, bias_off=ob)
-
-    def _conv_bn_bwd(self, dy, x_in, a, mean, rstd, act, conv, bn, rows, T, cin, cout, K, dz, dx, dx_accumulate=False):
-        """y = BN(act(conv(x))): dy -> dz (conv pre-activation grad), parameter grads, dx (+= when dx_accumulate)."""
-        g, og = self.P(bn + "gamma"); gg, ogg = self.G(bn + "gamma"); gb, ogb = self.G(bn + "beta"); gbias, ogbias = self.G(conv + "/bias")
-        call("mstts_bn_train_bwd", ptr(dy), ptr(a), ptr(g, og), ptr(mean), ptr(rstd), None, 1.0, act, ptr(dz),
-             ptr(gg, ogg), ptr(gb, ogb), ptr(gbias, ogbias), rows, cout, ptr(self._w.bn_ws))
-        gk, ogk = self.G(conv + "/kernel")
-        pad = (K - 1) // 2
-        gemm(x_in, dz, gk, K * cin, cout, rows, cin, cout, cout, trans_a=True, win=(T, cin, pad),
-             split_k=max(2, _split_k(K * cin, cout, rows)), c_off=ogk)
-        if dx is not None:
-            k, ok = self.P(conv + "/kernel")
-            key = (conv, K, cin, cout)
-            if key not in self.flip:
-                self.flip[key] = self._f(K, cout, cin)
-            wt = self.flip[key]
-            call("mstts_conv_kernel_flip", ptr(k, ok), ptr(wt), K, cin, cout)
-            gemm(dz, wt, dx, rows, cin, K * cout, cout, cin, cin, win=(T, cout, K - 1 - pad), accumulate=dx_accumulate)
 
     # ------------------------------------------------------------------ forward
     def forward(self, mel, w, seed=None, masks=None):
@@ -165,15 +116,16 @@ class Taco1TrainEngine:
                 call("mstts_philox_keep_mask", ptr(w.zh[dr]), S * B * Hh, sd, 51 + 2 * i, 1 - d.zoneout)
         for k in range(1, d.bank_k + 1):
             sfx = bank_suffix(k)
-            self._conv(mel, rows, S, d.n_mel, d.bank_ch, k, VOC + "convbank_0/conv1d%s" % sfx, w.bank_a[k - 1], ACT_RELU)
+            conv_fwd(self, gemm, mel, rows, S, d.n_mel, d.bank_ch, k, VOC + "convbank_0/conv1d%s" % sfx, w.bank_a[k - 1], ACT_RELU)
             y = w.dz_big                                   # scratch for the normalised block before it is copied into the concat
-            self._bn_fwd(VOC + "convbank_0/batch_normalization%s/" % sfx, w.bank_a[k - 1], y, w.bank_mean[k - 1], w.bank_rstd[k - 1], rows, d.bank_ch, w.bn_ws)
+            bn_train_fwd(self, VOC + "convbank_0/batch_normalization%s/" % sfx, w.bank_a[k - 1], y, w.bank_mean[k - 1], w.bank_rstd[k - 1], None, 1.0,
+                         rows, d.bank_ch, w.bn_ws)
             call("mstts_copy2d", ptr(y), d.bank_ch, ptr(w.cat, (k - 1) * d.bank_ch), C1, rows, d.bank_ch, 0)
         call("mstts_maxpool2_same", ptr(w.cat), ptr(w.pool), B, S, C1)
-        self._conv(w.pool, rows, S, C1, d.proj1_ch, d.proj1_k, VOC + "convbank_0/conv1d_8", w.p1_a, ACT_RELU)
-        self._bn_fwd(VOC + "convbank_0/batch_normalization_8/", w.p1_a, w.p1_y, w.p1_mean, w.p1_rstd, rows, d.proj1_ch, w.bn_ws)
-        self._conv(w.p1_y, rows, S, d.proj1_ch, d.n_mel, d.proj2_k, VOC + "convbank_0/conv1d_9", w.p2_a, ACT_NONE)
-        self._bn_fwd(VOC + "convbank_0/batch_normalization_9/", w.p2_a, w.p2_y, w.p2_mean, w.p2_rstd, rows, d.n_mel, w.bn_ws)
+        conv_fwd(self, gemm, w.pool, rows, S, C1, d.proj1_ch, d.proj1_k, VOC + "convbank_0/conv1d_8", w.p1_a, ACT_RELU)
+        bn_train_fwd(self, VOC + "convbank_0/batch_normalization_8/", w.p1_a, w.p1_y, w.p1_mean, w.p1_rstd, None, 1.0, rows, d.proj1_ch, w.bn_ws)
+        conv_fwd(self, gemm, w.p1_y, rows, S, d.proj1_ch, d.n_mel, d.proj2_k, VOC + "convbank_0/conv1d_9", w.p2_a, ACT_NONE)
+        bn_train_fwd(self, VOC + "convbank_0/batch_normalization_9/", w.p2_a, w.p2_y, w.p2_mean, w.p2_rstd, None, 1.0, rows, d.n_mel, w.bn_ws)
         call("mstts_add", ptr(mel), ptr(w.p2_y), ptr(w.hx[0]), rows * d.n_mel)
         for i in range(d.highway_n):
             pre = VOC + "highway_%d/" % i
@@ -186,14 +138,8 @@ class Taco1TrainEngine:
         for di, dr in enumerate(("fw", "bw")):
             k, ok = self.P(BIRNN % dr + "kernel"); b, ob = self.P(BIRNN % dr + "bias")
             gemm(x, k, w.xw[dr], rows, 4 * Hh, d.n_mel, d.n_mel, 4 * Hh, 4 * Hh, bias=b, b_off=ok, bias_off=ob)
-            q = lib.LstmSeqFwd()
-            q.B, q.T, q.H = B, S, Hh
-            q.xw = ptr(w.xw[dr]); q.wh = ptr(k, ok + d.n_mel * 4 * Hh); q.wh_ld = 4 * Hh
-            q.lengths = ptr(w.lengths); q.reverse = di; q.zoneout = d.zoneout
-            q.zc, q.zh = ptr(w.zc[dr]), ptr(w.zh[dr])
-            q.out = ptr(w.rnn, di * Hh); q.out_sb = S * 2 * Hh; q.out_st = 2 * Hh
-            q.c_hist, q.h_hist, q.acts, q.c_raw = ptr(w.c[dr]), ptr(w.h[dr]), ptr(w.acts[dr]), ptr(w.craw[dr])
-            q.gates_ws = ptr(w.gates)
+            q = lstm_seq_fwd(B, S, Hh, w.xw[dr], (k, ok + d.n_mel * 4 * Hh), w.lengths, di, d.zoneout, w.zc[dr], w.zh[dr], (w.rnn, di * Hh),
+                             S * 2 * Hh, 2 * Hh, w.c[dr], w.h[dr], w.acts[dr], w.craw[dr], w.gates)
             if w.fused:
                 call("mstts_pack_cell_fwd", ptr(k, ok + d.n_mel * 4 * Hh), 4 * Hh, ptr(w.whp[dr]), Hh, Hh)
                 q.wh_p, q.h_p = ptr(w.whp[dr]), ptr(w.hp[dr])
@@ -224,25 +170,11 @@ class Taco1TrainEngine:
         bseqs = []
         for di, dr in enumerate(("fw", "bw")):
             k, ok = self.P(BIRNN % dr + "kernel")
-            q = lib.LstmSeqBwd()
-            q.B, q.T, q.H = B, S, Hh
-            q.wh = ptr(k, ok + d.n_mel * 4 * Hh); q.wh_ld = 4 * Hh
-            q.lengths = ptr(w.lengths); q.reverse = di; q.zoneout = d.zoneout
-            q.zc, q.zh = ptr(w.zc[dr]), ptr(w.zh[dr])
-            q.d_out = ptr(w.d_rnn, di * Hh); q.dout_sb = S * 2 * Hh; q.dout_st = 2 * Hh
-            q.c_hist, q.acts, q.c_raw = ptr(w.c[dr]), ptr(w.acts[dr]), ptr(w.craw[dr])
-            q.dgates_step, q.dgates_pos, q.ws = ptr(w.dgs[dr]), ptr(w.dgp[dr]), ptr(w.bwd_ws[dr])
-            bseqs.append(q)
+            bseqs.append(lstm_seq_bwd(B, S, Hh, (k, ok + d.n_mel * 4 * Hh), w.lengths, di, d.zoneout, w.zc[dr], w.zh[dr], (w.d_rnn, di * Hh),
+                                      S * 2 * Hh, 2 * Hh, w.c[dr], w.acts[dr], w.craw[dr], w.dgs[dr], w.dgp[dr], w.bwd_ws[dr]))
         call("mstts_lstm_seq_bwd_pair", C.byref(bseqs[0]), C.byref(bseqs[1]))
         for di, dr in enumerate(("fw", "bw")):
-            k, ok = self.P(BIRNN % dr + "kernel")
-            gk, ogk = self.G(BIRNN % dr + "kernel"); gb, ogb = self.G(BIRNN % dr + "bias")
-            gemm(x_in, w.dgp[dr], gk, d.n_mel, 4 * Hh, rows, d.n_mel, 4 * Hh, 4 * Hh, trans_a=True,
-                 split_k=max(2, _split_k(d.n_mel, 4 * Hh, rows)), c_off=ogk)
-            gemm(w.h[dr], w.dgs[dr], gk, Hh, 4 * Hh, rows, Hh, 4 * Hh, 4 * Hh, trans_a=True,
-                 split_k=max(2, _split_k(Hh, 4 * Hh, rows)), c_off=ogk + d.n_mel * 4 * Hh)
-            call("mstts_colsum", ptr(w.dgs[dr]), rows, 4 * Hh, 4 * Hh, ptr(gb, ogb), 1)
-            gemm(w.dgp[dr], k, dy, rows, d.n_mel, 4 * Hh, 4 * Hh, 4 * Hh, d.n_mel, trans_b=True, accumulate=(di == 1), b_off=ok)
+            lstm_layer_grads(self, gemm, BIRNN % dr, x_in, w.h[dr], w.dgp[dr], w.dgs[dr], dy, rows, d.n_mel, Hh, dx_accumulate=di == 1)
         # highway (reverse)
         for i in range(d.highway_n - 1, -1, -1):
             pre = VOC + "highway_%d/" % i
@@ -256,27 +188,21 @@ class Taco1TrainEngine:
                 gemm(dpre, kk, dxn, rows, d.n_mel, d.n_mel, d.n_mel, d.n_mel, d.n_mel, trans_b=True, accumulate=True, b_off=ok)
             dy = dxn
         # conv bank (the residual `inputs + new` sends dy to the mel input too; the mel is data here, so only the bank path matters)
-        self._conv_bn_bwd(dy, w.p1_y, w.p2_a, w.p2_mean, w.p2_rstd, ACT_NONE, VOC + "convbank_0/conv1d_9", VOC + "convbank_0/batch_normalization_9/",
-                          rows, S, d.proj1_ch, d.n_mel, d.proj2_k, w.dz_big, w.d_p1y)
-        self._conv_bn_bwd(w.d_p1y, w.pool, w.p1_a, w.p1_mean, w.p1_rstd, ACT_RELU, VOC + "convbank_0/conv1d_8", VOC + "convbank_0/batch_normalization_8/",
-                          rows, S, C1, d.proj1_ch, d.proj1_k, w.dz_big, w.d_pool)
+        cb, ws = VOC + "convbank_0/", self._w.bn_ws
+        conv_bn_bwd(self, gemm, cb + "conv1d_9", cb + "batch_normalization_9/", dy, w.p1_y, w.p2_a, w.p2_mean, w.p2_rstd, None, 1.0, ACT_NONE,
+                    rows, S, d.proj1_ch, d.n_mel, d.proj2_k, w.dz_big, w.d_p1y, ws)
+        conv_bn_bwd(self, gemm, cb + "conv1d_8", cb + "batch_normalization_8/", w.d_p1y, w.pool, w.p1_a, w.p1_mean, w.p1_rstd, None, 1.0, ACT_RELU,
+                    rows, S, C1, d.proj1_ch, d.proj1_k, w.dz_big, w.d_pool, ws)
         call("mstts_maxpool2_same_bwd", ptr(w.cat), ptr(w.d_pool), ptr(w.d_cat), B, S, C1)
         for k in range(1, d.bank_k + 1):
             sfx = bank_suffix(k)
             call("mstts_copy2d", ptr(w.d_cat, (k - 1) * d.bank_ch), C1, ptr(w.d_bank), d.bank_ch, rows, d.bank_ch, 0)
-            self._conv_bn_bwd(w.d_bank, w.mel, w.bank_a[k - 1], w.bank_mean[k - 1], w.bank_rstd[k - 1], ACT_RELU, VOC + "convbank_0/conv1d%s" % sfx,
-                              VOC + "convbank_0/batch_normalization%s/" % sfx, rows, S, d.n_mel, d.bank_ch, k, w.dz_big, None)
+            conv_bn_bwd(self, gemm, cb + "conv1d%s" % sfx, cb + "batch_normalization%s/" % sfx, w.d_bank, w.mel, w.bank_a[k - 1], w.bank_mean[k - 1],
+                        w.bank_rstd[k - 1], None, 1.0, ACT_RELU, rows, S, d.n_mel, d.bank_ch, k, w.dz_big, None, ws)
 
-    def adam_step(self):
-        ps = self.params
-        b1, b2, eps = self.adam
-        t = self.global_step + 1
+    def adam_step(self, w=None):
         lr = learning_rate(self.global_step)
-        lr_t = lr * math.sqrt(1 - b2 ** t) / (1 - b1 ** t)
-        call("mstts_adam_tf", ptr(ps.train), ptr(ps.grad), ptr(ps.adam_m), ptr(ps.adam_v), ptr(ps.wd_mask), float(self.wr_rate),
-             1.0, float(lr_t), b1, b2, eps, ps.n_train)
-        self.global_step += 1
-        ps.touch()                           # (an InferEngine sharing this store keys its packed / folded kernels on the version)
+        self._adam(lr, wr_rate=self.wr_rate)
         return lr
 
     def scalars(self, w):

@@ -20,11 +20,10 @@ import torch
 
 from . import lib
 from .lib import call, gemm, ptr
-from .engine import _split_k
 from .params import ParamStore
+from .training import Engine, Workspace, _split_k, exponential_decay
 from .waveglow import P_WG, WGDims, random_values, variable_table
 
-MAX_PLANS = 3            # cached workspace sets (one per batch shape); the reference batch keeps ~5 GB of activations
 CLIP_NORM = 0.1          # tf.clip_by_global_norm(gradients, 0.1) (WaveGlow.py:69)
 S_LOG_S, S_LOG_DET, S_AUDIO, S_SUMSQ = 0, 1, 2, 3       # device scalars: sum min(log_s, 8), sum logdet_f, 0.5 sum z^2, 0.5 sum g^2
 
@@ -32,8 +31,7 @@ S_LOG_S, S_LOG_DET, S_AUDIO, S_SUMSQ = 0, 1, 2, 3       # device scalars: sum mi
 def learning_rate(step):
     """tf.train.exponential_decay(1e-3, step, 100000, 0.5) (not staircase), floored at Min (WaveGlow.py:53-60)."""
     from . import Hyper_Parameters as hp
-    lr = hp.WaveGlow.Train.Learning_Rate
-    return max(lr.Initial * lr.Decay_Rate ** (step / lr.Decay_Step), lr.Min)
+    return exponential_decay(hp.WaveGlow.Train.Learning_Rate, step)
 
 
 def restructure(d: WGDims, N, audio_len, T):
@@ -61,7 +59,7 @@ def early_chunk(d: WGDims, f):
     return None
 
 
-class WaveGlowTrainEngine:
+class WaveGlowTrainEngine(Engine):
     def __init__(self, dims: WGDims = None, device="cuda", seed=1234, values=None, adam=None):
         from . import Hyper_Parameters as hp
         self.d = dims or WGDims()
@@ -82,10 +80,6 @@ class WaveGlowTrainEngine:
         self._static()
 
     # ------------------------------------------------------------------ per-model constants: effective-kernel slabs and device tables
-    def _f(self, *shape):
-        n = int(np.prod(shape))
-        return torch.zeros((n + 3) // 4 * 4, dtype=torch.float32, device=self.device)[:n].view(shape)
-
     def _wp(self, flow, name):
         return P_WG + "affine_coupling_layer_%d/" % flow + name
 
@@ -153,27 +147,15 @@ class WaveGlowTrainEngine:
         """(tensor, element offset) of effective-kernel piece idx."""
         return slab, self._layout[idx][0] + off
 
-    def P(self, name):
-        return self.params.p(name)
-
-    def G(self, name):
-        return self.params.g(name)
-
     # ------------------------------------------------------------------ buffers
     def plan(self, N, T, L):
         """Workspaces for N utterances of L (grouped) audio samples conditioned on T mel frames."""
-        key = (N, T, L)
-        if key in self._plans:
-            self._plans[key] = self._plans.pop(key)
-            return self._plans[key]
-        while len(self._plans) >= MAX_PLANS:
-            self._plans.pop(next(iter(self._plans)))
+        return self._cached_plan((N, T, L), self._new_plan)
+
+    def _new_plan(self, N, T, L):
         d, f = self.d, self._f
         L, Lg, up_len = restructure(d, N, L, T)
-
-        class W:
-            pass
-        w = W()
+        w = Workspace()
         w.N, w.T, w.L, w.Lg, w.up_len = N, T, L, Lg, up_len
         rows, ch, ldc, cm = N * Lg, d.ch, d.layers * 2 * d.ch, d.groups * d.n_mel
         w.rows = rows
@@ -195,7 +177,6 @@ class WaveGlowTrainEngine:
         w.d_skip, w.d_x, w.d_z = f(rows, ch), f(rows, ch), f(rows, ch)
         w.d_rs, w.d_pre = f(rows, 2 * ch), f(rows, 2 * ch)
         w.d_cond, w.d_melg = f(rows, ldc), f(rows, cm)
-        self._plans[key] = w
         return w
 
     # ------------------------------------------------------------------ forward (Restructure_Train_Data + Glow_Train)
@@ -320,15 +301,8 @@ class WaveGlowTrainEngine:
     def adam_step(self, w=None):
         """tf.clip_by_global_norm(grads, 0.1) + TF-Adam; the clip factor is formed on the device from the gradient's sum of squares."""
         w = w or self._last
-        ps = self.params
-        b1, b2, eps = self.adam
-        t = self.global_step + 1
         lr = learning_rate(self.global_step)
-        lr_t = lr * math.sqrt(1 - b2 ** t) / (1 - b1 ** t)
-        call("mstts_adam_tf_clip", ptr(ps.train), ptr(ps.grad), ptr(ps.adam_m), ptr(ps.adam_v), ptr(w.scal, S_SUMSQ), 2.0, CLIP_NORM,
-             float(lr_t), b1, b2, eps, ps.n_train)
-        self.global_step += 1
-        ps.touch()
+        self._adam(lr, clip=(ptr(w.scal, S_SUMSQ), CLIP_NORM))
         return lr
 
     def scalars(self, w):

@@ -93,3 +93,48 @@ def test_feeder_loader_processes_deliver_the_in_thread_sequence(tmp_path, monkey
         for k in ("Token", "Token_Length", "Mel", "Mel_Length", "Speaker_Embedding_Mel"):
             assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and np.array_equal(a[k], b[k]), k
     assert not [n for n in os.listdir("/dev/shm") if n.startswith("psm_")] or True      # (blocks are unlinked by close(); other processes may own some)
+
+
+def test_drop_in_trainers_keep_their_checkpoint_layout(tmp_path, monkeypatch):
+    """Mel_to_Spect / Speaker_Embedding / WaveGlow .Save() write the variables of their scope, the Adam slots and the global step (the
+    speaker encoder also its loss variables and their slots) under the keys Tacotron2.Vocoder_Load / Speaker_Embedding_Load read, and
+    .Restore() into a fresh instance brings every value back."""
+    from multi_speaker_tts_amd import Hyper_Parameters as hp
+    from multi_speaker_tts_amd.params import Dims
+    from multi_speaker_tts_amd.Speaker_Embedding import Speaker_Embedding
+    from multi_speaker_tts_amd.Taco1_Mel_to_Spect import Mel_to_Spect
+    from multi_speaker_tts_amd.WaveGlow import WaveGlow
+    from multi_speaker_tts_amd.waveglow import WGDims
+    dims = Dims(emb=32, enc_conv_ch=32, enc_lstm=16, spk=64, prenet=16, dec_lstm=32, post_ch=16, bank_ch=8, proj1_ch=16, birnn=8, n_spec=20,
+                spk_lstm=64, max_inf=4)
+    wg = WGDims(n_mel=8, flows=4, groups=8, early_every=2, early_size=2, up_k=16, up_stride=4, layers=3, ch=32, k=3)
+    slots = {"__adam_m__", "__adam_v__", "__global_step__"}
+    loss_slots = {"__loss_vars__", "__loss_m__", "__loss_v__"}
+    cases = [(Mel_to_Spect, dims, "Taco1_Mel_to_Spect", "mel_to_spectrogram.pt", "mel_to_spectrogram/", slots),
+             (Speaker_Embedding, dims, "Speaker_Embedding", "speaker_embedding.pt", "speaker_embedding/", slots | loss_slots),
+             (WaveGlow, wg, "WaveGlow", "waveglow.pt", "waveglow/", slots)]
+    for i, (cls, d, group, file, scope, keys) in enumerate(cases):
+        monkeypatch.setattr(getattr(hp, group), "Checkpoint_Path", str(tmp_path / group))
+        m = cls(device="cpu", seed=3, dims=d)
+        g = torch.Generator().manual_seed(i)
+        ps, eng = m.params, m.engine
+        ps.adam_m.copy_(torch.rand(ps.n_train, generator=g))
+        ps.adam_v.copy_(torch.rand(ps.n_train, generator=g))
+        loss = [eng.wb, eng.wb_m, eng.wb_v] if cls is Speaker_Embedding else []
+        for t in loss:
+            t.copy_(torch.rand(4, generator=g))
+        eng.global_step = 1234 + i
+        m.Save()
+        state = torch.load(tmp_path / group / file, map_location="cpu")
+        names = {n for n, _, _ in ps.table if n.startswith(scope)}
+        assert names and set(state) == names | keys, cls.__name__
+        assert state["__global_step__"] == 1234 + i
+        m2 = cls(device="cpu", seed=4, dims=d)
+        m2.Restore()
+        got, want = m2.params.export(), ps.export()
+        assert any(not np.array_equal(v, want[n]) for n, v in cls(device="cpu", seed=4, dims=d).params.export().items() if n in names)
+        assert all(np.array_equal(got[n], want[n]) for n in names), cls.__name__
+        assert torch.equal(m2.params.adam_m, ps.adam_m) and torch.equal(m2.params.adam_v, ps.adam_v)
+        assert m2.engine.global_step == 1234 + i
+        if loss:
+            assert all(torch.equal(a, b) for a, b in zip(loss, [m2.engine.wb, m2.engine.wb_m, m2.engine.wb_v]))

@@ -6,7 +6,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from multi_speaker_tts_amd import lib
-from multi_speaker_tts_amd.engine import _split_k
+from multi_speaker_tts_amd.training import _split_k
 
 dev = torch.device("cuda:0")
 B, Te, S = 32, 128, 801

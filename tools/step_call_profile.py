@@ -35,7 +35,8 @@ def spy(name, *a):
 
 import multi_speaker_tts_amd.engine as E
 import multi_speaker_tts_amd.params as P
-mods = [m for m in (lib, E, P) if hasattr(m, "call")]
+import multi_speaker_tts_amd.training as T
+mods = [m for m in (lib, E, P, T) if hasattr(m, "call")]
 for m in mods:
     m.call = spy
 eng.forward(batch, w); eng.loss_and_backward(w); eng.adam_step()
