@@ -444,6 +444,25 @@ int mstts_stft_fft(const float* wav, const int64_t* wav_off, const int64_t* fram
                    int32_t n_mel, float max_abs, float ref_level_db, float* mel_out, float* spec_out, int64_t total_frames,
                    const float* mag_in, const float* sub, float sub_scale, int32_t flags, mstts_stream_t s);
 
+/* Griffin-Lim, normalised spectrogram -> waveform, for nu utterances at once (Audio.py:15-27,50-60; Taco1_Mel_to_Spect/Modules.py:110-119;
+ * csrc/griffin_lim.hip).  spec [total_frames, n_fft/2+1] = the utterances' [frames, num_freq] spectrograms in [0, 1] back to back;
+ * frame_off[nu+1] = frame offsets, once as a HOST array (checked before anything is launched: every utterance needs 2 frames and
+ * 2 samples) and once as a DEVICE array (read by the kernels).  Utterance w with T frames yields hop (T - 1) samples at
+ * wav_out + hop (frame_off[w] - w); wav_out holds hop (total_frames - nu) floats.  window[win] / twiddle[n_fft] = the tables of
+ * mstts_stft_fft.  A = (10 ^ ((clip(spec, 0, 1) * 100 - 100 + ref_level_db) / 20)) ^ power; initial phase e^{2 pi i u} with u from
+ * phase_u [total_frames, n_fft/2+1] or, when phase_u is NULL, drawn on the device: Philox4x32-10 keyed by seeds[w] (DEVICE array, nu
+ * entries), counter (bin / 4, frame of the utterance) - the same seed gives the same waveform wherever the utterance sits in a batch.
+ * Then `iters` rounds of istft -> stft -> keep the phase (one launch each, a workgroup per frame, overlap-add as a gather in a fixed
+ * order: bit-reproducible), the final istft and inv_preemphasis (lfilter([1], [1, -preemph])).  fp32; ws = mstts_griffin_lim_ws_floats
+ * floats (the magnitudes and two sets of windowed frames).  mstts_griffin_lim_supported: n_fft as mstts_stft_fft_supported accepts it
+ * and hop <= win <= 4 hop (the gather sums four frames per sample). */
+int mstts_griffin_lim_supported(int32_t n_fft, int32_t hop, int32_t win);
+int64_t mstts_griffin_lim_ws_floats(int64_t total_frames, int32_t n_fft, int32_t win);
+int mstts_griffin_lim(const float* spec, const float* phase_u, const uint64_t* seeds, const int64_t* frame_off_host,
+                      const int64_t* frame_off, int32_t nu, const float* window, const float* twiddle, int32_t n_fft, int32_t hop,
+                      int32_t win, float power, float ref_level_db, float preemph, int32_t iters, float* ws, float* wav_out,
+                      mstts_stream_t s);
+
 /* ---- skinny (M <= 32 rows per block) weight-streaming products of the recurrent steps -------------
  * fwd: P[ks][M][N] = X[M, K-slice ks] . W[K-slice ks, N]   (W row-major [K,N], ld ldw); ksplit from
  *      mstts_skinny_fwd_splits (0 = shape not supported -> use mstts_gemm_f32).

@@ -260,3 +260,111 @@ def Griffin_Lim(spectrogram, rng=None):
     return inv_spectrogram(np.asarray(spectrogram).transpose(), num_freq=hp.Sound.Spectrogram_Dim, frame_shift_ms=hp.Sound.Frame_Shift,
                            frame_length_ms=hp.Sound.Frame_Length, sample_rate=hp.Sound.Sample_Rate,
                            griffin_lim_iters=hp.Taco1_Mel_to_Spect.Griffin_Lim_Iteration, rng=rng)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The same algorithm on the GPU for a whole batch (mstts_griffin_lim, csrc/griffin_lim.hip): fp32, one launch per iteration for all
+# utterances.  The host functions above stay what they are and are its checker.
+# ---------------------------------------------------------------------------------------------------------------------
+def griffin_lim_offsets(frames, hop):
+    """Layout of the batched call: (frame_off, wav_off) int64 arrays of len(frames) + 1 entries.  Utterance i owns the frames
+    frame_off[i] .. frame_off[i + 1] of the concatenated spectrograms and, T_i frames giving hop (T_i - 1) samples (istft with the
+    centre padding removed), the samples wav_off[i] .. wav_off[i + 1] of the concatenated waveforms."""
+    frames = np.asarray(frames, np.int64).reshape(-1)
+    frame_off = np.concatenate([[0], np.cumsum(frames)]).astype(np.int64)
+    wav_off = np.concatenate([[0], np.cumsum(hop * np.maximum(frames - 1, 0))]).astype(np.int64)
+    return frame_off, wav_off
+
+
+def griffin_lim_phases(frames, num_freq, rng):
+    """The initial-phase uniforms of a batch, drawn utterance by utterance in list order exactly as the host path draws them
+    (`_griffin_lim`: rng.rand(num_freq, frames) per call) -> list of float64 arrays [num_freq, frames_i]."""
+    return [rng.rand(num_freq, int(t)) for t in frames]
+
+
+def griffin_lim_supported(num_freq, frame_shift_ms, frame_length_ms, sample_rate, frames=None):
+    """Does the device path cover these STFT parameters (a power-of-two n_fft in [512, 4096], hop <= win <= 4 hop) and, when given,
+    utterances of these frame counts (two frames and two samples at least)?"""
+    n_fft, hop, win = _stft_parameters(num_freq, frame_shift_ms, frame_length_ms, sample_rate)
+    if not lib.load().mstts_griffin_lim_supported(n_fft, hop, win):
+        return False
+    return frames is None or all(int(t) >= 2 and hop * (int(t) - 1) >= 2 for t in frames)
+
+
+class _FixedPhase:
+    """`rng` of the host path that hands out given uniforms."""
+
+    def __init__(self, u):
+        self.u = np.asarray(u, np.float64)
+
+    def rand(self, *shape):
+        assert tuple(shape) == self.u.shape, (shape, self.u.shape)
+        return self.u
+
+
+def griffin_lim_batch(spectrograms, num_freq, frame_shift_ms, frame_length_ms, sample_rate, ref_level_db=20, power=1.5,
+                      griffin_lim_iters=60, phase=None, rng=None, seed=0, device="cuda", return_tensor=False):
+    """`inv_spectrogram` for several utterances at once on the GPU.  spectrograms: list of [frames_i, num_freq] arrays or device
+    tensors normalised to [0, 1] (the layout Inference returns and `Griffin_Lim` takes) -> list of float32 waveforms of
+    hop (frames_i - 1) samples (NumPy, or device tensors with return_tensor).
+
+    Initial phase e^{2 pi i u}: `phase` = the uniforms themselves, one [num_freq, frames_i] array per utterance as the host draws
+    them; else `rng` = a NumPy RandomState, drawn per utterance in list order exactly as the host path would; else a device generator:
+    utterance i uses seed + i (`seed` an int) or seed[i] (a sequence) - the same seed gives the same bits, alone or in any batch.
+    STFT parameters outside the device envelope (`griffin_lim_supported`) go through the host path utterance by utterance; an
+    utterance of fewer than two frames is an error on both."""
+    frames = [int(s.shape[0]) for s in spectrograms]
+    if any(tuple(s.shape) != (t, num_freq) for s, t in zip(spectrograms, frames)):
+        raise ValueError("spectrograms must be [frames, %d]" % num_freq)
+    n_fft, hop, win = _stft_parameters(num_freq, frame_shift_ms, frame_length_ms, sample_rate)
+    if any(t < 2 or hop * (t - 1) < 2 for t in frames):
+        raise ValueError("a spectrogram of fewer than two frames has no waveform")
+    nu = len(frames)
+    if nu == 0:
+        return []
+    if phase is not None and (len(phase) != nu or any(tuple(u.shape) != (num_freq, t) for u, t in zip(phase, frames))):
+        raise ValueError("phase must hold one [num_freq, frames] array per utterance")
+    if phase is None and rng is not None:
+        phase = griffin_lim_phases(frames, num_freq, rng)
+    seeds = [int(seed) + i for i in range(nu)] if np.isscalar(seed) else [int(s) for s in seed]
+    if len(seeds) != nu:
+        raise ValueError("seed must be an int or one int per utterance")
+    if not griffin_lim_supported(num_freq, frame_shift_ms, frame_length_ms, sample_rate):
+        out = []
+        for i, s in enumerate(spectrograms):
+            s = s.detach().cpu().numpy() if torch.is_tensor(s) else np.asarray(s)
+            u = phase[i].detach().cpu().numpy() if phase is not None and torch.is_tensor(phase[i]) else (phase[i] if phase is not None else None)
+            r = _FixedPhase(u) if u is not None else np.random.RandomState(seeds[i] % (1 << 32))
+            y = inv_spectrogram(s.T, num_freq, frame_shift_ms, frame_length_ms, sample_rate, ref_level_db=ref_level_db, power=power,
+                                griffin_lim_iters=griffin_lim_iters, rng=r).astype(np.float32)
+            out.append(torch.as_tensor(y).to(device) if return_tensor else y)
+        return out
+    _, _, _, hann, tw, _, _ = _fft_constants(num_freq, frame_shift_ms, frame_length_ms, 1, sample_rate, str(device))
+    dev = hann.device
+    up = lambda a: (a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a, np.float32))).to(dev, torch.float32)
+    spec = torch.cat([up(s) for s in spectrograms]).contiguous()
+    u = torch.cat([up(p).t() for p in phase]).contiguous() if phase is not None else None
+    frame_off, wav_off = griffin_lim_offsets(frames, hop)
+    total = int(frame_off[-1])
+    foff = torch.as_tensor(frame_off).to(dev)
+    sd = torch.as_tensor(np.asarray([s % (1 << 64) for s in seeds], np.uint64).view(np.int64)).to(dev) if u is None else None
+    ws = torch.empty(int(lib.load().mstts_griffin_lim_ws_floats(total, n_fft, win)), dtype=torch.float32, device=dev)
+    wav = torch.empty(int(wav_off[-1]), dtype=torch.float32, device=dev)
+    import ctypes
+    host_off = (ctypes.c_int64 * (nu + 1))(*[int(v) for v in frame_off])
+    lib.call("mstts_griffin_lim", lib.ptr(spec), lib.ptr(u), lib.ptr(sd), host_off, lib.ptr(foff), nu, lib.ptr(hann), lib.ptr(tw), n_fft, hop,
+             win, float(power), float(ref_level_db), 0.97, int(griffin_lim_iters), lib.ptr(ws), lib.ptr(wav))
+    if return_tensor:
+        return [wav[int(a):int(b)] for a, b in zip(wav_off[:-1], wav_off[1:])]
+    host = wav.cpu().numpy()                                  # (synchronises: spec, u, ws may go once this returns)
+    return [host[int(a):int(b)].copy() for a, b in zip(wav_off[:-1], wav_off[1:])]
+
+
+def Griffin_Lim_Batch(spectrograms, phase=None, rng=None, seed=0, device="cuda", return_tensor=False):
+    """`Griffin_Lim` for a list of [Time, Dim] spectrograms in one device call, hp defaults (power 1.5, ref_level_db 20,
+    hp.Taco1_Mel_to_Spect.Griffin_Lim_Iteration iterations) -> list of float32 waveforms at hp.Sound.Sample_Rate."""
+    from . import Hyper_Parameters as hp
+    return griffin_lim_batch(spectrograms, num_freq=hp.Sound.Spectrogram_Dim, frame_shift_ms=hp.Sound.Frame_Shift,
+                             frame_length_ms=hp.Sound.Frame_Length, sample_rate=hp.Sound.Sample_Rate,
+                             griffin_lim_iters=hp.Taco1_Mel_to_Spect.Griffin_Lim_Iteration, phase=phase, rng=rng, seed=seed, device=device,
+                             return_tensor=return_tensor)

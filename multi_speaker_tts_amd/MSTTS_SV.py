@@ -512,7 +512,11 @@ class Tacotron2:
             log(pending)
 
     # ---- inference (MSTTS_SV.py:295-323,391-400)
-    def Inference(self, path_List, text_List, file_Prefix=None, speaker_Mel_List=None, masks=None, export=True):
+    def Inference(self, path_List, text_List, file_Prefix=None, speaker_Mel_List=None, masks=None, export=True, wav=None, griffin_lim_seed=0):
+        """With the Taco1 vocoder the cut spectrograms of the whole call go through ONE batched Griffin-Lim on the GPU
+        (Audio.Griffin_Lim_Batch, initial phases from the device generator seeded by `griffin_lim_seed`): res["Wav"] holds one float32
+        waveform per sentence (None where none could be made: a cut of one frame, an export error).  wav: None = with the export;
+        True = the waveforms without any file (export=False); False = NPZ files only, as if no vocoder leg existed."""
         if len(text_List) != (len(path_List) if speaker_Mel_List is None else len(speaker_Mel_List)):
             raise ValueError("path_List and text_List must have the same length")
         if hp.Use_Vocoder.upper() == "WaveGlow".upper():          # MSTTS_SV.py:295-299
@@ -527,6 +531,10 @@ class Tacotron2:
             cut.append({"Linear": res["Linear"][i, :s], "Mel": res["Mel"][i, :s], "Stop": res["Stop"][i, :s],
                         "Attention_History": res["Attention_History"][i, :len(text) + 2, :s], "Spectrogram": res["Spectrogram"][i, :s]})
         res["Cut"] = cut
+        want_wav = export if wav is None else bool(wav)
+        if want_wav:
+            names = ["{}.IDX_{}.WAV".format(prefix, i) for i in range(len(cut))]
+            res["Wav"] = self._griffin_lim([c["Spectrogram"] for c in cut], names, griffin_lim_seed)
         if export:
             out_dir = os.path.join(hp.Inference_Path, "NPZ").replace("\\", "/")
             wav_dir = os.path.join(hp.Inference_Path, "WAV").replace("\\", "/")
@@ -535,10 +543,44 @@ class Tacotron2:
                 os.makedirs(wav_dir, exist_ok=True)
                 for i, c in enumerate(cut):
                     np.savez_compressed(os.path.join(out_dir, "{}.IDX_{}.npz".format(prefix, i)), **c)
-                    self._export_wav(c["Spectrogram"], os.path.join(wav_dir, "{}.IDX_{}.WAV".format(prefix, i)))
+                    if want_wav and res["Wav"][i] is not None:
+                        self._write_wav(os.path.join(wav_dir, names[i]), res["Wav"][i])
             except OSError as e:      # the reference's default path is a Windows drive letter
                 print("Inference export skipped: {}".format(e))
         return res
+
+    def _griffin_lim(self, spectrograms, names, seed=0):
+        """Export_Inference_Mel_to_Spectrogram's Griffin-Lim leg (MSTTS_SV.py:403-414) for all sentences of a call: the spectrograms
+        the reference accepts (more than one frame) in one device batch, utterance i keyed by seed + i.  Hyper parameters the
+        device path does not cover take the host path inside Audio.griffin_lim_batch.  Errors are reported, not raised, like the
+        reference's export thread does: the waveform is None then."""
+        from . import Audio
+        wavs = [None] * len(spectrograms)
+        todo = []
+        for i, (s, name) in enumerate(zip(spectrograms, names)):
+            if s.shape[0] <= 1:
+                print("WAV '{}' exporting failed. The exported spectrogram is too short.".format(name))
+            else:
+                todo.append(i)
+        if not todo:
+            return wavs
+        try:
+            if any(spectrograms[i].shape[1] != hp.Sound.Spectrogram_Dim for i in todo):
+                raise ValueError("spectrogram width != hp.Sound.Spectrogram_Dim")
+            out = Audio.Griffin_Lim_Batch([spectrograms[i] for i in todo], seed=[seed + i for i in todo], device=self.device)
+            for i, y in zip(todo, out):
+                wavs[i] = y
+        except Exception as e:       # the reference swallows and reports every export error
+            print("Wav exporting failed: {}".format(e))
+        return wavs
+
+    @staticmethod
+    def _write_wav(path, wav):
+        try:
+            from scipy.io import wavfile
+            wavfile.write(path, hp.Sound.Sample_Rate, np.asarray(wav, np.float32))
+        except Exception as e:
+            print("Wav exporting failed: {}".format(e))
 
     @staticmethod
     def _export_wav(spectrogram, path):

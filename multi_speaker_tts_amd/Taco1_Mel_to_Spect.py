@@ -45,3 +45,62 @@ class Mel_to_Spect(DropIn):
         res = self.engine.scalars(w)
         res.update({"Global_Step": step, "Learning_Rate": learning_rate(step), "Train_OP": None})
         return res
+
+    def Inference(self, speaker_Wav_Paths, export=True, griffin_lim_seed=0):
+        """Taco1_Mel_to_Spect.py:137-178 (the feeder's Get_Inference_Pattern, Feeder.py:114-147, included): wav files -> trimmed
+        signals x 0.99 -> mels on the GPU (one launch) -> the vocoder graph in inference mode from THIS trainer's variables,
+        hp.Taco1_Mel_to_Spect.Train.Inference.Batch_Size wavs at a time, zero-padded to the longest of the group -> one batched
+        Griffin-Lim on the GPU for all of them -> <Inference.Path>/WAV/GS_<step>.IDX_<i>.WAV.  Returns {'Global_Step', 'Mel': list of
+        [frames_i, n_mel], 'Spectrogram': list of [frames_i, n_spec], 'Wav': list of float32 waveforms (None where Griffin-Lim
+        could not run: one frame, an export error)}.  The reference exports from a thread and returns nothing; its PLOT files are
+        out of scope here."""
+        import os
+
+        import torch
+
+        from . import Audio, Feeder as F
+        from .inference import InferEngine
+        if isinstance(speaker_Wav_Paths, str):
+            speaker_Wav_Paths = [speaker_Wav_Paths]
+        d, dev = self.engine.d, self.engine.device
+        sigs = [F.load_wav(p, top_db=60.0) for p in speaker_Wav_Paths]          # librosa.effects.trim's default threshold
+        feats = Audio.stft_features(sigs, hp.Sound.Spectrogram_Dim, hp.Sound.Frame_Shift, hp.Sound.Frame_Length, hp.Sound.Sample_Rate,
+                                    num_mels=hp.Sound.Mel_Dim, max_abs_value=hp.Sound.Max_Abs_Mel, device=dev)
+        mels = [m for m, _ in feats]
+        if getattr(self, "_infer", None) is None:
+            self._infer = InferEngine(d, device=dev, params=self.params)
+        specs = []
+        bs = hp.Taco1_Mel_to_Spect.Train.Inference.Batch_Size
+        for b0 in range(0, len(mels), bs):
+            group = mels[b0:b0 + bs]
+            S = max(m.shape[0] for m in group)
+            x = torch.zeros(len(group), S, d.n_mel, dtype=torch.float32, device=dev)
+            for i, m in enumerate(group):
+                x[i, :m.shape[0]] = m
+            y = self._infer.mel_to_spectrogram(x.view(len(group) * S, d.n_mel), len(group), S)
+            specs.extend(y[i, :m.shape[0]].contiguous() for i, m in enumerate(group))
+        prefix = "GS_{}".format(self.engine.global_step)
+        names = ["{}.IDX_{}.WAV".format(prefix, i) for i in range(len(specs))]
+        wavs = [None] * len(specs)
+        todo = []
+        for i, s in enumerate(specs):
+            if s.shape[0] <= 1:
+                print("WAV '{}' exporting failed. The exported spectrogram is too short.".format(names[i]))
+            else:
+                todo.append(i)
+        try:
+            if todo:
+                for i, y in zip(todo, Audio.Griffin_Lim_Batch([specs[i] for i in todo], seed=[griffin_lim_seed + i for i in todo], device=dev)):
+                    wavs[i] = y
+            if export:
+                from scipy.io import wavfile
+                wav_dir = os.path.join(hp.Taco1_Mel_to_Spect.Train.Inference.Path, "WAV").replace("\\", "/")
+                os.makedirs(wav_dir, exist_ok=True)
+                for i in todo:
+                    wavfile.write(os.path.join(wav_dir, names[i]), hp.Sound.Sample_Rate, wavs[i])
+        except Exception as e:           # the reference swallows and reports every export error
+            print("Wav exporting failed: {}".format(e))
+        out = {"Global_Step": self.engine.global_step, "Mel": [m.cpu().numpy() for m in mels], "Spectrogram": [s.cpu().numpy() for s in specs],
+               "Wav": wavs}
+        self._infer._keep = []           # (the copies above synchronised: the forward's temporaries may go)
+        return out

@@ -4,6 +4,7 @@
 // fp32 MFMA GEMM (overlapping frames are just rows with stride hop), followed by the 1025 -> 80 mel
 // filterbank GEMM and a fused dB / normalise pass.
 #include "common.h"
+#include "fft_stages.h"
 
 namespace mstts {
 
@@ -92,42 +93,10 @@ __global__ __launch_bounds__(256) void stft_fft_kernel(const float* __restrict__
     } else {
     for (int m = tid; m < N2; m += 256) bufa[m] = make_float2(sample(2 * m), sample(2 * m + 1));
     __syncthreads();
-    // Stockham autosort, radix 4 while it fits and one radix-2 stage for the odd power (N2 = 512, 2048).  Stage with sub-transform
-    // size p: thread i takes x[i + m t], m < radix, t = N2 / radix, twiddles e^{-2 pi i m k / (radix p)} = tw[m k n_fft / (radix p)]
-    // (tw has n_fft entries; 3 m k n_fft / (4 p) < 3 n_fft / 4).
-    int p = 1;
-    for (; p * 4 <= N2; p <<= 2) {
-        const int t4 = N2 >> 2, tmul = n_fft / (4 * p);
-        for (int i = tid; i < t4; i += 256) {
-            const int k = i & (p - 1), m = k * tmul;         // e^{-2 pi i k / (4 p)} = tw[k n_fft / (4 p)]
-            const float2 w1 = tw[m], w2 = tw[2 * m], w3 = tw[3 * m];
-            const float2 x0 = bufa[i], x1 = bufa[i + t4], x2 = bufa[i + 2 * t4], x3 = bufa[i + 3 * t4];
-            const float2 u1 = make_float2(x1.x * w1.x - x1.y * w1.y, x1.x * w1.y + x1.y * w1.x);
-            const float2 u2 = make_float2(x2.x * w2.x - x2.y * w2.y, x2.x * w2.y + x2.y * w2.x);
-            const float2 u3 = make_float2(x3.x * w3.x - x3.y * w3.y, x3.x * w3.y + x3.y * w3.x);
-            const float2 v0 = make_float2(x0.x + u2.x, x0.y + u2.y), v1 = make_float2(x0.x - u2.x, x0.y - u2.y);
-            const float2 v2 = make_float2(u1.x + u3.x, u1.y + u3.y), v3 = make_float2(u1.y - u3.y, u3.x - u1.x);   // (u1 - u3) * (-i)
-            const int j0 = ((i - k) << 2) + k;
-            bufb[j0] = make_float2(v0.x + v2.x, v0.y + v2.y);
-            bufb[j0 + p] = make_float2(v1.x + v3.x, v1.y + v3.y);
-            bufb[j0 + 2 * p] = make_float2(v0.x - v2.x, v0.y - v2.y);
-            bufb[j0 + 3 * p] = make_float2(v1.x - v3.x, v1.y - v3.y);
-        }
-        __syncthreads();
-        float2* t_ = bufa; bufa = bufb; bufb = t_;
-    }
-    if (p < N2) {                                            // p == N2 / 2: the last radix-2 stage
-        const int tmul = n_fft / (2 * p);
-        for (int i = tid; i < (N2 >> 1); i += 256) {
-            const int k = i & (p - 1);
-            const float2 a = bufa[i], b = bufa[i + (N2 >> 1)], t = tw[k * tmul];
-            const float2 bt = make_float2(b.x * t.x - b.y * t.y, b.x * t.y + b.y * t.x);
-            const int j0 = ((i - k) << 1) + k;
-            bufb[j0] = make_float2(a.x + bt.x, a.y + bt.y);
-            bufb[j0 + p] = make_float2(a.x - bt.x, a.y - bt.y);
-        }
-        __syncthreads();
-        float2* t_ = bufa; bufa = bufb; bufb = t_;
+    // Stockham radix-4 stages (csrc/fft_stages.h); the spectrum ends up in bufa, bufb is the other buffer
+    {
+        float2* z = fft_stockham_stages(bufa, bufb, tw, N2, n_fft, tid);
+        if (z != bufa) { bufb = bufa; bufa = z; }
     }
     // real-input post-processing -> magnitudes in LDS (bufb is free)
     mag = reinterpret_cast<float*>(bufb);
