@@ -463,6 +463,39 @@ int mstts_griffin_lim(const float* spec, const float* phase_u, const uint64_t* s
                       int32_t win, float power, float ref_level_db, float preemph, int32_t iters, float* ws, float* wav_out,
                       mstts_stream_t s);
 
+/* Waveform front end: what Feeder.load_wav does to decoded samples, for nw waveforms at once (csrc/wav_front_end.hip).  Waveforms lie
+ * back to back; every offset array is a DEVICE array of nw + 1 int64 entries, as mstts_stft_fft takes them.  fp32; everything is
+ * enqueued on the stream, nothing synchronises; parameters are checked on the host before any launch (MSTTS_ERR_SHAPE).
+ *
+ * mstts_wav_resample: scipy.signal.resample_poly(x, up, down) at its defaults (Kaiser 5.0 window, zero padding):
+ *   y[m] = sum_j h[half + m down - j up] x[j],  half = 10 max(up, down),  h = up * firwin(2 half + 1, 1 / max(up, down)),
+ * waveform w's ceil(n_w up / down) outputs at out + out_off[w].  phase_table [up][T], T = mstts_wav_resample_taps(up, down) =
+ * ceil((2 half + 1) / up) made odd: phase_table[p][i] = h[p + (T - 1 - i) up], 0 beyond the filter - an output reads one row
+ * against T consecutive inputs.  max_out = the longest output (sizes the grid).  One sum per output in ascending j by one thread: a
+ * waveform gives the same bits alone or in any batch.  mstts_wav_resample_supported: the table and a tile's input span fit in LDS
+ * (every pair of 8000 / 16000 / 22050 / 24000 / 44100 / 48000 Hz -> 16000 / 22050 Hz does).
+ *
+ * mstts_wav_trim: the silence trim of Feeder.load_wav.  Frames [i hop, i hop + frame), i < 1 + (len - frame) / hop, are kept when
+ * 20 log10(max(rms_i, 1e-10) / max(max_i rms_i, 1e-10)) > -top_db; bounds[w] = (start, end) = (first hop, min(len, (last + 1) hop))
+ * relative to the waveform, (0, len) when it is shorter than a frame or no frame is kept; peak[w] = max |x| inside [start, end).
+ * Two launches: the frames' mean squares spread over the whole device (each one sum in a fixed order) into ws, then a workgroup per
+ * waveform.  total_samples = off[nw] - off[0], max_len = the longest waveform (both known to the host, which made the offsets);
+ * ws = mstts_wav_trim_ws_floats(total_samples, nw) floats.
+ *
+ * mstts_wav_gather_scale: out_off / frame_off [nw + 1] = offsets of the kept lengths and of their 1 + len / stft_hop STFT frames
+ * (a one-workgroup scan), out + out_off[w] = the kept range of waveform w times scale (peak_normalize: scale / peak[w] where the peak
+ * is positive).  max_len = an upper bound of the kept lengths (sizes the grid); out holds at least the sum of the kept lengths. */
+int mstts_wav_resample_supported(int32_t up, int32_t down);
+int32_t mstts_wav_resample_taps(int32_t up, int32_t down);
+int mstts_wav_resample(const float* wav, const int64_t* in_off, const int64_t* out_off, int32_t nw, int64_t max_out,
+                       const float* phase_table, int32_t up, int32_t down, float* out, mstts_stream_t s);
+int64_t mstts_wav_trim_ws_floats(int64_t total_samples, int32_t nw);
+int mstts_wav_trim(const float* wav, const int64_t* off, int32_t nw, int64_t total_samples, int64_t max_len, int32_t frame, int32_t hop,
+                   float top_db, float* ws, int64_t* bounds, float* peak, mstts_stream_t s);
+int mstts_wav_gather_scale(const float* wav, const int64_t* in_off, const int64_t* bounds, const float* peak, int32_t nw,
+                           int64_t max_len, float scale, int32_t peak_normalize, int32_t stft_hop, float* out, int64_t* out_off,
+                           int64_t* frame_off, mstts_stream_t s);
+
 /* ---- skinny (M <= 32 rows per block) weight-streaming products of the recurrent steps -------------
  * fwd: P[ks][M][N] = X[M, K-slice ks] . W[K-slice ks, N]   (W row-major [K,N], ld ldw); ksplit from
  *      mstts_skinny_fwd_splits (0 = shape not supported -> use mstts_gemm_f32).

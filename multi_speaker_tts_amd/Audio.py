@@ -101,6 +101,16 @@ def stft_features(wavs, num_freq, frame_shift_ms, frame_length_ms, sample_rate, 
     woff = torch.tensor(np.concatenate([[0], np.cumsum(lens)]), dtype=torch.int64, device=dev)
     foff = torch.tensor(np.concatenate([[0], np.cumsum(frames)]), dtype=torch.int64, device=dev)
     cat = torch.cat([w.to(dev) for w in ws]).contiguous()
+    return _stft_packed(cat, woff, foff, frames, (n_fft, hop, win, hann, tw, fb, rng), num_mels, max_abs_value, ref_level_db, want_mel, want_spec,
+                        spectral_subtract)
+
+
+def _stft_packed(cat, woff, foff, frames, consts, num_mels, max_abs_value, ref_level_db, want_mel, want_spec, spectral_subtract):
+    """The launches of `stft_features` / `wav_features` on waveforms that already lie back to back on the device: cat = the samples,
+    woff / foff = device int64 offset arrays of len(frames) + 1 entries, frames = the frame counts (host)."""
+    n_fft, hop, win, hann, tw, fb, rng = consts
+    dev = hann.device
+    nw = len(frames)
     total, nb = int(sum(frames)), n_fft // 2 + 1
     mel = torch.empty(total, num_mels, dtype=torch.float32, device=dev) if want_mel else None
     spec = torch.empty(total, nb, dtype=torch.float32, device=dev) if want_spec else None
@@ -108,11 +118,11 @@ def stft_features(wavs, num_freq, frame_shift_ms, frame_length_ms, sample_rate, 
     mabs = float(max_abs_value) if max_abs_value is not None else 1.0
     common = (lib.ptr(fb) if want_mel else None, lib.ptr(rng) if want_mel else None, n_fft, hop, win, int(num_mels or 0), mabs, float(ref_level_db))
     if not spectral_subtract:
-        lib.call("mstts_stft_fft", lib.ptr(cat), lib.ptr(woff), lib.ptr(foff), len(ws), 0.97, lib.ptr(hann), lib.ptr(tw), *common,
+        lib.call("mstts_stft_fft", lib.ptr(cat), lib.ptr(woff), lib.ptr(foff), nw, 0.97, lib.ptr(hann), lib.ptr(tw), *common,
                  lib.ptr(mel) if want_mel else None, lib.ptr(spec) if want_spec else None, total, None, None, 0.0, flags)
     else:
         mag = torch.empty(total, nb, dtype=torch.float32, device=dev)
-        lib.call("mstts_stft_fft", lib.ptr(cat), lib.ptr(woff), lib.ptr(foff), len(ws), 0.97, lib.ptr(hann), lib.ptr(tw), None, None,
+        lib.call("mstts_stft_fft", lib.ptr(cat), lib.ptr(woff), lib.ptr(foff), nw, 0.97, lib.ptr(hann), lib.ptr(tw), None, None,
                  n_fft, hop, win, 0, mabs, float(ref_level_db), None, lib.ptr(mag), total, None, None, 0.0, 2)
         sub = torch.empty(nb, dtype=torch.float32, device=dev)
         one = torch.tensor([0, 0], dtype=torch.int64, device=dev)
@@ -368,3 +378,245 @@ def Griffin_Lim_Batch(spectrograms, phase=None, rng=None, seed=0, device="cuda",
                              frame_length_ms=hp.Sound.Frame_Length, sample_rate=hp.Sound.Sample_Rate,
                              griffin_lim_iters=hp.Taco1_Mel_to_Spect.Griffin_Lim_Iteration, phase=phase, rng=rng, seed=seed, device=device,
                              return_tensor=return_tensor)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Waveform front end on the GPU (csrc/wav_front_end.hip): what Feeder.load_wav does to decoded samples - polyphase rate conversion
+# (scipy.signal.resample_poly's arithmetic), the frame-RMS silence trim, the 0.99 scale - for a batch of waveforms, packed so that
+# the result feeds mstts_stft_fft without a copy back.  Feeder.load_wav stays what it is and is the checker.
+# ---------------------------------------------------------------------------------------------------------------------
+def resample_ratio(rate, sample_rate):
+    """(up, down) of a conversion rate -> sample_rate in lowest terms, as load_wav forms them."""
+    g = int(np.gcd(int(rate), int(sample_rate)))
+    return int(sample_rate) // g, int(rate) // g
+
+
+def resample_out_len(n, up, down):
+    """Samples resample_poly(x, up, down) returns for len(x) = n: ceil(n up / down)."""
+    return -(-int(n) * int(up) // int(down))
+
+
+def resample_filter(up, down):
+    """The filter resample_poly designs at its defaults, float64: up * firwin(2 half + 1, 1 / max(up, down), window=('kaiser', 5.0)) with
+    half = 10 max(up, down) - a Kaiser-windowed sinc, centred on tap `half`."""
+    from scipy.signal import firwin
+    mx = max(int(up), int(down))
+    return int(up) * firwin(20 * mx + 1, 1.0 / mx, window=("kaiser", 5.0))
+
+
+def resample_taps(up, down):
+    """Taps per output sample in the phase layout: ceil((2 half + 1) / up), made odd (mstts_wav_resample_taps)."""
+    return (-(-(20 * max(int(up), int(down)) + 1) // int(up))) | 1
+
+
+def resample_phase_table(up, down):
+    """The filter laid out by phase, float64 [up, T]: table[p, i] = h[p + (T - 1 - i) up] (0 beyond the filter).  With q = half + m down,
+    output m is  sum_i table[q % up, i] * x[q // up - (T - 1) + i]  (x = 0 outside the signal): one row against a contiguous run of
+    the input, in ascending sample order."""
+    up, down = int(up), int(down)
+    h = resample_filter(up, down)
+    T = resample_taps(up, down)
+    idx = np.arange(up)[:, None] + (T - 1 - np.arange(T))[None, :] * up
+    table = np.zeros((up, T))
+    ok = idx < h.shape[0]
+    table[ok] = h[idx[ok]]
+    return table
+
+
+def resample_supported(up, down):
+    return int(up) >= 1 and int(down) >= 1 and bool(lib.load().mstts_wav_resample_supported(int(up), int(down)))
+
+
+@functools.lru_cache(maxsize=16)
+def _resample_table(up, down, device):
+    assert lib.load().mstts_wav_resample_taps(up, down) == resample_taps(up, down)
+    return _upload(resample_phase_table(up, down).astype(np.float32).reshape(-1), torch.float32, torch.device(device))
+
+
+def _pinned(array):
+    """Host array -> page-locked tensor (what a non-blocking upload needs)."""
+    a = torch.as_tensor(np.ascontiguousarray(array))
+    p = torch.empty(a.shape, dtype=a.dtype, pin_memory=True)
+    p.copy_(a)
+    return p
+
+
+def _upload(array, dtype, dev):
+    """Host array -> device tensor of `dtype` through page-locked memory, enqueued on the current stream (no synchronisation)."""
+    return _pinned(np.asarray(array, dtype={torch.float32: np.float32, torch.int64: np.int64}[dtype])).to(dev, non_blocking=True)
+
+
+def _as_host_wav(y):
+    if torch.is_tensor(y):
+        y = y.detach().cpu().numpy()
+    return np.ascontiguousarray(np.asarray(y, dtype=np.float32).reshape(-1))
+
+
+def _resample_groups(sigs, ups_downs, dev):
+    """Upload and rate-convert: sigs = float32 host arrays, ups_downs = (up, down) per signal, (1, 1) = as it is.  One upload of all
+    samples, one of all offsets, one resample launch per distinct ratio.  Returns (buf, off, order, lens): the converted waveforms lie
+    back to back in buf from off[0] on, in the order `order` (indices into sigs), off = device int64 [len + 1] absolute offsets into
+    buf, lens = their lengths (host, in that order)."""
+    groups = {}
+    for i, ud in enumerate(ups_downs):
+        groups.setdefault(ud, []).append(i)
+    plain = groups.pop((1, 1), [])
+    order = plain + [i for ud in groups for i in groups[ud]]
+    raw_order = [i for ud in groups for i in groups[ud]] + plain            # the upload: raw groups first, then the signals that stay
+    host = np.concatenate([sigs[i] for i in raw_order]) if raw_order else np.zeros(0, np.float32)
+    raw_start = dict(zip(raw_order, np.concatenate([[0], np.cumsum([sigs[i].shape[0] for i in raw_order])]).tolist()))
+    n_raw = int(host.shape[0])
+    lens = [sigs[i].shape[0] if ups_downs[i] == (1, 1) else resample_out_len(sigs[i].shape[0], *ups_downs[i]) for i in order]
+    base = raw_start[plain[0]] if plain else n_raw                           # the converted set begins where the unchanged signals lie
+    off_host = base + np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    meta, launches, pos = [off_host], [], len(plain)
+    cursor = off_host.shape[0]
+    for ud, members in groups.items():
+        in_off = np.asarray([raw_start[i] for i in members] + [raw_start[members[-1]] + sigs[members[-1]].shape[0]], np.int64)
+        out_off = off_host[pos:pos + len(members) + 1]
+        launches.append((ud, len(members), cursor, cursor + len(members) + 1, int(max(lens[pos:pos + len(members)]))))
+        meta += [in_off, out_off]
+        cursor += 2 * (len(members) + 1)
+        pos += len(members)
+    buf = torch.empty(max(int(off_host[-1]), 1), dtype=torch.float32, device=dev)
+    if n_raw:
+        buf[:n_raw].copy_(_pinned(host), non_blocking=True)
+    meta_dev = _upload(np.concatenate(meta), torch.int64, dev)
+    for (up, down), n, a, b, longest in launches:
+        lib.call("mstts_wav_resample", lib.ptr(buf), lib.ptr(meta_dev, a), lib.ptr(meta_dev, b), n, longest, lib.ptr(_resample_table(up, down, str(dev))),
+                 up, down, lib.ptr(buf))
+    return buf, meta_dev[:len(order) + 1], order, lens
+
+
+def resample_poly_batch(wavs, up, down, device="cuda", return_tensor=False):
+    """scipy.signal.resample_poly(x, up, down) for a list of waveforms in one launch (mstts_wav_resample), float32 ->
+    list of ceil(len up / down)-sample waveforms.  Ratios outside the device envelope (`resample_supported`) take the host path."""
+    g = int(np.gcd(int(up), int(down))) if up >= 1 and down >= 1 else 1
+    up, down = int(up) // g, int(down) // g
+    sigs = [_as_host_wav(y) for y in wavs]
+    if not sigs:
+        return []
+    dev = torch.device(device)
+    if not resample_supported(up, down):
+        from scipy.signal import resample_poly
+        out = [resample_poly(s, up, down).astype(np.float32) for s in sigs]
+        return [torch.as_tensor(o).to(dev) for o in out] if return_tensor else out
+    buf, off, order, lens = _resample_groups(sigs, [(up, down)] * len(sigs), dev)
+    bounds = np.concatenate([[0], np.cumsum(lens)]) + (0 if (up, down) == (1, 1) else sum(s.shape[0] for s in sigs))
+    res = buf if return_tensor else buf.cpu().numpy()
+    out = [None] * len(sigs)
+    for k, i in enumerate(order):
+        piece = res[int(bounds[k]):int(bounds[k + 1])]
+        out[i] = piece if return_tensor else piece.copy()
+    return out
+
+
+def _trim(buf, off, lens, top_db, frame, hop):
+    """mstts_wav_trim on waveforms of the (host-known) lengths `lens` at the device offsets `off` into buf -> device (bounds [nw, 2], peak [nw])."""
+    nw, total = len(lens), int(sum(lens))
+    bounds = torch.empty(nw, 2, dtype=torch.int64, device=buf.device)
+    peak = torch.empty(nw, dtype=torch.float32, device=buf.device)
+    ws = torch.empty(max(int(lib.load().mstts_wav_trim_ws_floats(total, nw)), 1), dtype=torch.float32, device=buf.device)
+    lib.call("mstts_wav_trim", lib.ptr(buf), lib.ptr(off), nw, total, int(max(lens)), int(frame), int(hop), float(top_db), lib.ptr(ws),
+             lib.ptr(bounds), lib.ptr(peak))
+    return bounds, peak
+
+
+def trim_bounds_batch(wavs, top_db=15.0, frame=32, hop=16, device="cuda"):
+    """The silence trim of Feeder.load_wav for a list of waveforms in one launch (mstts_wav_trim) -> (start, end, peak): int64 arrays
+    of the kept range [start, end) of each waveform and float32 max |x| inside it."""
+    sigs = [_as_host_wav(y) for y in wavs]
+    dev = torch.device(device)
+    nw = len(sigs)
+    cat = _upload(np.concatenate(sigs), torch.float32, dev) if sum(s.shape[0] for s in sigs) else torch.zeros(1, dtype=torch.float32, device=dev)
+    off = _upload(np.concatenate([[0], np.cumsum([s.shape[0] for s in sigs])]).astype(np.int64), torch.int64, dev)
+    bounds, peak = _trim(cat, off, [s.shape[0] for s in sigs], top_db, frame, hop)
+    b = bounds.cpu().numpy()
+    return b[:, 0].copy(), b[:, 1].copy(), peak.cpu().numpy()
+
+
+def _front_end_packed(signals, rates, sample_rate, top_db, frame, hop, scale, peak_normalize, stft_hop, dev):
+    """Everything of the front end up to (not including) the one host read: returns (packed, offs, order) - packed = the trimmed,
+    scaled waveforms back to back, offs = device int64 [2, nw + 1] (sample offsets; frame offsets for an STFT of hop `stft_hop`),
+    order = which input each packed waveform is."""
+    sigs = [_as_host_wav(y) for y in signals]
+    ratios = []
+    for i, r in enumerate(rates):
+        ud = resample_ratio(r, sample_rate) if int(r) != int(sample_rate) else (1, 1)
+        if ud != (1, 1) and not resample_supported(*ud):              # outside the device envelope: the host's converter
+            from scipy.signal import resample_poly
+            sigs[i], ud = resample_poly(sigs[i], *ud).astype(np.float32), (1, 1)
+        ratios.append(ud)
+    nw = len(sigs)
+    buf, off, order, lens = _resample_groups(sigs, ratios, dev)
+    bounds, peak = _trim(buf, off, lens, top_db, frame, hop)
+    packed = torch.empty(max(sum(lens), 1), dtype=torch.float32, device=dev)
+    offs = torch.empty(2, nw + 1, dtype=torch.int64, device=dev)
+    lib.call("mstts_wav_gather_scale", lib.ptr(buf), lib.ptr(off), lib.ptr(bounds), lib.ptr(peak), nw, int(max(lens)), float(scale),
+             int(bool(peak_normalize)), int(stft_hop), lib.ptr(packed), lib.ptr(offs), lib.ptr(offs, nw + 1))
+    return packed, offs, order
+
+
+def wav_front_end(signals, rates, sample_rate, top_db=15.0, frame=32, hop=16, scale=0.99, peak_normalize=False, device="cuda",
+                  return_tensor=False):
+    """The trimmed, scaled waveforms Feeder.load_wav returns for the same decoded samples, for a batch: signals = float mono arrays,
+    rates = their sample rates.  Signals of one source rate are converted in one launch, signals already at sample_rate skip it; one
+    trim, one gather.  peak_normalize: scale / max |x| of the kept range instead of scale.  -> list of float32 waveforms."""
+    if len(signals) != len(rates):
+        raise ValueError("one sample rate per signal")
+    if not len(signals):
+        return []
+    dev = torch.device(device)
+    packed, offs, order = _front_end_packed(signals, rates, sample_rate, top_db, frame, hop, scale, peak_normalize, 1, dev)
+    o = offs[0].cpu().numpy()                                    # (the one host read: the lengths)
+    res = packed if return_tensor else packed[:int(o[-1])].cpu().numpy()
+    out = [None] * len(order)
+    for k, i in enumerate(order):
+        piece = res[int(o[k]):int(o[k + 1])]
+        out[i] = piece if return_tensor else piece.copy()
+    return out
+
+
+def wav_features(signals, rates, num_freq, frame_shift_ms, frame_length_ms, sample_rate, num_mels=None, max_abs_value=4, ref_level_db=20,
+                 want_mel=True, want_spec=False, spectral_subtract=False, top_db=15.0, frame=32, hop=16, scale=0.99, peak_normalize=False,
+                 length_range=None, device="cuda", return_tensor=False, return_lengths=False):
+    """`wav_front_end` followed by the one-launch STFT (mstts_stft_fft) on the packed buffer, without a copy back: list of
+    (mel [frames, num_mels] or None, spec [frames, num_freq] or None), the options of `stft_features`.  One host read (the trimmed
+    lengths) lies between the upload and the feature launch.  A waveform whose trimmed length is not longer than n_fft / 2 raises the ValueError
+    `stft_features` raises.  length_range = (lo, hi) in samples: a waveform whose trimmed length lies outside it gets (None, None) and
+    no transform.  return_lengths: also the list of trimmed lengths in samples."""
+    if len(signals) != len(rates):
+        raise ValueError("one sample rate per signal")
+    if not len(signals):
+        return ([], []) if return_lengths else []
+    consts = _fft_constants(num_freq, frame_shift_ms, frame_length_ms, num_mels or 1, sample_rate, str(device))
+    n_fft, stft_hop = consts[0], consts[1]
+    dev = consts[3].device
+    packed, offs, order = _front_end_packed(signals, rates, sample_rate, top_db, frame, hop, scale, peak_normalize, stft_hop, dev)
+    o = offs.cpu().numpy()                                       # (the one host read: sample and frame offsets)
+    nw = len(order)
+    lens, frames = [int(v) for v in np.diff(o[0])], [int(v) for v in np.diff(o[1])]
+    keep = [length_range is None or length_range[0] <= n <= length_range[1] for n in lens]
+    for k, i in enumerate(order):
+        if keep[k] and lens[k] <= n_fft // 2:
+            raise ValueError("waveform %d: %d samples after the trim, shorter than the STFT's reflect padding (%d samples)" % (i, lens[k], n_fft // 2))
+    feats = [(None, None)] * nw
+    args = (consts, num_mels, max_abs_value, ref_level_db, want_mel, want_spec, spectral_subtract)
+    if all(keep):
+        feats = _stft_packed(packed, offs[0], offs[1], frames, *args)
+    else:                                                        # a launch per run of kept waveforms: the sample offsets are absolute, the frame offsets restart
+        a = 0
+        while a < nw:
+            b = a
+            while b < nw and keep[b] == keep[a]:
+                b += 1
+            if keep[a]:
+                foff = _upload(np.concatenate([[0], np.cumsum(frames[a:b])]).astype(np.int64), torch.int64, dev)
+                feats[a:b] = _stft_packed(packed, offs[0, a:b + 1], foff, frames[a:b], *args)
+            a = b
+    out, out_len = [None] * nw, [0] * nw
+    for k, i in enumerate(order):
+        m, s = feats[k]
+        out[i] = (m, s) if return_tensor else (m.cpu().numpy() if m is not None else None, s.cpu().numpy() if s is not None else None)
+        out_len[i] = lens[k]
+    return (out, out_len) if return_lengths else out

@@ -2,7 +2,9 @@
 TensorFlow: the same tensor names / dtypes / padding, tokenisation and speaker-window extraction,
 plus synthetic train patterns of the benchmark shape.  Mel extraction of speaker wavs runs on the
 GPU through ``Audio.melspectrogram``; wav file reading/resampling/trimming is scipy plumbing (the
-reference uses librosa.core.load + librosa.effects.trim, which are not available here).
+reference uses librosa.core.load + librosa.effects.trim, which are not available here); `load_wav_batch` and
+``Get_Inference_Pattern(front_end="device")`` run resampling, trim and scale on the GPU for all wavs at once
+(``Audio.wav_front_end``), with `load_wav` as their checker.
 """
 from __future__ import annotations
 
@@ -172,6 +174,48 @@ def load_wav(path, sample_rate=None, top_db=15.0, frame=32, hop=16):
         if keep.size:
             data = data[keep[0] * hop: min(data.shape[0], (keep[-1] + 1) * hop)]
     return data * 0.99
+
+
+def decode_wav(path):
+    """(sample_rate, float32 mono samples) of an audio file: the decoding and the int / uint / multi-channel conversion of `load_wav`."""
+    rate, data = read_audio(path)
+    if data.dtype.kind == "i":
+        data = data.astype(np.float32) / float(np.iinfo(data.dtype).max)
+    elif data.dtype.kind == "u":
+        data = (data.astype(np.float32) - 128.0) / 128.0
+    data = data.astype(np.float32)
+    if data.ndim > 1:
+        data = data.mean(axis=1)
+    return int(rate), data
+
+
+def load_wav_batch(paths, sample_rate=None, top_db=15.0, frame=32, hop=16, device="cuda"):
+    """`load_wav` for a list of files: decoding on the host exactly as there, rate conversion, trim and the 0.99 scale on the GPU for
+    the whole list (Audio.wav_front_end: one resample launch per source rate, one trim, one gather) -> list of float32 waveforms."""
+    from . import Audio
+    decoded = [decode_wav(p) for p in paths]
+    return Audio.wav_front_end([d for _, d in decoded], [r for r, _ in decoded], sample_rate or hp.Sound.Sample_Rate, top_db=top_db, frame=frame,
+                               hop=hop, scale=0.99, device=device)
+
+
+def wav_front_end_mode(front_end=None):
+    """"device" or "host": the argument, else the environment variable MSTTS_WAV_FRONT_END, else "host" (Get_Inference_Pattern's windows
+    are pinned bit for bit to load_wav + Audio.melspectrogram; a device resampler cannot promise scipy's last bit)."""
+    mode = front_end if front_end is not None else os.environ.get("MSTTS_WAV_FRONT_END", "host")
+    if mode not in ("device", "host"):
+        raise ValueError("front_end must be 'device' or 'host', not {!r}".format(mode))
+    return mode
+
+
+def mels_to_host(mels):
+    """Device mels [T_i, dim] -> list of float32 host arrays through ONE copy back."""
+    import torch
+    host = torch.cat(mels).cpu().numpy()
+    out, t0 = [], 0
+    for m in mels:
+        out.append(host[t0:t0 + m.shape[0]].astype(np.float32))
+        t0 += m.shape[0]
+    return out
 
 
 def metadata_path():
@@ -411,10 +455,18 @@ class Feeder:
     def Speaker_Embedding_Mel(self, mel_List):
         return speaker_windows(mel_List)
 
-    def Get_Inference_Pattern(self, speaker_Wav_Path_List, text_List, speaker_Mel_List=None):
-        """Feeder.py:186-233.  `speaker_Mel_List` ([T,80] arrays) may be given instead of wav paths."""
+    def Get_Inference_Pattern(self, speaker_Wav_Path_List, text_List, speaker_Mel_List=None, front_end=None):
+        """Feeder.py:186-233.  `speaker_Mel_List` ([T,80] arrays) may be given instead of wav paths.  front_end "device": every speaker
+        wav through the batched GPU front end (Audio.wav_features: one upload, one resample launch per source rate, one trim, one
+        gather, one mel launch, one copy back); "host": load_wav and one mel launch per wav; None: `wav_front_end_mode`."""
         from . import Audio
         token, length = tokenize(text_List, self.metadata_Dict["Token_Index_Dict"])
+        if speaker_Mel_List is None and wav_front_end_mode(front_end) == "device":
+            decoded = [decode_wav(path) for path in speaker_Wav_Path_List]
+            feats = Audio.wav_features([d for _, d in decoded], [r for r, _ in decoded], num_freq=hp.Sound.Spectrogram_Dim,
+                                       frame_shift_ms=hp.Sound.Frame_Shift, frame_length_ms=hp.Sound.Frame_Length, sample_rate=hp.Sound.Sample_Rate,
+                                       num_mels=hp.Sound.Mel_Dim, max_abs_value=hp.Sound.Max_Abs_Mel, device=self.device, return_tensor=True)
+            speaker_Mel_List = mels_to_host([m for m, _ in feats])
         if speaker_Mel_List is None:
             speaker_Mel_List = [
                 np.transpose(Audio.melspectrogram(

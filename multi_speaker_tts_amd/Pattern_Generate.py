@@ -3,7 +3,8 @@ utterance holding {'Token': int32[T_tok], 'Mel': float32[T_mel, 80], 'Text': str
 '<DATASET>.<prefix><wav basename>.PICKLE', plus METADATA.PICKLE with the hyper parameters the set was made with and the
 per-file lengths, the corpus walkers of Pattern_Generate.py:115-243 (LJSpeech, VCTK, LibriSpeech, TEDLIUM, TIMIT directory
 layouts -> (audio path, filtered text) pairs) and the reference's command line (`-lj -vctk -ls -tl -timit -all`, :277-285).
-Mel extraction runs on the GPU (mstts_stft_mel); file decoding is scipy / the SPHERE reader in Feeder.read_sphere.
+Mel extraction runs on the GPU (mstts_stft_fft); file decoding is scipy / the SPHERE reader in Feeder.read_sphere.  `-batch N` hands N
+files at a time to Mel_Generate_Batch, which also converts the rate, trims and scales on the GPU (Audio.wav_features).
 """
 from __future__ import annotations
 
@@ -48,6 +49,26 @@ def Mel_Generate(path, spectral_Subtract=False, range_Ignore=False, device="cuda
                                              device=device)).astype(np.float32)
 
 
+def Mel_Generate_Batch(paths, spectral_Subtract=False, range_Ignore=False, device="cuda"):
+    """`Mel_Generate` for a list of files through the batched GPU front end (Audio.wav_features with the 2048 / 512 trim): one mel
+    [frames, Mel_Dim] or None per path, the hp.Train.Use_Wav_Length_Range filter applied to the trimmed length as there."""
+    from . import Audio
+    decoded = [_Feeder.decode_wav(p) for p in paths]
+    if not decoded:
+        return []
+    sigs, rates = [d for _, d in decoded], [r for r, _ in decoded]
+    stft = dict(num_freq=hp.Sound.Spectrogram_Dim, frame_shift_ms=hp.Sound.Frame_Shift, frame_length_ms=hp.Sound.Frame_Length,
+                sample_rate=hp.Sound.Sample_Rate, num_mels=hp.Sound.Mel_Dim, max_abs_value=hp.Sound.Max_Abs_Mel, device=device)
+    rng = None if range_Ignore else tuple(v / 1000 * hp.Sound.Sample_Rate for v in hp.Train.Use_Wav_Length_Range)       # ms -> samples
+    feats = Audio.wav_features(sigs, rates, spectral_subtract=spectral_Subtract, frame=2048, hop=512, length_range=rng, return_tensor=True, **stft)
+    keep = [i for i, (m, _) in enumerate(feats) if m is not None]
+    out = [None] * len(paths)
+    if keep:
+        for i, mel in zip(keep, _Feeder.mels_to_host([feats[i][0] for i in keep])):
+            out[i] = mel
+    return out
+
+
 def Pattern_File_Write(file_Name, text, mel, token_Index_Dict, dataset, pattern_path=None):
     """Pattern_Generate.py:66-76."""
     token = np.array([token_Index_Dict[letter] for letter in text]).astype(np.int32)
@@ -57,11 +78,18 @@ def Pattern_File_Write(file_Name, text, mel, token_Index_Dict, dataset, pattern_
         pickle.dump({"Token": token, "Mel": np.asarray(mel, np.float32), "Text": text, "Dataset": dataset}, f, protocol=2)
 
 
+_FROM_FILE = object()
+
+
 def Pattern_File_Generate(path, text, token_Index_Dict, dataset, spectral_Subtract=False, file_Prefix="", display_Prefix="", range_Ignore=False,
-                          device="cuda"):
-    """Pattern_Generate.py:60-82 for one (wav, text) pair; returns the pickle name or None when the utterance is skipped."""
+                          device="cuda", mel=_FROM_FILE):
+    """Pattern_Generate.py:60-82 for one (wav, text) pair; returns the pickle name or None when the utterance is skipped.  `mel`: the
+    result of Mel_Generate_Batch for this file (None = rejected) instead of a Mel_Generate call."""
     text = Text_Filtering(text)
-    mel = Mel_Generate(path, spectral_Subtract, range_Ignore, device=device) if text is not None else None
+    if mel is _FROM_FILE:
+        mel = Mel_Generate(path, spectral_Subtract, range_Ignore, device=device) if text is not None else None
+    elif text is None:
+        mel = None
     if mel is None:
         return None
     name = "{}.{}{}.PICKLE".format(dataset, file_Prefix, os.path.splitext(os.path.basename(path))[0]).upper()
@@ -256,6 +284,7 @@ def main(argv=None, device="cuda"):
     ap.add_argument("-tl", "--tl_path", required=False)
     ap.add_argument("-timit", "--timit_path", required=False)
     ap.add_argument("-all", "--all_save", action="store_true")
+    ap.add_argument("-batch", "--batch_size", type=int, default=0)       # N > 0: N files at a time through Mel_Generate_Batch (0: file by file)
     args = ap.parse_args(argv)
     token_Index_Dict = _Feeder.load_token_dict()
     jobs = []                                            # (dataset, path, text or segment list)
@@ -273,12 +302,24 @@ def main(argv=None, device="cuda"):
         raise ValueError("Total pattern count is zero.")
     os.makedirs(hp.Train.Pattern_Path, exist_ok=True)
     written = 0
+    batched = {}                                         # job index -> mel or None, filled batch_size files ahead (TEDLIUM's segment walk stays file by file)
     for i, (dataset, path, what) in enumerate(jobs):
+        if args.batch_size > 0 and dataset != "TL" and i not in batched:
+            ahead = []                                   # the next batch_size files of this corpus (its jobs are consecutive)
+            for k in range(i, len(jobs)):
+                if jobs[k][0] != dataset or len(ahead) == args.batch_size:
+                    break
+                ahead.append(k)
+            mels = Mel_Generate_Batch([jobs[k][1] for k in ahead], spectral[dataset], args.all_save, device=device)
+            batched.update(zip(ahead, mels))
         if dataset == "TL":
             names = Pattern_File_Generate_from_SPH(path, what, token_Index_Dict, dataset, spectral[dataset], range_Ignore=args.all_save, device=device)
         else:
             prefix = "{}.".format(path.split("/")[-2]) if dataset == "TIMIT" else ""
-            name = Pattern_File_Generate(path, what, token_Index_Dict, dataset, spectral[dataset], prefix, range_Ignore=args.all_save, device=device)
+            if args.batch_size > 0:
+                name = Pattern_File_Generate(path, what, token_Index_Dict, dataset, file_Prefix=prefix, mel=batched.pop(i, None))
+            else:
+                name = Pattern_File_Generate(path, what, token_Index_Dict, dataset, spectral[dataset], prefix, range_Ignore=args.all_save, device=device)
             names = [name] if name else []
         written += len(names)
         print("[{} {:05d}/{:05d}]".format(dataset, i, len(jobs)), path, "->", ", ".join(names) if names else "Ignored because of length.")
