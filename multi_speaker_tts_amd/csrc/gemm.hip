@@ -10,27 +10,17 @@
 // while the current one is multiplied.  Replaces tf.layers.conv1d / tf.layers.dense /
 // tf.matmul call sites of the reference (Modules.py:29-36,125-132,243-247,311-314;
 // ZoneoutLSTMCell.py:228) and their autodiff gradients.
-#include "common.h"
+#include "gemm_tile.h"
 #include <type_traits>
 #include <cmath>
 #include <cstdlib>
 
 namespace mstts {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int BK = 32;
 constexpr int BN = 128;
 
-struct GemmArgs {
-    const float* A; const float* B; float* C; const float* bias;
-    int M, N, K;
-    long lda, ldb, ldc;
-    int win_T, win_C, win_pad, win_dil;
-    int act, accumulate, split_k;
-    long stride_a, stride_b, stride_c;
-    float alpha;
-    int k_per_split;
+struct GemmArgs : GemmTileArgs {
     // body + tail (see mstts_gemm_f32): blocks [0, body) own one whole output tile each; the last tiles of the list are cut along K
     // into tail_s pieces of tail_kps each, blocks body + (tile - body) * tail_s + piece, accumulated with atomics.  body = all tiles
     // when the split is off.
@@ -38,39 +28,14 @@ struct GemmArgs {
     int band;                     // gemm_split_kernel: tile list in column bands of this many tiles (0: row-major)
 };
 
-__device__ __forceinline__ float apply_act(float v, int act) {
-    if (act == MSTTS_ACT_RELU) return fmaxf(v, 0.f);
-    if (act == MSTTS_ACT_TANH) return tanhf_(v);
-    if (act == MSTTS_ACT_SIGMOID) return sigmoidf_(v);
-    return v;
-}
-
-// ---- tile loaders -------------------------------------------------------------------------
-// "KC": operand contiguous along k in memory (A row-major, or B given as [N,K]).
-//   rows = the M (or N) index, R rows per tile.  reg[] holds R*BK/256/4 float4 per thread.
-// "MC": operand contiguous along its M/N index (B row-major [K,N], or A given as [K,M]).
-// Out-of-range elements are read from this zero block instead of being skipped: the loads stay unconditional (no exec-mask
-// branches in the K loop, the scheduler can hide them behind the MFMAs) and the padding is zero without a select on the data.
-__device__ __attribute__((aligned(16))) const float gemm_zero16[4] = {0.f, 0.f, 0.f, 0.f};
-// ... and they go through an explicit GLOBAL-address-space pointer: the select between the operand and the zero block otherwise degrades to
-// a flat pointer, flat loads count in lgkmcnt as well as vmcnt, and every s_waitcnt lgkmcnt(0) in front of an MFMA group (placed for the
-// LDS fragment reads) would then also wait for the K-tile prefetch issued just before - the whole global latency exposed once per K-tile.
-typedef float gemm_f32x4 __attribute__((ext_vector_type(4)));
-typedef const gemm_f32x4 __attribute__((address_space(1)))* gemm_gptr4;
-__device__ __forceinline__ float4 gemm_ld4(const float* p) {
-    const gemm_f32x4 v = *(gemm_gptr4)p;
-    return make_float4(v[0], v[1], v[2], v[3]);
-}
-
-// Addressing: every load is  uniform base (SGPRs, advanced once per K-tile)  +  a 32-bit per-thread offset fixed at prepare()  -
-// no 64-bit address arithmetic and no bounds arithmetic beyond one compare in the K loop (it cost 9 % of the matrix-core time).
+// ---- tile loaders of gemm_kernel ------------------------------------------------------------
+// KC / MC, the zero block and the global-address-space load as in gemm_tile.h; reg[] holds R*BK/256/4 float4 per thread.  These two stage
+// fp32 k-major and take the window as run-time values: folding them into TileLoaderKC / TileLoaderMC would change gemm_kernel's code.
 template <int R, bool VEC>
 struct LoaderKC {
     static constexpr int NV = R * BK / 4 / 256;      // float4 per thread
     float4 reg[NV];
-    // window: element (row, k) is tap j = k / C of a dilated 'same' conv: source row = row + (j - pad) * dil, valid iff it
-    // stays inside the row's length-T sequence.  A thread's rows never change (t_row = row % T once) and k advances by BK per
-    // load (tap / kc kept incrementally): prepare() once, then load() for k0, k0 + BK, ...
+    // window bookkeeping and addressing as TileLoaderKC (gemm_tile.h): prepare() once, then load() for k0, k0 + BK, ...
     const float* ubase;                               // non-window: base + row0 ld + k0 ; window: base + (row0 - pad dil) ld (for the
                                                       // first tile that is in front of the operand: only ever added to offsets of valid taps)
     unsigned voff[NV], rmask;                         // (r + 32 i) ld (+ 4 k4 without window); bit i: row inside the operand
@@ -142,9 +107,7 @@ struct LoaderMC {
     static constexpr int KR = 256 / C4;               // k-rows per pass
     static constexpr int NV = BKT / KR;
     float4 reg[NV];
-    // window (A only): element (m, kk) with kk=(b,t) row index, m=(tap, c):
-    //   valid iff 0 <= (kk % T) + m / C - pad < T; address = base[(kk + (tap - pad) dil) * ld + c]
-    // a thread's column (tap, c) is fixed, its k-rows advance by BK per load.
+    // window (A only) as TileLoaderMC (gemm_tile.h): a thread's column (tap, c) is fixed, its k-rows advance by BK per load.
     const float* ubase;                               // base + k0 ld + col0 (window: base + (k0 - pad dil) ld), advanced by BK ld per load
     unsigned voff[NV];
     int sh, t_k[NV], cols_left;                       // cols_left: columns of the operand from this thread's first one (<= 0: none)
@@ -204,34 +167,6 @@ struct LoaderMC {
     }
 };
 
-// epilogue of one wave's WM x WN grid of 32 x 32 MFMA tiles: C/D layout col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
-template <int WM, int WN>
-__device__ __forceinline__ void gemm_store_tile(const GemmArgs& g, const f32x16 (&acc)[WM][WN], float* __restrict__ C, int row0, int col0,
-                                                int lane, bool with_bias, bool atomic) {
-#pragma unroll
-    for (int i = 0; i < WM; ++i)
-#pragma unroll
-        for (int j = 0; j < WN; ++j) {
-            const int col = col0 + j * 32 + (lane & 31);
-            if (col >= g.N) continue;
-            const float bv = (g.bias != nullptr && with_bias) ? g.bias[col] : 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = row0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (row >= g.M) continue;
-                float v = g.alpha * acc[i][j][r] + bv;
-                float* dst = C + (long)row * g.ldc + col;
-                if (atomic) {
-                    atomicAdd(dst, v);
-                } else {
-                    v = apply_act(v, g.act);
-                    if (g.accumulate) v += *dst;
-                    *dst = v;
-                }
-            }
-        }
-}
-
 template <int BM, bool TA, bool TB, bool VEC>
 __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
     // LDS tiles, k-major.  Row stride: +4 floats where the tile is filled with float4 stores (keeps
@@ -244,12 +179,9 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
     float* Bs = smem + A_FLOATS;
 
     const int tiles_n = (g.N + BN - 1) / BN;
-    // XCD-aware tile order: block b runs on XCD b % 8 and every XCD has its own L2, so give each XCD a contiguous range
-    // of the (tile_m-major) tile list - a band of A rows it re-reads from its own L2 - instead of every eighth tile.
     int tile = blockIdx.x, piece = -1;
     if (tile < g.body) {
-        const int nb = g.body, q = nb >> 3, r = nb & 7, xcd = tile & 7, idx = tile >> 3;
-        if (nb >= 64) tile = xcd * q + (xcd < r ? xcd : r) + idx;
+        tile = gemm_xcd_tile(tile, g.body);
     } else {
         const int u = tile - g.body;
         tile = g.body + u / g.tail_s;
@@ -345,11 +277,13 @@ __global__ void gemm_tail_act_kernel(float* __restrict__ C, long ldc, int N, lon
     *p = apply_act(*p, act);
 }
 
-template <int BM, bool TA, bool TB>
-static void launch_gemm(const GemmArgs& g, bool vec, dim3 grid, hipStream_t st) {
-    if (vec) hipLaunchKernelGGL((gemm_kernel<BM, TA, TB, true>), grid, dim3(256), 0, st, g);
-    else     hipLaunchKernelGGL((gemm_kernel<BM, TA, TB, false>), grid, dim3(256), 0, st, g);
-}
+template <int BM>
+struct GemmF32 {                  // gemm_kernel<BM>: no WIN flag (run-time window), static LDS
+    using Args = GemmArgs;
+    static constexpr int THREADS = 256;
+    static constexpr size_t LDS_BYTES = 0;
+    template <bool TA, bool TB, bool VEC, bool WIN> static constexpr auto kernel() { return &gemm_kernel<BM, TA, TB, VEC>; }
+};
 
 #include "gemm_split.inc"
 
@@ -384,46 +318,18 @@ extern "C" int mstts_gemm_deterministic(int32_t on) { t_deterministic = on != 0;
 namespace mstts { int gemm_deterministic_now() { return t_deterministic; } }     // (csrc/gemm_bf16.hip asks before it cuts a contraction along K on its own)
 
 extern "C" int mstts_gemm_f32(const mstts_gemm_desc* d, mstts_stream_t stream) {
-    MSTTS_REQUIRE(d != nullptr, MSTTS_ERR_SHAPE, "gemm: null descriptor");
-    MSTTS_REQUIRE(d->M >= 0 && d->N >= 0 && d->K >= 0, MSTTS_ERR_SHAPE, "gemm: negative dims");
-    if (d->M == 0 || d->N == 0) return MSTTS_OK;
-    MSTTS_REQUIRE(d->A && d->B && d->C, MSTTS_ERR_SHAPE, "gemm: null operand");
-    MSTTS_REQUIRE(d->M < (1LL << 31) && d->N < (1LL << 31) && d->K < (1LL << 31), MSTTS_ERR_SHAPE, "gemm: dims exceed int32");
-    MSTTS_REQUIRE(d->lda >= 0 && d->ldb >= 0 && d->lda < (1 << 24) && d->ldb < (1 << 24), MSTTS_ERR_SHAPE,
-                  "gemm: row strides must be below 2^24 elements (tile-relative offsets are 32-bit)");
-    const int batch = d->batch > 0 ? (int)d->batch : 1;
-    int split = d->split_k > 1 ? d->split_k : 1;
-    MSTTS_REQUIRE(split == 1 || (d->act == MSTTS_ACT_NONE), MSTTS_ERR_SHAPE,
-                  "gemm: split_k needs act=none (output must be pre-zeroed or accumulated into)");
-    if (d->win_T > 0) {
-        MSTTS_REQUIRE(d->win_C > 0 && d->lda == d->win_C, MSTTS_ERR_SHAPE, "gemm: window mode needs lda == win_C");
-        MSTTS_REQUIRE(d->win_C % 4 == 0, MSTTS_ERR_SHAPE, "gemm: window mode needs win_C %% 4 == 0");
-    }
     GemmArgs g;
-    g.A = d->A; g.B = d->B; g.C = d->C; g.bias = d->bias;
-    g.M = (int)d->M; g.N = (int)d->N; g.K = (int)d->K;
-    g.lda = d->lda; g.ldb = d->ldb; g.ldc = d->ldc;
-    g.win_T = d->win_T; g.win_C = d->win_C > 0 ? d->win_C : 1; g.win_pad = d->win_pad; g.win_dil = d->win_dil > 0 ? d->win_dil : 1;
-    g.act = d->act; g.accumulate = d->accumulate; g.split_k = split;
-    g.stride_a = d->stride_a; g.stride_b = d->stride_b; g.stride_c = d->stride_c;
-    g.alpha = d->alpha;
-    int kps = ((g.K + split - 1) / split + BK - 1) / BK * BK;
-    if (kps < BK) kps = BK;
-    g.k_per_split = kps;
-    // vector path: every float4 the loaders form must be 16-byte aligned and must not straddle
-    // a conv tap or the end of a row
-    bool vec = aligned16(d->A) && aligned16(d->B) && (d->lda % 4 == 0) && (d->ldb % 4 == 0) &&
-               (d->stride_a % 4 == 0) && (d->stride_b % 4 == 0);
-    vec = vec && (d->trans_a ? (d->M % 4 == 0) : (d->K % 4 == 0));
-    vec = vec && (d->trans_b ? (d->K % 4 == 0) : (d->N % 4 == 0));
-    if (d->win_T > 0) vec = vec && (d->win_C % 4 == 0);
+    bool vec;
+    const int rc = gemm_args_from(d, "gemm", BK, 1 << 24, &g, &vec);
+    if (rc != MSTTS_OK || g.M == 0 || g.N == 0) return rc;
+    const int batch = d->batch > 0 ? (int)d->batch : 1, split = g.split_k, kps = g.k_per_split;
     const bool skinny = d->M <= 32;
     // 128-row tiles unless 64-row tiles fill the 256 CUs' rounds visibly better (25 632 x 512: 804 tiles = 3.14 rounds -> 4, but
     // 1 608 half tiles = 6.28 -> 7; 4 096 x 512: 128 tiles use half the chip, 256 half tiles all of it); the half tile re-reads
     // the B operand twice as often, so it has to win by more than 5 %
     int bm = skinny ? 32 : 128, tail_s = 1, tail_rem = 0;
     // (K < 160: the pipeline's prologue and padding tile outweigh the matrix-core time saved; the split kernel has 128-row tiles only)
-    const bool split3 = g_split3 && !skinny && d->K >= 160 && (d->win_T <= 0 || (d->win_T >= BK && d->win_C >= BK)) && gemm_split_lds_ready();
+    const bool split3 = g_split3 && !skinny && d->K >= 160 && (d->win_T <= 0 || (d->win_T >= BK && d->win_C >= BK)) && gemm_ready<GemmSplit>();
     if (!skinny) {
         const double t128 = (double)cdiv(d->M, 128) * cdiv(d->N, BN) * batch * split, t64 = (double)cdiv(d->M, 64) * cdiv(d->N, BN) * batch * split;
         const double e128 = t128 / (ceil(t128 / 256.0) * 256.0), e64 = t64 / (ceil(t64 / 256.0) * 256.0);
@@ -454,20 +360,16 @@ extern "C" int mstts_gemm_f32(const mstts_gemm_desc* d, mstts_stream_t stream) {
         }
     }
     hipStream_t st = (hipStream_t)stream;
+    const bool ta = d->trans_a != 0, tb = d->trans_b != 0, win = g.win_T > 0;
     {   // the 256 x 256 x 16 form of the split where such tiles fill the chip (from 160 workgroups on; one per CU)
         const long big_wgs = (long)cdiv(d->M, GSB_BM) * cdiv(d->N, GSB_BN) * batch * split;
         if (split3 && g_split_big && d->M >= 192 && d->N >= 192 && big_wgs >= g_split_big_min && d->lda < (1 << 22) && d->ldb < (1 << 22) &&
-            (d->win_T <= 0 || (d->win_T >= GSB_BK && d->win_C >= GSB_BK)) && (d->act == MSTTS_ACT_NONE || split == 1) && gemm_split_big_ready()) {
-            int kpsb = ((g.K + split - 1) / split + GSB_BK - 1) / GSB_BK * GSB_BK;
-            if (kpsb < GSB_BK) kpsb = GSB_BK;
+            (d->win_T <= 0 || (d->win_T >= GSB_BK && d->win_C >= GSB_BK)) && (d->act == MSTTS_ACT_NONE || split == 1) && gemm_ready<GemmSplitBig>()) {
+            const int kpsb = gemm_k_per_split(g.K, split, GSB_BK);
             g.k_per_split = kpsb;
             g.body = 0; g.tail_s = 1; g.tail_kps = kpsb; g.band = 0;
             dim3 gridb(cdiv(d->M, GSB_BM) * cdiv(d->N, GSB_BN), 1, batch * split);
-            const bool ta_ = d->trans_a != 0, tb_ = d->trans_b != 0;
-            if (!ta_ && !tb_) launch_gemm_split_big<false, false>(g, vec, gridb, st);
-            else if (!ta_ && tb_) launch_gemm_split_big<false, true>(g, vec, gridb, st);
-            else if (ta_ && !tb_) launch_gemm_split_big<true, false>(g, vec, gridb, st);
-            else launch_gemm_split_big<true, true>(g, vec, gridb, st);
+            gemm_launch<GemmSplitBig>(g, ta, tb, vec, win, gridb, st);
             MSTTS_CHECK_LAUNCH("gemm_f32 (split, 256 x 256 tile)");
             return MSTTS_OK;
         }
@@ -487,28 +389,10 @@ extern "C" int mstts_gemm_f32(const mstts_gemm_desc* d, mstts_stream_t stream) {
         }
     }
     dim3 grid(g.body + (tiles - g.body) * g.tail_s, 1, batch * split);
-    const bool ta = d->trans_a != 0, tb = d->trans_b != 0;
-    if (split3) {
-        if (!ta && !tb) launch_gemm_split<false, false>(g, vec, grid, st);
-        else if (!ta && tb) launch_gemm_split<false, true>(g, vec, grid, st);
-        else if (ta && !tb) launch_gemm_split<true, false>(g, vec, grid, st);
-        else launch_gemm_split<true, true>(g, vec, grid, st);
-    } else if (skinny) {
-        if (!ta && !tb) launch_gemm<32, false, false>(g, vec, grid, st);
-        else if (!ta && tb) launch_gemm<32, false, true>(g, vec, grid, st);
-        else if (ta && !tb) launch_gemm<32, true, false>(g, vec, grid, st);
-        else launch_gemm<32, true, true>(g, vec, grid, st);
-    } else if (bm == 64) {
-        if (!ta && !tb) launch_gemm<64, false, false>(g, vec, grid, st);
-        else if (!ta && tb) launch_gemm<64, false, true>(g, vec, grid, st);
-        else if (ta && !tb) launch_gemm<64, true, false>(g, vec, grid, st);
-        else launch_gemm<64, true, true>(g, vec, grid, st);
-    } else {
-        if (!ta && !tb) launch_gemm<128, false, false>(g, vec, grid, st);
-        else if (!ta && tb) launch_gemm<128, false, true>(g, vec, grid, st);
-        else if (ta && !tb) launch_gemm<128, true, false>(g, vec, grid, st);
-        else launch_gemm<128, true, true>(g, vec, grid, st);
-    }
+    if (split3) gemm_launch<GemmSplit>(g, ta, tb, vec, win, grid, st);
+    else if (skinny) gemm_launch<GemmF32<32>>(g, ta, tb, vec, win, grid, st);
+    else if (bm == 64) gemm_launch<GemmF32<64>>(g, ta, tb, vec, win, grid, st);
+    else gemm_launch<GemmF32<128>>(g, ta, tb, vec, win, grid, st);
     MSTTS_CHECK_LAUNCH("gemm_f32");
     if (tail_s > 1 && d->act != MSTTS_ACT_NONE) {        // the tail's tile rows hold bias + the summed pieces: apply the activation there
         const long r0 = (long)(g.body / cdiv(d->N, BN)) * bm;

@@ -62,156 +62,28 @@ __device__ __forceinline__ Split3 gs_split4(float a, float b, float c, float d) 
     s.hi = __builtin_bit_cast(gs_bf16x4, h); s.mid = __builtin_bit_cast(gs_bf16x4, m); s.lo = __builtin_bit_cast(gs_bf16x4, l);
     return s;
 }
-__device__ __forceinline__ void gs_put(__bf16* __restrict__ p, const Split3& s) {
-    *reinterpret_cast<gs_bf16x4*>(p) = s.hi;
-    *reinterpret_cast<gs_bf16x4*>(p + GS_PLANE) = s.mid;
-    *reinterpret_cast<gs_bf16x4*>(p + 2 * GS_PLANE) = s.lo;
-}
-
-// operand contiguous along k in memory (A row-major, or B given as [N,K]): thread (k4 = tid & 7, r = tid >> 3) takes the float4 k-run k4
-// of rows r, r + 32, r + 64, r + 96.  Addressing as LoaderKC above (uniform base + 32-bit offsets, out-of-range lanes read a zero block).
-// WIN (conv window mode) is a template parameter and the window bookkeeping is branch-free (one conditional subtract per K-tile: needs
-// win_C >= BK and win_T >= BK, mstts_gemm_f32 sends anything smaller to gemm_kernel): the producers' loop must be ONE basic block - with
-// branches inside the loaders the register allocator put copies behind the loads of the loop-carried register sets, and a copy waits for its load.
-template <bool VEC, bool WIN>
-struct GsLoaderKC {
-    const float* ubase;
-    unsigned voff[4], rmask;
-    int t_row[4], tap, kc, ld_;
-    __device__ __forceinline__ void prepare(int tid, const float* __restrict__ base, long ld, int row0, int k0, int rows, int wT, int wC, int wpad, int wdil) {
-        const int k4 = tid & 7, r = tid >> 3;
-        rmask = 0; ld_ = (int)ld;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int row = row0 + r + i * 32;
-            if (row < rows) rmask |= 1u << i;
-            voff[i] = (unsigned)((r + i * 32) * (int)ld) + (WIN ? 0u : (unsigned)(k4 * 4));
-            if (WIN) t_row[i] = row % wT;
-        }
-        if (WIN) {
-            const int k = k0 + k4 * 4;
-            tap = k / wC; kc = k - tap * wC;
-            ubase = base + ((long)row0 - (long)wpad * wdil) * ld;
-        } else {
-            ubase = base + (long)row0 * ld + k0;
-        }
-    }
-    __device__ __forceinline__ void load(int tid, float4 (&reg)[4], int k0, int kmax, int wT, int wC, int wpad, int wdil) {
-        const int k4 = tid & 7;
-        const int k = k0 + k4 * 4;
-        const bool kok = k < kmax;
-        const int sh = WIN ? (tap - wpad) * wdil : 0;
-        const unsigned wadd = WIN ? (unsigned)(tap * wdil * ld_ + kc) : 0u;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            bool ok = kok && ((rmask >> i) & 1u);
-            if (WIN) {
-                const int t = t_row[i] + sh;
-                ok = ok && t >= 0 && t < wT;
-            }
-            if (VEC) {
-                v = gemm_ld4(ok ? ubase + (voff[i] + wadd) : gemm_zero16);
-            } else if (ok) {
-                const float* p = ubase + (voff[i] + wadd);
-                v.x = p[0];
-                if (k + 1 < kmax) v.y = p[1];
-                if (k + 2 < kmax) v.z = p[2];
-                if (k + 3 < kmax) v.w = p[3];
-            }
-            reg[i] = v;
-        }
-        if (WIN) {
-            kc += BK;
-            const bool wrap = kc >= wC;
-            kc -= wrap ? wC : 0; tap += wrap ? 1 : 0;
-        } else {
-            ubase += BK;
-        }
-    }
-    __device__ __forceinline__ void store(int tid, const float4 (&reg)[4], __bf16* __restrict__ s) const {
-        const int k4 = tid & 7, r = tid >> 3;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) gs_put(s + (r + i * 32) * GS_LD + k4 * 4, gs_split4(reg[i].x, reg[i].y, reg[i].z, reg[i].w));
+// staging policy of the split kernels (gemm_tile.h): four values -> the hi / mid / lo planes, PLANE bf16 elements apart
+template <int PLANE>
+struct SplitPlanes {
+    static __device__ __forceinline__ void put(__bf16* __restrict__ p, float a, float b, float c, float d) {
+        const Split3 s = gs_split4(a, b, c, d);
+        *reinterpret_cast<gs_bf16x4*>(p) = s.hi;
+        *reinterpret_cast<gs_bf16x4*>(p + PLANE) = s.mid;
+        *reinterpret_cast<gs_bf16x4*>(p + 2 * PLANE) = s.lo;
     }
 };
 
-// operand contiguous along its M/N index (B row-major [K,N], or A given as [K,M]): thread (kq = tid & 7, c4 = tid >> 3) takes the 4 x 4
-// block of k rows 4 kq .. 4 kq + 3 x columns 4 c4 .. 4 c4 + 3 as four float4 and writes it transposed (four 8-byte k-runs per plane).
-// kq in the LOW lane bits: a wave reads 8 float4 = 128 contiguous bytes from each of 32 k-rows, and its transposed 8-byte LDS writes walk
-// along k inside a row (16 words) over 8 rows - 4 lanes per bank pair instead of the 32 that c4-in-the-low-bits gives (rows 4 apart are
-// 80 words = 16 banks apart: every lane of a wave landed on two bank groups, a 16-way conflict on each of the 24 stores per K-tile).
-template <bool VEC, bool WIN>
-struct GsLoaderMC {
-    const float* ubase;
-    unsigned voff[4];
-    int sh, t_k[4], cols_left;
-    __device__ __forceinline__ void prepare(int tid, const float* __restrict__ base, long ld, int col0, int k0, int cols, int wT, int wC, int wpad, int wdil) {
-        const int kq = tid & 7, c4 = tid >> 3;
-        const int col = col0 + c4 * 4;
-        cols_left = cols - col;
-        if (WIN) {
-            const int tp = col / wC, cm = col - tp * wC;
-            sh = (tp - wpad) * wdil;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                t_k[i] = (k0 + kq * 4 + i) % wT;
-                voff[i] = (unsigned)((kq * 4 + i + tp * wdil) * (int)ld + cm);
-            }
-            ubase = base + ((long)k0 - (long)wpad * wdil) * ld;
-        } else {
-            sh = 0;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) voff[i] = (unsigned)((kq * 4 + i) * (int)ld + c4 * 4);
-            ubase = base + (long)k0 * ld + col0;
-        }
-    }
-    __device__ __forceinline__ void load(int tid, float4 (&reg)[4], int k0, int kmax, long ld, int wT) {
-        const int kq = tid & 7;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int k = k0 + kq * 4 + i;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            bool ok = k < kmax && cols_left > 0;
-            if (WIN) {
-                const int t = t_k[i] + sh;
-                ok = ok && t >= 0 && t < wT;
-                t_k[i] += BK;
-                t_k[i] -= (t_k[i] >= wT) ? wT : 0;
-            }
-            if (VEC) {
-                v = gemm_ld4(ok ? ubase + voff[i] : gemm_zero16);
-            } else if (ok) {
-                const float* p = ubase + voff[i];
-                v.x = p[0];
-                if (cols_left > 1) v.y = p[1];
-                if (cols_left > 2) v.z = p[2];
-                if (cols_left > 3) v.w = p[3];
-            }
-            reg[i] = v;
-        }
-        ubase += BK * ld;
-    }
-    __device__ __forceinline__ void store(int tid, const float4 (&reg)[4], __bf16* __restrict__ s) const {
-        const int kq = tid & 7, c4 = tid >> 3;
-        __bf16* p = s + (c4 * 4) * GS_LD + kq * 4;
-        gs_put(p, gs_split4(reg[0].x, reg[1].x, reg[2].x, reg[3].x));
-        gs_put(p + GS_LD, gs_split4(reg[0].y, reg[1].y, reg[2].y, reg[3].y));
-        gs_put(p + 2 * GS_LD, gs_split4(reg[0].z, reg[1].z, reg[2].z, reg[3].z));
-        gs_put(p + 3 * GS_LD, gs_split4(reg[0].w, reg[1].w, reg[2].w, reg[3].w));
-    }
-};
+// operand contiguous along k in memory: thread (k4 = tid & 7, r = tid >> 3) takes the float4 k-run k4 of rows r, r + 32, r + 64, r + 96
+template <bool VEC, bool WIN> using GsLoaderKC = TileLoaderKC<8, 4, 32, GS_LD, SplitPlanes<GS_PLANE>, VEC, WIN>;
+// operand contiguous along its M/N index: thread (kq = tid & 7, c4 = tid >> 3) takes the 4 x 4 block of k rows 4 kq .. x columns 4 c4 ..
+template <bool VEC, bool WIN> using GsLoaderMC = TileLoaderMC<8, GS_LD, SplitPlanes<GS_PLANE>, VEC, WIN>;
 
-// The workgroup barrier of this kernel: LDS traffic of the wave drained, then s_barrier.  NOT __syncthreads(): its fence also drains vmcnt, and
-// a producer always has the loads of the next two K-tiles in flight - every barrier would wait out a full global-memory latency (measured:
-// 2.3 us per K-tile instead of 0.7).
-__device__ __forceinline__ void gs_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 #ifdef GS_STAMP
 // dev only: wave 0 (a consumer) of block 0 accumulates the time it spends inside the barrier (arrival -> release) and in the whole loop
 // into g.bias (used as 3 x uint64)
-#define GS_BAR(slot) do { if (stamp) { const unsigned long long t0_ = __builtin_readcyclecounter(); gs_barrier(); acc_wait += __builtin_readcyclecounter() - t0_; } else gs_barrier(); } while (0)
+#define GS_BAR(slot) do { if (stamp) { const unsigned long long t0_ = __builtin_readcyclecounter(); gemm_barrier(); acc_wait += __builtin_readcyclecounter() - t0_; } else gemm_barrier(); } while (0)
 #else
-#define GS_BAR(slot) gs_barrier()
+#define GS_BAR(slot) gemm_barrier()
 #endif
 
 __device__ __forceinline__ int tiles_m_of(const GemmArgs& g) { return (g.M + GS_BM - 1) / GS_BM; }
@@ -229,14 +101,14 @@ __device__ __forceinline__ void gs_produce(LoadFn load, StoreFn store, __bf16* l
     load(r[1], kbeg + BK);
     store(r[0], lds0);
     load(r[0], kbeg + 2 * BK);
-    gs_barrier();
+    gemm_barrier();
     for (int t = 0; t < nt2; t += 2) {
         store(r[1], lds0 + GS_BUF);
         load(r[1], kbeg + (t + 3) * BK);
-        gs_barrier();
+        gemm_barrier();
         store(r[0], lds0);
         load(r[0], kbeg + (t + 4) * BK);
-        gs_barrier();
+        gemm_barrier();
     }
 }
 
@@ -247,8 +119,7 @@ __global__ __launch_bounds__(GS_THREADS) void gemm_split_kernel(GemmArgs g) {
     const int tiles_n = (g.N + BN - 1) / BN;
     int tile = blockIdx.x, piece = -1;             // XCD-aware tile order and the body + tail schedule of gemm_kernel
     if (tile < g.body) {
-        const int nb = g.body, q = nb >> 3, r = nb & 7, xcd = tile & 7, idx = tile >> 3;
-        if (nb >= 64) tile = xcd * q + (xcd < r ? xcd : r) + idx;
+        tile = gemm_xcd_tile(tile, g.body);
     } else {
         const int u = tile - g.body;
         tile = g.body + u / g.tail_s;
@@ -282,19 +153,13 @@ __global__ __launch_bounds__(GS_THREADS) void gemm_split_kernel(GemmArgs g) {
             const int tid = threadIdx.x - 256;
             LA la;
             la.prepare(tid, g.A + (long)batch * g.stride_a, g.lda, m0, kbeg, g.M, g.win_T, g.win_C, g.win_pad, g.win_dil);
-            gs_produce([&](float4 (&r)[4], int k) {
-                           if constexpr (TA) la.load(tid, r, k, kend, g.lda, g.win_T);
-                           else la.load(tid, r, k, kend, g.win_T, g.win_C, g.win_pad, g.win_dil);
-                       },
+            gs_produce([&](float4 (&r)[4], int k) { la.load(tid, r, k, kend, g.lda, g.win_T, g.win_C, g.win_pad, g.win_dil); },
                        [&](const float4 (&r)[4], __bf16* dst) { la.store(tid, r, dst); }, gs_lds, kbeg, nt2);
         } else {
             const int tid = threadIdx.x - 512;
             LB lb;
             lb.prepare(tid, g.B + (long)batch * g.stride_b, g.ldb, n0, kbeg, g.N, 0, 1, 0, 1);
-            gs_produce([&](float4 (&r)[4], int k) {
-                           if constexpr (TB) lb.load(tid, r, k, kend, 0, 1, 0, 1);
-                           else lb.load(tid, r, k, kend, g.ldb, 0);
-                       },
+            gs_produce([&](float4 (&r)[4], int k) { lb.load(tid, r, k, kend, g.ldb, 0, 1, 0, 1); },
                        [&](const float4 (&r)[4], __bf16* dst) { lb.store(tid, r, dst); }, gs_lds + 3 * GS_PLANE, kbeg, nt2);
         }
         return;
@@ -375,150 +240,25 @@ constexpr int GSB_BM = 256, GSB_BN = 256, GSB_BK = 16, GSB_LD = 24, GSB_THREADS 
 constexpr int GSB_PLANE = 256 * GSB_LD;                           // bf16 elements per plane
 constexpr int GSB_BUF = 6 * GSB_PLANE;                            // A planes hi / mid / lo, then B planes
 constexpr size_t GSB_LDS_BYTES = 2 * GSB_BUF * sizeof(__bf16);
-__device__ __forceinline__ void gsb_put(__bf16* __restrict__ p, const Split3& s) {
-    *reinterpret_cast<gs_bf16x4*>(p) = s.hi;
-    *reinterpret_cast<gs_bf16x4*>(p + GSB_PLANE) = s.mid;
-    *reinterpret_cast<gs_bf16x4*>(p + 2 * GSB_PLANE) = s.lo;
-}
 // operand contiguous along k: thread (k4 = tid & 3, r = tid >> 2 in 0..127) takes the float4 k-run k4 of rows r and r + 128 (all 512 threads)
-template <bool VEC, bool WIN>
-struct GsbLoaderKC {
-    static constexpr int NV = 2;
-    const float* ubase;
-    unsigned voff[2], rmask;
-    int t_row[2], tap, kc, ld_;
-    __device__ __forceinline__ bool mine(int) const { return true; }
-    __device__ __forceinline__ void prepare(int tid, const float* __restrict__ base, long ld, int row0, int k0, int rows, int wT, int wC, int wpad, int wdil) {
-        const int k4 = tid & 3, r = tid >> 2;
-        rmask = 0; ld_ = (int)ld;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int row = row0 + r + i * 128;
-            if (row < rows) rmask |= 1u << i;
-            voff[i] = (unsigned)((r + i * 128) * (int)ld) + (WIN ? 0u : (unsigned)(k4 * 4));
-            if (WIN) t_row[i] = row % wT;
-        }
-        if (WIN) {
-            const int k = k0 + k4 * 4;
-            tap = k / wC; kc = k - tap * wC;
-            ubase = base + ((long)row0 - (long)wpad * wdil) * ld;
-        } else {
-            ubase = base + (long)row0 * ld + k0;
-        }
-    }
-    __device__ __forceinline__ void load(int tid, float4 (&reg)[4], int k0, int kmax, long, int wT, int wC, int wpad, int wdil) {
-        const int k4 = tid & 3;
-        const int k = k0 + k4 * 4;
-        const bool kok = k < kmax;
-        const int sh = WIN ? (tap - wpad) * wdil : 0;
-        const unsigned wadd = WIN ? (unsigned)(tap * wdil * ld_ + kc) : 0u;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            bool ok = kok && ((rmask >> i) & 1u);
-            if (WIN) {
-                const int t = t_row[i] + sh;
-                ok = ok && t >= 0 && t < wT;
-            }
-            if (VEC) {
-                v = gemm_ld4(ok ? ubase + (voff[i] + wadd) : gemm_zero16);
-            } else if (ok) {
-                const float* p = ubase + (voff[i] + wadd);
-                v.x = p[0];
-                if (k + 1 < kmax) v.y = p[1];
-                if (k + 2 < kmax) v.z = p[2];
-                if (k + 3 < kmax) v.w = p[3];
-            }
-            reg[i] = v;
-        }
-        if (WIN) {
-            kc += GSB_BK;
-            const bool wrap = kc >= wC;
-            kc -= wrap ? wC : 0; tap += wrap ? 1 : 0;
-        } else {
-            ubase += GSB_BK;
-        }
-    }
-    __device__ __forceinline__ void store(int tid, const float4 (&reg)[4], __bf16* __restrict__ s) const {
-        const int k4 = tid & 3, r = tid >> 2;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) gsb_put(s + (r + i * 128) * GSB_LD + k4 * 4, gs_split4(reg[i].x, reg[i].y, reg[i].z, reg[i].w));
-    }
-};
-// operand contiguous along its M/N index: 64 column quads x 4 k-quads = 256 blocks of 4 x 4: ONE half of the workgroup (threads HALF * 256 ..)
-// takes a block each as four float4 and writes it transposed - operand A on waves 0..3, operand B on waves 4..7, so that two such operands
-// (the weight gradients) load every thread equally
-template <bool VEC, bool WIN, int HALF>
-struct GsbLoaderMC {
-    const float* ubase;
-    unsigned voff[4];
-    int sh, t_k[4], cols_left;
-    __device__ __forceinline__ bool mine(int tid) const { return (tid >> 8) == HALF; }
-    __device__ __forceinline__ void prepare(int tid, const float* __restrict__ base, long ld, int col0, int k0, int cols, int wT, int wC, int wpad, int wdil) {
-        const int u = tid & 255, kq = u & 3, c4 = u >> 2;
-        const int col = col0 + c4 * 4;
-        cols_left = cols - col;
-        if (WIN) {
-            const int tp = col / wC, cm = col - tp * wC;
-            sh = (tp - wpad) * wdil;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                t_k[i] = (k0 + kq * 4 + i) % wT;
-                voff[i] = (unsigned)((kq * 4 + i + tp * wdil) * (int)ld + cm);
-            }
-            ubase = base + ((long)k0 - (long)wpad * wdil) * ld;
-        } else {
-            sh = 0;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) voff[i] = (unsigned)((kq * 4 + i) * (int)ld + c4 * 4);
-            ubase = base + (long)k0 * ld + col0;
-        }
-    }
-    __device__ __forceinline__ void load(int tid, float4 (&reg)[4], int k0, int kmax, long ld, int wT, int, int, int) {
-        const int kq = tid & 3;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int k = k0 + kq * 4 + i;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            bool ok = k < kmax && cols_left > 0;
-            if (WIN) {
-                const int t = t_k[i] + sh;
-                ok = ok && t >= 0 && t < wT;
-                t_k[i] += GSB_BK;
-                t_k[i] -= (t_k[i] >= wT) ? wT : 0;
-            }
-            if (VEC) {
-                v = gemm_ld4(ok ? ubase + voff[i] : gemm_zero16);
-            } else if (ok) {
-                const float* p = ubase + voff[i];
-                v.x = p[0];
-                if (cols_left > 1) v.y = p[1];
-                if (cols_left > 2) v.z = p[2];
-                if (cols_left > 3) v.w = p[3];
-            }
-            reg[i] = v;
-        }
-        ubase += GSB_BK * ld;
-    }
-    __device__ __forceinline__ void store(int tid, const float4 (&reg)[4], __bf16* __restrict__ s) const {
-        const int u = tid & 255, kq = u & 3, c4 = u >> 2;
-        __bf16* p = s + (c4 * 4) * GSB_LD + kq * 4;
-        gsb_put(p, gs_split4(reg[0].x, reg[1].x, reg[2].x, reg[3].x));
-        gsb_put(p + GSB_LD, gs_split4(reg[0].y, reg[1].y, reg[2].y, reg[3].y));
-        gsb_put(p + 2 * GSB_LD, gs_split4(reg[0].z, reg[1].z, reg[2].z, reg[3].z));
-        gsb_put(p + 3 * GSB_LD, gs_split4(reg[0].w, reg[1].w, reg[2].w, reg[3].w));
-    }
-};
+template <bool VEC, bool WIN> using GsbLoaderKC = TileLoaderKC<4, 2, 128, GSB_LD, SplitPlanes<GSB_PLANE>, VEC, WIN>;
+// operand contiguous along its M/N index: 64 column quads x 4 k-quads = 256 blocks of 4 x 4, so ONE half of the workgroup takes a block each
+// (thread u = tid & 255 of the half: kq = u & 3, c4 = u >> 2) as four float4 and writes it transposed
+template <bool VEC, bool WIN> using GsbLoaderMC = TileLoaderMC<4, GSB_LD, SplitPlanes<GSB_PLANE>, VEC, WIN>;
+
+// who stages an operand: all 512 threads one that is contiguous along k, ONE half of the workgroup (threads HALF * 256 ..) a transposed one -
+// operand A on waves 0..3, operand B on waves 4..7, so that two such operands (the weight gradients) load every thread equally
+template <bool TRANSPOSED, int HALF>
+__device__ __forceinline__ bool gsb_stages(int tid) {
+    if (TRANSPOSED) return (tid >> 8) == HALF;
+    return true;
+}
 
 template <bool TA, bool TB, bool VEC, bool WIN>
 __global__ __launch_bounds__(GSB_THREADS) void gemm_split_big_kernel(GemmArgs g) {
     extern __shared__ __attribute__((aligned(16))) __bf16 gs_lds[];
     const int tiles_n = (g.N + GSB_BN - 1) / GSB_BN;
-    int tile = blockIdx.x;
-    {
-        const int nb = gridDim.x, q = nb >> 3, r = nb & 7, xcd = tile & 7, idx = tile >> 3;
-        if (nb >= 64) tile = xcd * q + (xcd < r ? xcd : r) + idx;
-    }
+    const int tile = gemm_xcd_tile(blockIdx.x, gridDim.x);
     const int tile_m = tile / tiles_n, tile_n = tile % tiles_n;
     const int batch = blockIdx.z / g.split_k, split = blockIdx.z % g.split_k;
     float* C = g.C + (long)batch * g.stride_c;
@@ -530,20 +270,21 @@ __global__ __launch_bounds__(GSB_THREADS) void gemm_split_big_kernel(GemmArgs g)
     const int wrow = (wave >> 2) * 128, wcol = (wave & 3) * 64;
     const int l31 = lane & 31, kg = lane >> 5;
 
-    using LA = typename std::conditional<TA, GsbLoaderMC<VEC, WIN, 0>, GsbLoaderKC<VEC, WIN>>::type;
-    using LB = typename std::conditional<TB, GsbLoaderKC<VEC, false>, GsbLoaderMC<VEC, false, 1>>::type;
+    using LA = typename std::conditional<TA, GsbLoaderMC<VEC, WIN>, GsbLoaderKC<VEC, WIN>>::type;
+    using LB = typename std::conditional<TB, GsbLoaderKC<VEC, false>, GsbLoaderMC<VEC, false>>::type;
     LA la; LB lb;
-    const bool a_mine = la.mine(tid), b_mine = lb.mine(tid);              // (wave-uniform)
-    if (a_mine) la.prepare(tid, g.A + (long)batch * g.stride_a, g.lda, m0, kbeg, g.M, g.win_T, g.win_C, g.win_pad, g.win_dil);
-    if (b_mine) lb.prepare(tid, g.B + (long)batch * g.stride_b, g.ldb, n0, kbeg, g.N, 0, 1, 0, 1);
+    const bool a_mine = gsb_stages<TA, 0>(tid), b_mine = gsb_stages<!TB, 1>(tid);              // (wave-uniform)
+    const int tid_a = TA ? (tid & 255) : tid, tid_b = TB ? tid : (tid & 255);                 // index within the threads that stage the operand
+    if (a_mine) la.prepare(tid_a, g.A + (long)batch * g.stride_a, g.lda, m0, kbeg, g.M, g.win_T, g.win_C, g.win_pad, g.win_dil);
+    if (b_mine) lb.prepare(tid_b, g.B + (long)batch * g.stride_b, g.ldb, n0, kbeg, g.N, 0, 1, 0, 1);
     float4 ra[4], rb[4];
     auto load = [&](int k) {
-        if (a_mine) la.load(tid, ra, k, kend, g.lda, g.win_T, g.win_C, g.win_pad, g.win_dil);
-        if (b_mine) lb.load(tid, rb, k, kend, g.ldb, 0, 1, 0, 1);
+        if (a_mine) la.load(tid_a, ra, k, kend, g.lda, g.win_T, g.win_C, g.win_pad, g.win_dil);
+        if (b_mine) lb.load(tid_b, rb, k, kend, g.ldb, 0, 1, 0, 1);
     };
     auto store = [&](int buf) {
-        if (a_mine) la.store(tid, ra, gs_lds + buf * GSB_BUF);
-        if (b_mine) lb.store(tid, rb, gs_lds + buf * GSB_BUF + 3 * GSB_PLANE);
+        if (a_mine) la.store(tid_a, ra, gs_lds + buf * GSB_BUF);
+        if (b_mine) lb.store(tid_b, rb, gs_lds + buf * GSB_BUF + 3 * GSB_PLANE);
     };
 
     f32x16 acc[4][2];
@@ -581,7 +322,7 @@ __global__ __launch_bounds__(GSB_THREADS) void gemm_split_big_kernel(GemmArgs g)
         load(kbeg);
         store(0);
         load(kbeg + GSB_BK);                // (past the end: the loaders read the zero block)
-        gs_barrier();
+        gemm_barrier();
         for (int t = 0; t < nt; ++t) {
             const __bf16* buf = gs_lds + (t & 1) * GSB_BUF;
             ldB(buf); ldA(fa0, buf, 0); ldA(fa1, buf, 1);
@@ -591,60 +332,21 @@ __global__ __launch_bounds__(GSB_THREADS) void gemm_split_big_kernel(GemmArgs g)
             load(kbeg + (t + 2) * GSB_BK);
             mm(fa1, 0); mm(fa1, 1);
             mm(fa0, 0);
-            gs_barrier();
+            gemm_barrier();
         }
     }
     gemm_store_tile<4, 2>(g, acc, C, m0 + wrow, n0 + wcol, lane, split == 0, g.split_k > 1);
 }
 
-static int gemm_split_big_ready() {
-    static int memo[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-    if (!memo[dev]) {
-        bool ok = true;
-#define GSB_ATTR1(TA_, TB_, V_, W_) ok = ok && hipFuncSetAttribute((const void*)gemm_split_big_kernel<TA_, TB_, V_, W_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GSB_LDS_BYTES) == hipSuccess
-#define GSB_ATTR(TA_, TB_) GSB_ATTR1(TA_, TB_, true, true); GSB_ATTR1(TA_, TB_, true, false); GSB_ATTR1(TA_, TB_, false, true); GSB_ATTR1(TA_, TB_, false, false)
-        GSB_ATTR(false, false); GSB_ATTR(false, true); GSB_ATTR(true, false); GSB_ATTR(true, true);
-#undef GSB_ATTR
-#undef GSB_ATTR1
-        if (!ok) (void)hipGetLastError();
-        memo[dev] = ok ? 2 : 1;
-    }
-    return memo[dev] == 2;
-}
-
-template <bool TA, bool TB>
-static void launch_gemm_split_big(const GemmArgs& g, bool vec, dim3 grid, hipStream_t st) {
-    const bool win = g.win_T > 0;
-    if (vec && win)  hipLaunchKernelGGL((gemm_split_big_kernel<TA, TB, true, true>), grid, dim3(GSB_THREADS), GSB_LDS_BYTES, st, g);
-    else if (vec)    hipLaunchKernelGGL((gemm_split_big_kernel<TA, TB, true, false>), grid, dim3(GSB_THREADS), GSB_LDS_BYTES, st, g);
-    else if (win)    hipLaunchKernelGGL((gemm_split_big_kernel<TA, TB, false, true>), grid, dim3(GSB_THREADS), GSB_LDS_BYTES, st, g);
-    else             hipLaunchKernelGGL((gemm_split_big_kernel<TA, TB, false, false>), grid, dim3(GSB_THREADS), GSB_LDS_BYTES, st, g);
-}
-
-static int gemm_split_lds_ready() {
-    static int memo[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-    if (!memo[dev]) {
-        bool ok = true;
-#define GS_ATTR1(TA_, TB_, V_, W_) ok = ok && hipFuncSetAttribute((const void*)gemm_split_kernel<TA_, TB_, V_, W_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GS_LDS_BYTES) == hipSuccess
-#define GS_ATTR(TA_, TB_) GS_ATTR1(TA_, TB_, true, true); GS_ATTR1(TA_, TB_, true, false); GS_ATTR1(TA_, TB_, false, true); GS_ATTR1(TA_, TB_, false, false)
-        GS_ATTR(false, false); GS_ATTR(false, true); GS_ATTR(true, false); GS_ATTR(true, true);
-#undef GS_ATTR
-#undef GS_ATTR1
-        if (!ok) (void)hipGetLastError();
-        memo[dev] = ok ? 2 : 1;
-    }
-    return memo[dev] == 2;
-}
-
-template <bool TA, bool TB>
-static void launch_gemm_split(const GemmArgs& g, bool vec, dim3 grid, hipStream_t st) {
-    const bool win = g.win_T > 0;
-    if (vec && win)  hipLaunchKernelGGL((gemm_split_kernel<TA, TB, true, true>), grid, dim3(GS_THREADS), GS_LDS_BYTES, st, g);
-    else if (vec)    hipLaunchKernelGGL((gemm_split_kernel<TA, TB, true, false>), grid, dim3(GS_THREADS), GS_LDS_BYTES, st, g);
-    else if (win)    hipLaunchKernelGGL((gemm_split_kernel<TA, TB, false, true>), grid, dim3(GS_THREADS), GS_LDS_BYTES, st, g);
-    else             hipLaunchKernelGGL((gemm_split_kernel<TA, TB, false, false>), grid, dim3(GS_THREADS), GS_LDS_BYTES, st, g);
-}
+struct GemmSplit {
+    using Args = GemmArgs;
+    static constexpr int THREADS = GS_THREADS;
+    static constexpr size_t LDS_BYTES = GS_LDS_BYTES;
+    template <bool TA, bool TB, bool VEC, bool WIN> static constexpr auto kernel() { return &gemm_split_kernel<TA, TB, VEC, WIN>; }
+};
+struct GemmSplitBig {
+    using Args = GemmArgs;
+    static constexpr int THREADS = GSB_THREADS;
+    static constexpr size_t LDS_BYTES = GSB_LDS_BYTES;
+    template <bool TA, bool TB, bool VEC, bool WIN> static constexpr auto kernel() { return &gemm_split_big_kernel<TA, TB, VEC, WIN>; }
+};

@@ -55,6 +55,25 @@ def test_library_reads_no_environment_variable():
         assert setter in lib.SIGNATURES
 
 
+def test_every_local_include_is_hashed_by_the_build():
+    """build.py decides staleness by content: an object's hash covers its source and build.HEADERS.  A file that a source under csrc/ pulls
+    in with #include "..." and that is missing from that list could be edited without the library being rebuilt."""
+    import glob
+    from multi_speaker_tts_amd import build
+    csrc = os.path.join(ROOT, "multi_speaker_tts_amd", "csrc")
+    hashed = {os.path.realpath(h) for h in build.HEADERS}
+    seen = 0
+    for f in sorted(glob.glob(os.path.join(csrc, "*"))):
+        if not f.endswith((".hip", ".h", ".inc")):
+            continue
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(f).read(), re.M):
+            seen += 1
+            target = os.path.realpath(os.path.join(os.path.dirname(f), inc))
+            assert os.path.exists(target), "%s includes %s, which does not exist" % (os.path.basename(f), inc)
+            assert target in hashed, "%s includes %s, which build.HEADERS does not list" % (os.path.basename(f), inc)
+    assert seen >= len(build.SOURCES)
+
+
 def test_struct_layouts_match_header_sizes():
     """ctypes.Structure sizes == sizeof in C (compiled with the same header)."""
     import subprocess, tempfile
