@@ -18,6 +18,10 @@
 //   m1 row    -> [16 query units, partial energies over those 16 units for all 128 positions]   -> partial energies
 //   energies  -> (sum of 8, softmax, cumulative alignment, 96 context columns)                   -> ctx_s
 //
+// In the fp32 / folded / T <= 128 instantiation (the headline's) the m1 hop is replaced: the query projection is formed at the cell-1 OWNERS, 256
+// partials q[32 rows][128 units] over 4 hidden units each, summed in a fixed order by the attention workgroups (FWD_QOWN below) - no query-kernel
+// slice in LDS, whose 64 KB hold the `lo` planes of the recurrent kernel halves, which then run as six-product bf16 splits (SPLIT_H1, SPLIT_H0).
+//
 // The recurrent halves of both products (h0_{s-1} . W0[h rows], h1_{s-1} . W1[h rows]) do not depend on the step's own chain and run
 // in the shadow of the hand-offs.  Exact fp32 (v_mfma_f32_16x16x4_f32), fixed summation order (deterministic run to run).
 //
@@ -41,11 +45,37 @@ namespace mstts {
 #define SPLIT_C0 1              // 0: the on-chain cell-0 product (context + prenet rows) on the f32-input MFMA
 #endif
 
+#ifndef FWD_QOWN
+#define FWD_QOWN 1              // fp32 instantiation with the split on-chain products: the query projection as 256 partials formed at the cell-1 owners (no m1 ring, no query-kernel slice in LDS)
+#endif
+#ifndef SPLIT_H1
+#define SPLIT_H1 1              // with FWD_QOWN: the recurrent half of cell 1 (h1 rows, shadow of the P0 hand-off) as a six-product split, its `lo` plane in the LDS the query-kernel slice left
+#endif
+#ifndef SPLIT_H0
+#define SPLIT_H0 1              // with FWD_QOWN: the same for the recurrent half of cell 0 (h0 rows, the two shadow pieces behind P1 and the cell-1 update)
+#endif
+#ifndef QP_LATE
+#define QP_LATE 1               // FWD_QOWN: 1 = the request for the query partials leaves behind the location product, 0 = in front of it
+#endif
+#ifndef QP_SLEEP
+#define QP_SLEEP 12             // FWD_QOWN: ... and after an s_sleep of this many 64-clock units (a poll that reaches the memory side before the partials do costs a second round trip; a timed wait as M1_LATE's needs two more SGPRs than the kernel has: 30 spilled registers)
+#endif
+#ifndef H0_LATE
+#define H0_LATE 1               // SPLIT_H0: the whole h0 product behind the cell-1 update (the slice is still staged behind the P1 publication): the request for the cell-1 partials leaves earlier
+#endif
+#ifndef H1_REQ_EARLY
+#define H1_REQ_EARLY 1          // SPLIT_H1: the request for the h1 slice (published a step ago) leaves in front of the P0 publication instead of behind it
+#endif
+#ifndef P0_EARLY
+#define P0_EARLY 0              // SPLIT_H1: the request for the cell-0 partials leaves in front of the h1 product instead of behind it
+#endif
+
 // ring sizes in floats per slot
 constexpr long XCTX = 8L * 128 * 24, XACT = 8L * 128 * 32, XPART = 256L * 8 * 2 * 256, XM1 = 32L * PH, XEN = 32L * 8 * PTMAX;
 constexpr long OFF_CTX = 0, OFF_M0 = OFF_CTX + PRING * XCTX, OFF_H0 = OFF_M0 + PRING * XACT, OFF_H1 = OFF_H0 + PRING * XACT,
                OFF_M1 = OFF_H1 + PRING * XACT, OFF_EN = OFF_M1 + PRING * XM1, OFF_P0 = OFF_EN + PRING * XEN, OFF_P1 = OFF_P0 + PRING * XPART,
-               XCH_FLOATS = OFF_P1 + PRING * XPART;
+               OFF_QP = OFF_P1 + PRING * XPART, XQP = 32L * 8 * 256 * 16,      // FWD_QOWN: query partials [row][unit slice gi][owner][16 units], one poller's 256 pieces contiguous
+               XCH_FLOATS = OFF_QP + (FWD_QOWN ? PRING * XQP : 0);
 // LDS layout (floats)
 // ONE staging buffer serves the four slices a step consumes, in turn: ctx_{s-1} -> m0_s -> h0_s -> h1_s (each is dead before the next arrives)
 // (small arrays first: a DS instruction's immediate offset reaches 64 KB, and every access beyond that needs an address register of its
@@ -97,10 +127,16 @@ __global__ __launch_bounds__(PTH) void persist_fwd_kernel(PersistFwd d) {
     // SC0: the same for the on-chain half of cell 0 (context rows + prenet rows: k-steps 0 .. 31 of w0).  Its 16 registers come from the
     // owner's biases, the score constants (both to a spare corner of S_Q, read where they are used) and SM0's location filter
     constexpr bool SC0 = SPLIT_C0 && SM0;
+    // QO: the query projection moves to the cell-1 owners.  Owner g holds m1[32 rows][units 4 g .. 4 g + 3] right behind its cell update; with its four rows
+    // of the query kernel (2 KB, where the m1 row was staged) it forms the partial q[32 rows][128 units] and publishes it; attention workgroup (row, gi) sums
+    // the 256 partials of its 16 units in a fixed order.  The 64 KB the query-kernel slice took hold the `lo` planes of the recurrent kernel halves
+    // ([octet][thread], 32 KB each), whose hi / mid planes take the registers of the fp32 halves: SH1 / SH0 run them as six-product splits.
+    constexpr bool QO = FWD_QOWN && SC0, SH1 = SPLIT_H1 && QO, SH0 = SPLIT_H0 && QO;
     constexpr int S_BIA = FL<TT>::S_Q + 128;          // [2 cells][4 gates][4 units] biases, [16] score bias + location bias, [16] score weights (S_Q itself uses 128 of its 512 floats)
     typedef FL<TT> Y;
     constexpr int S_STG = Y::S_STG, S_RED = Y::S_RED, S_TR = Y::S_TR, S_M1 = Y::S_M1, S_EN = Y::S_EN, S_CUM = Y::S_CUM, S_A = Y::S_A, S_Q = Y::S_Q,
                   S_CO = Y::S_CO, S_LK = Y::S_LK, S_FLAG = Y::S_FLAG, S_STAMP = Y::S_STAMP, S_VAL = Y::S_VAL, S_WQ = Y::S_WQ;
+    constexpr int S_WQO = S_M1, S_W1LO = S_WQ, S_W0LO = S_WQ + 4 * 512 * 4;      // QO: query-kernel rows [4 units][128]; lo planes [4 octets][512 threads] x 16 B
     constexpr int NH = TT / 128;                  // halves of 128 encoder positions
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int g0 = blockIdx.x, tid0 = threadIdx.x, wave0 = __builtin_amdgcn_readfirstlane(tid0 >> 6);
@@ -137,9 +173,9 @@ __global__ __launch_bounds__(PTH) void persist_fwd_kernel(PersistFwd d) {
             for (int r = 0; r < 64; ++r) { wb0[r >> 3][r & 7] = (__bf16)p0[r * 64]; wb1[r >> 3][r & 7] = (__bf16)p1[r * 64]; }
         } else {
 #pragma unroll
-            for (int r = 0; r < 64; ++r) w0[r] = (SC0 && r < 32) ? 0.f : (FOLD || r < 24 || r >= 32) ? p0[r * 64] : 0.f;
+            for (int r = 0; r < 64; ++r) w0[r] = ((SC0 && r < 32) || (SH0 && r >= 32)) ? 0.f : (FOLD || r < 24 || r >= 32) ? p0[r * 64] : 0.f;
 #pragma unroll
-            for (int r = 0; r < 64; ++r) w1[r] = (SM0 && r < 32) ? 0.f : p1[r * 64];
+            for (int r = 0; r < 64; ++r) w1[r] = ((SM0 && r < 32) || (SH1 && r >= 32)) ? 0.f : p1[r * 64];
         }
     }
     pbf16x8 w1s[SM0 ? 3 : 1][SM0 ? 4 : 1];                        // SM0: planes hi / mid / lo of the m0 rows, octet j = k-steps 8 j .. 8 j + 7
@@ -161,6 +197,33 @@ __global__ __launch_bounds__(PTH) void persist_fwd_kernel(PersistFwd d) {
                 const __bf16 mid = (__bf16)r1; const float r2 = r1 - (float)mid;
                 w0s[0][r >> 3][r & 7] = hi; w0s[1][r >> 3][r & 7] = mid; w0s[2][r >> 3][r & 7] = (__bf16)r2;
             }
+        }
+    }
+    pbf16x8 w1h[SH1 ? 2 : 1][SH1 ? 4 : 1];                        // SH1: planes hi / mid of the h1 rows (k-steps 32 .. 63); the lo plane goes to LDS
+    pbf16x8 w0h[SH0 ? 2 : 1][SH0 ? 4 : 1];                        // SH0: ... of the h0 rows
+    if constexpr (SH1 || SH0) {
+        const float* p1 = d.w1pk + ((long)(g * 8 + wave) * 64) * 64 + lane;
+        const float* p0 = d.w0pk + ((long)(g * 8 + wave) * 64) * 64 + lane;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            pbf16x8 lo1, lo0;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                if constexpr (SH1) {
+                    const float x = p1[(32 + 8 * j + i) * 64];
+                    const __bf16 hi = (__bf16)x; const float r1 = x - (float)hi;
+                    const __bf16 mid = (__bf16)r1; const float r2 = r1 - (float)mid;
+                    w1h[0][j][i] = hi; w1h[1][j][i] = mid; lo1[i] = (__bf16)r2;
+                }
+                if constexpr (SH0) {
+                    const float x = p0[(32 + 8 * j + i) * 64];
+                    const __bf16 hi = (__bf16)x; const float r1 = x - (float)hi;
+                    const __bf16 mid = (__bf16)r1; const float r2 = r1 - (float)mid;
+                    w0h[0][j][i] = hi; w0h[1][j][i] = mid; lo0[i] = (__bf16)r2;
+                }
+            }
+            if constexpr (SH1) *reinterpret_cast<pbf16x8*>(sm + S_W1LO + (j * PTH + tid) * 4) = lo1;
+            if constexpr (SH0) *reinterpret_cast<pbf16x8*>(sm + S_W0LO + (j * PTH + tid) * 4) = lo0;
         }
     }
     // attention role: row ab = gj, unit slice gi (query units / key columns 16 gi ..), value columns 96 gi ..
@@ -191,11 +254,21 @@ __global__ __launch_bounds__(PTH) void persist_fwd_kernel(PersistFwd d) {
             sm[S_VAL + x] = (arow && t < alen && t < T) ? d.values[((long)ab * T + t) * PM + 96 * gi + c] : 0.f;
         }
         for (int x = tid; x < TT + 48; x += PTH) sm[S_CUM + x] = 0.f;
-        const pf32x4* wqs = reinterpret_cast<const pf32x4*>(d.wqpk) + (long)gi * 8 * 512;      // query kernel slice: [8][512 threads] float4
-        for (int x = tid; x < 8 * 512; x += PTH) {
-            pf32x4 v = wqs[x];
-            if constexpr (BF16) { v[0] = bf16_round(v[0]); v[1] = bf16_round(v[1]); v[2] = bf16_round(v[2]); v[3] = bf16_round(v[3]); }
-            reinterpret_cast<pf32x4*>(sm + S_WQ)[x] = v;
+        if constexpr (QO) {
+            // rows 4 g .. 4 g + 3 of the query kernel as [unit][128 columns]: in the packed copy (persist_pack_wq_kernel) the four rows of one column are
+            // the float4 of (slice c >> 4, x4 = g & 7, thread 16 (g >> 3) + (c & 15))
+            if (tid < 128) {
+                const pf32x4 v = reinterpret_cast<const pf32x4*>(d.wqpk)[((long)(tid >> 4) * 8 + gi) * 512 + 16 * gj + (tid & 15)];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) sm[S_WQO + u * 128 + tid] = v[u];
+            }
+        } else {
+            const pf32x4* wqs = reinterpret_cast<const pf32x4*>(d.wqpk) + (long)gi * 8 * 512;      // query kernel slice: [8][512 threads] float4
+            for (int x = tid; x < 8 * 512; x += PTH) {
+                pf32x4 v = wqs[x];
+                if constexpr (BF16) { v[0] = bf16_round(v[0]); v[1] = bf16_round(v[1]); v[2] = bf16_round(v[2]); v[3] = bf16_round(v[3]); }
+                reinterpret_cast<pf32x4*>(sm + S_WQ)[x] = v;
+            }
         }
     }
     float lkb[SM0 ? 1 : 8];                                      // filter slice as MFMA B operand: lk[4 ks + (lane >> 4)][unit lane & 15]; tap 31 is zero
@@ -216,9 +289,8 @@ __global__ __launch_bounds__(PTH) void persist_fwd_kernel(PersistFwd d) {
     for (int b = 0; b < 2; ++b) { acc0[b] = (pf32x4){0.f, 0.f, 0.f, 0.f}; acc1[b] = acc0[b]; }
     // PROF: per-stage wall-clock ticks summed in LDS by thread 0 (no registers held across the loop)
     unsigned long long* sstamp = reinterpret_cast<unsigned long long*>(sm + S_STAMP);
-    unsigned tprev = 0;
-    if (PROF && tid < NSTAMP) sstamp[tid] = 0;
-#define PSTAMP(idx) do { if (PROF && tid == 0) { const unsigned n__ = (unsigned)wall_clock64(); sstamp[idx] += (unsigned)(n__ - tprev); tprev = n__; } } while (0)
+    if (PROF && tid < NSTAMP) sstamp[tid] = 0;       // (the previous stamp lives in a spare word next to the abort flag: no register held across the loop)
+#define PSTAMP(idx) do { if (PROF && tid == 0) { const unsigned n__ = (unsigned)wall_clock64(); sstamp[idx] += (unsigned)(n__ - sflag[2]); sflag[2] = n__; } } while (0)
 #define PABORT_CHECK() do { __syncthreads(); if (sflag[0]) return; } while (0)
     // (the first code raised stays: a workgroup that merely found the abort word while waiting does not overwrite it)
 #define PFAIL() do { sflag[0] = 1; unsigned z__ = 0u; __hip_atomic_compare_exchange_strong(d.ctrl + 1, &z__, 2u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); } while (0)
@@ -248,7 +320,7 @@ __global__ __launch_bounds__(PTH) void persist_fwd_kernel(PersistFwd d) {
     ((*reinterpret_cast<const pf32x4*>(sm + S_RED + ((0 * 2 + et) * 64 + lane) * 4) + *reinterpret_cast<const pf32x4*>(sm + S_RED + ((1 * 2 + et) * 64 + lane) * 4)) + \
      (*reinterpret_cast<const pf32x4*>(sm + S_RED + ((2 * 2 + et) * 64 + lane) * 4) + *reinterpret_cast<const pf32x4*>(sm + S_RED + ((3 * 2 + et) * 64 + lane) * 4)))
     __syncthreads();
-    if (PROF && tid == 0) tprev = (unsigned)wall_clock64();
+    if (PROF && tid == 0) sflag[2] = (unsigned)wall_clock64();
 
     // ---- cell-update operands of both cells (plain loads of loop-invariant inputs: hoisted prenet product, zoneout keep-masks).  They are
     // HBM-cold, so they are requested ONE STEP AHEAD - here for step 0, at the bottom of the loop body for step s + 1 - by EVERY wave
@@ -258,13 +330,18 @@ __global__ __launch_bounds__(PTH) void persist_fwd_kernel(PersistFwd d) {
     float xwv[4] = {0.f, 0.f, 0.f, 0.f};
     pf32x4 prv = {0.f, 0.f, 0.f, 0.f};           // FOLD: this thread's 16 bytes of the step's prenet slice (staging row rho = (tid & 255) >> 1, half tid & 1)
     uint8_t zc0v, zh0v, zc1v, zh1v;
+    // (QO: from the per-step opaque ids - derived from tid0 / g0 / wave0 the four mask addresses and the prenet address are loop invariants the compiler keeps as
+    //  64-bit pointers in VGPRs, two of which it spilled: their reload at the loop bottom waits, vmcnt being one counter, for the context publication's acknowledgement)
+#define PL_TID (QO ? tid : tid0)
+#define PL_WAVE (QO ? wave : wave0)
+#define PL_G (QO ? g : g0)
 #define LOAD_PRE(ST) do { const long bp__ = (long)(ST) * B;                                                                                  \
-            const unsigned rho__ = ((unsigned)tid0 & 255u) >> 1, pb__ = 16 * ((rho__ >> 4) & 1u) + (rho__ & 15u);                                     \
-            const pf32x4 v__ = *reinterpret_cast<const pf32x4*>(d.pre + (bp__ + (pb__ < (unsigned)B ? pb__ : 0u)) * 256 + 32 * (g0 & 7) + 8 * (rho__ >> 5) + 4 * ((unsigned)tid0 & 1u)); \
+            const unsigned rho__ = ((unsigned)PL_TID & 255u) >> 1, pb__ = 16 * ((rho__ >> 4) & 1u) + (rho__ & 15u);                                     \
+            const pf32x4 v__ = *reinterpret_cast<const pf32x4*>(d.pre + (bp__ + (pb__ < (unsigned)B ? pb__ : 0u)) * 256 + 32 * (PL_G & 7) + 8 * (rho__ >> 5) + 4 * ((unsigned)PL_TID & 1u)); \
             prv = pb__ < (unsigned)B ? v__ : (pf32x4){0.f, 0.f, 0.f, 0.f}; } while (0)
-#define LOAD_OPERANDS(ST) do { const long b__ = (long)(ST) * B; const unsigned r__ = (16 * (wave0 & 1) + (tid0 & 15)) < (unsigned)B ? 16 * (wave0 & 1) + (tid0 & 15) : 0u;  \
+#define LOAD_OPERANDS(ST) do { const long b__ = (long)(ST) * B; const unsigned r__ = (16 * (PL_WAVE & 1) + (PL_TID & 15)) < (unsigned)B ? 16 * (PL_WAVE & 1) + (PL_TID & 15) : 0u;  \
         /* (waves 2..7 only repeat the update: their lanes all read ONE address, a single cache-line request instead of 16 scattered ones) */ \
-        const unsigned u__ = 4 * g0 + ((tid0 & 63) >> 4), h__ = wave0 < 2 ? r__ * PH + u__ : 0u, q__ = wave0 < 2 ? r__ * 4 * PH + u__ : 0u;                                     \
+        const unsigned u__ = 4 * PL_G + ((PL_TID & 63) >> 4), h__ = PL_WAVE < 2 ? r__ * PH + u__ : 0u, q__ = PL_WAVE < 2 ? r__ * 4 * PH + u__ : 0u;                                     \
         if (FOLD) {                                                                                                                         \
             if (!PE) LOAD_PRE(ST);                                                                                                          \
         } else {                                                                                                                            \
@@ -338,21 +415,25 @@ __global__ __launch_bounds__(PTH) void persist_fwd_kernel(PersistFwd d) {
             }
             if constexpr (!BF16) { if (s > 0) mfma_part<0, 6, LC, 0, 64>(w0, stg, lane, acc0); }
         }
+        if constexpr (SH1 && H1_REQ_EARLY) { if (s > 0) slice_issue<8>(xr, OFF_H1 + pslot * XACT + gi * 4096L, tid, soff, sv); }
         PUBLISH_PARTIAL(OFF_P0, acc0)
         PSTAMP(2);
         // in the shadow of the partial-gates hand-off (the longest wait of the step, and the staging buffer is free): h1_{s-1} . W1[h rows]
         if (s > 0) {
-            slice_issue<8>(xr, OFF_H1 + pslot * XACT + gi * 4096L, tid, soff, sv);
+            if constexpr (!(SH1 && H1_REQ_EARLY)) slice_issue<8>(xr, OFF_H1 + pslot * XACT + gi * 4096L, tid, soff, sv);
             __syncthreads();                                         // the context rows are consumed by every wave
             if constexpr (BF16) { if (!slice_complete_bf16<8>(xr, stg16, tid, soff, sv, d.ctrl, pgen)) PFAIL(); }
+            else if constexpr (SH1) { if (!slice_complete_split3(xr, stg16, tid, soff, sv, d.ctrl, pgen)) PFAIL(); }
             else { if (!slice_complete<8, LA>(xr, stg, tid, soff, sv, d.ctrl, pgen)) PFAIL(); }
             PABORT_CHECK();
+            if constexpr (SH1 && P0_EARLY) { ISSUE_PARTIALS(OFF_P0) }
             if constexpr (BF16) mfma_part_bf16<0, 4, 4>(wb1, stg16, lane, acc1);
+            else if constexpr (SH1) mfma_part_split3_lds<0, 4>(w1h, sm + S_W1LO + 4 * tid, stg16, lane, acc1);
             else mfma_part<0, 8, LA, 32, 64>(w1, stg, lane, acc1);
         }
         PSTAMP(13);
         // ================= B: sum of the eight partials, cell-0 update
-        ISSUE_PARTIALS(OFF_P0)
+        if (!(SH1 && P0_EARLY) || s == 0) { ISSUE_PARTIALS(OFF_P0) }
         COMPLETE_PARTIALS()
         PABORT_CHECK();
         PSTAMP(3);
@@ -409,9 +490,11 @@ __global__ __launch_bounds__(PTH) void persist_fwd_kernel(PersistFwd d) {
         // in the shadow of the partial-gates hand-off: h0_s staged, first half of h0_s . W0[h rows] for step s+1
         __syncthreads();                                             // m0 is consumed by every wave
         if constexpr (BF16) { if (!slice_complete_bf16<8>(xr, stg16, tid, soff, sv, d.ctrl, gen)) PFAIL(); }
+        else if constexpr (SH0) { if (!slice_complete_split3(xr, stg16, tid, soff, sv, d.ctrl, gen)) PFAIL(); }
         else { if (!slice_complete<8, LA>(xr, stg, tid, soff, sv, d.ctrl, gen)) PFAIL(); }
         PABORT_CHECK();
         if constexpr (BF16) mfma_part_bf16<0, 2, 4>(wb0, stg16, lane, acc0);
+        else if constexpr (SH0) mfma_part_split3_lds<0, H0_LATE ? 0 : 2>(w0h, sm + S_W0LO + 4 * tid, stg16, lane, acc0);
         else mfma_part<0, 4, LA, 32, 64>(w0, stg, lane, acc0);
         PSTAMP(7);
         // ================= D: sum of the eight partials, cell-1 update
@@ -431,7 +514,24 @@ __global__ __launch_bounds__(PTH) void persist_fwd_kernel(PersistFwd d) {
                 sm[S_TR + 128 + er * 4 + ee] = h1s;
             }
             __syncthreads();
-            if (tid < 64) {
+            if constexpr (QO) {
+                // this owner's partial of the query projection, q[row][c] = sum over its 4 units of m1[row][u] Wq[4 g + u][c]: thread (rows tid >> 5 and
+                // 16 + (tid >> 5), columns 4 (tid & 31) ..) forms and publishes two 16-byte pieces - ahead of everything else this stage stores
+                const int c4 = tid & 31;
+                pf32x4 wq4[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) wq4[u] = *reinterpret_cast<const pf32x4*>(sm + S_WQO + u * 128 + 4 * c4);
+#pragma unroll
+                for (int hh = 0; hh < 2; ++hh) {
+                    const int row = (tid >> 5) + 16 * hh;
+                    const pf32x4 mv = *reinterpret_cast<const pf32x4*>(sm + S_TR + row * 4);
+                    pf32x4 q4 = wq4[0] * mv[0];
+                    q4 += wq4[1] * mv[1]; q4 += wq4[2] * mv[2]; q4 += wq4[3] * mv[3];
+                    const long o2 = ((long)(row * 8 + (c4 >> 2)) * 256 + g) * 16 + 4 * (c4 & 3);
+                    xpublish(xr, (unsigned)((OFF_QP + slot * XQP + o2) * 4), q4, gen);
+                }
+            }
+            if (tid < 64 && (!QO || tid >= 32)) {
                 const int arr = tid >> 5, row = tid & 31;
                 const pf32x4 val = *reinterpret_cast<const pf32x4*>(sm + S_TR + arr * 128 + row * 4);
                 if (arr == 0) {     // m1: row-major [32][1024] for the attention workgroups of the row
@@ -461,6 +561,7 @@ __global__ __launch_bounds__(PTH) void persist_fwd_kernel(PersistFwd d) {
         PSTAMP(9);
         // in the shadow of the m1 hand-off: second half of h0_s . W0[h rows]
         if constexpr (BF16) mfma_part_bf16<2, 4, 4>(wb0, stg16, lane, acc0);
+        else if constexpr (SH0) mfma_part_split3_lds<H0_LATE ? 0 : 2, 4>(w0h, sm + S_W0LO + 4 * tid, stg16, lane, acc0);
         else mfma_part<4, 8, LA, 32, 64>(w0, stg, lane, acc0);
         PSTAMP(10);
         // ================= E: attention, query units and partial energies of row ab
@@ -468,8 +569,14 @@ __global__ __launch_bounds__(PTH) void persist_fwd_kernel(PersistFwd d) {
         unsigned long long t_e0 = 0;
         if constexpr (BF16 && M1_LATE > 1) t_e0 = wall_clock64();
         if (arow) {
+            if constexpr (QO) {     // the 256 owners' partials of this workgroup's 16 query units: 16 KB contiguous, two pieces per thread
+                soff[0] = (unsigned)((OFF_QP + slot * XQP + ((long)ab * 8 + gi) * 4096) * 4 + 16 * tid);
+                soff[1] = soff[0] + 16 * PTH;
+                if constexpr (!QP_LATE) issue<2>(xr, soff, sv);
+            } else {
             if (tid < 256) roff[0] = (unsigned)((OFF_M1 + slot * XM1 + (long)ab * PH) * 4 + 16 * tid);
             if constexpr (!(BF16 && M1_LATE)) { if (tid < 256) issue<1>(xr, roff, rv); }
+            }
             // while the m1 row is in flight: the location filter over the cumulative alignment (known since the last step's softmax) as a
             // Toeplitz product on the matrix core: loc[t][k] = sum_j cum[t + j - 15] lk[j][k] = A . B with A[t][j] = cum window (one LDS word per
             // lane and k-step), B[j][k] = the filter slice (8 registers, loaded once); wave w takes positions 16 w .. 16 w + 15, and the D layout
@@ -490,6 +597,27 @@ __global__ __launch_bounds__(PTH) void persist_fwd_kernel(PersistFwd d) {
                 if (M1_LATE > 1) { while (wall_clock64() - t_e0 < (unsigned long long)M1_LATE) __builtin_amdgcn_s_sleep(1); }
                 if (tid < 256) issue<1>(xr, roff, rv);
             }
+            if constexpr (QO) {
+                if constexpr (QP_SLEEP > 0) __builtin_amdgcn_s_sleep(QP_SLEEP);
+                if constexpr (QP_LATE) issue<2>(xr, soff, sv);
+                { const unsigned g2[2] = {gen, gen}; if (!complete<2>(xr, soff, sv, d.ctrl, g2)) PFAIL(); }
+                PABORT_CHECK();
+                PSTAMP(11);
+                // fixed order: the thread's two owners (tid >> 2, 128 + (tid >> 2)), then the 16 lanes that hold the same four units (lane & 3: inside a
+                // row of 16 lanes by two row rotations, across the four rows through the LDS crossbar), then the eight waves through S_Q as below
+                pf32x4 q4 = sv[0] + sv[1];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    q4[e] += dpp_mov<0x124, 0xf>(0.f, q4[e]);
+                    q4[e] += dpp_mov<0x128, 0xf>(0.f, q4[e]);
+                }
+#pragma unroll
+                for (int sh = 16; sh < 64; sh <<= 1) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) q4[e] += __shfl_xor(q4[e], sh);
+                }
+                if (lane < 4) *reinterpret_cast<pf32x4*>(sm + S_Q + wave * 16 + 4 * lane) = q4;
+            } else {
             if (tid < 256) {
                 { const unsigned g1[1] = {gen}; if (!complete<1>(xr, roff, rv, d.ctrl, g1)) PFAIL(); }
                 if constexpr (BF16) { rv[0][0] = bf16_round(rv[0][0]); rv[0][1] = bf16_round(rv[0][1]); rv[0][2] = bf16_round(rv[0][2]); rv[0][3] = bf16_round(rv[0][3]); }
@@ -510,6 +638,7 @@ __global__ __launch_bounds__(PTH) void persist_fwd_kernel(PersistFwd d) {
                 qp += __shfl_xor(qp, 16);
                 qp += __shfl_xor(qp, 32);
                 if (lane < 16) sm[S_Q + wave * 16 + lane] = qp;
+            }
             }
             __syncthreads();
             float qsum = 0.f;
@@ -640,6 +769,9 @@ __global__ __launch_bounds__(PTH) void persist_fwd_kernel(PersistFwd d) {
 #undef PSTAMP
 #undef LOAD_OPERANDS
 #undef LOAD_PRE
+#undef PL_TID
+#undef PL_WAVE
+#undef PL_G
 #undef PABORT_CHECK
 #undef PFAIL
 #undef PUBLISH_PARTIAL

@@ -159,6 +159,29 @@ __device__ __forceinline__ void mfma_part_split3(const pbf16x8 (&wsp)[3][4], con
     }
 }
 
+// the same with the kernel half's hi / mid planes in registers and its lo plane in LDS as [octet][512 threads] x 16 bytes (wlo = this thread's
+// octet 0; conflict-free ds_read_b128, read where it is used: four registers live instead of sixteen)
+template <int JA, int JB>
+__device__ __forceinline__ void mfma_part_split3_lds(const pbf16x8 (&whm)[2][4], const float* wlo, const __bf16* sx, int lane, pf32x4 (&acc)[2]) {
+    const int row0 = ((lane >> 4) * 2) * 16 + (lane & 15);
+#pragma unroll
+    for (int j = JA; j < JB; ++j) {
+        const pbf16x8 wl = *reinterpret_cast<const pbf16x8*>(wlo + j * PTH * 4);
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const __bf16* p = sx + sp3_off(row0 + 16 * t, j);
+            const pbf16x8 xh = *reinterpret_cast<const pbf16x8*>(p), xm = *reinterpret_cast<const pbf16x8*>(p + SP3_PLANE),
+                          xl = *reinterpret_cast<const pbf16x8*>(p + 2 * SP3_PLANE);
+            acc[t] = PMFMA_BF16(whm[0][j], xh, acc[t]);
+            acc[t] = PMFMA_BF16(whm[1][j], xh, acc[t]);
+            acc[t] = PMFMA_BF16(whm[0][j], xm, acc[t]);
+            acc[t] = PMFMA_BF16(whm[1][j], xm, acc[t]);
+            acc[t] = PMFMA_BF16(wl, xh, acc[t]);
+            acc[t] = PMFMA_BF16(whm[0][j], xl, acc[t]);
+        }
+    }
+}
+
 struct CellOut { float si, tj, sf, so, c, m; };
 // ZoneoutLSTMCell.py:228-271 for one (row, unit): gates i, j, f, o (forget bias 1.0 added here); zoneout as state' = k (new - old) + old with
 // k = (1 - z) * keep-mask in training (:266-271) and k = 1 - z at inference (:259-264)
