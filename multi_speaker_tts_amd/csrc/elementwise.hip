@@ -233,7 +233,15 @@ __global__ void bn_finalize_kernel(const float* __restrict__ ws, float inv_rows,
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     const float mean = ws[c] * inv_rows;
-    float var = ws[C + c] * inv_rows - mean * mean;
+    // mean * mean rounded on its own (no contraction into an fma with the subtraction): the sum of squares was rounded term by term, so only
+    // then does a constant column - a batch of one row - get the variance 0 it has; contracted, the difference is the rounding residual of
+    // x^2 (up to 2^-24 x^2, positive as often as not, so the clamp below does not catch it), 1.4e-4 of rstd against eps = 1e-3
+    float var;
+    {
+#pragma clang fp contract(off)
+        const float msq = mean * mean;
+        var = ws[C + c] * inv_rows - msq;
+    }
     var = fmaxf(var, 0.f);
     save_mean[c] = mean;
     save_rstd[c] = rsqrtf(var + eps);
