@@ -815,6 +815,18 @@ __global__ void persist_pack_wq_kernel(const float* __restrict__ wq, float* __re
 }  // namespace mstts
 using namespace mstts;
 
+// Every instantiation, once: 128 or 256 encoder positions (the 128-position one keeps the whole value slice in LDS); form 0 plain, 1 folded
+// prenet product, 2 bf16 recurrent products (folded); with or without the stage stamps.  fwd_index() is the row's place in the table.
+#define PFW_INST(P_, F_, T_, B16_) {persist_fwd_kernel<P_, F_, T_, B16_>, (int)(FL<T_>::S_FLOATS * 4)}
+#define PFW_FORMS(T_)                                                                                                                  \
+    PFW_INST(false, false, T_, false), PFW_INST(true, false, T_, false), PFW_INST(false, true, T_, false), PFW_INST(true, true, T_, false), \
+    PFW_INST(false, true, T_, true), PFW_INST(true, true, T_, true)
+static const PersistInst<PersistFwd> FWD_TABLE[] = {PFW_FORMS(128), PFW_FORMS(256)};
+#undef PFW_FORMS
+#undef PFW_INST
+constexpr int fwd_index(bool t256, int form, bool stamps) { return (t256 * 3 + form) * 2 + stamps; }
+static_assert(sizeof(FWD_TABLE) / sizeof(FWD_TABLE[0]) == fwd_index(true, 2, true) + 1, "one table row per (positions, form, stamps)");
+
 extern "C" int64_t mstts_persist_fwd_ws_bytes(void) { return XCH_FLOATS * 4; }
 extern "C" int64_t mstts_persist_pack_floats(int32_t which) { return which == 0 ? 256L * 8 * 64 * 64 : which == 1 ? 256L * 8 * 64 * 64 : 8L * 64 * 256; }
 
@@ -825,25 +837,7 @@ extern "C" int64_t mstts_persist_pack_floats(int32_t which) { return which == 0 
 extern "C" int32_t mstts_persist_fwd_supported(int64_t B, int64_t H, int64_t M, int64_t A, int64_t T, int64_t KS) {
     if (!(B >= 1 && B <= PROWS && H == PH && M == PM && A == PA && T >= 1 && T <= PTMAX && KS == PKS)) return 0;
     static int memo[PERSIST_MAX_DEVICES];
-    return persist_device_memo(memo, [](int dev) {
-        int cus = 0, per_cu = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < PWG) return false;
-        bool ok = true;
-        int per = 0;
-#define PFW_SETUP(P_, F_, T_)                                                                                                                          \
-        ok = ok && hipFuncSetAttribute((const void*)persist_fwd_kernel<P_, F_, T_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(FL<T_>::S_FLOATS * 4)) == hipSuccess && \
-             hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void*)persist_fwd_kernel<P_, F_, T_>, PTH, (size_t)FL<T_>::S_FLOATS * 4) == hipSuccess && per >= 1;
-        PFW_SETUP(false, false, 128) PFW_SETUP(true, false, 128) PFW_SETUP(false, true, 128) PFW_SETUP(true, true, 128)
-        PFW_SETUP(false, false, 256) PFW_SETUP(true, false, 256) PFW_SETUP(false, true, 256) PFW_SETUP(true, true, 256)
-#undef PFW_SETUP
-#define PFW_SETUP16(P_, T_)                                                                                                                            \
-        ok = ok && hipFuncSetAttribute((const void*)persist_fwd_kernel<P_, true, T_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(FL<T_>::S_FLOATS * 4)) == hipSuccess && \
-             hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void*)persist_fwd_kernel<P_, true, T_, true>, PTH, (size_t)FL<T_>::S_FLOATS * 4) == hipSuccess && per >= 1;
-        PFW_SETUP16(false, 128) PFW_SETUP16(true, 128) PFW_SETUP16(false, 256) PFW_SETUP16(true, 256)
-#undef PFW_SETUP16
-        (void)per_cu;
-        return ok;
-    });
+    return persist_device_memo(memo, [](int dev) { return persist_probe(dev, FWD_TABLE); });
 }
 
 extern "C" int mstts_persist_pack(const float* w0f, const float* w1, const float* wq, const float* wx0, float* w0pk, float* w1pk, float* wqpk, mstts_stream_t s) {
@@ -874,9 +868,8 @@ extern "C" int mstts_decoder_train_fwd_persistent(const mstts_decoder_train_desc
     if (e == hipSuccess) e = hipMemsetAsync(d->c0, 0, B * H * sizeof(float), hs);
     if (e == hipSuccess) e = hipMemsetAsync(d->c1, 0, B * H * sizeof(float), hs);
     if (e == hipSuccess) e = hipMemsetAsync(d->cum_hist, 0, B * T * sizeof(float), hs);
-    if (e == hipSuccess) e = hipMemsetAsync(p->xch, 0xFF, XCH_FLOATS * 4, hs);                  // every word "generation 1": stale for the first pass
-    if (e == hipSuccess) e = hipMemsetAsync(p->ctrl, 0, PCTRL_WORDS * sizeof(unsigned), hs);
     if (e != hipSuccess) return set_err(MSTTS_ERR_LAUNCH, "decoder_train_fwd_persistent: memset: %s", hipGetErrorString(e));
+    if (int r = persist_arm("decoder_train_fwd_persistent", p->xch, XCH_FLOATS * 4, p->ctrl, PCTRL_WORDS, hs)) return r;
     PersistFwd a;
     MSTTS_REQUIRE(!fold || (d->P == 256 && aligned16(p->pre)), MSTTS_ERR_SHAPE, "decoder_train_fwd_persistent: the folded prenet product needs a 256-wide prenet, 16-byte aligned");
     a.w0pk = p->w0pk; a.w1pk = p->w1pk; a.wqpk = p->wqpk; a.xw0 = d->xw0; a.b1 = d->b1; a.pre = p->pre; a.b0 = p->b0;
@@ -886,24 +879,11 @@ extern "C" int mstts_decoder_train_fwd_persistent(const mstts_decoder_train_desc
     a.B = (int)B; a.S = (int)S; a.T = (int)T;
     a.in0 = d->in0; a.in1 = d->in1; a.pj = d->pj; a.c0 = d->c0; a.c1 = d->c1; a.acts0 = d->acts0; a.acts1 = d->acts1;
     a.craw0 = d->craw0; a.craw1 = d->craw1; a.q_hist = d->q_hist; a.align_hist = d->align_hist; a.cum_hist = d->cum_hist;
-    a.opk = p->opk; a.xch = p->xch; a.ctrl = p->ctrl; a.stamps = (unsigned long long*)p->stamps; a.fail_step = p->selftest_fail_step > 0 ? p->selftest_fail_step - 1 : -1; a.near_xcd = p->near_xcd;
+    a.opk = p->opk; a.xch = p->xch; a.ctrl = p->ctrl; a.stamps = (unsigned long long*)p->stamps;
+    persist_knobs(a, p->selftest_fail_step, p->near_xcd);
     MSTTS_REQUIRE(!p->recurrent_bf16 || fold, MSTTS_ERR_SHAPE, "decoder_train_fwd_persistent: the bf16 form needs the folded prenet product (pre / b0)");
-#define PFW_LAUNCH(T_)                                                                                                                  \
-    {                                                                                                                                   \
-        const size_t lds = (size_t)FL<T_>::S_FLOATS * 4;                                                                                \
-        if (p->recurrent_bf16) {                                                                                                        \
-            if (p->stamps) hipLaunchKernelGGL((persist_fwd_kernel<true, true, T_, true>), dim3(PWG), dim3(PTH), lds, hs, a);            \
-            else hipLaunchKernelGGL((persist_fwd_kernel<false, true, T_, true>), dim3(PWG), dim3(PTH), lds, hs, a);                     \
-        } else if (fold) {                                                                                                              \
-            if (p->stamps) hipLaunchKernelGGL((persist_fwd_kernel<true, true, T_>), dim3(PWG), dim3(PTH), lds, hs, a);                  \
-            else hipLaunchKernelGGL((persist_fwd_kernel<false, true, T_>), dim3(PWG), dim3(PTH), lds, hs, a);                           \
-        } else {                                                                                                                        \
-            if (p->stamps) hipLaunchKernelGGL((persist_fwd_kernel<true, false, T_>), dim3(PWG), dim3(PTH), lds, hs, a);                 \
-            else hipLaunchKernelGGL((persist_fwd_kernel<false, false, T_>), dim3(PWG), dim3(PTH), lds, hs, a);                          \
-        }                                                                                                                               \
-    }
-    if (T <= 128) PFW_LAUNCH(128) else PFW_LAUNCH(256)   // (the 128-position instantiation keeps the whole value slice in LDS)
-#undef PFW_LAUNCH
+    const PersistInst<PersistFwd>& k = FWD_TABLE[fwd_index(T > 128, p->recurrent_bf16 ? 2 : fold ? 1 : 0, p->stamps != nullptr)];
+    hipLaunchKernelGGL(k.kernel, dim3(PWG), dim3(PTH), (size_t)k.lds_bytes, hs, a);
     MSTTS_CHECK_LAUNCH("persist_fwd");
     return MSTTS_OK;
 }

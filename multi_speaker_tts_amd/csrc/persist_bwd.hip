@@ -848,30 +848,23 @@ extern "C" int mstts_persist_unpack_history(const float* opk, const mstts_decode
     return MSTTS_OK;
 }
 
+// Every instantiation, once: 128 or 256 encoder positions (beyond 128 the positions from 128 on are read from memory); fp32 or bf16
+// recurrent products; with or without the stage stamps.  bwd_index() is the row's place in the table.
+#define PBW_INST(P_, T_, B16_) {persist_bwd_kernel<P_, T_, B16_>, (int)(BL<T_>::B_FLOATS * 4)}
+static const PersistInst<PersistBwd> BWD_TABLE[] = {
+    PBW_INST(false, 128, false), PBW_INST(true, 128, false), PBW_INST(false, 128, true), PBW_INST(true, 128, true),
+    PBW_INST(false, 256, false), PBW_INST(true, 256, false), PBW_INST(false, 256, true), PBW_INST(true, 256, true)};
+#undef PBW_INST
+constexpr int bwd_index(bool t256, bool bf16, bool stamps) { return (t256 * 2 + bf16) * 2 + stamps; }
+static_assert(sizeof(BWD_TABLE) / sizeof(BWD_TABLE[0]) == bwd_index(true, true, true) + 1, "one table row per (positions, bf16, stamps)");
+
 extern "C" int64_t mstts_persist_bwd_ws_bytes(void) { return BXCH_FLOATS * 4; }
 extern "C" int64_t mstts_persist_bwd_pack_floats(int32_t which) { return which < 2 ? 256L * 8 * 64 * 64 : 8L * 16 * 256 * 4; }
 
 extern "C" int32_t mstts_persist_bwd_supported(int64_t B, int64_t H, int64_t M, int64_t A, int64_t T, int64_t KS) {
     if (!(B >= 1 && B <= PROWS && H == PH && M == PM && A == PA && T >= 1 && T <= PTMAX && KS == PKS)) return 0;
     static int memo[PERSIST_MAX_DEVICES];
-    return persist_device_memo(memo, [](int dev) {
-        int cus = 0, per_cu = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < PWG) return false;
-        bool ok = true;
-        int per = 0;
-#define PBW_SETUP(P_, T_)                                                                                                                              \
-        ok = ok && hipFuncSetAttribute((const void*)persist_bwd_kernel<P_, T_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BL<T_>::B_FLOATS * 4)) == hipSuccess && \
-             hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void*)persist_bwd_kernel<P_, T_>, PTH, (size_t)BL<T_>::B_FLOATS * 4) == hipSuccess && per >= 1;
-        PBW_SETUP(false, 128) PBW_SETUP(true, 128) PBW_SETUP(false, 256) PBW_SETUP(true, 256)
-#undef PBW_SETUP
-#define PBW_SETUP16(P_, T_)                                                                                                                            \
-        ok = ok && hipFuncSetAttribute((const void*)persist_bwd_kernel<P_, T_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BL<T_>::B_FLOATS * 4)) == hipSuccess && \
-             hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void*)persist_bwd_kernel<P_, T_, true>, PTH, (size_t)BL<T_>::B_FLOATS * 4) == hipSuccess && per >= 1;
-        PBW_SETUP16(false, 128) PBW_SETUP16(true, 128) PBW_SETUP16(false, 256) PBW_SETUP16(true, 256)
-#undef PBW_SETUP16
-        (void)per_cu;
-        return ok;
-    });
+    return persist_device_memo(memo, [](int dev) { return persist_probe(dev, BWD_TABLE); });
 }
 
 extern "C" int mstts_persist_bwd_pack(const float* w0f, const float* w1, const float* wq, float* w0t, float* w1t, float* wqt, mstts_stream_t s) {
@@ -896,9 +889,7 @@ extern "C" int mstts_decoder_train_bwd_persistent(const mstts_decoder_train_bwd_
                   d->lsa.loc_k && d->lsa.loc_b && d->lsa.score_w && d->lsa.score_b, MSTTS_ERR_SHAPE, "decoder_train_bwd_persistent: forward state missing");
     MSTTS_REQUIRE(aligned16(p->xch) && aligned16(bd->d_in0) && (M + H) % 4 == 0, MSTTS_ERR_ALIGN, "decoder_train_bwd_persistent: 16-byte alignment");
     hipStream_t hs = (hipStream_t)s;
-    hipError_t e = hipMemsetAsync(p->xch, 0xFF, BXCH_FLOATS * 4, hs);
-    if (e == hipSuccess) e = hipMemsetAsync(p->ctrl, 0, PCTRL_WORDS * sizeof(unsigned), hs);
-    if (e != hipSuccess) return set_err(MSTTS_ERR_LAUNCH, "decoder_train_bwd_persistent: memset: %s", hipGetErrorString(e));
+    if (int r = persist_arm("decoder_train_bwd_persistent", p->xch, BXCH_FLOATS * 4, p->ctrl, PCTRL_WORDS, hs)) return r;
     PersistBwd a;
     a.w1t = p->w1pk; a.w0t = p->w0pk; a.wqt = p->wqpk;
     a.acts0 = d->acts0; a.acts1 = d->acts1; a.craw0 = d->craw0; a.craw1 = d->craw1; a.c0 = d->c0; a.c1 = d->c1;
@@ -908,20 +899,10 @@ extern "C" int mstts_decoder_train_bwd_persistent(const mstts_decoder_train_bwd_
     a.loc_k = d->lsa.loc_k; a.loc_b = d->lsa.loc_b; a.score_w = d->lsa.score_w; a.score_b = d->lsa.score_b;
     a.d_pj = bd->d_pj; a.opk = p->opk; a.B = (int)B; a.S = (int)S; a.T = (int)T;
     a.dg0 = bd->dg0; a.dg1 = bd->dg1; a.dq_hist = bd->dq_hist; a.de_hist = bd->de_hist; a.d_in0 = bd->d_in0;
-    a.xch = p->xch; a.ctrl = p->ctrl; a.stamps = (unsigned long long*)p->stamps; a.fail_step = p->selftest_fail_step > 0 ? p->selftest_fail_step - 1 : -1; a.near_xcd = p->near_xcd;
-#define PBW_LAUNCH(T_)                                                                                                                  \
-    {                                                                                                                                   \
-        const size_t lds = (size_t)BL<T_>::B_FLOATS * 4;                                                                                \
-        if (p->recurrent_bf16) {                                                                                                        \
-            if (p->stamps) hipLaunchKernelGGL((persist_bwd_kernel<true, T_, true>), dim3(PWG), dim3(PTH), lds, hs, a);                  \
-            else hipLaunchKernelGGL((persist_bwd_kernel<false, T_, true>), dim3(PWG), dim3(PTH), lds, hs, a);                           \
-        } else {                                                                                                                        \
-            if (p->stamps) hipLaunchKernelGGL((persist_bwd_kernel<true, T_>), dim3(PWG), dim3(PTH), lds, hs, a);                        \
-            else hipLaunchKernelGGL((persist_bwd_kernel<false, T_>), dim3(PWG), dim3(PTH), lds, hs, a);                                 \
-        }                                                                                                                               \
-    }
-    if (a.T <= 128) PBW_LAUNCH(128) else PBW_LAUNCH(256)      // (the 128-position instantiation; beyond that the positions from 128 on are read from memory)
-#undef PBW_LAUNCH
+    a.xch = p->xch; a.ctrl = p->ctrl; a.stamps = (unsigned long long*)p->stamps;
+    persist_knobs(a, p->selftest_fail_step, p->near_xcd);
+    const PersistInst<PersistBwd>& k = BWD_TABLE[bwd_index(T > 128, p->recurrent_bf16 != 0, p->stamps != nullptr)];
+    hipLaunchKernelGGL(k.kernel, dim3(PWG), dim3(PTH), (size_t)k.lds_bytes, hs, a);
     MSTTS_CHECK_LAUNCH("persist_bwd");
     return MSTTS_OK;
 }

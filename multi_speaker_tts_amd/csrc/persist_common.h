@@ -1,4 +1,6 @@
-// Shared pieces of the two persistent decoder kernels (persist.hip: forward loop, persist_bwd.hip: BPTT): the hand-off primitives.
+// Shared pieces of the persistent kernels (persist.hip: decoder forward loop, persist_bwd.hip: its BPTT, persist_infer.hip: the free-running
+// decoder, persist_lstm.hip: the LSTM sequences).  Device side: the hand-off primitives.  Host side (at the end): the instantiation table with
+// its probe, the arming of rings and control words, and the decoding of the descriptors' test / placement knobs.
 // THE DATA IS THE FLAG: every word that crosses a ring carries the GENERATION of its ring slot in the lowest bit of its mantissa (a ring
 // of 4 slots: step k uses slot k & 3, generation (k >> 2) & 1; the rings are pre-filled with all-ones words = "generation 1" before the
 // launch, the first pass over the ring is generation 0).  A producer stores its values write-through (sc1) with that bit forced; a
@@ -64,7 +66,8 @@ __device__ __forceinline__ void persist_scrub(__amdgpu_buffer_rsrc_t r, long flo
 }
 // XCC id of the CU this wave runs on (HW_REG_XCC_ID, bits 3:0) + 1
 __device__ __forceinline__ unsigned xcc_id_plus1() { return (__builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xfu) + 1u; }
-constexpr int PCTRL_WORDS = 16 + 256;            // control words: arrivals, abort code, finished count, ...; then one XCC id per workgroup
+constexpr int PCTRL_HEAD_WORDS = 16;             // control words: arrivals, abort code, finished count, ... (all that the LSTM launches keep)
+constexpr int PCTRL_WORDS = PCTRL_HEAD_WORDS + 256;   // ... then one XCC id per workgroup of a decoder launch
 // Start rendezvous of the 256 workgroups (thread 0 of each): records the XCC id, arrives, waits for the others (bounded).  Returns 0 on
 // time-out / abort, 1 when resident, 2 when in addition the 32 workgroups that share this workgroup's slice index (id & 7) all sit on its XCD.
 __device__ __forceinline__ int persist_rendezvous(unsigned* ctrl, int g) {
@@ -151,6 +154,17 @@ __device__ __forceinline__ bool complete(__amdgpu_buffer_rsrc_t r, const unsigne
 __device__ __forceinline__ long opk_index(int s, int g, int cell, int half, int tid) { return ((((long)s * PWG + g) * 2 + cell) * 2 + half) * 128 + tid; }
 constexpr long OPK_FLOATS_PER_STEP = (long)PWG * 2 * 2 * 128 * 4;
 
+// ---- host side of a launch
+
+// One instantiation of a persistent decoder kernel (Args: its argument struct).  Each kernel's .hip file names every instantiation ONCE, in
+// a table indexed by a constexpr selector; the probe below prepares exactly that table and the launch statement launches out of it, so an
+// instantiation cannot be launched without its LDS attribute.
+template <typename Args>
+struct PersistInst {
+    void (*kernel)(Args);
+    int lds_bytes;                               // dynamic LDS
+};
+
 // Per-device memo of a "can this device take the launch" probe (CU count, occupancy, the kernels' dynamic-LDS attribute): the probe runs
 // once for EVERY device a process drives - hipFuncSetAttribute applies to the current device only - not once per process.
 constexpr int PERSIST_MAX_DEVICES = 64;
@@ -160,6 +174,31 @@ static inline int persist_device_memo(int* memo, Probe probe) {
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= PERSIST_MAX_DEVICES) { (void)hipGetLastError(); return 0; }
     if (memo[dev] == 0) { memo[dev] = probe(dev) ? 2 : 1; (void)hipGetLastError(); }
     return memo[dev] == 2 ? 1 : 0;
+}
+// The probe of a decoder kernel: a device that takes all PWG workgroups at once, one per CU - at least PWG CUs, and every instantiation of
+// the table admitted by the occupancy query with its LDS (whose attribute is set here).
+template <typename Args, size_t N>
+static inline bool persist_probe(int dev, const PersistInst<Args> (&table)[N]) {
+    int cus = 0, per = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < PWG) return false;
+    bool ok = true;
+    for (const PersistInst<Args>& k : table)
+        ok = ok && hipFuncSetAttribute((const void*)k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds_bytes) == hipSuccess &&
+             hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void*)k.kernel, PTH, (size_t)k.lds_bytes) == hipSuccess && per >= 1;
+    return ok;
+}
+
+// Arms a launch on its stream: every ring word "generation 1" (stale for the first pass), the control words cleared.
+static inline int persist_arm(const char* who, float* xch, size_t ring_bytes, uint32_t* ctrl, int ctrl_words, hipStream_t hs) {
+    hipError_t e = hipMemsetAsync(xch, 0xFF, ring_bytes, hs);
+    if (e == hipSuccess) e = hipMemsetAsync(ctrl, 0, ctrl_words * sizeof(unsigned), hs);
+    return e == hipSuccess ? MSTTS_OK : set_err(MSTTS_ERR_LAUNCH, "%s: memset: %s", who, hipGetErrorString(e));
+}
+
+// The descriptors' self-test and placement knobs as the kernels take them: selftest_fail_step k > 0 = abort at step k - 1 (-1: never)
+template <typename Args>
+static inline void persist_knobs(Args& a, int32_t selftest_fail_step, int32_t near_xcd) {
+    a.fail_step = selftest_fail_step > 0 ? selftest_fail_step - 1 : -1; a.near_xcd = near_xcd;
 }
 
 #define PMFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)

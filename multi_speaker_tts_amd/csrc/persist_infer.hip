@@ -623,6 +623,16 @@ __global__ void persist_pack_qp_kernel(const float* __restrict__ wq, const float
 }  // namespace mstts
 using namespace mstts;
 
+// Every instantiation, once: 128 or 256 encoder positions; one row tile for batches of at most 16 rows (half the matrix-core work and
+// partial-sum bytes), else two; with or without the stage stamps.  infer_index() is the row's place in the table.
+#define PI_INST(P_, N_, T_) {persist_infer_kernel<P_, N_, T_>, (int)(IL<T_>::I_FLOATS * 4)}
+static const PersistInst<PersistInfer> INFER_TABLE[] = {
+    PI_INST(false, 1, 128), PI_INST(true, 1, 128), PI_INST(false, 2, 128), PI_INST(true, 2, 128),
+    PI_INST(false, 1, 256), PI_INST(true, 1, 256), PI_INST(false, 2, 256), PI_INST(true, 2, 256)};
+#undef PI_INST
+constexpr int infer_index(bool t256, bool two_tiles, bool stamps) { return (t256 * 2 + two_tiles) * 2 + stamps; }
+static_assert(sizeof(INFER_TABLE) / sizeof(INFER_TABLE[0]) == infer_index(true, true, true) + 1, "one table row per (positions, row tiles, stamps)");
+
 extern "C" int64_t mstts_persist_infer_ws_bytes(void) { return IXCH_FLOATS * 4; }
 extern "C" int64_t mstts_persist_infer_pack_floats(void) { return 256L * 8 * 8 * 64; }
 
@@ -631,20 +641,7 @@ extern "C" int64_t mstts_persist_infer_pack_floats(void) { return 256L * 8 * 8 *
 extern "C" int32_t mstts_persist_infer_supported(int64_t B, int64_t H, int64_t P, int64_t M, int64_t A, int64_t T, int64_t KS, int64_t n_mel) {
     if (!(B >= 1 && B <= PROWS && H == PH && P == 256 && M == PM && A == PA && T >= 1 && T <= PTMAX && KS == PKS && n_mel == 80)) return 0;
     static int memo[PERSIST_MAX_DEVICES];
-    return persist_device_memo(memo, [](int dev) {
-        int cus = 0, per_cu = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < PWG) return false;
-        bool ok = true;
-        int per = 0;
-#define PI_SETUP(P_, N_, T_)                                                                                                                            \
-        ok = ok && hipFuncSetAttribute((const void*)persist_infer_kernel<P_, N_, T_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(IL<T_>::I_FLOATS * 4)) == hipSuccess && \
-             hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void*)persist_infer_kernel<P_, N_, T_>, PTH, (size_t)IL<T_>::I_FLOATS * 4) == hipSuccess && per >= 1;
-        PI_SETUP(false, 1, 128) PI_SETUP(true, 1, 128) PI_SETUP(false, 2, 128) PI_SETUP(true, 2, 128)
-        PI_SETUP(false, 1, 256) PI_SETUP(true, 1, 256) PI_SETUP(false, 2, 256) PI_SETUP(true, 2, 256)
-#undef PI_SETUP
-        (void)per_cu;
-        return ok;
-    });
+    return persist_device_memo(memo, [](int dev) { return persist_probe(dev, INFER_TABLE); });
 }
 
 extern "C" int mstts_persist_infer_pack(const float* wq, const float* wp_pad, int64_t wp_ld, const float* wfm, float* wqppk, mstts_stream_t s) {
@@ -667,9 +664,7 @@ extern "C" int mstts_decoder_infer_persistent(const mstts_decoder_infer_desc* d,
     MSTTS_REQUIRE(aligned16(p->xch) && aligned16(p->pre0) && ((uintptr_t)d->pm0 & 3u) == 0 && ((uintptr_t)d->pm1 & 3u) == 0 && d->prenet_keep > 0.f, MSTTS_ERR_ALIGN,
                   "decoder_infer_persistent: alignment (rings and step-0 prenet 16 bytes, masks 4 bytes)");
     hipStream_t hs = (hipStream_t)s;
-    hipError_t e = hipMemsetAsync(p->xch, 0xFF, IXCH_FLOATS * 4, hs);                      // every word "generation 1": stale for the first pass
-    if (e == hipSuccess) e = hipMemsetAsync(p->ctrl, 0, PCTRL_WORDS * sizeof(unsigned), hs);
-    if (e != hipSuccess) return set_err(MSTTS_ERR_LAUNCH, "decoder_infer_persistent: memset: %s", hipGetErrorString(e));
+    if (int r = persist_arm("decoder_infer_persistent", p->xch, IXCH_FLOATS * 4, p->ctrl, PCTRL_WORDS, hs)) return r;
     PersistInfer a;
     a.w0pk = p->w0pk; a.w1pk = p->w1pk; a.wqppk = p->wqppk; a.b0 = d->b0; a.b1 = d->b1; a.pre0 = p->pre0;
     a.pm0 = d->pm0; a.pm1 = d->pm1; a.inv_keep = 1.f / d->prenet_keep; a.bf = p->bf; a.w2 = d->pw1; a.b2 = d->pb1; a.u = p->u; a.vp = p->vp; a.bp = p->bp_pad;
@@ -679,17 +674,9 @@ extern "C" int mstts_decoder_infer_persistent(const mstts_decoder_infer_desc* d,
     a.B = (int)B; a.S = (int)S; a.T = (int)T; a.NM = (int)d->n_mel;
     a.linear = d->linear; a.stop = d->stop; a.align_hist = d->align_hist;
     a.xch = p->xch; a.ctrl = p->ctrl; a.stamps = (unsigned long long*)p->stamps;
-    a.fail_step = p->selftest_fail_step > 0 ? p->selftest_fail_step - 1 : -1; a.near_xcd = p->near_xcd;
-#define PI_LAUNCH(N_, T_)                                                                                                               \
-    {                                                                                                                                   \
-        const size_t lds = (size_t)IL<T_>::I_FLOATS * 4;                                                                                \
-        if (p->stamps) hipLaunchKernelGGL((persist_infer_kernel<true, N_, T_>), dim3(PWG), dim3(PTH), lds, hs, a);                      \
-        else hipLaunchKernelGGL((persist_infer_kernel<false, N_, T_>), dim3(PWG), dim3(PTH), lds, hs, a);                               \
-    }
-    // one row tile for batches of at most 16 rows (half the matrix-core work and partial-sum bytes); 128 or 256 encoder positions
-    if (B <= 16) { if (T <= 128) PI_LAUNCH(1, 128) else PI_LAUNCH(1, 256) }
-    else { if (T <= 128) PI_LAUNCH(2, 128) else PI_LAUNCH(2, 256) }
-#undef PI_LAUNCH
+    persist_knobs(a, p->selftest_fail_step, p->near_xcd);
+    const PersistInst<PersistInfer>& k = INFER_TABLE[infer_index(T > 128, B > 16, p->stamps != nullptr)];
+    hipLaunchKernelGGL(k.kernel, dim3(PWG), dim3(PTH), (size_t)k.lds_bytes, hs, a);
     MSTTS_CHECK_LAUNCH("persist_infer");
     return MSTTS_OK;
 }

@@ -570,8 +570,7 @@ static int lstm_fwd_launch_h(const mstts_lstm_seq_fwd_desc* const* dd, const flo
     }
     p.ndir = ndir; p.gpd = lstm_groups(a->B); p.B = (int)a->B; p.T = (int)a->T; p.keep = 1.f - a->zoneout; p.xch = xch; p.ctrl = ctrl;
     const int ngr = ndir * p.gpd;
-    if (hipMemsetAsync(xch, 0xFF, (size_t)ngr * PRING * L::SLOT * 4, hs) != hipSuccess || hipMemsetAsync(ctrl, 0, 16 * sizeof(unsigned), hs) != hipSuccess)
-        return set_err(MSTTS_ERR_LAUNCH, "lstm_seq_fwd_persistent: memset failed");
+    if (int r = persist_arm("lstm_seq_fwd_persistent", xch, (size_t)ngr * PRING * L::SLOT * 4, ctrl, PCTRL_HEAD_WORDS, hs)) return r;
     const long nl = (long)p.T * ngr * L::PGROUP;
     pf32x4* ipx = reinterpret_cast<pf32x4*>(hist);
     unsigned* ipm = reinterpret_cast<unsigned*>(hist + nl * 4);
@@ -614,8 +613,7 @@ static int lstm_bwd_launch(const mstts_lstm_seq_bwd_desc* const* dd, const float
     }
     p.ndir = ndir; p.gpd = lstm_groups(a->B); p.B = (int)a->B; p.T = (int)a->T; p.keep = 1.f - a->zoneout; p.xch = xch; p.ctrl = ctrl;
     const int ngr = ndir * p.gpd;
-    if (hipMemsetAsync(xch, 0xFF, (size_t)ngr * PRING * EB_SLOT * 4, hs) != hipSuccess || hipMemsetAsync(ctrl, 0, 16 * sizeof(unsigned), hs) != hipSuccess)
-        return set_err(MSTTS_ERR_LAUNCH, "lstm_seq_bwd_persistent: memset failed");
+    if (int r = persist_arm("lstm_seq_bwd_persistent", xch, (size_t)ngr * PRING * EB_SLOT * 4, ctrl, PCTRL_HEAD_WORDS, hs)) return r;
     const long nl = (long)p.T * ngr * EP_GROUP;
     p.epk = reinterpret_cast<const pf32x4*>(hist + nl * 5);
     p.dop = bws; p.dpk = reinterpret_cast<pf32x4*>(bws + nl);

@@ -21,6 +21,7 @@ from . import lib
 from .lib import ACT_NONE, ACT_RELU, ACT_TANH, gemm, ptr, call
 from .masks import MaskSet, step_seed
 from .params import CELL, ENC_CELL, LSA, VOC, Dims, ParamStore, bank_suffix
+from .persist import PERSIST_COOLDOWN, PERSIST_STRIKES, CoolDown, Ticket, decoder_workgroups, lstm_bwd_workgroups, lstm_fwd_workgroups, near_xcd
 from .training import (Engine, _split_k, _split_k_big, bn_train_fwd, conv_bn_bwd, conv_fwd, exponential_decay, lstm_layer_grads, lstm_seq_bwd,
                        lstm_seq_fwd)
 
@@ -34,8 +35,6 @@ def learning_rate(step):
     return exponential_decay(hp.Train.Learning_Rate, step)
 
 
-PERSIST_STRIKES = 2          # consecutive steps with a fallback before the persistent plans are switched off ...
-PERSIST_COOLDOWN = 200       # ... for this many steps
 VOC_OVERLAP = os.environ.get("MSTTS_VOC_OVERLAP", "1") != "0"    # the vocoder conv-bank's statistics side effect (quirk Q20) on its own stream, under the loss and the postnet's backward pass
 POSTNET_WGRAD_OVERLAP = os.environ.get("MSTTS_POSTNET_WGRAD_OVERLAP", "1") != "0"   # ... and the postnet's weight-gradient products, beside its data-gradient chain
 ENC_TAIL_OVERLAP = os.environ.get("MSTTS_ENC_TAIL_OVERLAP", "1") != "0"   # ... and what follows the encoder's BPTT launch on that stream too, beside the decoder's weight-gradient products
@@ -181,8 +180,7 @@ class TrainEngine(Engine):
         # again.  persist_disabled_steps counts the steps run that way; non_persistent_plans the shapes planned without them although
         # the widths are the reference's (the T_enc / batch cliff of the persistent kernels).
         self._moving_snapshot = None
-        self._persist_strikes = 0
-        self._persist_off = 0                # steps left of the cool-down
+        self._persist_cool = CoolDown()
         self._persist_warned = False
         self.persist_disabled_steps = 0
         self.non_persistent_plans = 0
@@ -575,11 +573,11 @@ class TrainEngine(Engine):
             ready.record()
             with torch.cuda.stream(self._enc_stream):
                 self._enc_stream.wait_event(ready)
-                enc_ticket = self._enc_persistent(w, "mstts_lstm_seq_fwd_pair_persistent", seqs, 0, 64)   # (status read at the end of the pass)
+                enc_ticket = self._enc_persistent(w, "mstts_lstm_seq_fwd_pair_persistent", seqs, 0)   # (status read at the end of the pass)
                 enc_done = torch.cuda.Event()
                 enc_done.record()
         elif w.enc_hist_valid:
-            enc_ticket = self._enc_persistent(w, "mstts_lstm_seq_fwd_pair_persistent", seqs, 0, 64)
+            enc_ticket = self._enc_persistent(w, "mstts_lstm_seq_fwd_pair_persistent", seqs, 0)
         if not w.enc_hist_valid:
             self._ensure_fallback_packs()
             call("mstts_lstm_seq_fwd_pair", C.byref(seqs[0]), C.byref(seqs[1]))     # both directions advance together: one launch per step
@@ -637,7 +635,7 @@ class TrainEngine(Engine):
         dec.energy_ws_floats = w.energy_ws_floats if self.fuse_query else 0
         for nm in ("in0", "in1", "pj", "c0", "c1", "acts0", "acts1", "craw0", "craw1", "q_hist", "align_hist", "cum_hist", "gates_ws", "energy_ws", "q_ws"):
             setattr(dec, nm, ptr(getattr(w, nm)))
-        ev = None
+        dec_ticket = None
         if w.persist_now:
             # ONE launch for all S steps; the launch-per-step loop below is the fallback when the 256 workgroups were not co-resident
             # or a bounded wait expired (ctrl words, checked after the rest of the forward pass is enqueued - no bubble on the device)
@@ -647,7 +645,7 @@ class TrainEngine(Engine):
             pd.opk = ptr(w.opk) if w.persist_bwd_now else None
             w.opk_valid = pd.opk is not None
             pd.selftest_fail_step = int(self.persist_selftest)
-            pd.near_xcd = int(os.environ.get("MSTTS_PERSIST_NEAR", "1") != "0")
+            pd.near_xcd = near_xcd()
             pd.recurrent_bf16 = int(self.persist_bf16)
             pd.pre, pd.b0 = (ptr(x), ptr(b0, ob0)) if w.fold_prenet else (None, None)
             call("mstts_decoder_train_fwd_persistent", C.byref(dec), C.byref(pd))
@@ -656,24 +654,14 @@ class TrainEngine(Engine):
             # hardware queue, and HIP maps streams onto a few hardware queues: in a process with more streams - an RCCL group - the side stream
             # shared the main stream's queue, and every kernel enqueued behind such a barrier waited with it: profiles/r06_one_rank_rccl_timeline_before.txt,
             # the decoder's weight-gradient products sat out the encoder's BPTT launch, +1.0 ms per step.)
-            w.pctrl_host.copy_(w.pctrl, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
+            dec_ticket = Ticket(w.pctrl, w.pctrl_host, decoder_workgroups()).enqueue(torch.cuda.Event())
         else:
             w.opk_valid = False
             self._ensure_fallback_packs()
             call("mstts_decoder_train_fwd", C.byref(dec))
         self._forward_tail(w, overlap_vocoder=overlap_vocoder and VOC_OVERLAP and self.device.type == "cuda")
-        dec_ok = enc_ok = True
-        if ev is not None:
-            ev.synchronize()
-            st = w.pctrl_host
-            dec_ok = int(st[1]) == 0 and int(st[2]) == 256
-            if not dec_ok:
-                self.persist_fallbacks += 1
-                self.persist_last_status = (int(st[0]), int(st[1]), int(st[2]))
-        if enc_ticket is not None:
-            enc_ok = self._enc_check(w, enc_ticket)
+        dec_ok = dec_ticket is None or self._ticket_ok(dec_ticket, "persist_fallbacks")
+        enc_ok = enc_ticket is None or self._ticket_ok(enc_ticket, "persist_enc_fallbacks", keep_status=False)
         spk_ticket = None if _redo else batch.pop("_speaker_ticket", None)
         if spk_ticket is not None and not spk_ticket.ok():
             # the frozen speaker stack in front of this pass (MSTTS_SV.py:49-56) ran as persistent launches whose words are read only now:
@@ -690,50 +678,44 @@ class TrainEngine(Engine):
             return self.forward(batch, w, seed=seed, masks=masks, _redo=True, overlap_vocoder=overlap_vocoder)
         return w
 
-    def _enc_persistent(self, w, entry, seqs, which, n_wg):
+    def _enc_persistent(self, w, entry, seqs, which):
         """One persistent launch for all steps of both encoder directions (forward: which = 0, BPTT: 1).  Nothing waits here: the launch's
-        control words are copied to pinned host memory behind it on the same stream; the returned ticket is redeemed with _enc_check at the
+        control words are copied to pinned host memory behind it on the same stream; the returned ticket is redeemed with _ticket_ok at the
         end of the pass."""
         extra = (ptr(w.enc_hist),) if which == 0 else (ptr(w.enc_hist), ptr(w.enc_bws))
         call(entry, C.byref(seqs[0]), C.byref(seqs[1]), ptr(self.enc_pk["fw"][which]), ptr(self.enc_pk["bw"][which]), ptr(w.enc_xch), ptr(w.enc_ctrl), *extra)
         if getattr(self, "persist_enc_selftest", 0):              # tests: this encoder launch "gave up" - on the DEVICE, where the job-wide verdict reads it too
             self.persist_enc_selftest -= 1
             w.enc_ctrl[1:2].fill_(3)
-        host = w.enc_ctrl_host if which == 0 else w.enc_ctrl_host_b
-        host.copy_(w.enc_ctrl, non_blocking=True)            # on the launching stream, behind the launch (see forward(): no side-stream barrier)
-        done = torch.cuda.Event()
-        done.record()
-        return done, host, n_wg
+        n_wg = lstm_fwd_workgroups(w.B, self.d.enc_lstm, 2) if which == 0 else lstm_bwd_workgroups(w.B, 2)
+        # (the read-back: on the launching stream, behind the launch - see forward(): no side-stream barrier)
+        return Ticket(w.enc_ctrl, w.enc_ctrl_host if which == 0 else w.enc_ctrl_host_b, n_wg).enqueue(torch.cuda.Event())
 
-    def _enc_check(self, w, ticket):
-        """True when the encoder launch of the ticket ran to its end (False: the caller re-runs the pass with the launch-per-step pair)."""
-        done, host, n_wg = ticket
-        done.synchronize()
-        if int(host[1]) != 0 or int(host[2]) != n_wg:
-            self.persist_enc_fallbacks += 1
+    def _ticket_ok(self, ticket, counter, keep_status=True):
+        """True when the ticket's launch ran to its end.  False (the caller re-runs the pass launch by launch) is a fallback on `counter` and
+        makes the step one that fell back; a decoder launch also leaves its status words in persist_last_status."""
+        ok, status = ticket.redeem()
+        if not ok:
+            setattr(self, counter, getattr(self, counter) + 1)
             self._step_fell_back = True
-            return False
-        return True
+            if keep_status:
+                self.persist_last_status = status
+        return ok
 
     def _persist_begin_step(self):
         """Adaptive fallback policy, called once per OPTIMIZER STEP (train_step; a forward pass driven on its own calls it itself): closes the books on the previous step (a step in which any persistent
         launch gave up is a strike; PERSIST_STRIKES in a row start a cool-down) and says whether this step may use the persistent
         launches."""
         if getattr(self, "_step_fell_back", False):
-            self._persist_strikes += 1
-            if self._persist_strikes >= PERSIST_STRIKES:
-                self._persist_off = PERSIST_COOLDOWN
-                self._persist_strikes = 0
-                if not self._persist_warned:
-                    self._persist_warned = True
-                    warnings.warn("multi_speaker_tts_amd: %d consecutive steps fell back from the persistent launches (status %r: something "
-                                  "else holds compute units); running the launch-per-step loops for %d steps before probing again"
-                                  % (PERSIST_STRIKES, getattr(self, "persist_last_status", None), PERSIST_COOLDOWN), RuntimeWarning, stacklevel=4)
+            if self._persist_cool.strike(PERSIST_STRIKES, PERSIST_COOLDOWN) and not self._persist_warned:
+                self._persist_warned = True
+                warnings.warn("multi_speaker_tts_amd: %d consecutive steps fell back from the persistent launches (status %r: something "
+                              "else holds compute units); running the launch-per-step loops for %d steps before probing again"
+                              % (PERSIST_STRIKES, getattr(self, "persist_last_status", None), PERSIST_COOLDOWN), RuntimeWarning, stacklevel=4)
         elif getattr(self, "_step_was_persistent", False):
-            self._persist_strikes = 0
+            self._persist_cool.clear()
         self._step_fell_back = False
-        if self._persist_off > 0:
-            self._persist_off -= 1
+        if not self._persist_cool.admit():
             self.persist_disabled_steps += 1
             self._step_was_persistent = False
             return False
@@ -889,7 +871,7 @@ class TrainEngine(Engine):
         parts = w.d_in0_parts
         # (persist_bwd_now: this step's policy decision, taken in forward(); persist_bwd: the plan's flag, which tests clear between two backward passes)
         use_pbwd = bool(getattr(w, "persist_bwd_now", False)) and bool(getattr(w, "persist_bwd", False)) and bool(getattr(w, "opk_valid", False)) and not _redo
-        bwd_done = None
+        bwd_ticket = None
         if getattr(w, "opk_valid", False) and not use_pbwd:
             self.unpack_history(w)            # the persistent forward packed the cell operands; the launch-per-step BPTT reads the histories
         if use_pbwd:
@@ -900,15 +882,13 @@ class TrainEngine(Engine):
             pb.stamps = ptr(self.persist_bwd_stamps) if self.persist_bwd_stamps is not None else None
             pb.opk = ptr(w.opk)
             pb.selftest_fail_step = int(self.persist_bwd_selftest)
-            pb.near_xcd = int(os.environ.get("MSTTS_PERSIST_NEAR", "1") != "0")
+            pb.near_xcd = near_xcd()
             pb.recurrent_bf16 = int(self.persist_bf16)
             call("mstts_decoder_train_bwd_persistent", C.byref(db), C.byref(pb))
             ev = torch.cuda.Event(enable_timing=self.trace_events)
             ev.record()
             self.bptt_end_event = ev             # (bench.py --gpus N: where the first gradient collective starts relative to this)
-            w.pctrl_b_host.copy_(w.pctrl_b, non_blocking=True)
-            bwd_done = torch.cuda.Event()
-            bwd_done.record()
+            bwd_ticket = Ticket(w.pctrl_b, w.pctrl_b_host, decoder_workgroups()).enqueue(torch.cuda.Event())
             parts = 1                        # (on success d_in0 slab 0 holds the complete context gradient; a failed launch re-runs the pass)
         else:
             self._ensure_fallback_packs()
@@ -999,7 +979,7 @@ class TrainEngine(Engine):
             ready.record()
             with torch.cuda.stream(self._enc_stream):
                 self._enc_stream.wait_event(ready)
-                enc_ticket = self._enc_persistent(w, "mstts_lstm_seq_bwd_pair_persistent", bseqs, 1, 32)
+                enc_ticket = self._enc_persistent(w, "mstts_lstm_seq_bwd_pair_persistent", bseqs, 1)
                 if ENC_TAIL_OVERLAP:
                     # ... and the rest of the encoder's backward pass (weight gradients, convolution blocks, embedding: ~45 launches, 1.1 ms, none of
                     # it read by the decoder's products) stays on this stream, behind the launch and beside those products
@@ -1019,7 +999,7 @@ class TrainEngine(Engine):
             if on_ready is not None:
                 on_ready(*self._grad_range("attention/", "decoder/decoder"))
             if enc_persistent:
-                enc_ticket = self._enc_persistent(w, "mstts_lstm_seq_bwd_pair_persistent", bseqs, 1, 32)
+                enc_ticket = self._enc_persistent(w, "mstts_lstm_seq_bwd_pair_persistent", bseqs, 1)
             else:
                 self._ensure_fallback_packs()
                 call("mstts_lstm_seq_bwd_pair", C.byref(bseqs[0]), C.byref(bseqs[1]))    # BPTT of both directions: two launches per step
@@ -1031,31 +1011,22 @@ class TrainEngine(Engine):
         if agree_async is not None and not _redo:
             # every rank, every pass (also one that launched nothing persistent: its word is 1) - the ranks' collective sequences stay in step
             with torch.cuda.stream(self._side):
-                # behind both launches: the decoder's BPTT ended before `bwd_done`, the encoder's before its ticket's event - two waits for
-                # events that have (long) fired when the side stream gets here, at the end of the pass
-                if bwd_done is not None:
-                    self._side.wait_event(bwd_done)
-                if enc_ticket is not None:
-                    self._side.wait_event(enc_ticket[0])
-                if enc_ticket is None and bwd_done is None:      # (nothing persistent in this pass: order the word behind the pass so far)
+                # behind both launches: each ended before its ticket's event - two waits for events that have (long) fired when the side
+                # stream gets here, at the end of the pass
+                tickets = [t for t in (bwd_ticket, enc_ticket) if t is not None]
+                for t in tickets:
+                    self._side.wait_event(t.event)
+                if not tickets:                                  # (nothing persistent in this pass: order the word behind the pass so far)
                     self._side.wait_stream(torch.cuda.current_stream())
-                call("mstts_persist_status", ptr(w.pctrl_b) if bwd_done is not None else None, 256,
-                     ptr(w.enc_ctrl) if enc_ticket is not None else None, enc_ticket[2] if enc_ticket is not None else 0, ptr(w.job_flag))
+                words = [(ptr(t.ctrl), t.expect) if t is not None else (None, 0) for t in (bwd_ticket, enc_ticket)]
+                call("mstts_persist_status", *words[0], *words[1], ptr(w.job_flag))
                 agree_async(w.job_flag)
                 w.job_flag_host.copy_(w.job_flag, non_blocking=True)
                 job_flag = torch.cuda.Event()
                 job_flag.record()
-        passed = True
-        if enc_ticket is not None:
-            passed = self._enc_check(w, enc_ticket)
-        if bwd_done is not None:
-            bwd_done.synchronize()
-            st = w.pctrl_b_host
-            if int(st[1]) != 0 or int(st[2]) != 256:
-                self.persist_bwd_fallbacks += 1
-                self._step_fell_back = True
-                self.persist_last_status = (int(st[0]), int(st[1]), int(st[2]))
-                passed = False
+        passed = enc_ticket is None or self._ticket_ok(enc_ticket, "persist_enc_fallbacks", keep_status=False)
+        if bwd_ticket is not None and not self._ticket_ok(bwd_ticket, "persist_bwd_fallbacks"):
+            passed = False
         if job_flag is not None:
             job_flag.synchronize()
             job_ok = int(w.job_flag_host[0]) == 1            # MIN over the ranks of what mstts_persist_status saw on each

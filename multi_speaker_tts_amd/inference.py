@@ -22,6 +22,7 @@ from . import lib
 from .lib import ACT_NONE, ACT_RELU, ACT_TANH, gemm, ptr, call
 from .masks import MaskSet, step_seed
 from .params import CELL, ENC_CELL, LSA, SPK, SPK_CELL, VOC, VOC_CELL, Dims, ParamStore, bank_suffix
+from .persist import LAST_STEP, PERSIST_COOLDOWN, PERSIST_STRIKES, ROWS_FINISHED, CoolDown, Ticket, decoder_workgroups, lstm_fwd_workgroups, near_xcd
 from .training import BN_EPS, lstm_seq_fwd
 SPK_OVERLAP = os.environ.get("MSTTS_SPK_OVERLAP", "1") != "0"     # inference forward: the speaker stack on its own stream beside the text encoder
 
@@ -48,18 +49,17 @@ def to_host(tensors):
 class _DeferredCheck:
     """Ticket of a sub-graph whose persistent LSTM launches have not been checked yet (InferEngine.speaker_embedding(defer=True))."""
 
-    def __init__(self, eng, fn, a, k, pending, event, host):
-        self.eng, self.fn, self.a, self.k, self.pending, self.event, self.host = eng, fn, a, k, pending, event, host
+    def __init__(self, eng, fn, a, k, ticket):
+        self.eng, self.fn, self.a, self.k, self.ticket, self.pending, self.host = eng, fn, a, k, ticket, ticket.expect, ticket.host
 
     def ok(self):
         """After (or as) the caller's host sync: did every launch of the sub-graph run to its end?  The ticket owns its page-locked read-back
         block (a second deferred call before this one is redeemed - batch prefetch - reads back into ANOTHER block); it goes back to the
         engine's pool here."""
-        self.event.synchronize()
         eng, host = self.eng, self.host
         if host is None:
             raise RuntimeError("a deferred check is redeemed once")
-        good = all(int(host[slot][1]) == 0 and int(host[slot][2]) == n_wg for slot, n_wg in self.pending)
+        good, _ = self.ticket.redeem()
         self.host = None
         eng._deferred_host_pool.append(host)
         if eng.persist_lstm_selftest > 0:
@@ -77,7 +77,7 @@ class _DeferredCheck:
                 return self.fn(*self.a, **self.k)
         finally:
             eng._lstm_retry = False
-            eng._lstm_pending, eng._lstm_copied = [], 0
+            eng._lstm_pending, eng._lstm_ticket = [], None
 
 
 class InferEngine:
@@ -96,8 +96,7 @@ class InferEngine:
         self.persist_infer_selftest = 0      # tests: k > 0 makes the launch abort at step k - 1
         self.persist_infer_stamps = None     # bench: 256 x 24 int64 tensor -> per-stage ticks of the next launch
         self.persist_infer_status = None
-        self._persist_strikes = 0
-        self._persist_off = 0                # decodes left of the cool-down after PERSIST_STRIKES consecutive fallbacks
+        self._persist_cool = CoolDown()      # PERSIST_STRIKES consecutive fallbacks switch the launch off for PERSIST_COOLDOWN decodes
         self.persist_disabled_decodes = 0
         self.non_persistent_decodes = 0      # decodes at the reference widths whose shape the persistent loop does not cover
         self._warned_shapes = set()
@@ -112,7 +111,7 @@ class InferEngine:
         self._lstm_ctrl = None
         self._spk_stream = None
         self._lstm_ctrl_host = None
-        self._lstm_copied = 0
+        self._lstm_ticket = None             # read-back of the launches pending so far, once enqueued
         self._lcache = {}                    # packed recurrent kernels by cell, keyed on ParamStore.version
         self._dcache = {}                    # ... and those both decoder drivers share
         self._pcache = {}                    # variable-derived operands of the persistent decoder, keyed on ParamStore.version
@@ -192,26 +191,25 @@ class InferEngine:
         xch, hist = empty(L_.mstts_persist_lstm_ws_bytes_n(B, ndir) // 4), empty(L_.mstts_persist_lstm_hist_floats_n(T, B, ndir))
         self._keep.extend((xch, hist))
         slot = len(self._lstm_pending)
-        self._lstm_pending.append((slot, ndir * ((B + 31) // 32) * (H // 8)))
+        self._lstm_pending.append((slot, lstm_fwd_workgroups(B, H, ndir)))
         self.persist_lstm_launches += 1
         return pks, ptr(xch), ptr(self._lstm_ctrl, slot * 16), ptr(hist)
 
     def _lstm_ctrl_copy(self):
         """Enqueue the read-back of the control words of the persistent LSTM launches so far (call in front of a host sync)."""
-        if len(self._lstm_pending) > self._lstm_copied:
-            self._lstm_ctrl_host.copy_(self._lstm_ctrl, non_blocking=True)
-            self._lstm_copied = len(self._lstm_pending)
+        if len(self._lstm_pending) > (len(self._lstm_ticket.expect) if self._lstm_ticket is not None else 0):
+            self._lstm_ticket = Ticket(self._lstm_ctrl, self._lstm_ctrl_host, list(self._lstm_pending)).enqueue()
 
     def _lstm_verify(self):
         """After a host sync: did every persistent LSTM launch read back so far run to its end?  Raises _PersistRetry otherwise (the
         forward pass is then re-run with the launch-per-step drivers)."""
-        if self.persist_lstm_selftest > 0 and self._lstm_copied:
+        ticket = self._lstm_ticket
+        if self.persist_lstm_selftest > 0 and ticket is not None:
             self.persist_lstm_selftest -= 1
             raise _PersistRetry("persistent LSTM launch 0: self-test")
-        for slot, n_wg in self._lstm_pending[:self._lstm_copied]:
-            st = self._lstm_ctrl_host[slot]
-            if int(st[1]) != 0 or int(st[2]) != n_wg:
-                raise _PersistRetry("persistent LSTM launch %d: control words %r" % (slot, st[:3].tolist()))
+        ok, status = ticket.redeem() if ticket is not None else (True, ())
+        if not ok:
+            raise _PersistRetry("persistent LSTM launch %d: control words %r" % (ticket.failed, list(status)))
 
     def _lstm_seq(self, x, B, T, cin, H, cell_prefix, out, out_sb, out_st, out_off=0, residual=None, **kw):
         # residual wrapper (output = cell output + input, state untouched): with a dense [B, T, H] output the fused steps run without it
@@ -245,7 +243,7 @@ class InferEngine:
     def _guarded(self, fn, *a, **k):
         """A sub-graph called on its own (outside forward): the control words of its persistent LSTM launches are checked before its
         result is handed out (one stream sync), and the sub-graph is re-run launch by launch if one of them gave up."""
-        self._lstm_pending, self._lstm_copied = [], 0
+        self._lstm_pending, self._lstm_ticket = [], None
         try:
             out = fn(*a, **k)
             if self._lstm_pending:
@@ -261,7 +259,7 @@ class InferEngine:
                 return fn(*a, **k)
             finally:
                 self._lstm_retry = False
-                self._lstm_pending, self._lstm_copied = [], 0
+                self._lstm_pending, self._lstm_ticket = [], None
 
     def speaker_embedding(self, spk_mel, masks=None, defer=False):
         """defer=True (the TRAIN step's frozen speaker stack, MSTTS_SV.py:49-56,211): no host sync here.  Returns (embedding, ticket);
@@ -273,7 +271,7 @@ class InferEngine:
 
     @lib.deterministic_gemm()
     def _deferred(self, fn, *a, **k):
-        self._lstm_pending, self._lstm_copied = [], 0
+        self._lstm_pending, self._lstm_ticket = [], None
         out = fn(*a, **k)
         pending = list(self._lstm_pending)
         if not pending:
@@ -282,10 +280,7 @@ class InferEngine:
         # and in front of the next call's, which reuse the device slots from 0 - tickets may be outstanding together
         pool = self.__dict__.setdefault("_deferred_host_pool", [])
         host = pool.pop() if pool else torch.zeros(64, 16, dtype=torch.int32).pin_memory()
-        host.copy_(self._lstm_ctrl, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        return out, _DeferredCheck(self, fn, a, k, pending, ev, host)
+        return out, _DeferredCheck(self, fn, a, k, Ticket(self._lstm_ctrl, host, pending).enqueue(torch.cuda.Event()))
 
     def encoder(self, token, token_length, spk):
         return self._guarded(self._encoder, token, token_length, spk)
@@ -464,10 +459,27 @@ class InferEngine:
                     warnings.warn("multi_speaker_tts_amd: batch %d x %d tokens is outside the persistent free-running decoder's range "
                                   "(mstts_persist_infer_supported); decoding launch by launch" % (B, T), RuntimeWarning, stacklevel=4)
             return None
-        if self._persist_off > 0:
-            self._persist_off -= 1
+        if not self._persist_cool.admit():
             self.persist_disabled_decodes += 1
             return None
+        ticket = self._persist_infer_launch(q, values, w0f, mk, B, T)
+        ok, status = ticket.redeem()
+        rows, last = ticket.host[ROWS_FINISHED:LAST_STEP + 1].tolist()
+        self.persist_infer_status = status + (rows, last)
+        if not ok:
+            self.persist_infer_fallbacks += 1
+            if self._persist_cool.strike(PERSIST_STRIKES, PERSIST_COOLDOWN):
+                warnings.warn("multi_speaker_tts_amd: two consecutive persistent decoder launches gave up (status %r); decoding launch by "
+                              "launch for the next %d batches" % (self.persist_infer_status, PERSIST_COOLDOWN), RuntimeWarning, stacklevel=4)
+            return None
+        self._persist_cool.clear()
+        self.persist_infer_launches += 1
+        return last if last > 0 else Smax
+
+    def _persist_infer_launch(self, q, values, w0f, mk, B, T):
+        """Operands, the launch, the read-back of its control words and the stream's sync behind them; returns the ticket."""
+        d, L_ = self.d, lib.load()
+        H, A, Pn, NM, M = d.dec_lstm, d.att, d.prenet, d.n_mel, d.mem
         NP = 84
         pw0, opw0 = self.P("decoder/decoder/prenet_0/dense/kernel"); pb0, opb0 = self.P("decoder/decoder/prenet_0/dense/bias")
         pw1, opw1 = self.P("decoder/decoder/prenet_1/dense/kernel"); pb1, opb1 = self.P("decoder/decoder/prenet_1/dense/bias")
@@ -511,24 +523,12 @@ class InferEngine:
         pd.xch, pd.ctrl = ptr(xch), ptr(ctrl)
         pd.stamps = ptr(self.persist_infer_stamps) if self.persist_infer_stamps is not None else None
         pd.selftest_fail_step = int(self.persist_infer_selftest)
-        pd.near_xcd = int(os.environ.get("MSTTS_PERSIST_NEAR", "1") != "0")
+        pd.near_xcd = near_xcd()
         call("mstts_decoder_infer_persistent", C.byref(q), C.byref(pd))
         self._lstm_ctrl_copy()
-        c["ctrl_host"].copy_(ctrl, non_blocking=True)
+        ticket = Ticket(ctrl, c["ctrl_host"], decoder_workgroups()).enqueue()
         torch.cuda.current_stream().synchronize()
-        st = c["ctrl_host"].numpy()
-        self.persist_infer_status = (int(st[0]), int(st[1]), int(st[2]), int(st[4]), int(st[5]))
-        if int(st[1]) != 0 or int(st[2]) != 256:
-            self.persist_infer_fallbacks += 1
-            self._persist_strikes += 1
-            if self._persist_strikes >= 2:
-                self._persist_strikes, self._persist_off = 0, 200
-                warnings.warn("multi_speaker_tts_amd: two consecutive persistent decoder launches gave up (status %r); decoding launch by "
-                              "launch for the next 200 batches" % (self.persist_infer_status,), RuntimeWarning, stacklevel=4)
-            return None
-        self._persist_strikes = 0
-        self.persist_infer_launches += 1
-        return int(st[5]) if int(st[5]) > 0 else Smax
+        return ticket
 
     def postnet(self, linear_bsc, B, S):
         d = self.d
@@ -593,7 +593,7 @@ class InferEngine:
         [5B,64,80] or Speaker_Embedding [B,spk] (numpy or tensors).  Returns the reference's
         inference_Tensor_Dict as numpy arrays: Linear, Mel, Stop (sigmoid), Attention_History [B,T,S], Spectrogram."""
         self._keep = []
-        self._lstm_pending, self._lstm_copied = [], 0
+        self._lstm_pending, self._lstm_ticket = [], None
         dev = self.device
         prof = getattr(self, "profile_phases", False)          # tools/infer_bench.py: wall time per phase (adds a synchronisation behind each)
         marks = [("start", time.perf_counter())]

@@ -17,6 +17,7 @@ from . import lib
 from .lib import call, gemm, ptr
 from .masks import step_seed
 from .params import SPK, SPK_CELL, Dims, ParamStore
+from .persist import Ticket, lstm_bwd_workgroups, lstm_fwd_workgroups
 from .training import Engine, Workspace, _split_k, exponential_decay, lstm_layer_grads, lstm_seq_bwd, lstm_seq_fwd
 
 
@@ -85,7 +86,6 @@ class SpeakerTrainEngine(Engine):
             w.phist = [f(int(lb.mstts_persist_lstm_hist_floats_n(T, N, 1))) for _ in range(L)]   # packed history per layer (the BPTT reads it)
             w.pbws = f(int(lb.mstts_persist_lstm_bwd_floats_n(T, N, 1)))
             w.phist_valid = [False] * L
-            w.groups = (N + 31) // 32
         w.loss_ws = f(int(lb.mstts_ge2e_ws_floats(N, d.spk, 256)))
         w.out3 = f(4)
         w.d_out = f(N, T, d.spk)                                # gradient of a cell's output sequence
@@ -119,7 +119,7 @@ class SpeakerTrainEngine(Engine):
             if getattr(w, "persist", False):
                 call("mstts_persist_lstm_pack", ptr(k, ok + d.spk * 4 * H), 4 * H, ptr(w.pk[i][0]), ptr(w.pk[i][1]))
                 call("mstts_lstm_seq_fwd_persistent", C.byref(q), ptr(w.pk[i][0]), ptr(w.pxch), ptr(w.pctrl), ptr(w.phist[i]))
-                done = w.phist_valid[i] = self._persist_ok(w, 32 * w.groups)
+                done = w.phist_valid[i] = self._persist_ok(w, lstm_fwd_workgroups(N, H, 1))
             if not done:
                 if w.fused:
                     call("mstts_pack_cell_fwd", ptr(k, ok + d.spk * 4 * H), 4 * H, ptr(w.whp), H, H)
@@ -131,9 +131,9 @@ class SpeakerTrainEngine(Engine):
 
     def _persist_ok(self, w, n_wg):
         """Control words of the persistent launch just enqueued: True when it ran to its end (else the caller runs the launch-per-step loop)."""
-        w.pctrl_host.copy_(w.pctrl, non_blocking=True)
+        ticket = Ticket(w.pctrl, w.pctrl_host, n_wg).enqueue()
         torch.cuda.current_stream().synchronize()
-        ok = int(w.pctrl_host[1]) == 0 and int(w.pctrl_host[2]) == n_wg
+        ok, _ = ticket.redeem()
         if not ok:
             self.persist_lstm_fallbacks += 1
         return ok
@@ -157,7 +157,7 @@ class SpeakerTrainEngine(Engine):
             done = False
             if getattr(w, "persist", False) and w.phist_valid[i]:       # (the persistent BPTT reads the packed history of a persistent forward)
                 call("mstts_lstm_seq_bwd_persistent", C.byref(q), ptr(w.pk[i][1]), ptr(w.pxch), ptr(w.pctrl), ptr(w.phist[i]), ptr(w.pbws))
-                done = self._persist_ok(w, 16 * w.groups)
+                done = self._persist_ok(w, lstm_bwd_workgroups(N, 1))
             if not done:
                 call("mstts_lstm_seq_bwd", C.byref(q))
             d_in = w.d_in if d_out is w.d_out else w.d_out

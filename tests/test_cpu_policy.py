@@ -13,7 +13,7 @@ from helpers import dims_pair
 
 def _policy_obj():
     from multi_speaker_tts_amd import engine as E
-    o = types.SimpleNamespace(_persist_strikes=0, _persist_off=0, _persist_warned=False, persist_disabled_steps=0, persist_last_status=(256, 1, 0))
+    o = types.SimpleNamespace(_persist_cool=E.CoolDown(), _persist_warned=False, persist_disabled_steps=0, persist_last_status=(256, 1, 0))
     o.begin = types.MethodType(E.TrainEngine._persist_begin_step, o)
     return E, o
 
@@ -22,12 +22,12 @@ def test_two_consecutive_fallbacks_start_a_cooldown_and_probe_again(monkeypatch)
     E, o = _policy_obj()
     monkeypatch.setattr(E, "PERSIST_COOLDOWN", 4)
     assert o.begin() is True                               # step 1: healthy
-    assert o.begin() is True and o._persist_strikes == 0
+    assert o.begin() is True and o._persist_cool.strikes == 0
     o._step_fell_back = True                               # step 2 fell back
-    assert o.begin() is True and o._persist_strikes == 1   # one strike: still trying
-    assert o.begin() is True and o._persist_strikes == 0   # a healthy step in between clears the strike
+    assert o.begin() is True and o._persist_cool.strikes == 1   # one strike: still trying
+    assert o.begin() is True and o._persist_cool.strikes == 0   # a healthy step in between clears the strike
     o._step_fell_back = True
-    assert o.begin() is True and o._persist_strikes == 1
+    assert o.begin() is True and o._persist_cool.strikes == 1
     o._step_fell_back = True
     with warnings.catch_warnings(record=True) as rec:
         warnings.simplefilter("always")
