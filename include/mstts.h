@@ -718,7 +718,7 @@ typedef struct {
     float* q_hist; float* align_hist; float* cum_hist;
     float* gates_ws; float* energy_ws;      /* [parts,B,4H] (parts = max skinny K-splits, see mstts_decoder_train_ws_floats), 2*B*T+2 floats (8-byte aligned) */
     float* q_ws;                            /* [parts,B,A] query partials */
-    int32_t chains;                         /* independent row groups run on separate HIP streams (0/1 = one; must divide B) */
+    int32_t chains;                         /* ignored (row groups on separate HIP streams were removed; kept for the ABI) */
     /* optional bf16 mode of the recurrent products (BASELINE config 3): packed bf16 copies of w0f / w1 / wq made with
      * mstts_pack_bf16_fwd (first three) and mstts_pack_bf16_bwd (last three) using the split counts of
      * mstts_decoder_bf16_splits(H, M, A, out[6]); all six non-NULL -> cell / query products and their data gradients run

@@ -76,6 +76,10 @@ __device__ __forceinline__ float sum_parts(const float* __restrict__ p, int part
 }
 constexpr int MSTTS_MAX_PARTS = 16;
 
+// split counts of the packed bf16 skinny products with at most `cap` slices, 0 = shape not covered (skinny_bf16.hip)
+int skinny_bf16_fwd_split(long N, long K, int cap);
+int skinny_bf16_bwd_split(long R, long N, int cap);
+
 // Wave-wide reductions on the DPP path (row operations inside the VALU, a few cycles each) instead of ds_bpermute shuffles (an
 // LDS round trip per step: six dependent steps were ~0.25 us on the critical path of the latency-bound per-step kernels).
 //   quad_perm 1,0,3,2 / 2,3,0,1 -> quads ; row_half_mirror -> 8 ; row_mirror -> rows of 16 ; row_bcast15 (rows 1, 3) -> halves of 32

@@ -5,6 +5,23 @@
 //   mstts_decoder_train_fwd/bwd   - the teacher-forced attention decoder loop and its BPTT
 //                                   [Modules.py:76-119,323-472 + TF AttentionWrapper]
 //   mstts_decoder_infer_steps     - the free-running loop            [Modules.py:212-237]
+//
+// A step is the same chain in every driver - cell product, cell update, (query, attention, projection) - and each link has tiers,
+// chosen per call from the optional derived copies in the descriptor and the *_supported predicates:
+//   cell, forward     fused cell (mstts_cell_fwd: product + update in one launch): packed kernel and packed activation block
+//                     given (w0p / w1p / act_p, wh_p / h_p, w0sp; bf16: w0p16 / w1p16) and mstts_cell_fwd[_bf16]_supported;
+//                     else recurrent_fwd + mstts_lstm_point_fwd.
+//   recurrent_fwd     bf16 packed product (all six bf_* copies given and mstts_decoder_bf16_splits) > skinny K-split product
+//                     (mstts_skinny_fwd_splits > 0, float4-aligned operands) > tiled GEMM.
+//   attention         fused query (mstts_lsa_step_fwd_q: mstts_lsa_step_q_supported, lsa.loc_kt, A == 128, granule workspace large
+//                     enough) > query product + mstts_lsa_step_fwd.  Free-running loop only, on top of the fused query and the fused
+//                     cells: fused query + projection (mstts_lsa_step_fwd_qp: wp_own, vp, mstts_lsa_step_qp_supported), and with it
+//                     the next step's prenet (mstts_lsa_step_prenet_supported); else project_step (skinny product + proj_finish).
+//   attention, BPTT   single launch (mstts_lsa_step_bwd) when H + M and H are multiples of 4, else d_align + d_energy launches.
+//   recurrent_bwd     bf16 packed product > packed fp32 product (w0f_bp / w1_bp / wq_bp given, R % 32 == 0) > skinny N-split
+//                     product (mstts_skinny_bwd_splits > 0) > tiled GEMM.
+//   query gradient    folded into cell 1's pointwise backward (wq_t given, A == 128, H % 128 == 0, 1 / 2 / 4 / 8 slabs), else a
+//                     recurrent_bwd of its own.
 #include "common.h"
 #include "prenet_body.h"
 
@@ -71,78 +88,121 @@ static int zero(float* p, long n, mstts_stream_t s) {
     return MSTTS_OK;
 }
 
-// one fused cell step (product + cell update, cell.hip); out_p / hn_p: packed blocks of the cells that consume m / h' next
-static int cell_step(const float* Xp, const float* Wp, long K, const float* xw, long xw_ld, const float* bias,
-                     const float* c_prev, const float* h_prev, long h_prev_ld, const uint8_t* zc, const uint8_t* zh, float zoneout,
-                     float* out, long out_ld, float* c_next, float* h_next, long h_next_ld, float* acts, float* c_raw, long B, long H,
-                     float* out_p, long out_p_K, long out_p_col0, float* hn_p, long hn_p_K, long hn_p_col0, mstts_stream_t s, int bf16 = 0) {
+// ---------------------------------------------------------------------------------------------
+// One cell's per-step slots.  State slot k of c sits at c + k * B * H, of h at h + k * h_step (rows of stride h_ld: the decoder keeps
+// h inside the next product's input rows); the masks and the BPTT saves of step st at st * B * H (acts: 4 * B * H), NULL = none.
+// ---------------------------------------------------------------------------------------------
+struct CellSlots {
+    long B, H;
+    float* c;
+    float* h; long h_ld, h_step;
+    const uint8_t* zc; const uint8_t* zh; float zoneout;
+    float* acts; float* c_raw;
+};
+// what the BPTT reads of them
+struct CellSaved {
+    long B, H;
+    const float* c;
+    const uint8_t* zc; const uint8_t* zh; float zoneout;
+    const float* acts; const float* c_raw;
+};
+static CellSaved saved(const CellSlots& k) { return CellSaved{k.B, k.H, k.c, k.zc, k.zh, k.zoneout, k.acts, k.c_raw}; }
+#define SLOT(ptr, n) ((ptr) ? (ptr) + (n) : nullptr)
+
+// pointwise cell update of step st: state slot rd -> slot wr, gates = sum of `parts` slabs; the caller adds xw / bias / out (and the sequence fields)
+static void fill_point_fwd(mstts_lstm_point_fwd_desc* p, const CellSlots& k, long st, long rd, long wr, const float* gates, int parts) {
+    const long BH = k.B * k.H;
+    memset(p, 0, sizeof(*p));
+    p->B = k.B; p->H = k.H; p->gates_h = gates; p->gates_parts = parts; p->gates_pstride = 4 * BH;
+    p->c_prev = k.c + rd * BH; p->h_prev = k.h + rd * k.h_step; p->h_prev_ld = k.h_ld;
+    p->zc = SLOT(k.zc, st * BH); p->zh = SLOT(k.zh, st * BH); p->zoneout = k.zoneout;
+    p->c_next = k.c + wr * BH; p->h_next = k.h + wr * k.h_step; p->h_next_ld = k.h_ld;
+    p->acts_out = SLOT(k.acts, st * 4 * BH); p->c_raw = SLOT(k.c_raw, st * BH);
+}
+// the same slots of a fused cell step (product + cell update, cell.hip); the caller adds the operands, xw / bias / out and the packed destinations
+static void fill_cell_fwd(mstts_cell_fwd_desc* q, const CellSlots& k, long st, long rd, long wr) {
+    const long BH = k.B * k.H;
+    memset(q, 0, sizeof(*q));
+    q->B = k.B; q->H = k.H;
+    q->c_prev = k.c + rd * BH; q->h_prev = k.h + rd * k.h_step; q->h_prev_ld = k.h_ld;
+    q->zc = SLOT(k.zc, st * BH); q->zh = SLOT(k.zh, st * BH); q->zoneout = k.zoneout;
+    q->c_next = k.c + wr * BH; q->h_next = k.h + wr * k.h_step; q->h_next_ld = k.h_ld;
+    q->acts = SLOT(k.acts, st * 4 * BH); q->c_raw = SLOT(k.c_raw, st * BH);
+}
+// pointwise backward of step st: ds = the cell's state gradients [d_c 2][d_h 2][B][H], ping-pong (read `cur`, write the other); the
+// caller adds the output-gradient addends
+static void fill_point_bwd(mstts_lstm_point_bwd_desc* p, const CellSaved& k, long st, float* ds, int cur, float* dgates) {
+    const long BH = k.B * k.H;
+    memset(p, 0, sizeof(*p));
+    p->B = k.B; p->H = k.H;
+    p->d_c_state = ds + cur * BH; p->d_h_state = ds + (2 + cur) * BH; p->d_c_prev = ds + (cur ^ 1) * BH; p->d_h_prev = ds + (2 + (cur ^ 1)) * BH;
+    p->acts = k.acts + st * 4 * BH; p->c_raw = k.c_raw + st * BH; p->c_prev = k.c + st * BH;
+    p->zc = SLOT(k.zc, st * BH); p->zh = SLOT(k.zh, st * BH); p->zoneout = k.zoneout;
+    p->dgates = dgates;
+}
+
+static mstts_cell_packed_dst packed(float* base, long K, long col0, int bf16) {
+    mstts_cell_packed_dst o = {base, K, col0, bf16};
+    return o;
+}
+// one fused cell step; out_p / hn_p: packed blocks of the cells that consume m / h' next
+static int cell_step(const CellSlots& k, long st, long rd, long wr, const float* Xp, const float* Wp, long K, const float* xw, const float* bias,
+                     float* out, long out_ld, mstts_cell_packed_dst out_p, mstts_cell_packed_dst hn_p, int bf16, mstts_stream_t s) {
     mstts_cell_fwd_desc q;
-    memset(&q, 0, sizeof(q));
-    q.bf16 = bf16; q.out_p.bf16 = bf16; q.h_next_p.bf16 = bf16;
-    q.B = B; q.H = H; q.K = K; q.Xp = Xp; q.Wp = Wp; q.xw = xw; q.xw_ld = xw_ld; q.bias = bias;
-    q.c_prev = c_prev; q.h_prev = h_prev; q.h_prev_ld = h_prev_ld; q.zc = zc; q.zh = zh; q.zoneout = zoneout;
-    q.out = out; q.out_ld = out_ld; q.c_next = c_next; q.h_next = h_next; q.h_next_ld = h_next_ld; q.acts = acts; q.c_raw = c_raw;
-    q.out_p.base = out_p; q.out_p.K = out_p_K; q.out_p.col0 = out_p_col0;
-    q.h_next_p.base = hn_p; q.h_next_p.K = hn_p_K; q.h_next_p.col0 = hn_p_col0;
+    fill_cell_fwd(&q, k, st, rd, wr);
+    q.bf16 = bf16; q.K = K; q.Xp = Xp; q.Wp = Wp; q.xw = xw; q.xw_ld = xw ? 4 * k.H : 0; q.bias = bias;
+    q.out = out; q.out_ld = out_ld; q.out_p = out_p; q.h_next_p = hn_p;
     return mstts_cell_fwd(&q, s);
 }
 
-// X[M,K] . W[K,N]: skinny K-split kernel when the shape fits (parts slabs in P), else the tiled GEMM
-static int xw_fwd(const float* X, long ldx, const float* W, long ldw, float* P, long M, long N, long K, int splits, int* parts,
-                  mstts_stream_t s) {
-    if (splits > 0 && ldx % 4 == 0 && ldw % 4 == 0 && aligned16(X) && aligned16(W)) {
-        *parts = splits;
-        return mstts_skinny_fwd(X, ldx, W, ldw, P, 0, M, N, K, splits, s);
+// One kernel of a recurrent product: row-major [rows, cols] (row stride ld), its split count for the direction it is used in (0: the
+// tiled GEMM) and its optional derived copies
+struct Weights {
+    const float* W; long ld, rows, cols; int splits;
+    const float* Wp;                    // data-gradient product only: fp32 copy packed for exactly `splits` slices, or NULL
+    const void* Wbf; int bsplit;        // bf16 copy packed for `bsplit` slices, or NULL (fp32 products)
+};
+// X[M,rows] . W -> *parts slabs [M,cols] in P: the bf16 packed product, else the skinny K-split kernel when the shape fits, else the tiled GEMM
+static int recurrent_fwd(const Weights& w, const float* X, long ldx, float* P, long M, int* parts, mstts_stream_t s) {
+    if (w.Wbf) {
+        *parts = w.bsplit;
+        return mstts_skinny_fwd_bf16(X, ldx, w.Wbf, P, 0, M, w.cols, w.rows, w.bsplit, s);
+    }
+    if (w.splits > 0 && ldx % 4 == 0 && w.ld % 4 == 0 && aligned16(X) && aligned16(w.W)) {
+        *parts = w.splits;
+        return mstts_skinny_fwd(X, ldx, w.W, w.ld, P, 0, M, w.cols, w.rows, w.splits, s);
     }
     *parts = 1;
-    return gemm(X, ldx, W, ldw, 0, P, N, M, N, K, nullptr, 0, 0, s);
+    return gemm(X, ldx, w.W, w.ld, 0, P, w.cols, M, w.cols, w.rows, nullptr, 0, 0, s);
 }
-// dG[M,N] . W[R,N]^T   (Wp: optional packed copy of W for exactly `splits` slices)
-static int xw_bwd(const float* dG, long ldg, const float* W, long ldw, float* P, long pstride, long M, long R, long N, int splits,
-                  int* parts, mstts_stream_t s, const float* Wp = nullptr) {
-    if (Wp && splits > 0 && R % 32 == 0 && ldg % 4 == 0 && aligned16(dG) && aligned16(Wp)) {
-        *parts = splits;
-        return mstts_skinny_bwd_packed(dG, ldg, Wp, P, pstride, M, R, N, splits, s);
+// dG[M,cols] . W^T -> *parts slabs [M,rows] in P (stride pstride, 0 = M * rows): the bf16 packed product, else the packed fp32 product,
+// else the skinny N-split kernel, else the tiled GEMM
+static int recurrent_bwd(const Weights& w, const float* dG, long ldg, float* P, long pstride, long M, int* parts, mstts_stream_t s) {
+    if (w.Wbf) {
+        *parts = w.bsplit;
+        return mstts_skinny_bwd_bf16(dG, ldg, w.Wbf, P, pstride, M, w.rows, w.cols, w.bsplit, s);
     }
-    if (splits > 0 && ldg % 4 == 0 && ldw % 4 == 0 && aligned16(dG) && aligned16(W)) {
-        *parts = splits;
-        return mstts_skinny_bwd(dG, ldg, W, ldw, P, pstride, M, R, N, splits, s);
+    if (w.Wp && w.splits > 0 && w.rows % 32 == 0 && ldg % 4 == 0 && aligned16(dG) && aligned16(w.Wp)) {
+        *parts = w.splits;
+        return mstts_skinny_bwd_packed(dG, ldg, w.Wp, P, pstride, M, w.rows, w.cols, w.splits, s);
+    }
+    if (w.splits > 0 && ldg % 4 == 0 && w.ld % 4 == 0 && aligned16(dG) && aligned16(w.W)) {
+        *parts = w.splits;
+        return mstts_skinny_bwd(dG, ldg, w.W, w.ld, P, pstride, M, w.rows, w.cols, w.splits, s);
     }
     *parts = 1;
-    return gemm(dG, ldg, W, ldw, 1, P, R, M, R, N, nullptr, 0, 0, s);
+    return gemm(dG, ldg, w.W, w.ld, 1, P, w.rows, M, w.rows, w.cols, nullptr, 0, 0, s);
 }
 
 // ---- bf16 recurrent products (BASELINE config 3): split counts capped by the fp32 path's, so every workspace / slab count the
 // caller sized for fp32 also holds the bf16 path; the counts are baked into the packed kernels, hence exported.
-static int bf_fwd_split(long N, long K, int cap) {
-    if (N % 64 != 0 || K % 64 != 0 || cap < 1) return 0;
-    const long strips = N / 64, units = K / 64;
-    long best = 0, best_d = 1L << 40;
-    for (long ks = 1; ks <= cap && ks <= units; ++ks) {
-        if (units % ks != 0 || K / ks > 512) continue;
-        const long dd = labs(strips * ks - 512);
-        if (dd < best_d) { best_d = dd; best = ks; }
-    }
-    return (int)best;
-}
-static int bf_bwd_split(long R, long N, int cap) {
-    if (R % 32 != 0 || N % 64 != 0 || cap < 1) return 0;
-    const long strips = R / 32, units = N / 64;
-    long best = 0, best_d = 1L << 40;
-    for (long ns = 1; ns <= cap && ns <= units; ++ns) {
-        if (units % ns != 0 || N / ns > 1024) continue;
-        const long dd = labs(strips * ns - 512);
-        if (dd < best_d) { best_d = dd; best = ns; }
-    }
-    return (int)best;
-}
 /* out = {fwd cell0, fwd cell1, fwd query, bwd cell0, bwd cell1, bwd query}; returns 1 when the bf16 decoder path can run */
 extern "C" int32_t mstts_decoder_bf16_splits(int64_t H, int64_t M, int64_t A, int32_t* out) {
     const long W0 = M + H, W1 = 2 * H;
     const int c0 = mstts_skinny_fwd_splits(4 * H, W0), c1 = mstts_skinny_fwd_splits(4 * H, W1), cq = mstts_skinny_fwd_splits(A, H);
     const int d0 = mstts_skinny_bwd_splits(W0, 4 * H), d1 = mstts_skinny_bwd_splits(W1, 4 * H), dq = mstts_skinny_bwd_splits(H, A);
-    int v[6] = {bf_fwd_split(4 * H, W0, c0), bf_fwd_split(4 * H, W1, c1), bf_fwd_split(A, H, cq),
-                d0 > 0 ? bf_bwd_split(W0, 4 * H, d0) : 0, bf_bwd_split(W1, 4 * H, d1), bf_bwd_split(H, A, dq > 1 ? dq : 1)};
+    int v[6] = {skinny_bf16_fwd_split(4 * H, W0, c0), skinny_bf16_fwd_split(4 * H, W1, c1), skinny_bf16_fwd_split(A, H, cq),
+                d0 > 0 ? skinny_bf16_bwd_split(W0, 4 * H, d0) : 0, skinny_bf16_bwd_split(W1, 4 * H, d1), skinny_bf16_bwd_split(H, A, dq > 1 ? dq : 1)};
     // the d_in0 slabs are counted by the caller (mstts_decoder_train_bwd_parts): the bf16 product must write exactly as many
     if (v[3] != d0) v[3] = (d0 > 0 && (4 * H) % (64L * d0) == 0 && 4 * H / d0 <= 1024 && W0 % 32 == 0) ? d0 : 0;
     int ok = 1;
@@ -150,14 +210,37 @@ extern "C" int32_t mstts_decoder_bf16_splits(int64_t H, int64_t M, int64_t A, in
     return ok;
 }
 
-static bool seq_fused_ok(const mstts_lstm_seq_fwd_desc* d);
-static void seq_cell_desc(const mstts_lstm_seq_fwd_desc* d, long t, mstts_cell_fwd_desc* q);
-static int seq_fused_begin(const mstts_lstm_seq_fwd_desc* d, mstts_stream_t s);
-
+// ---------------------------------------------------------------------------------------------
+// sequence loops (tf.nn.dynamic_rnn)
+// ---------------------------------------------------------------------------------------------
 extern "C" int64_t mstts_lstm_seq_ws_floats(int64_t B, int64_t H, int32_t backward) {
     int p = backward ? mstts_skinny_bwd_splits(H, 4 * H) : mstts_skinny_fwd_splits(4 * H, H);
     if (p < 1) p = 1;
     return backward ? 4 * B * H + (int64_t)p * B * H : (int64_t)p * B * 4 * H;
+}
+
+static CellSlots seq_slots(const mstts_lstm_seq_fwd_desc* d) {
+    return CellSlots{d->B, d->H, d->c_hist, d->h_hist, d->H, d->B * d->H, d->zc, d->zh, d->zoneout, d->acts, d->c_raw};
+}
+// ---- fused sequence steps: one mstts_cell_fwd launch per step (recurrent product + cell update), h carried in packed blocks
+static bool seq_fused_ok(const mstts_lstm_seq_fwd_desc* d) {
+    return d->wh_p && d->h_p && !d->residual && mstts_cell_fwd_supported(d->H, d->H);
+}
+static void seq_cell_desc(const mstts_lstm_seq_fwd_desc* d, long t, mstts_cell_fwd_desc* q) {
+    const long T = d->T, H = d->H, blk = mstts_cell_act_floats(d->B, H);
+    fill_cell_fwd(q, seq_slots(d), t, t, t + 1);
+    q->K = H; q->Xp = d->h_p + (t & 1) * blk; q->Wp = d->wh_p;
+    q->xw = d->xw; q->xw_ld = T * 4 * H; q->xw_st = 4 * H;
+    q->out = d->out; q->out_ld = d->out_sb; q->out_st = d->out_st;
+    q->h_next_p = packed(d->h_p + ((t + 1) & 1) * blk, H, 0, 0);
+    q->lengths = d->lengths; q->step = (int)t; q->reverse = d->reverse;
+}
+static int seq_fused_begin(const mstts_lstm_seq_fwd_desc* d, mstts_stream_t s) {
+    MSTTS_REQUIRE(d->xw && d->c_hist && d->h_hist && d->out, MSTTS_ERR_SHAPE, "lstm_seq_fwd: null pointer");
+    MSTTS_REQUIRE(!(d->reverse && !d->lengths), MSTTS_ERR_SHAPE, "lstm_seq_fwd: reverse needs a lengths array (pass T for every row)");
+    RC(zero(d->c_hist, d->B * d->H, s));
+    RC(zero(d->h_hist, d->B * d->H, s));
+    return zero(d->h_p, 2 * mstts_cell_act_floats(d->B, d->H), s);
 }
 
 extern "C" int mstts_lstm_seq_fwd(const mstts_lstm_seq_fwd_desc* d, mstts_stream_t s) {
@@ -173,53 +256,22 @@ extern "C" int mstts_lstm_seq_fwd(const mstts_lstm_seq_fwd_desc* d, mstts_stream
         }
         return MSTTS_OK;
     }
-    const int sp = mstts_skinny_fwd_splits(4 * H, H);
+    const Weights wh = {d->wh, d->wh_ld, H, 4 * H, mstts_skinny_fwd_splits(4 * H, H), nullptr, nullptr, 0};
+    const CellSlots k = seq_slots(d);
     RC(zero(d->c_hist, BH, s));
     RC(zero(d->h_hist, BH, s));
     for (long t = 0; t < T; ++t) {
         int parts = 1;
-        RC(xw_fwd(d->h_hist + t * BH, H, d->wh, d->wh_ld, d->gates_ws, B, 4 * H, H, sp, &parts, s));
+        RC(recurrent_fwd(wh, d->h_hist + t * BH, H, d->gates_ws, B, &parts, s));
         mstts_lstm_point_fwd_desc p;
-        memset(&p, 0, sizeof(p));
-        p.B = B; p.H = H; p.gates_h = d->gates_ws; p.gates_parts = parts; p.gates_pstride = 4 * BH;
+        fill_point_fwd(&p, k, t, t, t + 1, d->gates_ws, parts);
         p.xw = d->xw; p.xw_sb = T * 4 * H; p.xw_st = 4 * H;
-        p.c_prev = d->c_hist + t * BH; p.h_prev = d->h_hist + t * BH;
-        p.zc = d->zc ? d->zc + t * BH : nullptr; p.zh = d->zh ? d->zh + t * BH : nullptr;
-        p.zoneout = d->zoneout; p.lengths = d->lengths; p.step = (int)t; p.reverse = d->reverse;
+        p.lengths = d->lengths; p.step = (int)t; p.reverse = d->reverse;
         p.residual = d->residual; p.res_sb = T * H; p.res_st = H;
         p.out = d->out; p.out_sb = d->out_sb; p.out_st = d->out_st;
-        p.c_next = d->c_hist + (t + 1) * BH; p.h_next = d->h_hist + (t + 1) * BH;
-        p.acts_out = d->acts ? d->acts + t * 4 * BH : nullptr;
-        p.c_raw = d->c_raw ? d->c_raw + t * BH : nullptr;
         RC(mstts_lstm_point_fwd(&p, s));
     }
     return MSTTS_OK;
-}
-
-// ---- fused sequence steps: one mstts_cell_fwd launch per step (recurrent product + cell update), h carried in packed blocks
-static bool seq_fused_ok(const mstts_lstm_seq_fwd_desc* d) {
-    return d->wh_p && d->h_p && !d->residual && mstts_cell_fwd_supported(d->H, d->H);
-}
-static void seq_cell_desc(const mstts_lstm_seq_fwd_desc* d, long t, mstts_cell_fwd_desc* q) {
-    const long B = d->B, T = d->T, H = d->H, BH = B * H, blk = mstts_cell_act_floats(B, H);
-    memset(q, 0, sizeof(*q));
-    q->B = B; q->H = H; q->K = H;
-    q->Xp = d->h_p + (t & 1) * blk; q->Wp = d->wh_p;
-    q->xw = d->xw; q->xw_ld = T * 4 * H; q->xw_st = 4 * H;
-    q->c_prev = d->c_hist + t * BH; q->h_prev = d->h_hist + t * BH; q->h_prev_ld = H;
-    q->zc = d->zc ? d->zc + t * BH : nullptr; q->zh = d->zh ? d->zh + t * BH : nullptr; q->zoneout = d->zoneout;
-    q->out = d->out; q->out_ld = d->out_sb; q->out_st = d->out_st;
-    q->c_next = d->c_hist + (t + 1) * BH; q->h_next = d->h_hist + (t + 1) * BH; q->h_next_ld = H;
-    q->acts = d->acts ? d->acts + t * 4 * BH : nullptr; q->c_raw = d->c_raw ? d->c_raw + t * BH : nullptr;
-    q->h_next_p.base = d->h_p + ((t + 1) & 1) * blk; q->h_next_p.K = H; q->h_next_p.col0 = 0;
-    q->lengths = d->lengths; q->step = (int)t; q->reverse = d->reverse;
-}
-static int seq_fused_begin(const mstts_lstm_seq_fwd_desc* d, mstts_stream_t s) {
-    MSTTS_REQUIRE(d->xw && d->c_hist && d->h_hist && d->out, MSTTS_ERR_SHAPE, "lstm_seq_fwd: null pointer");
-    MSTTS_REQUIRE(!(d->reverse && !d->lengths), MSTTS_ERR_SHAPE, "lstm_seq_fwd: reverse needs a lengths array (pass T for every row)");
-    RC(zero(d->c_hist, d->B * d->H, s));
-    RC(zero(d->h_hist, d->B * d->H, s));
-    return zero(d->h_p, 2 * mstts_cell_act_floats(d->B, d->H), s);
 }
 
 extern "C" int mstts_lstm_seq_fwd_pair(const mstts_lstm_seq_fwd_desc* a, const mstts_lstm_seq_fwd_desc* b, mstts_stream_t s) {
@@ -239,6 +291,35 @@ extern "C" int mstts_lstm_seq_fwd_pair(const mstts_lstm_seq_fwd_desc* a, const m
     return MSTTS_OK;
 }
 
+// BPTT step t of a sequence.  ws = [d_c 2][d_h 2][B][H] ping-pong, then dgates . Wh^T of the later step in `parts` slabs [parts][B][H]
+static void seq_point_bwd_desc(const mstts_lstm_seq_bwd_desc* d, long t, int cur, int parts, mstts_lstm_point_bwd_desc* p) {
+    const long B = d->B, T = d->T, H = d->H, BH = B * H;
+    const CellSaved k = {B, H, d->c_hist, d->zc, d->zh, d->zoneout, d->acts, d->c_raw};
+    fill_point_bwd(p, k, t, d->ws, cur, d->dgates_step + t * 4 * BH);
+    p->d_out = d->d_out; p->dout_sb = d->dout_sb; p->dout_st = d->dout_st;
+    p->d_h_state2 = (t == T - 1) ? nullptr : d->ws + 4 * BH; p->dhs2_ld = H; p->dhs2_parts = parts; p->dhs2_pstride = BH;
+    p->lengths = d->lengths; p->step = (int)t; p->reverse = d->reverse;
+    p->dgates_pos = d->dgates_pos; p->dgp_sb = T * 4 * H; p->dgp_st = 4 * H;
+}
+
+extern "C" int mstts_lstm_seq_bwd(const mstts_lstm_seq_bwd_desc* d, mstts_stream_t s) {
+    MSTTS_REQUIRE(d && d->wh && d->d_out && d->c_hist && d->acts && d->c_raw && d->dgates_step && d->ws, MSTTS_ERR_SHAPE,
+                  "lstm_seq_bwd: null pointer");
+    MSTTS_REQUIRE(!(d->reverse && !d->lengths), MSTTS_ERR_SHAPE, "lstm_seq_bwd: reverse needs a lengths array");
+    const long B = d->B, T = d->T, H = d->H, BH = B * H;
+    const Weights wh = {d->wh, d->wh_ld, H, 4 * H, mstts_skinny_bwd_splits(H, 4 * H), nullptr, nullptr, 0};
+    RC(zero(d->ws, 4 * BH, s));
+    int cur = 0, parts = 1;
+    for (long t = T - 1; t >= 0; --t, cur ^= 1) {
+        mstts_lstm_point_bwd_desc p;
+        seq_point_bwd_desc(d, t, cur, parts, &p);
+        RC(mstts_lstm_point_bwd(&p, s));
+        // recurrent part of d_h_prev = dgates . Wh^T (slabs, consumed by the next iteration)
+        RC(recurrent_bwd(wh, p.dgates, 4 * H, d->ws + 4 * BH, 0, B, &parts, s));
+    }
+    return MSTTS_OK;
+}
+
 extern "C" int mstts_lstm_seq_bwd_pair(const mstts_lstm_seq_bwd_desc* a, const mstts_lstm_seq_bwd_desc* b, mstts_stream_t s) {
     MSTTS_REQUIRE(a && b, MSTTS_ERR_SHAPE, "lstm_seq_bwd_pair: null descriptor");
     const long B = a->B, T = a->T, H = a->H, BH = B * H;
@@ -249,69 +330,18 @@ extern "C" int mstts_lstm_seq_bwd_pair(const mstts_lstm_seq_bwd_desc* a, const m
         RC(mstts_lstm_seq_bwd(a, s));
         return mstts_lstm_seq_bwd(b, s);
     }
-    const mstts_lstm_seq_bwd_desc* dd[2] = {a, b};
-    for (int k = 0; k < 2; ++k) {
-        MSTTS_REQUIRE(dd[k]->wh && dd[k]->d_out && dd[k]->c_hist && dd[k]->acts && dd[k]->c_raw && dd[k]->ws, MSTTS_ERR_SHAPE, "lstm_seq_bwd_pair: null pointer");
-        MSTTS_REQUIRE(!(dd[k]->reverse && !dd[k]->lengths), MSTTS_ERR_SHAPE, "lstm_seq_bwd_pair: reverse needs a lengths array");
-        RC(zero(dd[k]->ws, 4 * BH, s));
+    for (const mstts_lstm_seq_bwd_desc* d : {a, b}) {
+        MSTTS_REQUIRE(d->wh && d->d_out && d->c_hist && d->acts && d->c_raw && d->ws, MSTTS_ERR_SHAPE, "lstm_seq_bwd_pair: null pointer");
+        MSTTS_REQUIRE(!(d->reverse && !d->lengths), MSTTS_ERR_SHAPE, "lstm_seq_bwd_pair: reverse needs a lengths array");
+        RC(zero(d->ws, 4 * BH, s));
     }
     int cur = 0;
-    for (long t = T - 1; t >= 0; --t) {
-        const int nxt = cur ^ 1;
-        mstts_lstm_point_bwd_desc p[2];
-        for (int k = 0; k < 2; ++k) {
-            const mstts_lstm_seq_bwd_desc* d = dd[k];
-            float* dc[2] = {d->ws, d->ws + BH};
-            float* dh[2] = {d->ws + 2 * BH, d->ws + 3 * BH};
-            float* dhg = d->ws + 4 * BH;
-            memset(&p[k], 0, sizeof(p[k]));
-            p[k].B = B; p[k].H = H;
-            p[k].d_out = d->d_out; p[k].dout_sb = d->dout_sb; p[k].dout_st = d->dout_st;
-            p[k].d_c_state = dc[cur]; p[k].d_h_state = dh[cur];
-            p[k].d_h_state2 = (t == T - 1) ? nullptr : dhg; p[k].dhs2_ld = H; p[k].dhs2_parts = sp; p[k].dhs2_pstride = BH;
-            p[k].acts = d->acts + t * 4 * BH; p[k].c_raw = d->c_raw + t * BH; p[k].c_prev = d->c_hist + t * BH;
-            p[k].zc = d->zc ? d->zc + t * BH : nullptr; p[k].zh = d->zh ? d->zh + t * BH : nullptr;
-            p[k].zoneout = d->zoneout; p[k].lengths = d->lengths; p[k].step = (int)t; p[k].reverse = d->reverse;
-            p[k].dgates = d->dgates_step + t * 4 * BH;
-            p[k].dgates_pos = d->dgates_pos; p[k].dgp_sb = T * 4 * H; p[k].dgp_st = 4 * H;
-            p[k].d_c_prev = dc[nxt]; p[k].d_h_prev = dh[nxt];
-        }
-        RC(mstts_lstm_point_bwd_pair(&p[0], &p[1], s));
-        RC(mstts_skinny_bwd_pair(p[0].dgates, p[1].dgates, 4 * H, a->wh, b->wh, a->wh_ld, a->ws + 4 * BH, b->ws + 4 * BH, 0, B, H, 4 * H, sp, s));
-        cur = nxt;
-    }
-    return MSTTS_OK;
-}
-
-extern "C" int mstts_lstm_seq_bwd(const mstts_lstm_seq_bwd_desc* d, mstts_stream_t s) {
-    MSTTS_REQUIRE(d && d->wh && d->d_out && d->c_hist && d->acts && d->c_raw && d->dgates_step && d->ws, MSTTS_ERR_SHAPE,
-                  "lstm_seq_bwd: null pointer");
-    MSTTS_REQUIRE(!(d->reverse && !d->lengths), MSTTS_ERR_SHAPE, "lstm_seq_bwd: reverse needs a lengths array");
-    const long B = d->B, T = d->T, H = d->H, BH = B * H;
-    float* dc[2] = {d->ws, d->ws + BH};
-    float* dh[2] = {d->ws + 2 * BH, d->ws + 3 * BH};
-    float* dhg = d->ws + 4 * BH;                        // [parts][B][H]: dgates . Wh^T of the later step
-    const int sp = mstts_skinny_bwd_splits(H, 4 * H);
-    RC(zero(d->ws, 4 * BH, s));
-    int cur = 0, parts = 1;
-    for (long t = T - 1; t >= 0; --t) {
-        const int nxt = cur ^ 1;
-        mstts_lstm_point_bwd_desc p;
-        memset(&p, 0, sizeof(p));
-        p.B = B; p.H = H;
-        p.d_out = d->d_out; p.dout_sb = d->dout_sb; p.dout_st = d->dout_st;
-        p.d_c_state = dc[cur]; p.d_h_state = dh[cur];
-        p.d_h_state2 = (t == T - 1) ? nullptr : dhg; p.dhs2_ld = H; p.dhs2_parts = parts; p.dhs2_pstride = BH;
-        p.acts = d->acts + t * 4 * BH; p.c_raw = d->c_raw + t * BH; p.c_prev = d->c_hist + t * BH;
-        p.zc = d->zc ? d->zc + t * BH : nullptr; p.zh = d->zh ? d->zh + t * BH : nullptr;
-        p.zoneout = d->zoneout; p.lengths = d->lengths; p.step = (int)t; p.reverse = d->reverse;
-        p.dgates = d->dgates_step + t * 4 * BH;
-        p.dgates_pos = d->dgates_pos; p.dgp_sb = T * 4 * H; p.dgp_st = 4 * H;
-        p.d_c_prev = dc[nxt]; p.d_h_prev = dh[nxt];
-        RC(mstts_lstm_point_bwd(&p, s));
-        // recurrent part of d_h_prev = dgates . Wh^T (slabs, consumed by the next iteration)
-        RC(xw_bwd(p.dgates, 4 * H, d->wh, d->wh_ld, dhg, 0, B, H, 4 * H, sp, &parts, s));
-        cur = nxt;
+    for (long t = T - 1; t >= 0; --t, cur ^= 1) {
+        mstts_lstm_point_bwd_desc pa, pb;
+        seq_point_bwd_desc(a, t, cur, sp, &pa);
+        seq_point_bwd_desc(b, t, cur, sp, &pb);
+        RC(mstts_lstm_point_bwd_pair(&pa, &pb, s));
+        RC(mstts_skinny_bwd_pair(pa.dgates, pb.dgates, 4 * H, a->wh, b->wh, a->wh_ld, a->ws + 4 * BH, b->ws + 4 * BH, 0, B, H, 4 * H, sp, s));
     }
     return MSTTS_OK;
 }
@@ -329,9 +359,14 @@ extern "C" int mstts_decoder_train_ws_floats(int64_t B, int64_t H, int64_t M, in
     return MSTTS_OK;
 }
 
-// (Row chains - splitting the batch rows into groups whose kernel chains run on separate HIP streams - were built and measured
-// in round 1: correct, but slower (eager: host-bound; graph: branches serialised).  Removed; `chains` in the descriptor is ignored.)
-constexpr int MAX_CHAINS = 1;
+// the two decoder cells' slots in the histories of the train descriptor: h0 behind the context in in0's rows, h1 behind m0 in in1's
+static CellSlots train_cell0(const mstts_decoder_train_desc* d) {
+    const long W0 = d->lsa.M + d->H;
+    return CellSlots{d->B, d->H, d->c0, d->in0 + d->lsa.M, W0, d->B * W0, d->zc0, d->zh0, d->zoneout, d->acts0, d->craw0};
+}
+static CellSlots train_cell1(const mstts_decoder_train_desc* d) {
+    return CellSlots{d->B, d->H, d->c1, d->in1 + d->H, 2 * d->H, d->B * 2 * d->H, d->zc1, d->zh1, d->zoneout, d->acts1, d->craw1};
+}
 
 extern "C" int mstts_decoder_train_fwd(const mstts_decoder_train_desc* d, mstts_stream_t s) {
     MSTTS_REQUIRE(d && d->xw0 && d->w0f && d->w1 && d->b1 && d->wq && d->in0 && d->in1 && d->pj && d->c0 && d->c1 &&
@@ -341,13 +376,12 @@ extern "C" int mstts_decoder_train_fwd(const mstts_decoder_train_desc* d, mstts_
     MSTTS_REQUIRE(d->lsa.B == B, MSTTS_ERR_SHAPE, "decoder_train_fwd: lsa.B != B");
     const long BH = B * H, W0 = M + H, W1 = 2 * H, WP = H + M;
     const int sp0 = mstts_skinny_fwd_splits(4 * H, W0), sp1 = mstts_skinny_fwd_splits(4 * H, W1), spq = mstts_skinny_fwd_splits(A, H);
-    int32_t bfs[6];
+    int32_t bfs[6] = {0, 0, 0, 0, 0, 0};
     const bool bf = d->bf_w0f_f && d->bf_w1_f && d->bf_wq_f && mstts_decoder_bf16_splits(H, M, A, bfs);
-    const int pg = (sp0 > sp1 ? sp0 : sp1) > 0 ? (sp0 > sp1 ? sp0 : sp1) : 1, pq = spq > 0 ? spq : 1;
-    const int chains = 1;
-    const bool fused_lsa = true;         // (the time-out counter sits after the last row's granules)
-    // fused cell steps need the single-launch attention step (it writes the context into cell 0's packed block)
-    const bool fused_cells = fused_lsa && d->act_p && M % 4 == 0 &&
+    const Weights w0 = {d->w0f, 4 * H, W0, 4 * H, sp0, nullptr, bf ? d->bf_w0f_f : nullptr, bfs[0]}, w1 = {d->w1, 4 * H, W1, 4 * H, sp1, nullptr, bf ? d->bf_w1_f : nullptr, bfs[1]},
+                  wq = {d->wq, A, H, A, spq, nullptr, bf ? d->bf_wq_f : nullptr, bfs[2]};
+    // fused cell steps: the attention step writes the context into cell 0's packed block
+    const bool fused_cells = d->act_p && M % 4 == 0 &&
                              (bf ? (d->w0p16 && d->w1p16 && mstts_cell_fwd_bf16_supported(H, W0) && mstts_cell_fwd_bf16_supported(H, W1))
                                  : (d->w0p && d->w1p && mstts_cell_fwd_supported(H, W0) && mstts_cell_fwd_supported(H, W1)));
     const float* w0pk = bf ? (const float*)d->w0p16 : d->w0p;
@@ -360,92 +394,51 @@ extern "C" int mstts_decoder_train_fwd(const mstts_decoder_train_desc* d, mstts_
     RC(zero(d->c1, BH, s));
     RC(zero(d->cum_hist, B * T, s));
     // query projection inside the attention launch: geometry supported, by-unit filter given, granule buffer large enough
-    const bool fused_q = fused_lsa && chains == 1 && mstts_lsa_step_q_supported(T, M, H) && d->lsa.loc_kt && A == 128 &&
+    const bool fused_q = mstts_lsa_step_q_supported(T, M, H) && d->lsa.loc_kt && A == 128 &&
                          d->energy_ws_floats >= mstts_lsa_step_q_ws_bytes(B, T) / 4 && WP % 4 == 0;
-    if (fused_lsa) RC(zero(d->energy_ws, fused_q ? mstts_lsa_step_q_ws_bytes(B, T) / 4 : 2 * B * T + 2, s));   // granules + time-out counter
-    const long Bc = B / chains;
-    mstts_stream_t cs[MAX_CHAINS] = {s};
+    RC(zero(d->energy_ws, fused_q ? mstts_lsa_step_q_ws_bytes(B, T) / 4 : 2 * B * T + 2, s));   // granules + time-out counter (it sits after the last row's granules)
+    const CellSlots k0 = train_cell0(d), k1 = train_cell1(d);
+    unsigned long long* gran = (unsigned long long*)d->energy_ws;
     for (long st = 0; st < S; ++st) {
-        for (int c = 0; c < chains; ++c) {
-            const long b0 = c * Bc;
-            mstts_stream_t q_s = cs[c];
-            float* gates = d->gates_ws + (long)pg * b0 * 4 * H;         // [parts][Bc][4H]
-            float* qws = d->q_ws + (long)pq * b0 * A;                   // [parts][Bc][A]
-            float* energy = d->energy_ws + b0 * T;
-            mstts_lsa_const lc = d->lsa;
-            lc.B = Bc; lc.keys += b0 * T * A; lc.values += b0 * T * M;
-            if (lc.lengths) lc.lengths += b0;
+        const float* xw0 = d->xw0 + st * B * 4 * H;
+        const float* in0 = d->in0 + st * B * W0; float* in0n = d->in0 + (st + 1) * B * W0;   // rows [ctx | h0]
+        float* in1 = d->in1 + st * B * W1;                                                   // rows [m0 | h1]
+        float* pj = d->pj + st * B * WP;                                                     // rows [m1 | ctx]
+        mstts_cell_packed_dst ctx_p = packed(nullptr, 0, 0, 0);
+        int parts = 1;
+        if (fused_cells) {
+            // packed activation blocks, ping-pong by step parity: P0 = [ctx | h0] of cell 0, P1 = [m0 | h1] of cell 1.
+            // cell 0 (step st) reads P0[st&1], writes m0 -> P1[st&1] and h0' -> P0[~st&1]; cell 1 reads P1[st&1], writes
+            // h1' -> P1[~st&1]; the attention step writes ctx -> P0[~st&1].
+            float* P0c = d->act_p + (st & 1) * p0n; float* P0n = d->act_p + ((st + 1) & 1) * p0n;
+            float* P1c = d->act_p + 2 * p0n + (st & 1) * p1n; float* P1n = d->act_p + 2 * p0n + ((st + 1) & 1) * p1n;
+            PROBED(MSTTS_PROBE_CELL0_GEMM, s, cell_step(k0, st, st, st + 1, P0c, w0pk, W0, xw0, nullptr, in1, W1, packed(P1c, W1, 0, bf), packed(P0n, W0, M, bf), bf, s));
+            PROBED(MSTTS_PROBE_CELL1_GEMM, s, cell_step(k1, st, st, st + 1, P1c, w1pk, W1, nullptr, d->b1, pj, WP, packed(nullptr, 0, 0, bf), packed(P1n, W1, H, bf), bf, s));
+            ctx_p = packed(P0n, W0, 0, bf);
+        } else {
             mstts_lstm_point_fwd_desc p;
-            mstts_cell_packed_dst ctx_p = {nullptr, 0, 0, 0};
-            int parts = 1;
             // ---- cell 0: gates = [ctx | h0] . w0f + xw0[st]
-            const float* in0 = d->in0 + (st * B + b0) * W0;
-            float* in0n = d->in0 + ((st + 1) * B + b0) * W0;
-            const float* in1 = d->in1 + (st * B + b0) * W1;
-            float* in1w = d->in1 + (st * B + b0) * W1;
-            float* in1n = d->in1 + ((st + 1) * B + b0) * W1;
-            float* pj = d->pj + (st * B + b0) * WP;
-            if (fused_cells) {
-                // packed activation blocks, ping-pong by step parity: P0 = [ctx | h0] of cell 0, P1 = [m0 | h1] of cell 1.
-                // cell 0 (step st) reads P0[st&1], writes m0 -> P1[st&1] and h0' -> P0[~st&1]; cell 1 reads P1[st&1], writes
-                // h1' -> P1[~st&1]; the attention step writes ctx -> P0[~st&1].
-                float* P0c = d->act_p + (st & 1) * p0n; float* P0n = d->act_p + ((st + 1) & 1) * p0n;
-                float* P1c = d->act_p + 2 * p0n + (st & 1) * p1n; float* P1n = d->act_p + 2 * p0n + ((st + 1) & 1) * p1n;
-                PROBED(MSTTS_PROBE_CELL0_GEMM, q_s, cell_step(P0c, w0pk, W0, d->xw0 + (st * B + b0) * 4 * H, 4 * H, nullptr,
-                       d->c0 + (st * B + b0) * H, in0 + M, W0, d->zc0 ? d->zc0 + (st * B + b0) * H : nullptr, d->zh0 ? d->zh0 + (st * B + b0) * H : nullptr,
-                       d->zoneout, in1w, W1, d->c0 + ((st + 1) * B + b0) * H, in0n + M, W0, d->acts0 + (st * B + b0) * 4 * H,
-                       d->craw0 + (st * B + b0) * H, Bc, H, P1c, W1, 0, P0n, W0, M, q_s, bf ? 1 : 0));
-                PROBED(MSTTS_PROBE_CELL1_GEMM, q_s, cell_step(P1c, w1pk, W1, nullptr, 0, d->b1,
-                       d->c1 + (st * B + b0) * H, in1 + H, W1, d->zc1 ? d->zc1 + (st * B + b0) * H : nullptr, d->zh1 ? d->zh1 + (st * B + b0) * H : nullptr,
-                       d->zoneout, pj, WP, d->c1 + ((st + 1) * B + b0) * H, in1n + H, W1, d->acts1 + (st * B + b0) * 4 * H,
-                       d->craw1 + (st * B + b0) * H, Bc, H, nullptr, 0, 0, P1n, W1, H, q_s, bf ? 1 : 0));
-                ctx_p.base = P0n; ctx_p.K = W0; ctx_p.col0 = 0; ctx_p.bf16 = bf ? 1 : 0;
-            } else {
-            if (bf) { parts = bfs[0]; PROBED(MSTTS_PROBE_CELL0_GEMM, q_s, mstts_skinny_fwd_bf16(in0, W0, d->bf_w0f_f, gates, 0, Bc, 4 * H, W0, bfs[0], q_s)); }
-            else PROBED(MSTTS_PROBE_CELL0_GEMM, q_s, xw_fwd(in0, W0, d->w0f, 4 * H, gates, Bc, 4 * H, W0, sp0, &parts, q_s));
-            memset(&p, 0, sizeof(p));
-            p.B = Bc; p.H = H; p.gates_h = gates; p.gates_parts = parts; p.gates_pstride = 4 * Bc * H;
-            p.xw = d->xw0 + (st * B + b0) * 4 * H; p.xw_sb = 4 * H; p.xw_st = 0;
-            p.c_prev = d->c0 + (st * B + b0) * H; p.h_prev = in0 + M; p.h_prev_ld = W0;
-            p.zc = d->zc0 ? d->zc0 + (st * B + b0) * H : nullptr; p.zh = d->zh0 ? d->zh0 + (st * B + b0) * H : nullptr;
-            p.zoneout = d->zoneout;
-            p.out = in1w; p.out_sb = W1; p.out_st = 0;
-            p.c_next = d->c0 + ((st + 1) * B + b0) * H; p.h_next = in0n + M; p.h_next_ld = W0;
-            p.acts_out = d->acts0 + (st * B + b0) * 4 * H; p.c_raw = d->craw0 + (st * B + b0) * H;
-            RC(mstts_lstm_point_fwd(&p, q_s));
+            PROBED(MSTTS_PROBE_CELL0_GEMM, s, recurrent_fwd(w0, in0, W0, d->gates_ws, B, &parts, s));
+            fill_point_fwd(&p, k0, st, st, st + 1, d->gates_ws, parts);
+            p.xw = xw0; p.xw_sb = 4 * H; p.out = in1; p.out_sb = W1;
+            RC(mstts_lstm_point_fwd(&p, s));
             // ---- cell 1: gates = [m0 | h1] . w1 + b1
-            if (bf) { parts = bfs[1]; PROBED(MSTTS_PROBE_CELL1_GEMM, q_s, mstts_skinny_fwd_bf16(in1, W1, d->bf_w1_f, gates, 0, Bc, 4 * H, W1, bfs[1], q_s)); }
-            else PROBED(MSTTS_PROBE_CELL1_GEMM, q_s, xw_fwd(in1, W1, d->w1, 4 * H, gates, Bc, 4 * H, W1, sp1, &parts, q_s));
-            memset(&p, 0, sizeof(p));
-            p.B = Bc; p.H = H; p.gates_h = gates; p.gates_parts = parts; p.gates_pstride = 4 * Bc * H; p.bias = d->b1;
-            p.c_prev = d->c1 + (st * B + b0) * H; p.h_prev = in1 + H; p.h_prev_ld = W1;
-            p.zc = d->zc1 ? d->zc1 + (st * B + b0) * H : nullptr; p.zh = d->zh1 ? d->zh1 + (st * B + b0) * H : nullptr;
-            p.zoneout = d->zoneout;
-            p.out = pj; p.out_sb = WP; p.out_st = 0;
-            p.c_next = d->c1 + ((st + 1) * B + b0) * H; p.h_next = in1n + H; p.h_next_ld = W1;
-            p.acts_out = d->acts1 + (st * B + b0) * 4 * H; p.c_raw = d->craw1 + (st * B + b0) * H;
-            RC(mstts_lstm_point_fwd(&p, q_s));
-            }
-            // ---- query (partials summed inside the energy kernel, which also saves q) + attention
-            const float* cum = d->cum_hist + (st * B + b0) * T;
-            if (fused_q) {          // one launch: the eight slices of a row compute and exchange the query themselves
-                PROBED(MSTTS_PROBE_LSA_ENERGY, q_s, mstts_lsa_step_fwd_q(&lc, pj, WP, d->wq, H, bf ? 1 : 0, d->q_hist + (st * B + b0) * A, cum,
-                                         d->align_hist + (st * B + b0) * T, d->cum_hist + ((st + 1) * B + b0) * T, in0n, W0, pj + H, WP,
-                                         fused_cells ? &ctx_p : nullptr, (unsigned long long*)d->energy_ws + b0 * T, (uint32_t)(st + 1), -1, q_s));
-                continue;
-            }
-            if (bf) { parts = bfs[2]; RC(mstts_skinny_fwd_bf16(pj, WP, d->bf_wq_f, qws, 0, Bc, A, H, bfs[2], q_s)); }
-            else RC(xw_fwd(pj, WP, d->wq, A, qws, Bc, A, H, spq, &parts, q_s));
-            if (fused_lsa) {
-                PROBED(MSTTS_PROBE_LSA_ENERGY, q_s, mstts_lsa_step_fwd(&lc, qws, parts, Bc * A, d->q_hist + (st * B + b0) * A, cum,
-                                         d->align_hist + (st * B + b0) * T, d->cum_hist + ((st + 1) * B + b0) * T, in0n, W0, pj + H, WP,
-                                         fused_cells ? &ctx_p : nullptr, (unsigned long long*)d->energy_ws + b0 * T, (uint32_t)(st + 1), q_s));
-            } else {
-                PROBED(MSTTS_PROBE_LSA_ENERGY, q_s, mstts_lsa_energy_fwd(&lc, qws, parts, Bc * A, d->q_hist + (st * B + b0) * A, cum, energy, q_s));
-                PROBED(MSTTS_PROBE_LSA_CONTEXT, q_s, mstts_lsa_context_fwd(&lc, energy, cum, d->align_hist + (st * B + b0) * T,
-                                         d->cum_hist + ((st + 1) * B + b0) * T, in0n, W0, pj + H, WP, q_s));
-            }
+            PROBED(MSTTS_PROBE_CELL1_GEMM, s, recurrent_fwd(w1, in1, W1, d->gates_ws, B, &parts, s));
+            fill_point_fwd(&p, k1, st, st, st + 1, d->gates_ws, parts);
+            p.bias = d->b1; p.out = pj; p.out_sb = WP;
+            RC(mstts_lstm_point_fwd(&p, s));
         }
+        // ---- query (partials summed inside the attention kernel, which also saves q) + attention
+        float* q_hist = d->q_hist + st * B * A; float* align = d->align_hist + st * B * T;
+        const float* cum = d->cum_hist + st * B * T; float* cum_n = d->cum_hist + (st + 1) * B * T;
+        if (fused_q) {              // one launch: the eight slices of a row compute and exchange the query themselves
+            PROBED(MSTTS_PROBE_LSA_ENERGY, s, mstts_lsa_step_fwd_q(&d->lsa, pj, WP, d->wq, H, bf, q_hist, cum, align, cum_n, in0n, W0, pj + H, WP,
+                                                                    fused_cells ? &ctx_p : nullptr, gran, (uint32_t)(st + 1), -1, s));
+            continue;
+        }
+        RC(recurrent_fwd(wq, pj, WP, d->q_ws, B, &parts, s));
+        PROBED(MSTTS_PROBE_LSA_ENERGY, s, mstts_lsa_step_fwd(&d->lsa, d->q_ws, parts, B * A, q_hist, cum, align, cum_n, in0n, W0, pj + H, WP,
+                                                              fused_cells ? &ctx_p : nullptr, gran, (uint32_t)(st + 1), s));
     }
     return MSTTS_OK;
 }
@@ -467,104 +460,68 @@ extern "C" int mstts_decoder_train_bwd(const mstts_decoder_train_bwd_desc* bd, m
                   MSTTS_ERR_SHAPE, "decoder_train_bwd: null pointer");
     const mstts_decoder_train_desc* d = bd->fwd;
     const long B = d->B, S = d->S, H = d->H, M = d->lsa.M, A = d->lsa.A, T = d->lsa.T, CH = d->lsa.CH;
-    const long W0 = M + H, W1 = 2 * H, WP = H + M;
+    const long BH = B * H, BT = B * T, W0 = M + H, W1 = 2 * H, WP = H + M;
     const int sp1 = mstts_skinny_bwd_splits(W1, 4 * H), sp0 = mstts_skinny_bwd_splits(W0, 4 * H), spq = mstts_skinny_bwd_splits(H, A);
     const int np1 = sp1 > 0 ? sp1 : 1, npq = spq > 0 ? spq : 1;
-    int32_t bfs[6];
+    int32_t bfs[6] = {0, 0, 0, 0, 0, 0};
     const bool bf = d->bf_w0f_b && d->bf_w1_b && d->bf_wq_b && mstts_decoder_bf16_splits(H, M, A, bfs);
+    const Weights w0 = {d->w0f, 4 * H, W0, 4 * H, sp0, d->w0f_bp, bf ? d->bf_w0f_b : nullptr, bfs[3]}, w1 = {d->w1, 4 * H, W1, 4 * H, sp1, d->w1_bp, bf ? d->bf_w1_b : nullptr, bfs[4]},
+                  wq = {d->wq, A, H, A, spq, d->wq_bp, bf ? d->bf_wq_b : nullptr, bfs[5]};
     const long d_in0_slab = S * B * W0;
-    const int chains = 1;
-    const long Bc = B / chains, BcH = Bc * H, BcT = Bc * T;
-    const long ws_per_row = 8 * H + 2 * T + 2 * T * CH + T + (long)np1 * W1 + (long)npq * H;
     // single-launch attention backward: its granules (B*ceil(T/8)+1 8-byte words) live in the d_align block (B*T floats)
     const bool fused_lsa = WP % 4 == 0 && H % 4 == 0;            // (the single-launch backward reads the forward context rows as float4)
     // query-layer data gradient inside cell 1's pointwise kernel: fp32 mode, A == 128, slab counts the lean kernel is built for
     // (bf16 mode: the kernel rounds both operands to bf16 first - the same products as the bf16 product launch it replaces)
     const int np1_eff = bf ? bfs[4] : np1;
     const bool fuse_q = d->wq_t && A == 128 && H % 128 == 0 && (np1_eff == 8 || np1_eff == 4 || np1_eff == 2 || np1_eff == 1) && B * H * 4 < (1LL << 30);
-    RC(zero(bd->ws, ws_per_row * B, s));
-    mstts_stream_t cs[MAX_CHAINS] = {s};
-    struct ChainWs { float *dc0[2], *dh0[2], *dc1[2], *dh1[2], *G[2], *df[2], *d_align, *tmp1, *dqm; int parts0, parts1, partsq; } cw[MAX_CHAINS];
-    for (int c = 0; c < chains; ++c) {
-        float* w = bd->ws + ws_per_row * (c * Bc);
-        ChainWs& k = cw[c];
-        k.dc0[0] = w; k.dc0[1] = w + BcH; w += 2 * BcH;
-        k.dh0[0] = w; k.dh0[1] = w + BcH; w += 2 * BcH;
-        k.dc1[0] = w; k.dc1[1] = w + BcH; w += 2 * BcH;
-        k.dh1[0] = w; k.dh1[1] = w + BcH; w += 2 * BcH;
-        k.G[0] = w; k.G[1] = w + BcT; w += 2 * BcT;
-        k.df[0] = w; k.df[1] = w + BcT * CH; w += 2 * BcT * CH;
-        k.d_align = w; w += BcT;
-        k.tmp1 = w; w += (long)np1 * Bc * W1;
-        k.dqm = w; w += (long)npq * BcH;
-        k.parts0 = k.parts1 = k.partsq = 1;
-    }
-    int cur = 0;
-    for (long st = S - 1; st >= 0; --st) {
+    // workspace: the two cells' state gradients, then the attention's carried gradients and the product slabs
+    float* w = bd->ws;
+    RC(zero(w, 8 * BH + 2 * BT + 2 * BT * CH + BT + (long)np1 * B * W1 + (long)npq * BH, s));
+    float* ds0 = w;                                 w += 4 * BH;
+    float* ds1 = w;                                 w += 4 * BH;
+    float* G[2] = {w, w + BT};                      w += 2 * BT;
+    float* df[2] = {w, w + BT * CH};                w += 2 * BT * CH;
+    float* d_align = w;                             w += BT;
+    float* tmp1 = w;                                w += (long)np1 * B * W1;      // [parts1][B][m0 | h1 state]
+    float* dqm = w;                                                               // [partsq][B][H]
+    const CellSaved k0 = saved(train_cell0(d)), k1 = saved(train_cell1(d));
+    int cur = 0, parts0 = 1, parts1 = 1, partsq = 1;
+    for (long st = S - 1; st >= 0; --st, cur ^= 1) {
         const int nxt = cur ^ 1;
         const bool last = (st == S - 1);
-        for (int c = 0; c < chains; ++c) {
-            const long b0 = c * Bc;
-            mstts_stream_t q_s = cs[c];
-            ChainWs& k = cw[c];
-            mstts_lsa_const lc = d->lsa;
-            lc.B = Bc; lc.keys += b0 * T * A; lc.values += b0 * T * M;
-            if (lc.lengths) lc.lengths += b0;
-            float* dpj = bd->d_pj + (st * B + b0) * WP;
-            const float* d_in0_next = last ? nullptr : bd->d_in0 + ((st + 1) * B + b0) * W0;
-            // ---- attention backward
-            if (fused_lsa) {        // d_align stays on chip
-                PROBED(MSTTS_PROBE_LSA_DALIGN, q_s, mstts_lsa_step_bwd(&lc, dpj + H, WP, d_in0_next, W0, k.parts0, d_in0_slab,
-                                        last ? nullptr : k.G[cur], last ? nullptr : k.df[cur], k.G[nxt], d->align_hist + (st * B + b0) * T,
-                                        d->q_hist + (st * B + b0) * A, d->cum_hist + (st * B + b0) * T, d->pj + (st * B + b0) * WP + H, WP,
-                                        bd->de_hist + (st * B + b0) * T, bd->dq_hist + (st * B + b0) * A, k.df[nxt], q_s));
-            } else {
-                PROBED(MSTTS_PROBE_LSA_DALIGN, q_s, mstts_lsa_dalign_bwd(&lc, dpj + H, WP, d_in0_next, W0, k.parts0, d_in0_slab,
-                                        last ? nullptr : k.G[cur], last ? nullptr : k.df[cur], k.G[nxt], k.d_align, q_s));
-                PROBED(MSTTS_PROBE_LSA_DENERGY, q_s, mstts_lsa_denergy_bwd(&lc, d->align_hist + (st * B + b0) * T, k.d_align, d->q_hist + (st * B + b0) * A,
-                                         d->cum_hist + (st * B + b0) * T, bd->de_hist + (st * B + b0) * T, bd->dq_hist + (st * B + b0) * A, k.df[nxt], q_s));
-            }
-            // d_m1 (query path) = dq . Wq^T  -> slabs consumed by the cell-1 pointwise kernel
-            if (fuse_q) {}          // folded into the cell-1 pointwise kernel below
-            else if (bf) { k.partsq = bfs[5]; RC(mstts_skinny_bwd_bf16(bd->dq_hist + (st * B + b0) * A, A, d->bf_wq_b, k.dqm, 0, Bc, H, A, bfs[5], q_s)); }
-            else RC(xw_bwd(bd->dq_hist + (st * B + b0) * A, A, d->wq, A, k.dqm, 0, Bc, H, A, spq, &k.partsq, q_s, d->wq_bp));
-            // ---- cell 1 backward
-            mstts_lstm_point_bwd_desc p;
-            memset(&p, 0, sizeof(p));
-            p.B = Bc; p.H = H;
-            p.d_out = dpj; p.dout_sb = WP; p.dout_st = 0;
-            if (fuse_q) { p.dq = bd->dq_hist + (st * B + b0) * A; p.wq_t = d->wq_t; p.A = A; p.dq_bf16 = bf ? 1 : 0; }
-            else { p.d_out2 = k.dqm; p.dout2_parts = k.partsq; p.dout2_pstride = BcH; }
-            p.d_c_state = k.dc1[cur]; p.d_h_state = k.dh1[cur];
-            p.d_h_state2 = last ? nullptr : k.tmp1 + H; p.dhs2_ld = W1; p.dhs2_parts = k.parts1; p.dhs2_pstride = Bc * W1;
-            p.acts = d->acts1 + (st * B + b0) * 4 * H; p.c_raw = d->craw1 + (st * B + b0) * H; p.c_prev = d->c1 + (st * B + b0) * H;
-            p.zc = d->zc1 ? d->zc1 + (st * B + b0) * H : nullptr; p.zh = d->zh1 ? d->zh1 + (st * B + b0) * H : nullptr;
-            p.zoneout = d->zoneout;
-            p.dgates = bd->dg1 + (st * B + b0) * 4 * H;
-            p.d_c_prev = k.dc1[nxt]; p.d_h_prev = k.dh1[nxt];
-            RC(mstts_lstm_point_bwd(&p, q_s));
-            // [d_m0 | d_h1 state] = dg1 . w1^T
-            if (bf) { k.parts1 = bfs[4]; PROBED(MSTTS_PROBE_CELL1_DGEMM, q_s, mstts_skinny_bwd_bf16(p.dgates, 4 * H, d->bf_w1_b, k.tmp1, 0, Bc, W1, 4 * H, bfs[4], q_s)); }
-            else PROBED(MSTTS_PROBE_CELL1_DGEMM, q_s, xw_bwd(p.dgates, 4 * H, d->w1, 4 * H, k.tmp1, 0, Bc, W1, 4 * H, sp1, &k.parts1, q_s, d->w1_bp));
-            // ---- cell 0 backward
-            memset(&p, 0, sizeof(p));
-            p.B = Bc; p.H = H;
-            p.d_out = k.tmp1; p.dout_sb = W1; p.dout_st = 0; p.dout_parts = k.parts1; p.dout_pstride = Bc * W1;
-            p.d_c_state = k.dc0[cur]; p.d_h_state = k.dh0[cur];
-            p.d_h_state2 = last ? nullptr : d_in0_next + M; p.dhs2_ld = W0; p.dhs2_parts = k.parts0; p.dhs2_pstride = d_in0_slab;
-            p.acts = d->acts0 + (st * B + b0) * 4 * H; p.c_raw = d->craw0 + (st * B + b0) * H; p.c_prev = d->c0 + (st * B + b0) * H;
-            p.zc = d->zc0 ? d->zc0 + (st * B + b0) * H : nullptr; p.zh = d->zh0 ? d->zh0 + (st * B + b0) * H : nullptr;
-            p.zoneout = d->zoneout;
-            p.dgates = bd->dg0 + (st * B + b0) * 4 * H;
-            p.d_c_prev = k.dc0[nxt]; p.d_h_prev = k.dh0[nxt];
-            RC(mstts_lstm_point_bwd(&p, q_s));
-            // [d_ctx_{st-1} | d_h0 state] = dg0 . w0f^T   (slabs at stride S*B*W0)
-            if (bf) { k.parts0 = bfs[3]; PROBED(MSTTS_PROBE_CELL0_DGEMM, q_s, mstts_skinny_bwd_bf16(p.dgates, 4 * H, d->bf_w0f_b, bd->d_in0 + (st * B + b0) * W0,
-                                                                                                   d_in0_slab, Bc, W0, 4 * H, bfs[3], q_s)); }
-            else PROBED(MSTTS_PROBE_CELL0_DGEMM, q_s, xw_bwd(p.dgates, 4 * H, d->w0f, 4 * H, bd->d_in0 + (st * B + b0) * W0, d_in0_slab, Bc, W0, 4 * H,
-                                                            sp0, &k.parts0, q_s, d->w0f_bp));
+        float* dpj = bd->d_pj + st * B * WP;
+        float* dq = bd->dq_hist + st * B * A; float* de = bd->de_hist + st * B * T;
+        const float* align = d->align_hist + st * B * T; const float* q_hist = d->q_hist + st * B * A; const float* cum = d->cum_hist + st * B * T;
+        const float* d_in0_next = last ? nullptr : bd->d_in0 + (st + 1) * B * W0;
+        // ---- attention backward
+        if (fused_lsa) {        // d_align stays on chip
+            PROBED(MSTTS_PROBE_LSA_DALIGN, s, mstts_lsa_step_bwd(&d->lsa, dpj + H, WP, d_in0_next, W0, parts0, d_in0_slab, last ? nullptr : G[cur],
+                                                                  last ? nullptr : df[cur], G[nxt], align, q_hist, cum, d->pj + st * B * WP + H, WP, de, dq, df[nxt], s));
+        } else {
+            PROBED(MSTTS_PROBE_LSA_DALIGN, s, mstts_lsa_dalign_bwd(&d->lsa, dpj + H, WP, d_in0_next, W0, parts0, d_in0_slab, last ? nullptr : G[cur],
+                                                                    last ? nullptr : df[cur], G[nxt], d_align, s));
+            PROBED(MSTTS_PROBE_LSA_DENERGY, s, mstts_lsa_denergy_bwd(&d->lsa, align, d_align, q_hist, cum, de, dq, df[nxt], s));
         }
-        cur = nxt;
+        // ---- cell 1 backward; d_m1 (query path) = dq . Wq^T: folded into the pointwise kernel, or slabs it consumes
+        mstts_lstm_point_bwd_desc p;
+        fill_point_bwd(&p, k1, st, ds1, cur, bd->dg1 + st * B * 4 * H);
+        p.d_out = dpj; p.dout_sb = WP;
+        if (fuse_q) { p.dq = dq; p.wq_t = d->wq_t; p.A = A; p.dq_bf16 = bf; }
+        else {
+            RC(recurrent_bwd(wq, dq, A, dqm, 0, B, &partsq, s));
+            p.d_out2 = dqm; p.dout2_parts = partsq; p.dout2_pstride = BH;
+        }
+        p.d_h_state2 = last ? nullptr : tmp1 + H; p.dhs2_ld = W1; p.dhs2_parts = parts1; p.dhs2_pstride = B * W1;
+        RC(mstts_lstm_point_bwd(&p, s));
+        // [d_m0 | d_h1 state] = dg1 . w1^T
+        PROBED(MSTTS_PROBE_CELL1_DGEMM, s, recurrent_bwd(w1, p.dgates, 4 * H, tmp1, 0, B, &parts1, s));
+        // ---- cell 0 backward
+        fill_point_bwd(&p, k0, st, ds0, cur, bd->dg0 + st * B * 4 * H);
+        p.d_out = tmp1; p.dout_sb = W1; p.dout_parts = parts1; p.dout_pstride = B * W1;
+        p.d_h_state2 = last ? nullptr : d_in0_next + M; p.dhs2_ld = W0; p.dhs2_parts = parts0; p.dhs2_pstride = d_in0_slab;
+        RC(mstts_lstm_point_bwd(&p, s));
+        // [d_ctx_{st-1} | d_h0 state] = dg0 . w0f^T   (slabs at stride S*B*W0)
+        PROBED(MSTTS_PROBE_CELL0_DGEMM, s, recurrent_bwd(w0, p.dgates, 4 * H, bd->d_in0 + st * B * W0, d_in0_slab, B, &parts0, s));
     }
     return MSTTS_OK;
 }
@@ -604,11 +561,29 @@ extern "C" int32_t mstts_decoder_infer_fast(int64_t B, int64_t H, int64_t P, int
            mstts_skinny_fwd_splits(A, H) > 0 && mstts_skinny_fwd_splits(NP, H + M) > 0;
 }
 
+// the two cells' slots of the free-running loop: two state slots each, ping-pong by step parity; h0 sits `h0_col` columns into in0's rows
+static CellSlots infer_cell0(const mstts_decoder_infer_desc* d, long W0, long h0_col) {
+    return CellSlots{d->B, d->H, d->c0, d->in0 + h0_col, W0, d->B * W0, nullptr, nullptr, d->zoneout, nullptr, nullptr};
+}
+static CellSlots infer_cell1(const mstts_decoder_infer_desc* d) {
+    return CellSlots{d->B, d->H, d->c1, d->in1 + d->H, 2 * d->H, d->B * 2 * d->H, nullptr, nullptr, d->zoneout, nullptr, nullptr};
+}
+// projection of step st through the padded kernel: [m1 | ctx] . wp_pad in slabs at pp, then bias, linear and stop
+static int project_step(const mstts_decoder_infer_desc* d, long st, float* pp, const Weights& wp, mstts_stream_t s) {
+    const long B = d->B, NM = d->n_mel, NP = wp.cols;
+    int parts = 1;
+    RC(recurrent_fwd(wp, d->pj, wp.rows, pp, B, &parts, s));
+    hipLaunchKernelGGL(proj_finish_kernel, dim3((unsigned)((B * (NM + 1) + 255) / 256)), dim3(256), 0, (hipStream_t)s, pp, parts, B * NP, d->bproj,
+                       (int)B, (int)NP, (int)NM, d->linear + st * B * NM, d->stop + st * B);
+    MSTTS_CHECK_LAUNCH("proj_finish");
+    return MSTTS_OK;
+}
+
 static int infer_steps_fast(const mstts_decoder_infer_desc* d, int64_t step0, int64_t n, mstts_stream_t s) {
     const long B = d->B, H = d->H, P = d->P, NM = d->n_mel, M = d->lsa.M, A = d->lsa.A, T = d->lsa.T;
     const long BH = B * H, W0 = P + M + H, W1 = 2 * H, WP = H + M, BT = B * T, NP = (NM + 1 + 3) / 4 * 4;
-    const int sp0 = mstts_skinny_fwd_splits(4 * H, W0), sp1 = mstts_skinny_fwd_splits(4 * H, W1), spq = mstts_skinny_fwd_splits(A, H),
-              spp = mstts_skinny_fwd_splits(NP, WP);
+    const Weights w0 = {d->w0s, 4 * H, W0, 4 * H, mstts_skinny_fwd_splits(4 * H, W0), nullptr, nullptr, 0}, w1 = {d->w1, 4 * H, W1, 4 * H, mstts_skinny_fwd_splits(4 * H, W1), nullptr, nullptr, 0},
+                  wq = {d->wq, A, H, A, mstts_skinny_fwd_splits(A, H), nullptr, nullptr, 0}, wp = {d->wp_pad, NP, WP, NP, mstts_skinny_fwd_splits(NP, WP), nullptr, nullptr, 0};
     float* w = d->pre_ws;
     float* gates = w;       w += (long)MSTTS_MAX_PARTS * 4 * BH;
     const long gran_n = mstts_lsa_step_qp_ws_bytes(B, T) / 4;       // energy granules + counter, then the query and the frame granules
@@ -635,11 +610,13 @@ static int infer_steps_fast(const mstts_decoder_infer_desc* d, int64_t step0, in
     const bool fused = d->w0sp && d->w1p && d->act_p && mstts_cell_fwd_supported(H, W0) && mstts_cell_fwd_supported(H, W1);
     const long p0n = mstts_cell_act_floats(B, W0), p1n = mstts_cell_act_floats(B, W1);
     if (fused && step0 == 0) RC(zero(d->act_p, 2 * (p0n + p1n), s));
+    const CellSlots k0 = infer_cell0(d, W0, P + M), k1 = infer_cell1(d);
     for (long st = step0; st < step0 + n; ++st) {
         const int par = (int)(st & 1), nx = par ^ 1;
         const float* frame = (st == 0) ? zero_frame : d->linear + (st - 1) * B * NM;
         float* in0c = d->in0 + par * B * W0; float* in0n = d->in0 + nx * B * W0;      // rows [prenet P | ctx M | h0 H]
-        float* in1c = d->in1 + par * B * W1; float* in1n = d->in1 + nx * B * W1;      // rows [m0 H | h1 H]
+        float* in1c = d->in1 + par * B * W1;                                          // rows [m0 H | h1 H]
+        float* cum = d->cum + par * BT; float* cum_n = d->cum + nx * BT; float* align = d->align_hist + st * BT;
         float* P0c = fused ? d->act_p + par * p0n : nullptr; float* P0n = fused ? d->act_p + nx * p0n : nullptr;
         float* P1c = fused ? d->act_p + 2 * p0n + par * p1n : nullptr; float* P1n = fused ? d->act_p + 2 * p0n + nx * p1n : nullptr;
         PackedDst pre_p;
@@ -650,14 +627,11 @@ static int infer_steps_fast(const mstts_decoder_infer_desc* d, int64_t step0, in
                                d->pw0, d->pb0, d->pw1, d->pb1, d->pm0 + st * B * P, d->pm1 + st * B * P, 1.f / d->prenet_keep, (int)B, (int)P, in0c, W0, pre_p);
             MSTTS_CHECK_LAUNCH("prenet_step");
         }
-        mstts_lstm_point_fwd_desc p;
         int parts = 1;
         if (fused) {
-            RC(cell_step(P0c, d->w0sp, W0, nullptr, 0, d->b0, d->c0 + par * BH, in0c + P + M, W0, nullptr, nullptr, d->zoneout,
-                         in1c, W1, d->c0 + nx * BH, in0n + P + M, W0, nullptr, nullptr, B, H, P1c, W1, 0, P0n, W0, P + M, s));
-            RC(cell_step(P1c, d->w1p, W1, nullptr, 0, d->b1, d->c1 + par * BH, in1c + H, W1, nullptr, nullptr, d->zoneout,
-                         d->pj, WP, d->c1 + nx * BH, in1n + H, W1, nullptr, nullptr, B, H, nullptr, 0, 0, P1n, W1, H, s));
-            mstts_cell_packed_dst ctx_p = {P0n, W0, P, 0};
+            RC(cell_step(k0, 0, par, nx, P0c, d->w0sp, W0, nullptr, d->b0, in1c, W1, packed(P1c, W1, 0, 0), packed(P0n, W0, P + M, 0), 0, s));
+            RC(cell_step(k1, 0, par, nx, P1c, d->w1p, W1, nullptr, d->b1, d->pj, WP, packed(nullptr, 0, 0, 0), packed(P1n, W1, H, 0), 0, s));
+            mstts_cell_packed_dst ctx_p = packed(P0n, W0, P, 0);
             if (fused_qp) {
                 mstts_lsa_prenet pn;
                 memset(&pn, 0, sizeof(pn));
@@ -665,46 +639,34 @@ static int infer_steps_fast(const mstts_decoder_infer_desc* d, int64_t step0, in
                 if (pre_next) {
                     pn.w0 = d->pw0; pn.b0 = d->pb0; pn.w1 = d->pw1; pn.b1 = d->pb1; pn.m0 = d->pm0 + (st + 1) * B * P; pn.m1 = d->pm1 + (st + 1) * B * P;
                     pn.inv_keep = 1.f / d->prenet_keep; pn.P = (int32_t)P; pn.out = in0n; pn.out_ld = W0;
-                    pn.out_p.base = P0n; pn.out_p.K = W0; pn.out_p.col0 = 0; pn.out_p.bf16 = 0;
+                    pn.out_p = packed(P0n, W0, 0, 0);
                 }
                 RC(mstts_lsa_step_fwd_qp(&d->lsa, d->pj, WP, d->wq, H, d->wp_own, d->vp, d->bproj, NP, NM, d->linear + st * B * NM, d->stop + st * B,
-                                         d->cum + par * BT, d->align_hist + st * BT, d->cum + nx * BT, in0n + P, W0, d->pj + H, WP, &ctx_p,
-                                         pre_next ? &pn : nullptr, gran, (uint32_t)(st + 1), -1, s));
+                                         cum, align, cum_n, in0n + P, W0, d->pj + H, WP, &ctx_p, pre_next ? &pn : nullptr, gran, (uint32_t)(st + 1), -1, s));
                 continue;
             }
             if (fused_q) {
-                RC(mstts_lsa_step_fwd_q(&d->lsa, d->pj, WP, d->wq, H, 0, nullptr, d->cum + par * BT, d->align_hist + st * BT, d->cum + nx * BT,
-                                        in0n + P, W0, d->pj + H, WP, &ctx_p, gran, (uint32_t)(st + 1), -1, s));
+                RC(mstts_lsa_step_fwd_q(&d->lsa, d->pj, WP, d->wq, H, 0, nullptr, cum, align, cum_n, in0n + P, W0, d->pj + H, WP, &ctx_p, gran,
+                                        (uint32_t)(st + 1), -1, s));
             } else {
-                RC(xw_fwd(d->pj, WP, d->wq, A, q, B, A, H, spq, &parts, s));
-                RC(mstts_lsa_step_fwd(&d->lsa, q, parts, B * A, nullptr, d->cum + par * BT, d->align_hist + st * BT, d->cum + nx * BT,
-                                      in0n + P, W0, d->pj + H, WP, &ctx_p, gran, (uint32_t)(st + 1), s));
+                RC(recurrent_fwd(wq, d->pj, WP, q, B, &parts, s));
+                RC(mstts_lsa_step_fwd(&d->lsa, q, parts, B * A, nullptr, cum, align, cum_n, in0n + P, W0, d->pj + H, WP, &ctx_p, gran, (uint32_t)(st + 1), s));
             }
-            RC(xw_fwd(d->pj, WP, d->wp_pad, NP, pp, B, NP, WP, spp, &parts, s));
-            hipLaunchKernelGGL(proj_finish_kernel, dim3((unsigned)((B * (NM + 1) + 255) / 256)), dim3(256), 0, (hipStream_t)s, pp, parts, B * NP, d->bproj,
-                               (int)B, (int)NP, (int)NM, d->linear + st * B * NM, d->stop + st * B);
-            MSTTS_CHECK_LAUNCH("proj_finish");
+            RC(project_step(d, st, pp, wp, s));
             continue;
         }
-        RC(xw_fwd(in0c, W0, d->w0s, 4 * H, gates, B, 4 * H, W0, sp0, &parts, s));
-        memset(&p, 0, sizeof(p));
-        p.B = B; p.H = H; p.gates_h = gates; p.gates_parts = parts; p.gates_pstride = 4 * BH; p.bias = d->b0;
-        p.c_prev = d->c0 + par * BH; p.h_prev = in0c + P + M; p.h_prev_ld = W0; p.zoneout = d->zoneout;
-        p.out = in1c; p.out_sb = W1; p.c_next = d->c0 + nx * BH; p.h_next = in0n + P + M; p.h_next_ld = W0;
+        mstts_lstm_point_fwd_desc p;
+        RC(recurrent_fwd(w0, in0c, W0, gates, B, &parts, s));
+        fill_point_fwd(&p, k0, 0, par, nx, gates, parts);
+        p.bias = d->b0; p.out = in1c; p.out_sb = W1;
         RC(mstts_lstm_point_fwd(&p, s));
-        RC(xw_fwd(in1c, W1, d->w1, 4 * H, gates, B, 4 * H, W1, sp1, &parts, s));
-        memset(&p, 0, sizeof(p));
-        p.B = B; p.H = H; p.gates_h = gates; p.gates_parts = parts; p.gates_pstride = 4 * BH; p.bias = d->b1;
-        p.c_prev = d->c1 + par * BH; p.h_prev = in1c + H; p.h_prev_ld = W1; p.zoneout = d->zoneout;
-        p.out = d->pj; p.out_sb = WP; p.c_next = d->c1 + nx * BH; p.h_next = in1n + H; p.h_next_ld = W1;
+        RC(recurrent_fwd(w1, in1c, W1, gates, B, &parts, s));
+        fill_point_fwd(&p, k1, 0, par, nx, gates, parts);
+        p.bias = d->b1; p.out = d->pj; p.out_sb = WP;
         RC(mstts_lstm_point_fwd(&p, s));
-        RC(xw_fwd(d->pj, WP, d->wq, A, q, B, A, H, spq, &parts, s));
-        RC(mstts_lsa_step_fwd(&d->lsa, q, parts, B * A, nullptr, d->cum + par * BT, d->align_hist + st * BT, d->cum + nx * BT,
-                              in0n + P, W0, d->pj + H, WP, nullptr, gran, (uint32_t)(st + 1), s));
-        RC(xw_fwd(d->pj, WP, d->wp_pad, NP, pp, B, NP, WP, spp, &parts, s));
-        hipLaunchKernelGGL(proj_finish_kernel, dim3((unsigned)((B * (NM + 1) + 255) / 256)), dim3(256), 0, (hipStream_t)s, pp, parts, B * NP, d->bproj,
-                           (int)B, (int)NP, (int)NM, d->linear + st * B * NM, d->stop + st * B);
-        MSTTS_CHECK_LAUNCH("proj_finish");
+        RC(recurrent_fwd(wq, d->pj, WP, q, B, &parts, s));
+        RC(mstts_lsa_step_fwd(&d->lsa, q, parts, B * A, nullptr, cum, align, cum_n, in0n + P, W0, d->pj + H, WP, nullptr, gran, (uint32_t)(st + 1), s));
+        RC(project_step(d, st, pp, wp, s));
     }
     return MSTTS_OK;
 }
@@ -722,15 +684,15 @@ extern "C" int mstts_decoder_infer_steps(const mstts_decoder_infer_desc* d, int6
                   MSTTS_ERR_SHAPE, "decoder_infer_steps: null pointer");
     MSTTS_REQUIRE(step0 >= 0 && step0 + n <= d->Smax, MSTTS_ERR_SHAPE, "decoder_infer_steps: step range exceeds Smax");
     if (d->w0s && d->wp_pad && mstts_decoder_infer_fast(d->B, d->H, d->P, d->lsa.M, d->lsa.A, d->n_mel)) return infer_steps_fast(d, step0, n, s);
+    // any other shape: every product on the tiled GEMM, the prenet as separate launches
     const long B = d->B, H = d->H, P = d->P, NM = d->n_mel, M = d->lsa.M, A = d->lsa.A, T = d->lsa.T;
     const long BH = B * H, W0 = M + H, W1 = 2 * H, WP = H + M, BT = B * T;
-    const bool fused_lsa = true;
     float* w = d->pre_ws;
     float* pa = w;          w += B * P;
     float* pb = w;          w += B * P;
     float* xw = w;          w += 4 * BH;
     float* gates = w;       w += 4 * BH;
-    float* energy = w;      w += 2 * BT + 2;          // energies, or the 8-byte granules (+ counter) of the single-launch step
+    float* gran = w;        w += 2 * BT + 2;          // the 8-byte granules (+ counter) of the single-launch attention step
     float* q = w;           w += B * A;
     float* zero_frame = w;  w += B * NM;
     if (step0 == 0) {
@@ -740,8 +702,9 @@ extern "C" int mstts_decoder_infer_steps(const mstts_decoder_infer_desc* d, int6
         RC(zero(d->c1, BH, s));
         RC(zero(d->cum, BT, s));
         RC(zero(zero_frame, B * NM, s));
-        if (fused_lsa) RC(zero(energy, 2 * BT + 2, s));
+        RC(zero(gran, 2 * BT + 2, s));
     }
+    const CellSlots k0 = infer_cell0(d, W0, M), k1 = infer_cell1(d);
     for (long st = step0; st < step0 + n; ++st) {
         const int par = (int)(st & 1), nx = par ^ 1;
         const float* frame = (st == 0) ? zero_frame : d->linear + (st - 1) * B * NM;
@@ -752,32 +715,22 @@ extern "C" int mstts_decoder_infer_steps(const mstts_decoder_infer_desc* d, int6
         RC(mstts_dropout(pa, d->pm1 + st * B * P, d->prenet_keep, pb, B * P, s));
         RC(gemm(pb, P, d->wx0, 4 * H, 0, xw, 4 * H, B, 4 * H, P, d->b0, 0, 0, s));
         mstts_lstm_point_fwd_desc p;
-        // cell 0
         float* in0c = d->in0 + par * B * W0; float* in0n = d->in0 + nx * B * W0;
-        float* in1c = d->in1 + par * B * W1; float* in1n = d->in1 + nx * B * W1;
+        float* in1c = d->in1 + par * B * W1;
+        // cell 0
         RC(gemm(in0c, W0, d->w0f, 4 * H, 0, gates, 4 * H, B, 4 * H, W0, nullptr, 0, 0, s));
-        memset(&p, 0, sizeof(p));
-        p.B = B; p.H = H; p.gates_h = gates; p.xw = xw; p.xw_sb = 4 * H; p.xw_st = 0;
-        p.c_prev = d->c0 + par * BH; p.h_prev = in0c + M; p.h_prev_ld = W0; p.zoneout = d->zoneout;
-        p.out = in1c; p.out_sb = W1; p.c_next = d->c0 + nx * BH; p.h_next = in0n + M; p.h_next_ld = W0;
+        fill_point_fwd(&p, k0, 0, par, nx, gates, 1);
+        p.xw = xw; p.xw_sb = 4 * H; p.out = in1c; p.out_sb = W1;
         RC(mstts_lstm_point_fwd(&p, s));
         // cell 1
         RC(gemm(in1c, W1, d->w1, 4 * H, 0, gates, 4 * H, B, 4 * H, W1, nullptr, 0, 0, s));
-        memset(&p, 0, sizeof(p));
-        p.B = B; p.H = H; p.gates_h = gates; p.bias = d->b1;
-        p.c_prev = d->c1 + par * BH; p.h_prev = in1c + H; p.h_prev_ld = W1; p.zoneout = d->zoneout;
-        p.out = d->pj; p.out_sb = WP; p.c_next = d->c1 + nx * BH; p.h_next = in1n + H; p.h_next_ld = W1;
+        fill_point_fwd(&p, k1, 0, par, nx, gates, 1);
+        p.bias = d->b1; p.out = d->pj; p.out_sb = WP;
         RC(mstts_lstm_point_fwd(&p, s));
         // attention
         RC(gemm(d->pj, WP, d->wq, A, 0, q, A, B, A, H, nullptr, 0, 0, s));
-        if (fused_lsa) {
-            RC(mstts_lsa_step_fwd(&d->lsa, q, 1, 0, nullptr, d->cum + par * BT, d->align_hist + st * BT, d->cum + nx * BT,
-                                  in0n, W0, d->pj + H, WP, nullptr, energy, (uint32_t)(st + 1), s));
-        } else {
-            RC(mstts_lsa_energy_fwd(&d->lsa, q, 1, 0, nullptr, d->cum + par * BT, energy, s));
-            RC(mstts_lsa_context_fwd(&d->lsa, energy, d->cum + par * BT, d->align_hist + st * BT, d->cum + nx * BT,
-                                     in0n, W0, d->pj + H, WP, s));
-        }
+        RC(mstts_lsa_step_fwd(&d->lsa, q, 1, 0, nullptr, d->cum + par * BT, d->align_hist + st * BT, d->cum + nx * BT,
+                              in0n, W0, d->pj + H, WP, nullptr, gran, (uint32_t)(st + 1), s));
         // projection: [m1 | ctx] . Wp + b -> linear (n_mel) and stop (1)
         RC(gemm(d->pj, WP, d->wproj, NM + 1, 0, d->linear + st * B * NM, NM, B, NM, WP, d->bproj, 0, 0, s));
         RC(gemm(d->pj, WP, d->wproj + NM, NM + 1, 0, d->stop + st * B, 1, B, 1, WP, d->bproj ? d->bproj + NM : nullptr, 0, 0, s));

@@ -15,7 +15,7 @@
 // Arithmetic is v_mfma_f32_16x16x4_f32 (exact fp32).  A lane's float4 feeds four MFMAs with a
 // permuted k (fwd: column) assignment, so one load instruction of a wave covers 4 rows x 256 B
 // (fwd) or 16 rows x 64 B (bwd) of the row-major kernel.
-#include "common.h"
+#include "skinny_tile.h"
 #include <stdlib.h>
 
 namespace mstts {
@@ -249,46 +249,26 @@ __global__ void pack_skinny_bwd_kernel(const float* __restrict__ W, long ldw, fl
     }
 }
 
-static bool g_attr_set = false;
-static void set_lds_attr() {
-    if (g_attr_set) return;
-#define MSTTS_SK_ATTR(N, T)                                                                                                   \
-    hipFuncSetAttribute((const void*)skinny_fwd_kernel<N, T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);       \
-    hipFuncSetAttribute((const void*)skinny_bwd_kernel<N, T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-    hipFuncSetAttribute((const void*)skinny_bwd_kernel<N, T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    MSTTS_SK_ATTR(0, true) MSTTS_SK_ATTR(0, false) MSTTS_SK_ATTR(2, true) MSTTS_SK_ATTR(2, false) MSTTS_SK_ATTR(4, true) MSTTS_SK_ATTR(4, false)
-    MSTTS_SK_ATTR(8, true) MSTTS_SK_ATTR(8, false) MSTTS_SK_ATTR(14, true) MSTTS_SK_ATTR(14, false) MSTTS_SK_ATTR(16, true) MSTTS_SK_ATTR(16, false)
-    MSTTS_SK_ATTR(28, true) MSTTS_SK_ATTR(28, false) MSTTS_SK_ATTR(32, true) MSTTS_SK_ATTR(32, false)
-#undef MSTTS_SK_ATTR
-    g_attr_set = true;
-}
-
-// pick the guard-free instantiation when the trip count is one of the shapes the model produces
+// every instantiation, once: exact trip counts for the shapes the model produces, 0 = any
+typedef void (*SkinnyFwdFn)(const float*, long, const float*, long, float*, long, int, int, int, int);
+typedef void (*SkinnyBwdFn)(const float*, long, const float*, long, float*, long, int, int, int, int, int, long, long, long);
 #define SK_FWD(N, T) skinny_fwd_kernel<N, T>
 #define SK_BWD(N, T) skinny_bwd_kernel<N, T, false>
 #define SK_BWD_PACKED(N, T) skinny_bwd_kernel<N, T, true>
-#define MSTTS_SK_DISPATCH(KERNEL, nit, two, ...)                                                       \
-    do {                                                                                               \
-        if (two) {                                                                                     \
-            if (nit == 32) hipLaunchKernelGGL((KERNEL(32, true)), __VA_ARGS__);                        \
-            else if (nit == 28) hipLaunchKernelGGL((KERNEL(28, true)), __VA_ARGS__);                   \
-            else if (nit == 16) hipLaunchKernelGGL((KERNEL(16, true)), __VA_ARGS__);                   \
-            else if (nit == 14) hipLaunchKernelGGL((KERNEL(14, true)), __VA_ARGS__);                   \
-            else if (nit == 8) hipLaunchKernelGGL((KERNEL(8, true)), __VA_ARGS__);                     \
-            else if (nit == 4) hipLaunchKernelGGL((KERNEL(4, true)), __VA_ARGS__);                     \
-            else if (nit == 2) hipLaunchKernelGGL((KERNEL(2, true)), __VA_ARGS__);                     \
-            else hipLaunchKernelGGL((KERNEL(0, true)), __VA_ARGS__);                                   \
-        } else {                                                                                       \
-            if (nit == 32) hipLaunchKernelGGL((KERNEL(32, false)), __VA_ARGS__);                       \
-            else if (nit == 28) hipLaunchKernelGGL((KERNEL(28, false)), __VA_ARGS__);                  \
-            else if (nit == 16) hipLaunchKernelGGL((KERNEL(16, false)), __VA_ARGS__);                  \
-            else if (nit == 14) hipLaunchKernelGGL((KERNEL(14, false)), __VA_ARGS__);                  \
-            else if (nit == 8) hipLaunchKernelGGL((KERNEL(8, false)), __VA_ARGS__);                    \
-            else if (nit == 4) hipLaunchKernelGGL((KERNEL(4, false)), __VA_ARGS__);                    \
-            else if (nit == 2) hipLaunchKernelGGL((KERNEL(2, false)), __VA_ARGS__);                    \
-            else hipLaunchKernelGGL((KERNEL(0, false)), __VA_ARGS__);                                  \
-        }                                                                                              \
-    } while (0)
+#define SK_TABLE(K) {SKINNY_ROWS(K, 0), SKINNY_ROWS(K, 2), SKINNY_ROWS(K, 4), SKINNY_ROWS(K, 8), SKINNY_ROWS(K, 14), SKINNY_ROWS(K, 16), SKINNY_ROWS(K, 28), SKINNY_ROWS(K, 32)}
+static const SkinnyInst<SkinnyFwdFn> FWD_TABLE[] = SK_TABLE(SK_FWD);
+static const SkinnyInst<SkinnyBwdFn> BWD_TABLE[] = SK_TABLE(SK_BWD);
+static const SkinnyInst<SkinnyBwdFn> BWD_PACKED_TABLE[] = SK_TABLE(SK_BWD_PACKED);
+#undef SK_TABLE
+
+static void set_lds_attr() {
+    static bool done = false;
+    if (done) return;
+    skinny_lds_attr(FWD_TABLE);
+    skinny_lds_attr(BWD_TABLE);
+    skinny_lds_attr(BWD_PACKED_TABLE);
+    done = true;
+}
 
 }  // namespace mstts
 using namespace mstts;
@@ -321,15 +301,11 @@ extern "C" int mstts_skinny_fwd(const float* X, int64_t ldx, const float* W, int
     MSTTS_REQUIRE(N % 4 == 0 && ldw % 4 == 0 && ldx % 4 == 0 && aligned16(X) && aligned16(W), MSTTS_ERR_ALIGN,
                   "skinny_fwd: float4 alignment (N, ldx, ldw multiples of 4; 16-byte aligned pointers)");
     const int KL = (int)(K / ksplit);
-    size_t lds = sizeof(float) * (size_t)32 * (KL + 4);
-    const size_t red = sizeof(float) * 4 * 32 * 65;
-    if (lds < red) lds = red;
     dim3 grid((unsigned)((N + 63) / 64), (unsigned)ksplit, (unsigned)((M + 31) / 32));
     set_lds_attr();
-    const int nit = KL / 16;
-    const bool two = M > 16;      // blocks of 32 rows; with M <= 16 the second 16-row MFMA tile is all padding
-    MSTTS_SK_DISPATCH(SK_FWD, nit, two, grid, dim3(256), lds, (hipStream_t)s, X, (long)ldx, W, (long)ldw, P,
-                      (long)(pstride > 0 ? pstride : M * N), (int)M, (int)N, (int)K, KL);
+    // blocks of 32 rows; with M <= 16 the second 16-row MFMA tile is all padding
+    hipLaunchKernelGGL(skinny_pick(FWD_TABLE, KL / 16, M > 16), grid, dim3(256), skinny_lds_bytes(KL, 4, sizeof(float), 65), (hipStream_t)s, X, (long)ldx, W,
+                       (long)ldw, P, (long)(pstride > 0 ? pstride : M * N), (int)M, (int)N, (int)K, KL);
     MSTTS_CHECK_LAUNCH("skinny_fwd");
     return MSTTS_OK;
 }
@@ -353,24 +329,31 @@ extern "C" int32_t mstts_skinny_bwd_splits(int64_t R, int64_t N) {
     return (int32_t)ns;
 }
 
+// the one body behind mstts_skinny_bwd (W row-major), _packed (W in the lanes' order, ldw unused) and _pair (a second problem of the
+// same shape in the same launch: dG2 / W2 / P2)
+static int skinny_bwd_launch(const char* who, bool packed, bool pair, const float* dG, const float* dG2, long ldg, const float* W, const float* W2, long ldw,
+                             float* P, float* P2, long pstride, long M, long R, long N, int nsplit, mstts_stream_t s) {
+    MSTTS_REQUIRE(dG && W && P && (!pair || (dG2 && W2 && P2)) && M >= 1 && (packed ? R >= 32 && R % 32 == 0 : R >= 1), MSTTS_ERR_SHAPE,
+                  "%s: bad arguments%s", who, packed ? " (R % 32 == 0)" : "");
+    MSTTS_REQUIRE(nsplit >= 1 && N % (nsplit * 32L) == 0 && N / nsplit <= 1024, MSTTS_ERR_SHAPE,
+                  "%s: N must be a multiple of 32*nsplit with slices of at most 1024 columns", who);
+    MSTTS_REQUIRE((packed || ldw % 4 == 0) && ldg % 4 == 0 && aligned16(dG) && aligned16(W) && (!pair || (aligned16(dG2) && aligned16(W2))), MSTTS_ERR_ALIGN,
+                  "%s: float4 alignment", who);
+    const int NL = (int)(N / nsplit);
+    const unsigned nmb = (unsigned)((M + 31) / 32);
+    dim3 grid((unsigned)((R + 31) / 32), (unsigned)nsplit, pair ? 2 * nmb : nmb);
+    set_lds_attr();
+    const SkinnyBwdFn k = packed ? skinny_pick(BWD_PACKED_TABLE, NL / 32, M > 16) : skinny_pick(BWD_TABLE, NL / 32, M > 16);
+    hipLaunchKernelGGL(k, grid, dim3(256), skinny_lds_bytes(NL, 4, sizeof(float), 17), (hipStream_t)s, dG, ldg, W, packed ? 0L : ldw, P,
+                       pstride > 0 ? pstride : M * R, (int)M, (int)R, (int)N, NL, (int)nmb, pair ? (long)(dG2 - dG) : 0L, pair ? (long)(W2 - W) : 0L,
+                       pair ? (long)(P2 - P) : 0L);
+    MSTTS_CHECK_LAUNCH(who);
+    return MSTTS_OK;
+}
+
 extern "C" int mstts_skinny_bwd(const float* dG, int64_t ldg, const float* W, int64_t ldw, float* P, int64_t pstride, int64_t M, int64_t R,
                                 int64_t N, int32_t nsplit, mstts_stream_t s) {
-    MSTTS_REQUIRE(dG && W && P && M >= 1 && R >= 1, MSTTS_ERR_SHAPE, "skinny_bwd: bad arguments");
-    MSTTS_REQUIRE(nsplit >= 1 && N % (nsplit * 32L) == 0 && N / nsplit <= 1024, MSTTS_ERR_SHAPE,
-                  "skinny_bwd: N must be a multiple of 32*nsplit with slices of at most 1024 columns");
-    MSTTS_REQUIRE(ldw % 4 == 0 && ldg % 4 == 0 && aligned16(dG) && aligned16(W), MSTTS_ERR_ALIGN, "skinny_bwd: float4 alignment");
-    const int NL = (int)(N / nsplit);
-    size_t lds = sizeof(float) * (size_t)32 * (NL + 4);
-    const size_t red = sizeof(float) * 4 * 32 * 17;
-    if (lds < red) lds = red;
-    dim3 grid((unsigned)((R + 31) / 32), (unsigned)nsplit, (unsigned)((M + 31) / 32));
-    set_lds_attr();
-    const int nit = NL / 32;
-    const bool two = M > 16;
-    MSTTS_SK_DISPATCH(SK_BWD, nit, two, grid, dim3(256), lds, (hipStream_t)s, dG, (long)ldg, W, (long)ldw, P,
-                      (long)(pstride > 0 ? pstride : M * R), (int)M, (int)R, (int)N, NL, (int)grid.z, 0L, 0L, 0L);
-    MSTTS_CHECK_LAUNCH("skinny_bwd");
-    return MSTTS_OK;
+    return skinny_bwd_launch("skinny_bwd", false, false, dG, nullptr, ldg, W, nullptr, ldw, P, nullptr, pstride, M, R, N, nsplit, s);
 }
 
 extern "C" int mstts_pack_skinny_bwd(const float* W, int64_t ldw, float* Wp, int64_t R, int64_t N, int32_t nsplit, mstts_stream_t s) {
@@ -385,43 +368,12 @@ extern "C" int mstts_pack_skinny_bwd(const float* W, int64_t ldw, float* Wp, int
 
 extern "C" int mstts_skinny_bwd_packed(const float* dG, int64_t ldg, const float* Wp, float* P, int64_t pstride, int64_t M, int64_t R,
                                        int64_t N, int32_t nsplit, mstts_stream_t s) {
-    MSTTS_REQUIRE(dG && Wp && P && M >= 1 && R >= 32 && R % 32 == 0, MSTTS_ERR_SHAPE, "skinny_bwd_packed: bad arguments (R %% 32 == 0)");
-    MSTTS_REQUIRE(nsplit >= 1 && N % (nsplit * 32L) == 0 && N / nsplit <= 1024, MSTTS_ERR_SHAPE,
-                  "skinny_bwd_packed: N must be a multiple of 32*nsplit with slices of at most 1024 columns");
-    MSTTS_REQUIRE(ldg % 4 == 0 && aligned16(dG) && aligned16(Wp), MSTTS_ERR_ALIGN, "skinny_bwd_packed: float4 alignment");
-    const int NL = (int)(N / nsplit);
-    size_t lds = sizeof(float) * (size_t)32 * (NL + 4);
-    const size_t red = sizeof(float) * 4 * 32 * 17;
-    if (lds < red) lds = red;
-    dim3 grid((unsigned)(R / 32), (unsigned)nsplit, (unsigned)((M + 31) / 32));
-    set_lds_attr();
-    const int nit = NL / 32;
-    const bool two = M > 16;
-    MSTTS_SK_DISPATCH(SK_BWD_PACKED, nit, two, grid, dim3(256), lds, (hipStream_t)s, dG, (long)ldg, Wp, 0L, P,
-                      (long)(pstride > 0 ? pstride : M * R), (int)M, (int)R, (int)N, NL, (int)grid.z, 0L, 0L, 0L);
-    MSTTS_CHECK_LAUNCH("skinny_bwd_packed");
-    return MSTTS_OK;
+    return skinny_bwd_launch("skinny_bwd_packed", true, false, dG, nullptr, ldg, Wp, nullptr, 0, P, nullptr, pstride, M, R, N, nsplit, s);
 }
 
 /* two products of identical shape in one launch (the two directions of a BiLSTM backward step): problem 2's operands are given by
  * their own pointers; both must satisfy mstts_skinny_bwd's requirements */
 extern "C" int mstts_skinny_bwd_pair(const float* dG, const float* dG2, int64_t ldg, const float* W, const float* W2, int64_t ldw, float* P, float* P2,
                                      int64_t pstride, int64_t M, int64_t R, int64_t N, int32_t nsplit, mstts_stream_t s) {
-    MSTTS_REQUIRE(dG && W && P && dG2 && W2 && P2 && M >= 1 && R >= 1, MSTTS_ERR_SHAPE, "skinny_bwd_pair: bad arguments");
-    MSTTS_REQUIRE(nsplit >= 1 && N % (nsplit * 32L) == 0 && N / nsplit <= 1024, MSTTS_ERR_SHAPE,
-                  "skinny_bwd_pair: N must be a multiple of 32*nsplit with slices of at most 1024 columns");
-    MSTTS_REQUIRE(ldw % 4 == 0 && ldg % 4 == 0 && aligned16(dG) && aligned16(W) && aligned16(dG2) && aligned16(W2), MSTTS_ERR_ALIGN, "skinny_bwd_pair: float4 alignment");
-    const int NL = (int)(N / nsplit);
-    size_t lds = sizeof(float) * (size_t)32 * (NL + 4);
-    const size_t red = sizeof(float) * 4 * 32 * 17;
-    if (lds < red) lds = red;
-    const unsigned nmb = (unsigned)((M + 31) / 32);
-    dim3 grid((unsigned)((R + 31) / 32), (unsigned)nsplit, 2 * nmb);
-    set_lds_attr();
-    const int nit = NL / 32;
-    const bool two = M > 16;
-    MSTTS_SK_DISPATCH(SK_BWD, nit, two, grid, dim3(256), lds, (hipStream_t)s, dG, (long)ldg, W, (long)ldw, P,
-                      (long)(pstride > 0 ? pstride : M * R), (int)M, (int)R, (int)N, NL, (int)nmb, (long)(dG2 - dG), (long)(W2 - W), (long)(P2 - P));
-    MSTTS_CHECK_LAUNCH("skinny_bwd_pair");
-    return MSTTS_OK;
+    return skinny_bwd_launch("skinny_bwd_pair", false, true, dG, dG2, ldg, W, W2, ldw, P, P2, pstride, M, R, N, nsplit, s);
 }

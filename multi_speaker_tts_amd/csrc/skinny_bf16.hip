@@ -8,7 +8,7 @@
 //   forward  Wp[strip][ks][wave][kstep][lane][tile 0..3][4] : W[kb + wave*wl + 16*kstep + 4*(lane>>4) + e][64*strip + 16*tile + (lane&15)]
 //   backward Wq[rstrip][ns][wave][pair][lane][2][4]         : W[32*rstrip + 16*(wave&1) + (lane&15)][nb + (wave>>1)*hl + 16*(2*pair+s2) + 4*(lane>>4) + e]
 // so every wave-level load is one contiguous 2 KB / 1 KB stream.
-#include "common.h"
+#include "skinny_tile.h"
 
 namespace mstts {
 
@@ -237,43 +237,51 @@ __global__ void pack_bf16_bwd_kernel(const float* __restrict__ W, long ldw, unsi
     }
 }
 
-static bool g_bf_attr = false;
+typedef void (*SkinnyBf16FwdFn)(const float*, long, const u32x4*, float*, long, int, int, int);
+typedef void (*SkinnyBf16BwdFn)(const float*, long, const u32x4*, float*, long, int, int, int);
+#define SK_FWD16(N, T) skinny_fwd_bf16_kernel<N, T>
+#define SK_BWD16(N, T) skinny_bwd_bf16_kernel<N, T>
+static const SkinnyInst<SkinnyBf16FwdFn> FWD16_TABLE[] = {SKINNY_ROWS(SK_FWD16, 0), SKINNY_ROWS(SK_FWD16, 1), SKINNY_ROWS(SK_FWD16, 4)};
+static const SkinnyInst<SkinnyBf16BwdFn> BWD16_TABLE[] = {SKINNY_ROWS(SK_BWD16, 0), SKINNY_ROWS(SK_BWD16, 1), SKINNY_ROWS(SK_BWD16, 8)};
+
 static void bf_attr() {
-    if (g_bf_attr) return;
-#define A_(K) hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    A_((skinny_fwd_bf16_kernel<0, true>)) A_((skinny_fwd_bf16_kernel<0, false>)) A_((skinny_fwd_bf16_kernel<4, true>)) A_((skinny_fwd_bf16_kernel<4, false>))
-    A_((skinny_fwd_bf16_kernel<1, true>)) A_((skinny_fwd_bf16_kernel<1, false>))
-    A_((skinny_bwd_bf16_kernel<0, true>)) A_((skinny_bwd_bf16_kernel<0, false>)) A_((skinny_bwd_bf16_kernel<8, true>)) A_((skinny_bwd_bf16_kernel<8, false>))
-    A_((skinny_bwd_bf16_kernel<1, true>)) A_((skinny_bwd_bf16_kernel<1, false>))
-#undef A_
-    g_bf_attr = true;
+    static bool done = false;
+    if (done) return;
+    skinny_lds_attr(FWD16_TABLE);
+    skinny_lds_attr(BWD16_TABLE);
+    done = true;
+}
+
+// Split counts of the packed bf16 products, at most `cap`: the divisor of the 64-wide units that brings strips x splits closest to
+// 512 workgroups with slices the kernels hold (0 = none).  The decoder drivers cap them by the fp32 path's counts (decoder.hip).
+int skinny_bf16_fwd_split(long N, long K, int cap) {
+    if (N % 64 != 0 || K % 64 != 0 || cap < 1) return 0;
+    const long strips = N / 64, units = K / 64;
+    long best = 0, best_d = 1L << 40;
+    for (long ks = 1; ks <= cap && ks <= units; ++ks) {
+        if (units % ks != 0 || K / ks > 64 * BF_MAX_KS) continue;
+        const long d = labs(strips * ks - 512);
+        if (d < best_d) { best_d = d; best = ks; }
+    }
+    return (int)best;
+}
+int skinny_bf16_bwd_split(long R, long N, int cap) {
+    if (R % 32 != 0 || N % 64 != 0 || cap < 1) return 0;
+    const long strips = R / 32, units = N / 64;
+    long best = 0, best_d = 1L << 40;
+    for (long ns = 1; ns <= cap && ns <= units; ++ns) {
+        if (units % ns != 0 || N / ns > 64 * BF_MAX_PAIRS) continue;
+        const long d = labs(strips * ns - 512);
+        if (d < best_d) { best_d = d; best = ns; }
+    }
+    return (int)best;
 }
 
 }  // namespace mstts
 using namespace mstts;
 
-extern "C" int32_t mstts_skinny_bf16_fwd_splits(int64_t N, int64_t K) {
-    if (N <= 0 || K <= 0 || N % 64 != 0 || K % 64 != 0) return 0;
-    const long strips = N / 64, units = K / 64;
-    long best = 0, best_d = 1L << 40;
-    for (long ks = 1; ks <= 16 && ks <= units; ++ks) {
-        if (units % ks != 0 || K / ks > 64 * BF_MAX_KS) continue;
-        const long d = labs(strips * ks - 512);
-        if (d < best_d) { best_d = d; best = ks; }
-    }
-    return (int32_t)best;
-}
-extern "C" int32_t mstts_skinny_bf16_bwd_splits(int64_t R, int64_t N) {
-    if (R <= 0 || N <= 0 || R % 32 != 0 || N % 64 != 0) return 0;
-    const long strips = R / 32, units = N / 64;
-    long best = 0, best_d = 1L << 40;
-    for (long ns = 1; ns <= 8 && ns <= units; ++ns) {
-        if (units % ns != 0 || N / ns > 64 * BF_MAX_PAIRS) continue;
-        const long d = labs(strips * ns - 512);
-        if (d < best_d) { best_d = d; best = ns; }
-    }
-    return (int32_t)best;
-}
+extern "C" int32_t mstts_skinny_bf16_fwd_splits(int64_t N, int64_t K) { return N <= 0 || K <= 0 ? 0 : skinny_bf16_fwd_split(N, K, 16); }
+extern "C" int32_t mstts_skinny_bf16_bwd_splits(int64_t R, int64_t N) { return R <= 0 || N <= 0 ? 0 : skinny_bf16_bwd_split(R, N, 8); }
 static unsigned pk_grid(long n) { long b = (n + 255) / 256; if (b > 16384) b = 16384; return (unsigned)(b < 1 ? 1 : b); }
 
 extern "C" int mstts_pack_bf16_fwd(const float* W, int64_t ldw, void* Wp, int64_t K, int64_t N, int32_t ksplit, mstts_stream_t s) {
@@ -297,17 +305,10 @@ extern "C" int mstts_skinny_fwd_bf16(const float* X, int64_t ldx, const void* Wp
                   "skinny_fwd_bf16: N %% 64, K %% (64*ksplit), K/ksplit <= 512 required");
     MSTTS_REQUIRE(ldx % 4 == 0 && aligned16(X) && aligned16(Wp), MSTTS_ERR_ALIGN, "skinny_fwd_bf16: 16-byte alignment");
     bf_attr();
-    const int KL = (int)(K / ksplit), nks = KL / 64;
-    size_t lds = (size_t)32 * (KL + 8) * 2;
-    if (lds < sizeof(float) * 4 * 32 * 65) lds = sizeof(float) * 4 * 32 * 65;
+    const int KL = (int)(K / ksplit);
     dim3 grid((unsigned)(N / 64), (unsigned)ksplit, (unsigned)((M + 31) / 32));
-    const long ps = pstride ? pstride : M * N;
-    const bool two = M > 16;
-#define L_(NK, T) hipLaunchKernelGGL((skinny_fwd_bf16_kernel<NK, T>), grid, dim3(256), lds, (hipStream_t)s, X, (long)ldx, (const u32x4*)Wp, P, ps, (int)M, (int)N, KL)
-    if (nks == 4) { if (two) L_(4, true); else L_(4, false); }
-    else if (nks == 1) { if (two) L_(1, true); else L_(1, false); }
-    else { if (two) L_(0, true); else L_(0, false); }
-#undef L_
+    hipLaunchKernelGGL(skinny_pick(FWD16_TABLE, KL / 64, M > 16), grid, dim3(256), skinny_lds_bytes(KL, 8, 2, 65), (hipStream_t)s, X, (long)ldx, (const u32x4*)Wp, P,
+                       (long)(pstride ? pstride : M * N), (int)M, (int)N, KL);
     MSTTS_CHECK_LAUNCH("skinny_fwd_bf16");
     return MSTTS_OK;
 }
@@ -317,17 +318,10 @@ extern "C" int mstts_skinny_bwd_bf16(const float* dG, int64_t ldg, const void* W
                   "skinny_bwd_bf16: R %% 32, N %% (64*nsplit), N/nsplit <= 1024 required");
     MSTTS_REQUIRE(ldg % 4 == 0 && aligned16(dG) && aligned16(Wq), MSTTS_ERR_ALIGN, "skinny_bwd_bf16: 16-byte alignment");
     bf_attr();
-    const int NL = (int)(N / nsplit), np = NL / 64;
-    size_t lds = (size_t)32 * (NL + 8) * 2;
-    if (lds < sizeof(float) * 4 * 32 * 17) lds = sizeof(float) * 4 * 32 * 17;
+    const int NL = (int)(N / nsplit);
     dim3 grid((unsigned)(R / 32), (unsigned)nsplit, (unsigned)((M + 31) / 32));
-    const long ps = pstride ? pstride : M * R;
-    const bool two = M > 16;
-#define L_(NP_, T) hipLaunchKernelGGL((skinny_bwd_bf16_kernel<NP_, T>), grid, dim3(256), lds, (hipStream_t)s, dG, (long)ldg, (const u32x4*)Wq, P, ps, (int)M, (int)R, NL)
-    if (np == 8) { if (two) L_(8, true); else L_(8, false); }
-    else if (np == 1) { if (two) L_(1, true); else L_(1, false); }
-    else { if (two) L_(0, true); else L_(0, false); }
-#undef L_
+    hipLaunchKernelGGL(skinny_pick(BWD16_TABLE, NL / 64, M > 16), grid, dim3(256), skinny_lds_bytes(NL, 8, 2, 17), (hipStream_t)s, dG, (long)ldg, (const u32x4*)Wq, P,
+                       (long)(pstride ? pstride : M * R), (int)M, (int)R, NL);
     MSTTS_CHECK_LAUNCH("skinny_bwd_bf16");
     return MSTTS_OK;
 }

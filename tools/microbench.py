@@ -30,6 +30,23 @@ def timeit(fn, n, graph=False):
     return (time.perf_counter() - t0) / n * 1e6
 
 
+def skinny_rows():
+    """The weight-streaming products of the launch-per-step loops, forward and backward, fp32 and bf16: us per launch inside a hipGraph."""
+    for M, N, K in ((32, 4096, 1792), (32, 4096, 2048), (32, 128, 1024)):
+        X, W, dG = torch.randn(M, K, device=dev), torch.randn(K, N, device=dev) * 0.02, torch.randn(M, N, device=dev)
+        W16, P, p = torch.zeros(K * N, dtype=torch.int16, device=dev), torch.zeros(16 * M * max(N, K), device=dev), lib.ptr
+        ks, ns, ks16, ns16 = L.mstts_skinny_fwd_splits(N, K), L.mstts_skinny_bwd_splits(K, N), L.mstts_skinny_bf16_fwd_splits(N, K), L.mstts_skinny_bf16_bwd_splits(K, N)
+        print("skinny fwd f32  %dx%dx%d : %.2f us" % (M, N, K, timeit(lambda: lib.call("mstts_skinny_fwd", p(X), K, p(W), N, p(P), 0, M, N, K, ks), 1000, graph=True)))
+        print("skinny bwd f32  %dx%dx%d : %.2f us" % (M, N, K, timeit(lambda: lib.call("mstts_skinny_bwd", p(dG), N, p(W), N, p(P), 0, M, K, N, ns), 1000, graph=True)))
+        lib.call("mstts_pack_bf16_fwd", p(W), N, p(W16), K, N, ks16)
+        print("skinny fwd bf16 %dx%dx%d : %.2f us" % (M, N, K, timeit(lambda: lib.call("mstts_skinny_fwd_bf16", p(X), K, p(W16), p(P), 0, M, N, K, ks16), 1000, graph=True)))
+        lib.call("mstts_pack_bf16_bwd", p(W), N, p(W16), K, N, ns16)
+        print("skinny bwd bf16 %dx%dx%d : %.2f us" % (M, N, K, timeit(lambda: lib.call("mstts_skinny_bwd_bf16", p(dG), N, p(W16), p(P), 0, M, K, N, ns16), 1000, graph=True)))
+
+
+if "--skinny" in sys.argv:           # only these rows
+    skinny_rows()
+    sys.exit(0)
 x = torch.zeros(1 << 20, device=dev)
 small = lambda: lib.call("mstts_fill", lib.ptr(x), 1.0, 1024)
 print("tiny fill kernel, eager     : %.2f us/launch" % timeit(small, 2000))
