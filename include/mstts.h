@@ -363,9 +363,10 @@ int mstts_lsa_step_bwd(const mstts_lsa_const* c, const float* d_ctx, int64_t d_c
                        int32_t d_ctx2_parts, int64_t d_ctx2_pstride, const float* G_next, const float* d_f_next, float* G,
                        const float* align, const float* q, const float* cum, const float* ctx_fwd, int64_t ctx_fwd_ld,
                        float* d_e, float* dq, float* d_f, mstts_stream_t s);
-/* Test entry for the time-out path of the single-launch forward kernel: the same launch without the workgroups of one slice, which
- * forces the rest of each row to time out (milliseconds) and fall back to its serial recompute; the counter behind the granules
- * then reads > 0.  The skipped slice's own outputs are not written. */
+/* Test entry for the time-out path of the single-launch forward kernel: the launch mstts_lsa_step_fwd would make for the same c (the
+ * by-unit filter form when c->loc_kt is set), whose workgroups of one slice leave at once.  That forces the rest of each row to time
+ * out (milliseconds) and fall back to its serial recompute; the counter behind the energy granules then reads > 0.  The skipped slice's
+ * own outputs are not written. */
 int mstts_lsa_step_fwd_selftest(const mstts_lsa_const* c, const float* q, int32_t q_parts, int64_t q_pstride, float* q_sum,
                                 const float* cum, float* align, float* cum_next, float* ctx, int64_t ctx_ld, void* granules,
                                 uint32_t epoch, int32_t skip_slice, mstts_stream_t s);

@@ -76,6 +76,23 @@ __device__ __forceinline__ float sum_parts(const float* __restrict__ p, int part
 }
 constexpr int MSTTS_MAX_PARTS = 16;
 
+// The granule buffer of the single-launch attention step (lsa.hip), in 8-byte words: the energy granules [B][T], the time-out counter,
+// then - for the forms that have them - the query granules [B][QW] and the frame granules [B][FW].  The one place that knows the layout.
+struct LsaGranules {
+    static constexpr long QW = 128, FW = 96;       // query units per row (A); frame granules per row (n_mel + 1, padded)
+    unsigned long long* base;
+    long B, T;
+    __host__ __device__ LsaGranules(void* p, long B_, long T_) : base((unsigned long long*)p), B(B_), T(T_) {}
+    __host__ __device__ unsigned long long* energy(long b) const { return base + b * T; }
+    __host__ __device__ unsigned long long* timeouts() const { return base + B * T; }
+    __host__ __device__ unsigned long long* query(long b) const { return base + B * T + 1 + b * QW; }
+    __host__ __device__ unsigned long long* frame(long b) const { return base + B * T + 1 + B * QW + b * FW; }
+    // words per form: plain step | + in-launch query | + projection (and prenet)
+    __host__ __device__ long words() const { return B * T + 1; }
+    __host__ __device__ long words_q() const { return words() + B * QW; }
+    __host__ __device__ long words_qp() const { return words_q() + B * FW; }
+};
+
 // split counts of the packed bf16 skinny products with at most `cap` slices, 0 = shape not covered (skinny_bf16.hip)
 int skinny_bf16_fwd_split(long N, long K, int cap);
 int skinny_bf16_bwd_split(long R, long N, int cap);

@@ -396,7 +396,7 @@ extern "C" int mstts_decoder_train_fwd(const mstts_decoder_train_desc* d, mstts_
     // query projection inside the attention launch: geometry supported, by-unit filter given, granule buffer large enough
     const bool fused_q = mstts_lsa_step_q_supported(T, M, H) && d->lsa.loc_kt && A == 128 &&
                          d->energy_ws_floats >= mstts_lsa_step_q_ws_bytes(B, T) / 4 && WP % 4 == 0;
-    RC(zero(d->energy_ws, fused_q ? mstts_lsa_step_q_ws_bytes(B, T) / 4 : 2 * B * T + 2, s));   // granules + time-out counter (it sits after the last row's granules)
+    RC(zero(d->energy_ws, 2 * (fused_q ? LsaGranules(nullptr, B, T).words_q() : LsaGranules(nullptr, B, T).words()), s));   // 8-byte granules + time-out counter
     const CellSlots k0 = train_cell0(d), k1 = train_cell1(d);
     unsigned long long* gran = (unsigned long long*)d->energy_ws;
     for (long st = 0; st < S; ++st) {
@@ -673,7 +673,7 @@ static int infer_steps_fast(const mstts_decoder_infer_desc* d, int64_t step0, in
 
 extern "C" int64_t mstts_decoder_infer_ws_floats(int64_t B, int64_t H, int64_t P, int64_t T, int64_t A, int64_t n_mel) {
     const long np = (n_mel + 1 + 3) / 4 * 4;
-    const long slow = 2 * B * P + 8 * B * H + (2 * B * T + 2) + B * A + B * n_mel;
+    const long slow = 2 * B * P + 8 * B * H + 2 * LsaGranules(nullptr, B, T).words() + B * A + B * n_mel;
     const long fast = (long)MSTTS_MAX_PARTS * (4 * B * H + B * A + B * np) + mstts_lsa_step_qp_ws_bytes(B, T) / 4 + B * n_mel;
     return slow > fast ? slow : fast;
 }
@@ -692,7 +692,7 @@ extern "C" int mstts_decoder_infer_steps(const mstts_decoder_infer_desc* d, int6
     float* pb = w;          w += B * P;
     float* xw = w;          w += 4 * BH;
     float* gates = w;       w += 4 * BH;
-    float* gran = w;        w += 2 * BT + 2;          // the 8-byte granules (+ counter) of the single-launch attention step
+    float* gran = w;        w += 2 * LsaGranules(nullptr, B, T).words();          // the 8-byte granules (+ counter) of the single-launch attention step
     float* q = w;           w += B * A;
     float* zero_frame = w;  w += B * NM;
     if (step0 == 0) {
@@ -702,7 +702,7 @@ extern "C" int mstts_decoder_infer_steps(const mstts_decoder_infer_desc* d, int6
         RC(zero(d->c1, BH, s));
         RC(zero(d->cum, BT, s));
         RC(zero(zero_frame, B * NM, s));
-        RC(zero(gran, 2 * BT + 2, s));
+        RC(zero(gran, 2 * LsaGranules(nullptr, B, T).words(), s));
     }
     const CellSlots k0 = infer_cell0(d, W0, M), k1 = infer_cell1(d);
     for (long st = step0; st < step0 + n; ++st) {

@@ -3,7 +3,7 @@
 //
 // The decoder calls this once per mel frame, strictly in sequence, so one step has to spread over the whole chip and cost
 // as few dependent round trips as possible.
-//   forward, one launch  (lsa_step_kernel, grid (T/16 | M/96, B)): every workgroup computes the energies of 16 encoder
+//   forward, one launch  (lsa_step_kernel, 1-D grid of max(T/16, M/96) x B workgroups): every workgroup computes the energies of 16 encoder
 //       positions (folded 31-tap location filter -> tanh -> wave shuffle reduction), the workgroups of a row exchange
 //       their slices inside the launch as 8-byte {epoch, value} granules, then each runs the row softmax and streams its
 //       96-column slice of values[b].
@@ -17,12 +17,12 @@
 
 namespace mstts {
 
-constexpr int TS = 8;       // encoder positions per workgroup (T/8 x B workgroups: 512 at T=128, B=32 -> 2 waves per SIMD)
+constexpr int TS = 8;       // encoder positions per workgroup of the two-launch kernels and the backward (T/8 x B workgroups: 512 at T=128, B=32 -> 2 waves per SIMD)
 constexpr int A_ = 128;     // attention units  (hp.Attention.Memory_Size)
 constexpr int CH_ = 32;     // location conv channels (hp.Attention.Conv.Channel)
 constexpr int FLD = CH_ + 4; // LDS row stride of the location features: rows stay 16-byte aligned for b128 broadcast reads
-constexpr int KS_MAX = 31;
-constexpr int LKT_LD = 36;   // row stride of the by-unit filter copy: 144 B - 16-byte aligned rows that do not all start in the same cache set (128 B did: +0.3 us)  // location conv taps upper bound (= the reference's hp.Attention.Conv.Kernel_Size)
+constexpr int KS_MAX = 31;   // location conv taps upper bound (= the reference's hp.Attention.Conv.Kernel_Size)
+constexpr int LKT_LD = 36;   // row stride of the by-unit filter copy: 144 B - 16-byte aligned rows that do not all start in the same cache set (128 B did: +0.3 us)
 
 __device__ __forceinline__ float fast_tanh(float x) {
     // tanh via one exp; relative error ~1e-6 over the energy pre-activation range
@@ -188,8 +188,8 @@ __global__ __launch_bounds__(256) void lsa_context_kernel(mstts_lsa_const c, con
 // (MI355X hand-off form R2).  Then every workgroup runs the same T-float softmax and streams its own
 // column slice of values[b].  The caller zeroes the granule buffer once per sequence and passes epoch =
 // step + 1.  Every spin is bounded: a workgroup that gives up recomputes the missing energy itself
-// (serially, slow but correct) and counts the event in the word after the last granule, so a launch can
-// neither hang nor return a stale value.
+// (serially, slow but correct) and counts the event in the time-out counter (LsaGranules, common.h), so a launch
+// can neither hang nor return a stale value.
 // ---------------------------------------------------------------------------------------------
 typedef __attribute__((address_space(1))) unsigned long long gu64;
 
@@ -244,7 +244,7 @@ constexpr int QJ = 8;             // hidden units per thread of the in-launch qu
 // QIN: the query projection q = m1 . Wq runs inside this launch (it was a launch of its own, 4.9 us of almost pure fixed cost): the
 // workgroup of slice cs computes the 16 units 16 cs .. 16 cs + 15 of its row's query (1/8 of the product: 64 KB of the kernel), the
 // eight slices exchange them through a second granule array exactly like the energies, and the energy phase reads q from LDS.
-// SELFTEST instantiation (mstts_lsa_step_fwd_selftest only): the workgroup of slice `skip` leaves at once, so the rest of its row must take
+// skip >= 0 (the self-test calls; production passes -1): the workgroup of slice `skip` leaves before it writes anything, so the rest of its row must take
 // the time-out path - the only way to exercise it, since on a healthy chip no workgroup ever times out
 struct LsaQIn { const float* m1; long m1_ld; const float* wq; int H, bf16; };      // QIN operands: m1 rows [B, >= H], Wq [H, A] row-major
 // PROJ (free-running decoder): the output projection [m1 | ctx] . Wp + bias also comes out of this launch, with no exchange of its own:
@@ -265,7 +265,7 @@ constexpr int PF_Q = 21, PF_G = 24, PF_IT = 6;                        // whole-f
 // (every operand of these stages is fetched 16 bytes per lane: a wave's load costs the address unit 16 cycles whatever its width, and
 // with one-word loads - 110 per wave in the first version of this kernel - that alone was 6 us of the launch)
 struct LsaPre { const float* w0; const float* b0; const float* w1; const float* b1; const uint8_t* m0; const uint8_t* m1; float inv_keep;
-                float* out; long out_ld; PackedDst out_p; unsigned long long* gf; };
+                float* out; long out_ld; PackedDst out_p; };
 // (forceinline like the other serial paths: a call would take the address of the kernel's by-value argument blocks and put them - and
 // every later use of them - into scratch memory)
 // m1 . Wp_m[:, o] + bias[o] by one thread (time-out path of the whole-frame form)
@@ -275,7 +275,51 @@ __device__ __forceinline__ float lsa_pm_serial(const LsaQIn& qi, const LsaProj& 
     for (int j = 0; j < qi.H; ++j) acc += qi.m1[(long)b * qi.m1_ld + j] * pj.wp_own[((long)(so * QJ + (j & (QJ - 1))) * 128 + (j >> 3)) * PJ_OW + i];
     return acc;
 }
-template <bool SELFTEST, bool LKT = false, bool QIN = false, bool PROJ = false, bool PRE = false>
+// Bounded wait for one {epoch, value} granule of the query / frame exchange (the data is the flag): true with the value once its tag equals this launch's epoch, false
+// after FS_MAX_SPINS polls - the caller then recomputes the value itself and counts the time-out.  (The recompute stays at the call site:
+// handed in as a callable it would capture the kernel's argument blocks by address, see above.)
+__device__ __forceinline__ bool granule_wait(gu64* p, unsigned epoch, float* v) {
+    unsigned long long x = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    unsigned spins = 0;
+    while ((unsigned)(x >> 32) != epoch && spins < FS_MAX_SPINS) {
+        __builtin_amdgcn_s_sleep(1);
+        x = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ++spins;
+    }
+    *v = __uint_as_float((unsigned)x);
+    return (unsigned)(x >> 32) == epoch;
+}
+// the part of the energy pre-activation that does not need the query: keys + biases + filter . cumulative alignment, positions 4 tg .. + 3
+__device__ __forceinline__ void lsa_pre_no_query(const float* s_cum, int tg, const float (&kv)[4], float sb, const float (&lk)[KS_MAX], float (&pre0)[4]) {
+    float cw[4 + KS_MAX - 1];
+#pragma unroll
+    for (int i = 0; i < 4 + KS_MAX - 1; ++i) cw[i] = s_cum[4 * tg + i];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        float pre = kv[i] + sb;
+#pragma unroll
+        for (int j = 0; j < KS_MAX; ++j) pre += cw[i + j] * lk[j];
+        pre0[i] = pre;
+    }
+}
+// m1 . Wp_m for the own outputs of an owner slice, reduced like the query units: 8 hidden units per thread (m = its m1 registers), the 16
+// chunks of each 16-lane row through DPP row shifts, the row sums into s_pq
+__device__ __forceinline__ void lsa_pm_own(const float* m, const float4 (&pw)[QJ], float* s_pq, int tid) {
+    float a3[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int jj = 0; jj < QJ; ++jj) {
+        const float x = m[jj];
+        a3[0] += x * pw[jj].x; a3[1] += x * pw[jj].y; a3[2] += x * pw[jj].z; a3[3] += x * pw[jj].w;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        a3[i] += dpp_mov<0x114, 0xf>(0.f, a3[i]);
+        a3[i] += dpp_mov<0x118, 0xf>(0.f, a3[i]);
+    }
+    if ((tid & 15) >= 12) *reinterpret_cast<float4*>(&s_pq[(tid >> 4) * PJ_OW + 4 * (tid & 3)]) = make_float4(a3[0], a3[1], a3[2], a3[3]);
+}
+static_assert(A_ == LsaGranules::QW && PR_GLD == LsaGranules::FW, "granule layout (common.h) and the step kernel disagree");
+template <bool LKT, bool QIN, bool PROJ, bool PRE>
 __global__ __launch_bounds__(FS_THREADS) void lsa_step_kernel(mstts_lsa_const c, const float* __restrict__ q, int q_parts, long q_pstride,
                                                               float* __restrict__ q_sum, const float* cum,
                                                               float* __restrict__ align, float* __restrict__ cum_next,
@@ -284,7 +328,7 @@ __global__ __launch_bounds__(FS_THREADS) void lsa_step_kernel(mstts_lsa_const c,
                                                               LsaProj pjx, LsaPre prx) {
     int cs, b;
     row_slice_of_block(blockIdx.x, ncs, (int)c.B, &b, &cs);
-    if (SELFTEST && cs == skip) return;
+    const LsaGranules gr(gran, c.B, c.T);
     __shared__ __attribute__((aligned(16))) float s_pq[PROJ ? 32 * PJ_OW : 4];                               // PROJ: per-row-of-16-lanes partial sums of m1 . Wp_m (own outputs)
     __shared__ float s_pm[PROJ ? PJ_OW : 1];                                    //       m1 . Wp_m of the own outputs
     __shared__ float s_pv[PROJ ? (PJ_TG + 1) * PJ_OW : 1];                      //       per-position-group partial sums of sum_t a[t] vp[t]
@@ -383,6 +427,9 @@ __global__ __launch_bounds__(FS_THREADS) void lsa_step_kernel(mstts_lsa_const c,
         // between len and T are real memory and get a zero alignment below)
         vv[i] = *reinterpret_cast<const float4*>(v + (long)min(t, T - 1) * M);       // (used only under vlive && t < len)
     }
+    // (self-test: this slice leaves before it writes anything.  Tested here and not at the top, where the test would hold the kernel
+    // argument loads back behind the slice arithmetic: +0.1 us per launch)
+    if (cs == skip) return;
     // ---- own energy slice
     if (tid < FS_TSL + KS_MAX - 1 + 2) s_cum[tid] = cwin;          // entries past the window are zero
     if constexpr (QIN) {
@@ -405,23 +452,10 @@ __global__ __launch_bounds__(FS_THREADS) void lsa_step_kernel(mstts_lsa_const c,
         acc.z += dpp_mov<0x118, 0xf>(0.f, acc.z); acc.w += dpp_mov<0x118, 0xf>(0.f, acc.w);
         if ((tid & 15) >= 12) *reinterpret_cast<float4*>(&s_qp[(tid >> 4) * 16 + 4 * (tid & 3)]) = acc;   // lanes 12..15 of a row hold its sums
         if constexpr (PRE) {                                     // whole-frame form: m1 . Wp_m of the own outputs is handed over WITH the query
-            if (cs < 8) {
-                float a3[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int jj = 0; jj < QJ; ++jj) {
-                    const float x = reinterpret_cast<const float*>(qm)[jj];
-                    a3[0] += x * pw[jj].x; a3[1] += x * pw[jj].y; a3[2] += x * pw[jj].z; a3[3] += x * pw[jj].w;
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    a3[i] += dpp_mov<0x114, 0xf>(0.f, a3[i]);
-                    a3[i] += dpp_mov<0x118, 0xf>(0.f, a3[i]);
-                }
-                if ((tid & 15) >= 12) *reinterpret_cast<float4*>(&s_pq[(tid >> 4) * PJ_OW + 4 * (tid & 3)]) = make_float4(a3[0], a3[1], a3[2], a3[3]);
-            }
+            if (cs < 8) lsa_pm_own(reinterpret_cast<const float*>(qm), pw, s_pq, tid);
         }
         __syncthreads();
-        gu64* gq = (gu64*)(gran + (long)c.B * T + 1 + (long)b * A_);
+        gu64* gq = (gu64*)gr.query(b);
         if (tid < 16 && cs < 8) {
             float qa = 0.f;
 #pragma unroll
@@ -429,37 +463,12 @@ __global__ __launch_bounds__(FS_THREADS) void lsa_step_kernel(mstts_lsa_const c,
             s_q[16 * cs + tid] = qa;
             __hip_atomic_store(gq + 16 * cs + tid, ((unsigned long long)epoch << 32) | __float_as_uint(qa), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        // the part of the pre-activation that does not need the query (keys + filter . cumulative alignment) while the granules travel
-        {
-            float cw[4 + KS_MAX - 1];
-#pragma unroll
-            for (int i = 0; i < 4 + KS_MAX - 1; ++i) cw[i] = s_cum[4 * tg + i];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float pre = kv[i] + sb;
-#pragma unroll
-                for (int j = 0; j < KS_MAX; ++j) pre += cw[i + j] * lk[j];
-                pre0[i] = pre;
-            }
-        }
+        lsa_pre_no_query(s_cum, tg, kv, sb, lk, pre0);          // while the granules travel
         if constexpr (PROJ && !PRE) {                            // m1 . Wp_m for the own outputs, reduced like the query units
-            if (cs < 8) {
-                float a3[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int jj = 0; jj < QJ; ++jj) {
-                    const float x = reinterpret_cast<const float*>(qm)[jj];
-                    a3[0] += x * pw[jj].x; a3[1] += x * pw[jj].y; a3[2] += x * pw[jj].z; a3[3] += x * pw[jj].w;
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    a3[i] += dpp_mov<0x114, 0xf>(0.f, a3[i]);
-                    a3[i] += dpp_mov<0x118, 0xf>(0.f, a3[i]);
-                }
-                if ((tid & 15) >= 12) *reinterpret_cast<float4*>(&s_pq[(tid >> 4) * PJ_OW + 4 * (tid & 3)]) = make_float4(a3[0], a3[1], a3[2], a3[3]);
-            }
+            if (cs < 8) lsa_pm_own(reinterpret_cast<const float*>(qm), pw, s_pq, tid);
         }
         if constexpr (PRE) {
-            gu64* gm = (gu64*)(prx.gf + (long)b * PR_GLD);
+            gu64* gm = (gu64*)gr.frame(b);
             if (cs < 8 && tid >= 32 && tid < 32 + PJ_OWN && PJ_OWN * cs + tid - 32 <= pjx.NM) {
                 float a = pbias;
 #pragma unroll
@@ -469,35 +478,19 @@ __global__ __launch_bounds__(FS_THREADS) void lsa_step_kernel(mstts_lsa_const c,
             }
             const int o = tid - A_;
             if (cs < 8 && o >= 0 && o <= pjx.NM && o / PJ_OWN != cs) {
-                unsigned long long x = __hip_atomic_load(gm + o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                unsigned spins = 0;
-                while ((unsigned)(x >> 32) != epoch && spins < FS_MAX_SPINS) {
-                    __builtin_amdgcn_s_sleep(1);
-                    x = __hip_atomic_load(gm + o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    ++spins;
-                }
                 float a;
-                if ((unsigned)(x >> 32) == epoch) a = __uint_as_float((unsigned)x);
-                else {
+                if (!granule_wait(gm + o, epoch, &a)) {
                     a = lsa_pm_serial(qi, pjx, b, o);
-                    atomicAdd(gran + (long)c.B * T, 1ull);
+                    atomicAdd(gr.timeouts(), 1ull);
                 }
                 s_m[o] = a;
             }
         }
         if (tid < A_ && (tid >> 4) != cs) {                      // the other slices' units (the data is the flag)
-            unsigned long long x = __hip_atomic_load(gq + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            unsigned spins = 0;
-            while ((unsigned)(x >> 32) != epoch && spins < FS_MAX_SPINS) {
-                __builtin_amdgcn_s_sleep(1);
-                x = __hip_atomic_load(gq + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                ++spins;
-            }
             float qa;
-            if ((unsigned)(x >> 32) == epoch) qa = __uint_as_float((unsigned)x);
-            else {
+            if (!granule_wait(gq + tid, epoch, &qa)) {
                 qa = lsa_q_serial(qi.m1, qi.m1_ld, qi.wq, qi.H, b, tid, qi.bf16);
-                atomicAdd(gran + (long)c.B * T, 1ull);
+                atomicAdd(gr.timeouts(), 1ull);
             }
             s_q[tid] = qa;
         }
@@ -515,16 +508,7 @@ __global__ __launch_bounds__(FS_THREADS) void lsa_step_kernel(mstts_lsa_const c,
     if (q_sum && cs == 0 && tg == 0) q_sum[(long)b * A_ + k] = qv;
     if constexpr (!QIN) {
         __syncthreads();
-        float cw[4 + KS_MAX - 1];
-#pragma unroll
-        for (int i = 0; i < 4 + KS_MAX - 1; ++i) cw[i] = s_cum[4 * tg + i];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            float pre = kv[i] + sb;
-#pragma unroll
-            for (int j = 0; j < KS_MAX; ++j) pre += cw[i + j] * lk[j];
-            pre0[i] = pre;
-        }
+        lsa_pre_no_query(s_cum, tg, kv, sb, lk, pre0);
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -532,7 +516,7 @@ __global__ __launch_bounds__(FS_THREADS) void lsa_step_kernel(mstts_lsa_const c,
         if (lane == 0) s_red[4 * tg + i][(tid >> 6) & 1] = e;
     }
     __syncthreads();
-    gu64* g = (gu64*)(gran + (long)b * T);
+    gu64* g = (gu64*)gr.energy(b);
     if (tid < tsl && t0 + tid < T) {
         const float e = s_red[tid][0] + s_red[tid][1];
         s_e[t0 + tid] = e;
@@ -541,6 +525,7 @@ __global__ __launch_bounds__(FS_THREADS) void lsa_step_kernel(mstts_lsa_const c,
     // ---- gather the other slices of the row (the data is the flag)
     for (int t = tid; t < T; t += FS_THREADS) {
         if (t >= t0 && t < t0 + tsl) continue;
+        // (granule_wait written out: through the helper this loop cost the plain and by-unit forms 0.05 - 0.1 us, profiles/lsa_refactor_ab.txt)
         unsigned long long x = __hip_atomic_load(g + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         unsigned spins = 0;
         while ((unsigned)(x >> 32) != epoch && spins < FS_MAX_SPINS) {
@@ -552,7 +537,7 @@ __global__ __launch_bounds__(FS_THREADS) void lsa_step_kernel(mstts_lsa_const c,
         if ((unsigned)(x >> 32) == epoch) e = __uint_as_float((unsigned)x);
         else {
             e = QIN ? lsa_energy_serial(c, s_q, 1, 0, cum, 0, t, b) : lsa_energy_serial(c, q, q_parts, q_pstride, cum, b, t, b);
-            atomicAdd(gran + (long)c.B * T, 1ull);
+            atomicAdd(gr.timeouts(), 1ull);
         }
         s_e[t] = e;
     }
@@ -721,6 +706,38 @@ __global__ __launch_bounds__(FS_THREADS) void lsa_step_kernel(mstts_lsa_const c,
 constexpr int HLD = 32;        // row stride of h (KS_MAX = 31 taps, padded)
 constexpr int MROW = 4;        // float4 per lane per value row held in registers (M <= 1024)
 
+// d_ctx plus its partial slabs at columns i .. i + 3 of one row (dc, d_ctx2: the row's base pointers) - the M > 1024 tail loops, which hold
+// nothing in registers
+__device__ __forceinline__ float4 dctx_total(const float* dc, const float* d_ctx2, int parts, long pstride, int i) {
+    float4 y = *reinterpret_cast<const float4*>(dc + i);
+    if (d_ctx2)
+        for (int pp = 0; pp < max(parts, 1); ++pp) {
+            const float4 y2 = *reinterpret_cast<const float4*>(d_ctx2 + pp * pstride + i);
+            y.x += y2.x; y.y += y2.y; y.z += y2.z; y.w += y2.w;
+        }
+    return y;
+}
+// The end of both d_energy kernels: d_query (the two position groups of a unit through LDS, then one atomic per unit) and the
+// filter-transpose operand h[tt][j] = sum_k g[tt][k] * loc_k[j][k] (thread (tt = tid / 32, j = tid % 32)) from the g tile in s_g
+__device__ __forceinline__ void lsa_dq_h_tail(float dq_acc, const float (*s_g)[A_], const float (*s_lk)[A_ + 4], float* s_dq,
+                                              float* __restrict__ dq, float* __restrict__ h, int b, int t0, int T, int KS) {
+    const int k = threadIdx.x & (A_ - 1), grp = threadIdx.x >> 7;
+    if (grp == 1) s_dq[k] = dq_acc;
+    __syncthreads();
+    if (grp == 0) atomicAdd(dq + (long)b * A_ + k, dq_acc + s_dq[k]);
+    const int tt = threadIdx.x >> 5, j = threadIdx.x & 31;
+    float acc = 0.f;
+    if (j < KS) {
+#pragma unroll 8
+        for (int kk = 0; kk < A_; kk += 4) {
+            const float4 g4 = *reinterpret_cast<const float4*>(&s_g[tt][kk]);
+            const float4 l4 = *reinterpret_cast<const float4*>(&s_lk[j][kk]);
+            acc += g4.x * l4.x + g4.y * l4.y + g4.z * l4.z + g4.w * l4.w;
+        }
+    }
+    if (t0 + tt < T) h[((long)b * T + t0 + tt) * HLD + j] = acc;
+}
+
 __global__ __launch_bounds__(256) void lsa_dalign_kernel(mstts_lsa_const c, const float* __restrict__ d_ctx, long d_ctx_ld,
                                                          const float* __restrict__ d_ctx2, long d_ctx2_ld, int d_ctx2_parts, long d_ctx2_pstride,
                                                          const float* __restrict__ G_next, const float* __restrict__ h_next,
@@ -787,12 +804,7 @@ __global__ __launch_bounds__(256) void lsa_dalign_kernel(mstts_lsa_const c, cons
         if (t < len) {                                  // M > 1024: remaining columns
             for (int i = lane * 4 + 256 * MROW; i < M; i += 256) {
                 const float4 x = *reinterpret_cast<const float4*>(c.values + ((long)b * T + t) * M + i);
-                float4 y = *reinterpret_cast<const float4*>(dc + i);
-                if (d_ctx2)
-                    for (int pp = 0; pp < max(d_ctx2_parts, 1); ++pp) {
-                        const float4 y2 = *reinterpret_cast<const float4*>(d_ctx2 + pp * d_ctx2_pstride + (long)b * d_ctx2_ld + i);
-                        y.x += y2.x; y.y += y2.y; y.z += y2.z; y.w += y2.w;
-                    }
+                const float4 y = dctx_total(dc, d_ctx2 ? d_ctx2 + (long)b * d_ctx2_ld : nullptr, d_ctx2_parts, d_ctx2_pstride, i);
                 acc += x.x * y.x + x.y * y.y + x.z * y.z + x.w * y.w;
             }
         }
@@ -887,41 +899,16 @@ __global__ __launch_bounds__(256) void lsa_denergy_kernel(mstts_lsa_const c, con
         s_g[tt][k] = g;
         dq_acc += g;
     }
-    if (grp == 1) s_dq[k] = dq_acc;
-    __syncthreads();
-    if (grp == 0) atomicAdd(dq + (long)b * A_ + k, dq_acc + s_dq[k]);
-    // h[tt][j] = sum_k g[tt][k] * loc_k[j][k] : thread (tt = tid / 32, j = tid % 32)
-    {
-        const int tt = threadIdx.x >> 5, j = threadIdx.x & 31;
-        float acc = 0.f;
-        if (j < KS) {
-#pragma unroll 8
-            for (int kk = 0; kk < A_; kk += 4) {
-                const float4 g4 = *reinterpret_cast<const float4*>(&s_g[tt][kk]);
-                const float4 l4 = *reinterpret_cast<const float4*>(&s_lk[j][kk]);
-                acc += g4.x * l4.x + g4.y * l4.y + g4.z * l4.z + g4.w * l4.w;
-            }
-        }
-        if (t0 + tt < T) h[((long)b * T + t0 + tt) * HLD + j] = acc;
-    }
+    lsa_dq_h_tail(dq_acc, s_g, s_lk, s_dq, dq, h, b, t0, T, KS);
 }
 
-// ---------------------------------------------------------------------------------------------
-// backward, single launch: the two kernels above in one, grid (T/TS, B) so that the workgroups of a row have adjacent
-// block ids.  The only quantity a workgroup needs from the rest of its row is the softmax-backward scalar
-// dot(a, d_a); each workgroup publishes its slice's partial as ONE {epoch,value} granule right after the d_align
-// phase, recomputes its tanh terms while the granules travel, then gathers the T/TS partials (relaxed agent-scope
-// loads, bounded spin).  d_align never goes to memory.  A workgroup that times out recomputes the missing partial itself
-// (serially: slow but correct, like the forward kernel) and counts the event in the word after the last granule, so a launch can
-// neither hang nor poison the gradients.
-// ---------------------------------------------------------------------------------------------
 // ---------------------------------------------------------------------------------------------
 // backward, single launch, NO exchange: the two kernels above in one, grid B x T/TS workgroups.  The only row-wide quantity of the
 // softmax backward is dot(a, d_a), and with d_a = G + values . d_ctx it splits into
 //     dot(a, d_a) = dot(a, G) + (sum_t a[t] values[t]) . d_ctx = dot(a, G) + ctx . d_ctx
 // where ctx is the FORWARD context of this step (kept in the projection history) - so every workgroup forms the scalar itself from
 // 128 + 768 floats it can read directly (plus the row's G, a 128 x 31 filter-transpose sum it recomputes redundantly), and nothing
-// has to cross workgroups inside the launch.  d_align never goes to memory.  (The exchanged form of round 1 cost 13.5 us per step.)
+// has to cross workgroups inside the launch.  d_align never goes to memory.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void lsa_step_bwd_kernel(mstts_lsa_const c, const float* __restrict__ d_ctx, long d_ctx_ld,
                                                            const float* __restrict__ d_ctx2, long d_ctx2_ld, int d_ctx2_parts, long d_ctx2_pstride,
@@ -1093,12 +1080,7 @@ __global__ __launch_bounds__(256) void lsa_step_bwd_kernel(mstts_lsa_const c, co
         for (int m = 0; m < MROW; ++m) p2 += cxv[m].x * dcv[m].x + cxv[m].y * dcv[m].y + cxv[m].z * dcv[m].z + cxv[m].w * dcv[m].w;
         for (int i = lane * 4 + 256 * MROW; i < M; i += 256) {            // M > 1024 only
             const float4 x = *reinterpret_cast<const float4*>(ctx_fwd + (long)b * ctx_fwd_ld + i);
-            float4 y = *reinterpret_cast<const float4*>(dc + i);
-            if (d_ctx2)
-                for (int pp = 0; pp < max(d_ctx2_parts, 1); ++pp) {
-                    const float4 y2 = *reinterpret_cast<const float4*>(d_ctx2 + pp * d_ctx2_pstride + (long)b * d_ctx2_ld + i);
-                    y.x += y2.x; y.y += y2.y; y.z += y2.z; y.w += y2.w;
-                }
+            const float4 y = dctx_total(dc, d_ctx2 ? d_ctx2 + (long)b * d_ctx2_ld : nullptr, d_ctx2_parts, d_ctx2_pstride, i);
             p2 += x.x * y.x + x.y * y.y + x.z * y.z + x.w * y.w;
         }
         p2 = wave_sum(p2);
@@ -1119,12 +1101,7 @@ __global__ __launch_bounds__(256) void lsa_step_bwd_kernel(mstts_lsa_const c, co
         if (t < len) {
             for (int i = lane * 4 + 256 * MROW; i < M; i += 256) {
                 const float4 x = *reinterpret_cast<const float4*>(c.values + ((long)b * T + t) * M + i);
-                float4 y = *reinterpret_cast<const float4*>(dc + i);
-                if (d_ctx2)
-                    for (int pp = 0; pp < max(d_ctx2_parts, 1); ++pp) {
-                        const float4 y2 = *reinterpret_cast<const float4*>(d_ctx2 + pp * d_ctx2_pstride + (long)b * d_ctx2_ld + i);
-                        y.x += y2.x; y.y += y2.y; y.z += y2.z; y.w += y2.w;
-                    }
+                const float4 y = dctx_total(dc, d_ctx2 ? d_ctx2 + (long)b * d_ctx2_ld : nullptr, d_ctx2_parts, d_ctx2_pstride, i);
                 acc += x.x * y.x + x.y * y.y + x.z * y.z + x.w * y.w;
             }
         }
@@ -1150,22 +1127,7 @@ __global__ __launch_bounds__(256) void lsa_step_bwd_kernel(mstts_lsa_const c, co
         s_g[tt][k] = g;
         dq_acc += g;
     }
-    if (grp == 1) s_dq[k] = dq_acc;
-    __syncthreads();
-    if (grp == 0) atomicAdd(dq + (long)b * A_ + k, dq_acc + s_dq[k]);
-    {
-        const int tt = threadIdx.x >> 5, j = threadIdx.x & 31;
-        float acc = 0.f;
-        if (j < KS) {
-#pragma unroll 8
-            for (int kk = 0; kk < A_; kk += 4) {
-                const float4 g4 = *reinterpret_cast<const float4*>(&s_g[tt][kk]);
-                const float4 l4 = *reinterpret_cast<const float4*>(&s_lk[j][kk]);
-                acc += g4.x * l4.x + g4.y * l4.y + g4.z * l4.z + g4.w * l4.w;
-            }
-        }
-        if (t0 + tt < T) h[((long)b * T + t0 + tt) * HLD + j] = acc;
-    }
+    lsa_dq_h_tail(dq_acc, s_g, s_lk, s_dq, dq, h, b, t0, T, KS);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1398,7 +1360,13 @@ static void lsa_step_geometry(long T, long M, int* cs, int* tsl, int* dsl) {
     *tsl = (int)cdiv(T, n);
     *dsl = (int)(cdiv(cdiv(M, n), 4) * 4);
 }
-extern "C" int64_t mstts_lsa_step_ws_bytes(int64_t B, int64_t T) { return (B * T + 1) * 8; }
+extern "C" int64_t mstts_lsa_step_ws_bytes(int64_t B, int64_t T) { return LsaGranules(nullptr, B, T).words() * 8; }
+// The one launch of the single-launch forward step (entry points: include/mstts.h).  Forms, each on top of the one before:
+enum { LSA_PLAIN, LSA_LKT, LSA_Q, LSA_QP, LSA_QPP };        // plain | by-unit filter | + query | + projection | + prenet
+typedef decltype(&lsa_step_kernel<false, false, false, false>) lsa_step_fn;
+static const lsa_step_fn lsa_step_forms[5] = {
+    lsa_step_kernel<false, false, false, false>, lsa_step_kernel<true, false, false, false>, lsa_step_kernel<true, true, false, false>,
+    lsa_step_kernel<true, true, true, false>, lsa_step_kernel<true, true, true, true>};
 static int lsa_step_fwd_launch(const mstts_lsa_const* c, const float* q, int32_t q_parts, int64_t q_pstride, float* q_sum,
                                const float* cum, float* align, float* cum_next, float* ctx, int64_t ctx_ld, float* ctx2, int64_t ctx2_ld,
                                const mstts_cell_packed_dst* ctx_p, void* granules, uint32_t epoch, int skip, mstts_stream_t s,
@@ -1415,52 +1383,31 @@ static int lsa_step_fwd_launch(const mstts_lsa_const* c, const float* q, int32_t
     memset(&pz, 0, sizeof(pz));
     LsaPre px;
     memset(&px, 0, sizeof(px));
-    const bool lkt = c->loc_kt && aligned16(c->loc_kt);
-    if (qin && proj) {
-        qi = *qin; pz = *proj;
-        MSTTS_REQUIRE(cs >= 8 && qi.H == 128 * QJ && lkt, MSTTS_ERR_SHAPE, "lsa_step_fwd_qp: needs >= 8 slices, H == %d and the by-unit filter", 128 * QJ);
-        MSTTS_REQUIRE(qi.m1 && qi.wq && aligned16(qi.m1) && aligned16(qi.wq) && qi.m1_ld % 4 == 0, MSTTS_ERR_ALIGN, "lsa_step_fwd_qp: m1 / wq must be 16-byte aligned");
-        MSTTS_REQUIRE(pz.wp_own && aligned16(pz.wp_own) && pz.vp && pz.linear && pz.stop && pz.NP >= 2 && pz.NP <= 8 * PJ_OWN && pz.NM < pz.NP, MSTTS_ERR_SHAPE,
-                      "lsa_step_fwd_qp: projection width must be 2..%d columns", 8 * PJ_OWN);
-        if (pre) {
-            MSTTS_REQUIRE(pre->w0 && pre->b0 && pre->w1 && pre->b1 && pre->m0 && pre->m1 && pre->out && pre->P == PR_P && pz.NM <= 8 * PR_K0 &&
-                          pz.NM < PR_GLD && pz.NP == 4 * PF_Q && aligned16(pre->w0) && aligned16(pre->w1) && aligned16(pz.vp), MSTTS_ERR_SHAPE,
-                          "lsa_step_fwd_qp: in-launch prenet needs P == %d, n_mel <= %d, NP == %d and 16-byte aligned w0 / w1 / vp", PR_P, 8 * PR_K0, 4 * PF_Q);
-            px.w0 = pre->w0; px.b0 = pre->b0; px.w1 = pre->w1; px.b1 = pre->b1; px.m0 = pre->m0; px.m1 = pre->m1; px.inv_keep = pre->inv_keep;
-            px.out = pre->out; px.out_ld = (long)pre->out_ld;
-            rc = packed_dst_from(pre->out_p.base ? &pre->out_p : nullptr, PR_P, &px.out_p, "prenet out_p"); if (rc) return rc;
-            px.gf = (unsigned long long*)granules + (c->B * c->T + 1 + c->B * A_);
-            if (skip >= 0)
-                hipLaunchKernelGGL((lsa_step_kernel<true, true, true, true, true>), dim3((unsigned)(cs * c->B)), dim3(FS_THREADS), 0, ST(s), *c, q, 0, 0L, q_sum, cum,
-                                   align, cum_next, ctx, (long)ctx_ld, ctx2, (long)ctx2_ld, cp, (unsigned long long*)granules, (unsigned)epoch, tsl, dsl, cs, skip, qi, pz, px);
-            else
-                hipLaunchKernelGGL((lsa_step_kernel<false, true, true, true, true>), dim3((unsigned)(cs * c->B)), dim3(FS_THREADS), 0, ST(s), *c, q, 0, 0L, q_sum, cum,
-                                   align, cum_next, ctx, (long)ctx_ld, ctx2, (long)ctx2_ld, cp, (unsigned long long*)granules, (unsigned)epoch, tsl, dsl, cs, -1, qi, pz, px);
-        } else if (skip >= 0)
-            hipLaunchKernelGGL((lsa_step_kernel<true, true, true, true>), dim3((unsigned)(cs * c->B)), dim3(FS_THREADS), 0, ST(s), *c, q, 0, 0L, q_sum, cum,
-                               align, cum_next, ctx, (long)ctx_ld, ctx2, (long)ctx2_ld, cp, (unsigned long long*)granules, (unsigned)epoch, tsl, dsl, cs, skip, qi, pz, px);
-        else
-            hipLaunchKernelGGL((lsa_step_kernel<false, true, true, true>), dim3((unsigned)(cs * c->B)), dim3(FS_THREADS), 0, ST(s), *c, q, 0, 0L, q_sum, cum,
-                               align, cum_next, ctx, (long)ctx_ld, ctx2, (long)ctx2_ld, cp, (unsigned long long*)granules, (unsigned)epoch, tsl, dsl, cs, -1, qi, pz, px);
-    } else if (qin) {
+    int form = c->loc_kt && aligned16(c->loc_kt) ? LSA_LKT : LSA_PLAIN;
+    if (qin) {
         qi = *qin;
-        MSTTS_REQUIRE(cs >= 8 && qi.H == 128 * QJ && lkt, MSTTS_ERR_SHAPE, "lsa_step_fwd_q: needs at least 8 slices (T > 112 or M > 672), H == %d and the by-unit filter", 128 * QJ);
-        MSTTS_REQUIRE(qi.m1 && qi.wq && aligned16(qi.m1) && aligned16(qi.wq) && qi.m1_ld % 4 == 0, MSTTS_ERR_ALIGN, "lsa_step_fwd_q: m1 / wq must be 16-byte aligned");
-        if (skip >= 0)
-            hipLaunchKernelGGL((lsa_step_kernel<true, true, true>), dim3((unsigned)(cs * c->B)), dim3(FS_THREADS), 0, ST(s), *c, q, 0, 0L, q_sum, cum,
-                               align, cum_next, ctx, (long)ctx_ld, ctx2, (long)ctx2_ld, cp, (unsigned long long*)granules, (unsigned)epoch, tsl, dsl, cs, skip, qi, pz, px);
-        else
-            hipLaunchKernelGGL((lsa_step_kernel<false, true, true>), dim3((unsigned)(cs * c->B)), dim3(FS_THREADS), 0, ST(s), *c, q, 0, 0L, q_sum, cum,
-                               align, cum_next, ctx, (long)ctx_ld, ctx2, (long)ctx2_ld, cp, (unsigned long long*)granules, (unsigned)epoch, tsl, dsl, cs, -1, qi, pz, px);
-    } else if (skip >= 0)
-        hipLaunchKernelGGL(lsa_step_kernel<true>, dim3((unsigned)(cs * c->B)), dim3(FS_THREADS), 0, ST(s), *c, q, (int)q_parts, (long)q_pstride, q_sum, cum,
-                           align, cum_next, ctx, (long)ctx_ld, ctx2, (long)ctx2_ld, cp, (unsigned long long*)granules, (unsigned)epoch, tsl, dsl, cs, skip, qi, pz, px);
-    else if (lkt)
-        hipLaunchKernelGGL((lsa_step_kernel<false, true>), dim3((unsigned)(cs * c->B)), dim3(FS_THREADS), 0, ST(s), *c, q, (int)q_parts, (long)q_pstride, q_sum, cum,
-                           align, cum_next, ctx, (long)ctx_ld, ctx2, (long)ctx2_ld, cp, (unsigned long long*)granules, (unsigned)epoch, tsl, dsl, cs, -1, qi, pz, px);
-    else
-        hipLaunchKernelGGL(lsa_step_kernel<false>, dim3((unsigned)(cs * c->B)), dim3(FS_THREADS), 0, ST(s), *c, q, (int)q_parts, (long)q_pstride, q_sum, cum,
-                           align, cum_next, ctx, (long)ctx_ld, ctx2, (long)ctx2_ld, cp, (unsigned long long*)granules, (unsigned)epoch, tsl, dsl, cs, -1, qi, pz, px);
+        MSTTS_REQUIRE(cs >= 8 && qi.H == 128 * QJ && form == LSA_LKT, MSTTS_ERR_SHAPE, "lsa_step_fwd (in-launch query): needs at least 8 slices (T > 112 or M > 672), H == %d and the by-unit filter", 128 * QJ);
+        MSTTS_REQUIRE(qi.m1 && qi.wq && aligned16(qi.m1) && aligned16(qi.wq) && qi.m1_ld % 4 == 0, MSTTS_ERR_ALIGN, "lsa_step_fwd (in-launch query): m1 / wq must be 16-byte aligned");
+        form = LSA_Q;
+    }
+    if (proj) {
+        pz = *proj;
+        MSTTS_REQUIRE(qin && pz.wp_own && aligned16(pz.wp_own) && pz.vp && pz.linear && pz.stop && pz.NP >= 2 && pz.NP <= 8 * PJ_OWN && pz.NM < pz.NP, MSTTS_ERR_SHAPE,
+                      "lsa_step_fwd_qp: projection width must be 2..%d columns", 8 * PJ_OWN);
+        form = LSA_QP;
+    }
+    if (pre) {
+        MSTTS_REQUIRE(proj && pre->w0 && pre->b0 && pre->w1 && pre->b1 && pre->m0 && pre->m1 && pre->out && pre->P == PR_P && pz.NM <= 8 * PR_K0 &&
+                      pz.NM < PR_GLD && pz.NP == 4 * PF_Q && aligned16(pre->w0) && aligned16(pre->w1) && aligned16(pz.vp), MSTTS_ERR_SHAPE,
+                      "lsa_step_fwd_qp: in-launch prenet needs P == %d, n_mel <= %d, NP == %d and 16-byte aligned w0 / w1 / vp", PR_P, 8 * PR_K0, 4 * PF_Q);
+        px.w0 = pre->w0; px.b0 = pre->b0; px.w1 = pre->w1; px.b1 = pre->b1; px.m0 = pre->m0; px.m1 = pre->m1; px.inv_keep = pre->inv_keep;
+        px.out = pre->out; px.out_ld = (long)pre->out_ld;
+        rc = packed_dst_from(pre->out_p.base ? &pre->out_p : nullptr, PR_P, &px.out_p, "prenet out_p"); if (rc) return rc;
+        form = LSA_QPP;
+    }
+    hipLaunchKernelGGL(lsa_step_forms[form], dim3((unsigned)(cs * c->B)), dim3(FS_THREADS), 0, ST(s), *c, q, (int)q_parts, (long)q_pstride, q_sum, cum,
+                       align, cum_next, ctx, (long)ctx_ld, ctx2, (long)ctx2_ld, cp, (unsigned long long*)granules, (unsigned)epoch, tsl, dsl, cs,
+                       skip >= 0 ? skip : -1, qi, pz, px);
     MSTTS_CHECK_LAUNCH("lsa_step_fwd");
     return MSTTS_OK;
 }
@@ -1469,35 +1416,25 @@ extern "C" int mstts_lsa_step_fwd(const mstts_lsa_const* c, const float* q, int3
                                   const mstts_cell_packed_dst* ctx_p, void* granules, uint32_t epoch, mstts_stream_t s) {
     return lsa_step_fwd_launch(c, q, q_parts, q_pstride, q_sum, cum, align, cum_next, ctx, ctx_ld, ctx2, ctx2_ld, ctx_p, granules, epoch, -1, s);
 }
-/* The same step with the query projection inside the launch: q = m1 . Wq (m1 rows [B, H] with row stride m1_ld, Wq [H, A] row-major;
- * q_bf16 != 0 rounds both operands to bf16 first - BASELINE config 3), one launch less per decoder step.  Needs at least 8 slices
- * (T > 112 or M > 672: the first eight own 16 query units each), H == 1024 and c->loc_kt; granules = mstts_lsa_step_q_ws_bytes(B, T) bytes (the energy granules, the time-out counter,
- * then B * A query granules), zeroed before the first step.  skip_slice >= 0: the self-test form (see below), -1 otherwise. */
 extern "C" int32_t mstts_lsa_step_q_supported(int64_t T, int64_t M, int64_t H) {
     int cs, tsl, dsl;
     if (T < 1 || M < 4) return 0;
     lsa_step_geometry(T, M, &cs, &tsl, &dsl);
     return cs >= 8 && H == 128 * QJ;
 }
-extern "C" int64_t mstts_lsa_step_q_ws_bytes(int64_t B, int64_t T) { return (B * T + 1 + B * A_) * 8; }
+extern "C" int64_t mstts_lsa_step_q_ws_bytes(int64_t B, int64_t T) { return LsaGranules(nullptr, B, T).words_q() * 8; }
 extern "C" int mstts_lsa_step_fwd_q(const mstts_lsa_const* c, const float* m1, int64_t m1_ld, const float* wq, int64_t H, int32_t q_bf16,
                                     float* q_sum, const float* cum, float* align, float* cum_next, float* ctx, int64_t ctx_ld, float* ctx2,
                                     int64_t ctx2_ld, const mstts_cell_packed_dst* ctx_p, void* granules, uint32_t epoch, int32_t skip_slice,
                                     mstts_stream_t s) {
     LsaQIn qi;
     qi.m1 = m1; qi.m1_ld = (long)m1_ld; qi.wq = wq; qi.H = (int)H; qi.bf16 = q_bf16 ? 1 : 0;
-    return lsa_step_fwd_launch(c, nullptr, 0, 0, q_sum, cum, align, cum_next, ctx, ctx_ld, ctx2, ctx2_ld, ctx_p, granules, epoch,
-                               skip_slice >= 0 ? skip_slice : -1, s, &qi);
+    return lsa_step_fwd_launch(c, nullptr, 0, 0, q_sum, cum, align, cum_next, ctx, ctx_ld, ctx2, ctx2_ld, ctx_p, granules, epoch, skip_slice, s, &qi);
 }
-/* ... and with the output projection [m1 | ctx] . Wp + bias out of the same launch (free-running decoder): no further exchange -
- *   vp [B, T, NP] = values . Wp[H:, :] (the projected values: once per utterance, any GEMM), wp_own = mstts_lsa_proj_pack(Wp[:H, :]);
- *   bias [NM + 1] or NULL; linear [B, NM] <- columns 0..NM-1, stop [B] <- column NM.  NP <= 88.
- * Same availability as mstts_lsa_step_fwd_q; granules = mstts_lsa_step_qp_ws_bytes(B, T) bytes.
- * pre != NULL (mstts_lsa_step_prenet_supported(P, NM)): the NEXT step's prenet on this frame in the same launch - see LsaPre above. */
 extern "C" int32_t mstts_lsa_step_qp_supported(int64_t T, int64_t M, int64_t H, int64_t NP) {
     return mstts_lsa_step_q_supported(T, M, H) && NP >= 2 && NP <= 8 * PJ_OWN;
 }
-extern "C" int64_t mstts_lsa_step_qp_ws_bytes(int64_t B, int64_t T) { return (B * T + 1 + B * A_ + B * PR_GLD) * 8; }
+extern "C" int64_t mstts_lsa_step_qp_ws_bytes(int64_t B, int64_t T) { return LsaGranules(nullptr, B, T).words_qp() * 8; }
 extern "C" int32_t mstts_lsa_step_prenet_supported(int64_t P, int64_t NM) { return P == PR_P && NM >= 1 && NM <= 8 * PR_K0 && (NM + 1 + 3) / 4 == PF_Q; }
 extern "C" int64_t mstts_lsa_proj_pack_floats(void) { return 8L * QJ * 128 * PJ_OW; }
 namespace mstts {
@@ -1527,11 +1464,9 @@ extern "C" int mstts_lsa_step_fwd_qp(const mstts_lsa_const* c, const float* m1, 
     qi.m1 = m1; qi.m1_ld = (long)m1_ld; qi.wq = wq; qi.H = (int)H; qi.bf16 = 0;
     LsaProj pj;
     pj.wp_own = wp_own; pj.vp = vp; pj.bias = bias; pj.NP = (int)NP; pj.NM = (int)NM; pj.linear = linear; pj.stop = stop;
-    return lsa_step_fwd_launch(c, nullptr, 0, 0, nullptr, cum, align, cum_next, ctx, ctx_ld, ctx2, ctx2_ld, ctx_p, granules, epoch,
-                               skip_slice >= 0 ? skip_slice : -1, s, &qi, &pj, pre);
+    return lsa_step_fwd_launch(c, nullptr, 0, 0, nullptr, cum, align, cum_next, ctx, ctx_ld, ctx2, ctx2_ld, ctx_p, granules, epoch, skip_slice, s, &qi, &pj, pre);
 }
-/* test entry: same launch with the workgroups of slice `skip_slice` (0 .. slices-1) removed, which forces every other workgroup of each row
- * through its time-out path (takes milliseconds); the skipped slice's own outputs are not written */
+// (the form mstts_lsa_step_fwd launches for the same c, with skip_slice's workgroups leaving at once)
 extern "C" int mstts_lsa_step_fwd_selftest(const mstts_lsa_const* c, const float* q, int32_t q_parts, int64_t q_pstride, float* q_sum,
                                            const float* cum, float* align, float* cum_next, float* ctx, int64_t ctx_ld, void* granules,
                                            uint32_t epoch, int32_t skip_slice, mstts_stream_t s) {

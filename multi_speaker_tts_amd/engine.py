@@ -20,7 +20,7 @@ import torch
 from . import lib
 from .lib import ACT_NONE, ACT_RELU, ACT_TANH, gemm, ptr, call
 from .masks import MaskSet, step_seed
-from .params import CELL, ENC_CELL, LSA, VOC, Dims, ParamStore, bank_suffix
+from .params import CELL, ENC_CELL, LSA, LSA_VARS, VOC, Dims, ParamStore, bank_suffix
 from .persist import PERSIST_COOLDOWN, PERSIST_STRIKES, CoolDown, Ticket, decoder_workgroups, lstm_bwd_workgroups, lstm_fwd_workgroups, near_xcd
 from .training import (Engine, _split_k, _split_k_big, bn_train_fwd, conv_bn_bwd, conv_fwd, exponential_decay, lstm_layer_grads, lstm_seq_bwd,
                        lstm_seq_fwd)
@@ -323,11 +323,7 @@ class TrainEngine(Engine):
         self.bp_pad.zero_()
         call("mstts_copy2d", ptr(wp, owp), nm1, ptr(self.wp_pad), self.proj_ld, H + M, nm1, 0)
         call("mstts_copy2d", ptr(bp, obp), nm1, ptr(self.bp_pad), self.proj_ld, 1, nm1, 0)
-        ck, ock = self.P(LSA + "attention_convolution_dense_layer/conv1d/kernel"); cb, ocb = self.P(LSA + "attention_convolution_dense_layer/conv1d/bias")
-        dk, odk = self.P(LSA + "attention_convolution_dense_layer/dense/kernel")
-        call("mstts_lsa_fold_location", ptr(ck, ock), ptr(cb, ocb), ptr(dk, odk), ptr(self.loc_k), ptr(self.loc_b), d.att_k, d.att_ch, d.att)
-        if self.loc_kt is not None:
-            call("mstts_lsa_filter_by_unit", ptr(self.loc_k), ptr(self.loc_kt), d.att_k, d.att)
+        lib.lsa_fold(self.P, self.loc_k, self.loc_b, self.loc_kt, d.att_k, d.att_ch, d.att)
         self._derived_stale = False
 
     def _pin(self, name, n):
@@ -611,14 +607,7 @@ class TrainEngine(Engine):
         # ---- decoder loop
         dec = w.dec
         dec.B, dec.S, dec.H, dec.P = B, S, H, Pn
-        ls = dec.lsa
-        ls.B, ls.T, ls.A, ls.M, ls.KS, ls.CH = B, Te, A, M, d.att_k, d.att_ch
-        ls.keys, ls.values, ls.lengths = ptr(w.keys), ptr(w.values), ptr(tlen)
-        for field, name in (("conv_k", "attention_convolution_dense_layer/conv1d/kernel"), ("conv_b", "attention_convolution_dense_layer/conv1d/bias"),
-                            ("dense_k", "attention_convolution_dense_layer/dense/kernel"), ("score_w", "score_layer/weight_w"), ("score_b", "score_layer/bias_b")):
-            t, o = self.P(LSA + name)
-            setattr(ls, field, ptr(t, o))
-        ls.loc_k, ls.loc_b, ls.loc_kt = ptr(self.loc_k), ptr(self.loc_b), ptr(self.loc_kt)
+        lib.lsa_fill(dec.lsa, self.P, B, Te, A, M, d.att_k, d.att_ch, w.keys, w.values, tlen, self.loc_k, self.loc_b, self.loc_kt)
         k1, o1 = self.P(CELL % 1 + "kernel"); b1, ob1 = self.P(CELL % 1 + "bias"); wq, oq = self.P(LSA + "query_layer/kernel")
         dec.xw0, dec.w0f, dec.w1, dec.b1, dec.wq = ptr(w.xw0), ptr(self.w0f), ptr(k1, o1), ptr(b1, ob1), ptr(wq, oq)
         dec.zc0, dec.zh0, dec.zc1, dec.zh1 = ptr(mk["dec_zc_0"]), ptr(mk["dec_zh_0"]), ptr(mk["dec_zc_1"]), ptr(mk["dec_zh_1"])
@@ -916,11 +905,7 @@ class TrainEngine(Engine):
                     k, ok = self.P("decoder/decoder/prenet_%d/dense/kernel" % i)
                     self._gemm(dcur, k, dnxt, SB, cin, Pn, Pn, Pn, cin, trans_b=True, b_off=ok)
                     dcur, dnxt = dnxt, dcur
-            gs = {}
-            for field, name in (("conv_k", "attention_convolution_dense_layer/conv1d/kernel"), ("conv_b", "attention_convolution_dense_layer/conv1d/bias"),
-                                ("dense_k", "attention_convolution_dense_layer/dense/kernel"), ("score_w", "score_layer/weight_w"), ("score_b", "score_layer/bias_b")):
-                t, o = self.G(LSA + name)
-                gs[field] = ptr(t, o)
+            gs = {field: ptr(*self.G(name)) for field, name in LSA_VARS}
             ls = w.dec.lsa
             call("mstts_lsa_unfold_location_grad", ls.conv_k, ls.conv_b, ls.dense_k, ptr(self.d_loc_k), gs["score_b"],
                  gs["conv_k"], gs["conv_b"], gs["dense_k"], d.att_k, d.att_ch, d.att)

@@ -353,29 +353,13 @@ class InferEngine:
                          loc_b=torch.zeros(A, dtype=torch.float32, device=self.device),
                          loc_kt=torch.zeros(A * 36, dtype=torch.float32, device=self.device).view(A, 36) if d.att_k <= 31 else None)
             call("mstts_fold_rows", ptr(k0, o0 + Pn * 4 * H), ptr(c["w0f"]), 2 * M + H, 4 * H, 0, M)
-            cp = {}
-            for field, name in (("conv_k", "attention_convolution_dense_layer/conv1d/kernel"), ("conv_b", "attention_convolution_dense_layer/conv1d/bias"),
-                                ("dense_k", "attention_convolution_dense_layer/dense/kernel")):
-                t, o = self.P(LSA + name)
-                cp[field] = ptr(t, o)
-            call("mstts_lsa_fold_location", cp["conv_k"], cp["conv_b"], cp["dense_k"], ptr(c["loc_k"]), ptr(c["loc_b"]), d.att_k, d.att_ch, A)
-            if c["loc_kt"] is not None:
-                call("mstts_lsa_filter_by_unit", ptr(c["loc_k"]), ptr(c["loc_kt"]), d.att_k, A)
+            lib.lsa_fold(self.P, c["loc_k"], c["loc_b"], c["loc_kt"], d.att_k, d.att_ch, A)
             c["version"] = self.params.version
         w0f = c["w0f"]
         k0, o0 = self.P(CELL % 0 + "kernel"); b0, ob0 = self.P(CELL % 0 + "bias")
         q = lib.DecoderInfer()
         q.B, q.H, q.P, q.n_mel, q.Smax = B, H, Pn, NM, Smax
-        ls = q.lsa
-        ls.B, ls.T, ls.A, ls.M, ls.KS, ls.CH = B, T, A, M, d.att_k, d.att_ch
-        ls.keys, ls.values, ls.lengths = ptr(keys), ptr(values), ptr(token_length)
-        for field, name in (("conv_k", "attention_convolution_dense_layer/conv1d/kernel"), ("conv_b", "attention_convolution_dense_layer/conv1d/bias"),
-                            ("dense_k", "attention_convolution_dense_layer/dense/kernel"), ("score_w", "score_layer/weight_w"), ("score_b", "score_layer/bias_b")):
-            t, o = self.P(LSA + name)
-            setattr(ls, field, ptr(t, o))
-        ls.loc_k, ls.loc_b = ptr(c["loc_k"]), ptr(c["loc_b"])
-        if c["loc_kt"] is not None:
-            ls.loc_kt = ptr(c["loc_kt"])
+        lib.lsa_fill(q.lsa, self.P, B, T, A, M, d.att_k, d.att_ch, keys, values, token_length, c["loc_k"], c["loc_b"], c["loc_kt"])
         for field, name in (("pw0", "decoder/decoder/prenet_0/dense/kernel"), ("pb0", "decoder/decoder/prenet_0/dense/bias"),
                             ("pw1", "decoder/decoder/prenet_1/dense/kernel"), ("pb1", "decoder/decoder/prenet_1/dense/bias"),
                             ("w1", CELL % 1 + "kernel"), ("b1", CELL % 1 + "bias"), ("wq", LSA + "query_layer/kernel"),

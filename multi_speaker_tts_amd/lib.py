@@ -11,6 +11,8 @@ import os
 
 import torch
 
+from .params import LSA_VARS
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmstts_hip.so")
 
@@ -401,6 +403,24 @@ def call(name, *args):
     rc = getattr(lib, name)(*args, stream())
     if rc != 0:
         raise MsttsError("%s failed (%d): %s" % (name, rc, lib.mstts_last_error().decode()))
+
+
+def lsa_fold(P, loc_k, loc_b, loc_kt, KS, CH, A):
+    """Fold the location conv and its dense layer into one filter loc_k [KS, A] / loc_b [A] (mstts_lsa_fold_location) and, when loc_kt is
+    given, its by-unit copy [A, 36].  P(name) -> (tensor, element offset) of a variable."""
+    src = [ptr(*P(name)) for _, name in LSA_VARS[:3]]
+    call("mstts_lsa_fold_location", *src, ptr(loc_k), ptr(loc_b), KS, CH, A)
+    if loc_kt is not None:
+        call("mstts_lsa_filter_by_unit", ptr(loc_k), ptr(loc_kt), KS, A)
+
+
+def lsa_fill(ls, P, B, T, A, M, KS, CH, keys, values, lengths, loc_k, loc_b, loc_kt):
+    """Fill a mstts_lsa_const (LsaConst) from the memory tensors, the variables (P as in lsa_fold) and the folded filter."""
+    ls.B, ls.T, ls.A, ls.M, ls.KS, ls.CH = B, T, A, M, KS, CH
+    ls.keys, ls.values, ls.lengths = ptr(keys), ptr(values), ptr(lengths)
+    for field, name in LSA_VARS:
+        setattr(ls, field, ptr(*P(name)))
+    ls.loc_k, ls.loc_b, ls.loc_kt = ptr(loc_k), ptr(loc_b), ptr(loc_kt)
 
 
 def gemm(A, B, Cm, M, N, K, lda, ldb, ldc, bias=None, trans_a=False, trans_b=False, act=ACT_NONE, accumulate=False,

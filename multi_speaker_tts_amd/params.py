@@ -61,6 +61,9 @@ class Dims:
 
 
 LSA = "decoder/decoder/attention_wrapper/location_sensitive_attention/"
+# the attention's own variables as (mstts_lsa_const field, variable name); the first three fold into the location filter
+LSA_VARS = (("conv_k", LSA + "attention_convolution_dense_layer/conv1d/kernel"), ("conv_b", LSA + "attention_convolution_dense_layer/conv1d/bias"),
+            ("dense_k", LSA + "attention_convolution_dense_layer/dense/kernel"), ("score_w", LSA + "score_layer/weight_w"), ("score_b", LSA + "score_layer/bias_b"))
 CELL = "decoder/decoder/attention_wrapper/multi_rnn_cell/cell_%d/zoneout_lstm_cell/"
 ENC_CELL = "encoder/bilstm/stack_bidirectional_rnn/cell_0/bidirectional_rnn/%s/zoneout_lstm_cell/"
 VOC = "mel_to_spectrogram/"

@@ -55,9 +55,10 @@ def test_lstm_point_fwd_bwd(dev):
     assert rel_err(t2n(dcp), t2n(cp64.grad)) < 2e-5 and rel_err(t2n(dhp), t2n(hp64.grad)) < 2e-5
 
 
-@pytest.mark.parametrize("B,T,M,KS", [(3, 37, 48, 31), (2, 128, 768, 31), (1, 16, 16, 5), (4, 300, 768, 31), (33, 128, 100, 7)])
+@pytest.mark.parametrize("B,T,M,KS", [(3, 37, 48, 31), (2, 128, 768, 31), (1, 16, 16, 5), (4, 300, 768, 31), (33, 128, 100, 7), (2, 9, 1032, 3)])
 def test_lsa_step_fwd_bwd(dev, B, T, M, KS):
-    """One attention step (energy+context kernels, dalign+denergy kernels) vs the oracle's lsa_step."""
+    """One attention step (energy+context kernels, dalign+denergy kernels) vs the oracle's lsa_step.  (2, 9, 1032, 3): the smallest shape that
+    runs every M > 1024 tail loop of the backward kernels (1032 = 1024 + 8; two rows, one ragged)."""
     A, CH, Hq = 128, 32, 40
     od = OM.Dims(att_k=KS, dec_lstm=Hq)
     g = np.random.default_rng(3)
@@ -124,7 +125,7 @@ def test_lsa_step_fwd_bwd(dev, B, T, M, KS):
     assert rel_err(t2n(G), G_ref) < 2e-5
     de, dq, hh = torch.zeros(B, T, device=dev), torch.zeros(B, A, device=dev), torch.zeros(B, T, 32, device=dev)
     lib.call("mstts_lsa_denergy_bwd", C.byref(c), lib.ptr(al), lib.ptr(da), lib.ptr(q), lib.ptr(dcum), lib.ptr(de), lib.ptr(dq), lib.ptr(hh))
-    # single-launch form of the two calls above (row-wide dot(a, d_a) exchanged inside the launch)
+    # single-launch form of the two calls above (no exchange: the row-wide dot(a, d_a) closes through the forward context)
     G2, de2, dq2, hh2 = torch.zeros(B, T, device=dev), torch.zeros(B, T, device=dev), torch.zeros(B, A, device=dev), torch.zeros(B, T, 32, device=dev)
     ctx_f = f32(t2n(ctx))                                   # this step's forward context: dot(a, d_a) = dot(a, G) + ctx . d_ctx inside the kernel
     lib.call("mstts_lsa_step_bwd", C.byref(c), lib.ptr(d_ctx_d), M, None, 0, 0, 0, lib.ptr(G_next_d), lib.ptr(h_next_d), lib.ptr(G2),
@@ -298,6 +299,16 @@ def test_lsa_step_fwd_q(dev, B, T, bf16):
     keepc = np.ones(PN, bool); keepc[96:128] = False                                    # the missing slice's 32 prenet columns stay unwritten
     assert rel_err(t2n(pre3[:, :PN])[:, keepc], t2n(prenet_ref(ref[:, :NM]))[:, keepc]) < 2e-5
     assert float((pre3[:, 96:128] - 7.0).abs().max()) == 0.0
+    # the same time-out path in the projection-only form (no prenet requested), on a fresh granule buffer
+    lin4, stop4 = torch.full((B, NM), 7.0, device=dev), torch.full((B,), 7.0, device=dev)
+    pre3_before = pre3.clone()                                                          # (pn.out still points at pre3; this call passes no prenet)
+    gran_p4 = torch.zeros_like(gran_p)
+    lib.call("mstts_lsa_step_fwd_qp", C.byref(c), lib.ptr(pj), WP, lib.ptr(wq), H, lib.ptr(wp_own), lib.ptr(vp), lib.ptr(bias), NP, NM,
+             lib.ptr(lin4), lib.ptr(stop4), lib.ptr(cum), lib.ptr(al2), lib.ptr(cn2), lib.ptr(cx2), M, None, 0, None, None, lib.ptr(gran_p4), 9, 3)
+    torch.cuda.synchronize()
+    assert int(gran_p4[B * T]) > 0
+    assert rel_err(t2n(lin4)[:, keep], t2n(ref[:, :NM])[:, keep]) < 1e-5 and rel_err(t2n(stop4), t2n(ref[:, NM])) < 1e-5
+    assert float((lin4[:, 33:44] - 7.0).abs().max()) == 0.0 and torch.equal(pre3, pre3_before)
 
 
 def test_lsa_step_exchange_under_load(dev):
