@@ -497,6 +497,33 @@ int mstts_wav_gather_scale(const float* wav, const int64_t* in_off, const int64_
                            int64_t max_len, float scale, int32_t peak_normalize, int32_t stft_hop, float* out, int64_t* out_off,
                            int64_t* frame_off, mstts_stream_t s);
 
+/* The same front end by librosa's rules (Feeder.load_wav(rule="librosa"); csrc/wav_front_end_librosa.hip): resampy's kaiser_best as a
+ * polyphase FIR, librosa.effects.trim's centred frames.  Layout, stream and checking conventions as above; mstts_wav_gather_scale
+ * serves both rule sets.  Parity with the packages is unpinned.
+ *
+ * mstts_wav_resample_fir: a polyphase FIR with a host-supplied table [up][taps], an explicit origin and a valid length per waveform.
+ * With q = origin + m down, p = q mod up, jm = q div up:
+ *   y[m] = sum_{i < taps} table[p][i] x[jm - (taps - 1) + i]   (x = 0 outside the waveform)        for m < n_valid[w],
+ *   y[m] = 0                                                                                         for n_valid[w] <= m < n_out[w],
+ * n_out[w] = out_off[w + 1] - out_off[w]; n_valid = DEVICE array of nw int64.  For kaiser_best (Audio.kaiser_best_table: taps = 2 L)
+ * origin = L up.  One fmaf chain per output over i ascending from 0 by one thread: the same bits alone, in any batch and under either
+ * tiling.  mstts_wav_resample_fir_supported: 0 = outside the envelope (up, down <= 4096, up taps <= 2^22), 2 = the phase-major tiling
+ * serves the table (its rows of 32 residues and one period's input span fit in 64 KB of LDS), 1 = only the row-major tiling does (rows
+ * and input through L1 / L2).  tiling: 0 = phase-major where it serves, 1 = row-major, 2 = phase-major (refused where _supported != 2).
+ *
+ * mstts_wav_trim_centred: frames x[i hop - pad, i hop - pad + frame), pad = frame / 2, i < 1 + (len + 2 pad - frame) / hop, indices
+ * outside the waveform reflected (-j -> j, len - 1 + j -> len - 1 - j), kept when
+ * 10 log10(max(1e-10, ms_i)) - 10 log10(max(1e-10, max_i ms_i)) > -top_db; bounds[w] = (first hop, min(len, (last + 1) hop)), (0, 0)
+ * when no frame is kept or len = 0, (0, len) when 0 < len <= pad; peak[w] = max |x| inside.  Two launches as mstts_wav_trim;
+ * ws = mstts_wav_trim_centred_ws_floats(total_samples, nw) floats (a waveform can have len + 1 frames). */
+int mstts_wav_resample_fir_supported(int32_t up, int32_t down, int32_t taps);
+int mstts_wav_resample_fir(const float* wav, const int64_t* in_off, const int64_t* out_off, const int64_t* n_valid, int32_t nw,
+                           int64_t max_out, const float* table, int32_t up, int32_t down, int32_t taps, int64_t origin, int32_t tiling,
+                           float* out, mstts_stream_t s);
+int64_t mstts_wav_trim_centred_ws_floats(int64_t total_samples, int32_t nw);
+int mstts_wav_trim_centred(const float* wav, const int64_t* off, int32_t nw, int64_t total_samples, int64_t max_len, int32_t frame,
+                           int32_t hop, float top_db, float* ws, int64_t* bounds, float* peak, mstts_stream_t s);
+
 /* ---- skinny (M <= 32 rows per block) weight-streaming products of the recurrent steps -------------
  * fwd: P[ks][M][N] = X[M, K-slice ks] . W[K-slice ks, N]   (W row-major [K,N], ld ldw); ksplit from
  *      mstts_skinny_fwd_splits (0 = shape not supported -> use mstts_gemm_f32).

@@ -383,7 +383,8 @@ def Griffin_Lim_Batch(spectrograms, phase=None, rng=None, seed=0, device="cuda",
 # ---------------------------------------------------------------------------------------------------------------------
 # Waveform front end on the GPU (csrc/wav_front_end.hip): what Feeder.load_wav does to decoded samples - polyphase rate conversion
 # (scipy.signal.resample_poly's arithmetic), the frame-RMS silence trim, the 0.99 scale - for a batch of waveforms, packed so that
-# the result feeds mstts_stft_fft without a copy back.  Feeder.load_wav stays what it is and is the checker.
+# the result feeds mstts_stft_fft without a copy back.  Feeder.load_wav stays what it is and is the checker.  rule="librosa" selects
+# the second rule set (kaiser_best, centred trim; csrc/wav_front_end_librosa.hip) in every function that takes `rule`.
 # ---------------------------------------------------------------------------------------------------------------------
 def resample_ratio(rate, sample_rate):
     """(up, down) of a conversion rate -> sample_rate in lowest terms, as load_wav forms them."""
@@ -433,6 +434,145 @@ def _resample_table(up, down, device):
     return _upload(resample_phase_table(up, down).astype(np.float32).reshape(-1), torch.float32, torch.device(device))
 
 
+# --- the second rule set, rule = "librosa": librosa.core.load (resampy 0.2.x's kaiser_best) and librosa.effects.trim, restated from the
+# published algorithms in float64 (parity with the packages is unpinned).  The host functions are the checkers of
+# csrc/wav_front_end_librosa.hip.
+KAISER_BEST = dict(num_zeros=64, precision=9, rolloff=0.9475937167399596, beta=14.769656459379492)
+
+
+def wav_rule(rule=None):
+    """Feeder.wav_rule: "scipy" or "librosa" - the argument, else the environment variable MSTTS_WAV_RULE, else "scipy"."""
+    from .Feeder import wav_rule as _wav_rule
+    return _wav_rule(rule)
+
+
+@functools.lru_cache(maxsize=1)
+def kaiser_best_window():
+    """resampy's sinc_window at the kaiser_best settings -> (W, D): the right half of a Kaiser(14.77)-windowed sinc with 64 zero
+    crossings at 512 samples per crossing (32 769 entries, W[0] = rolloff) and its forward differences (D[-1] = 0), float64."""
+    P, Z = 2 ** KAISER_BEST["precision"], KAISER_BEST["num_zeros"]
+    N = P * Z
+    W = np.kaiser(2 * N + 1, KAISER_BEST["beta"])[N:] * KAISER_BEST["rolloff"] * np.sinc(KAISER_BEST["rolloff"] * np.linspace(0, Z, N + 1))
+    D = np.zeros_like(W)
+    D[:-1] = np.diff(W)
+    W.setflags(write=False)
+    D.setflags(write=False)
+    return W, D
+
+
+def kaiser_best_step(up, down):
+    """(scale, step, L): scale = min(1, up / down), step = int(scale 512) - TRUNCATED, as resampy does - and the taps per wing
+    L = 32768 // step + 1.  step = 0 (a ratio below 1 / 512) raises ValueError: resampy cannot convert it either."""
+    scale = min(1.0, float(up) / down)
+    step = int(scale * 2 ** KAISER_BEST["precision"])
+    if step < 1:
+        raise ValueError("kaiser_best cannot convert %d / %d: the filter step truncates to 0" % (up, down))
+    return scale, step, 32768 // step + 1
+
+
+def kaiser_best_table(up, down):
+    """resampy's resample_f at the exact time positions t down / up, as a polyphase table, float64 [up, 2 L]: output t with q = t down,
+    n0 = q // up, r = q % up is  sum_i table[r, i] x[n0 - L + 1 + i]  (x = 0 outside the signal).  Column L - 1 - i holds the left-wing
+    weight W[off + i step] + eta D[off + i step] of x[n0 - i] (off + eta = scale (r / up) 512), column L + k the right-wing weight of
+    x[n0 + 1 + k] (off + eta = (scale - scale (r / up)) 512); W and D are scaled by up / down when that is below 1."""
+    up, down = int(up), int(down)
+    W, D = kaiser_best_window()
+    ratio = float(up) / down
+    if ratio < 1:
+        W, D = W * ratio, D * ratio
+    scale, step, L = kaiser_best_step(up, down)
+    P, nwin = 2 ** KAISER_BEST["precision"], W.shape[0]
+    table = np.zeros((up, 2 * L))
+    for r in range(up):
+        frac = scale * (float(r) / up)
+        for wing, f in ((0, frac), (1, scale - frac)):
+            pos = f * P
+            off = int(pos)
+            eta = pos - off
+            idx = off + step * np.arange((nwin - off) // step)
+            w = W[idx] + eta * D[idx]
+            if wing == 0:
+                table[r, L - 1 - np.arange(idx.shape[0])] = w
+            else:
+                table[r, L + np.arange(idx.shape[0])] = w
+    return table
+
+
+def kaiser_best_out_len(n, up, down):
+    """(n_valid, n_out) for n input samples: resampy computes int(n ratio) samples, librosa's fix_length pads with zeros to
+    int(ceil(n ratio)); ratio = float(up) / down, evaluated in doubles exactly as the packages do."""
+    ratio = float(up) / down
+    return int(n * ratio), int(np.ceil(n * ratio))
+
+
+@functools.lru_cache(maxsize=8)
+def _kaiser_best_table_cached(up, down):
+    t = kaiser_best_table(up, down)
+    t.setflags(write=False)
+    return t
+
+
+def resample_kaiser_best(x, up, down):
+    """librosa.core.resample(x, res_type="kaiser_best") by the table form, float64 in and out: n_out samples, the last
+    n_out - n_valid of them zero.  One matrix product per table row over the outputs that share it."""
+    up, down = int(up), int(down)
+    x = np.asarray(x, np.float64).reshape(-1)
+    n = x.shape[0]
+    n_valid, n_out = kaiser_best_out_len(n, up, down)
+    y = np.zeros(n_out)
+    if n_valid == 0:
+        return y
+    table = _kaiser_best_table_cached(up, down)
+    L = table.shape[1] // 2
+    q = np.arange(n_valid, dtype=np.int64) * down
+    n0, r = q // up, q % up
+    xp = np.concatenate([np.zeros(L - 1), x, np.zeros(L + 1 + max(0, int(n0[-1]) - (n - 1)))])       # xp[j + L - 1] = x[j]
+    win = np.lib.stride_tricks.sliding_window_view(xp, 2 * L)                                      # win[n0] = x[n0 - L + 1 .. n0 + L]
+    order = np.argsort(r, kind="stable")
+    cuts = np.searchsorted(r[order], np.arange(up + 1))
+    for row in range(up):
+        t = order[cuts[row]:cuts[row + 1]]
+        for a in range(0, t.shape[0], 16384):                                                  # (bounds the gathered windows: 16384 x 2 L doubles)
+            y[t[a:a + 16384]] = win[n0[t[a:a + 16384]]] @ table[row]
+    return y
+
+
+def trim_bounds_centred(x, top_db=15.0, frame=2048, hop=512):
+    """librosa.effects.trim's kept range (start, end) in float64: frames of `frame` samples centred on i hop (x[i hop - pad, i hop - pad
+    + frame), pad = frame // 2, reflect-indexed outside the signal), i < 1 + (n + 2 pad - frame) // hop, kept when
+    10 log10(max(1e-10, mse_i)) - 10 log10(max(1e-10, max mse)) > -top_db -> (first hop, min(n, (last + 1) hop)); (0, 0) when no frame
+    is kept.  An all-zero signal keeps everything (every frame sits at 0 dB).  Our own choices: n = 0 gives (0, 0), and 0 < n <= pad - where
+    nothing can be reflected and librosa's answer depends on the NumPy version - keeps the whole signal."""
+    x = np.asarray(x, np.float64).reshape(-1)
+    n, pad = x.shape[0], int(frame) // 2
+    if n == 0:
+        return 0, 0
+    if n <= pad:
+        return 0, n
+    xp = np.pad(x, pad, mode="reflect")
+    nf = 1 + (n + 2 * pad - frame) // hop
+    mse = (np.lib.stride_tricks.sliding_window_view(xp, frame)[::hop][:nf] ** 2).mean(axis=1)
+    db = 10.0 * np.log10(np.maximum(1e-10, mse)) - 10.0 * np.log10(max(1e-10, mse.max()))
+    keep = np.nonzero(db > -top_db)[0]
+    if not keep.size:
+        return 0, 0
+    return int(keep[0]) * hop, min(n, (int(keep[-1]) + 1) * hop)
+
+
+def kaiser_best_supported(up, down):
+    """The device resampler serves this ratio (mstts_wav_resample_fir_supported); otherwise the host path of the same rule is used."""
+    try:
+        L = kaiser_best_step(up, down)[2]
+    except ValueError:
+        return False
+    return int(up) <= 4096 and int(down) <= 4096 and bool(lib.load().mstts_wav_resample_fir_supported(int(up), int(down), 2 * L))
+
+
+@functools.lru_cache(maxsize=16)
+def _kaiser_best_device_table(up, down, device):
+    return _upload(_kaiser_best_table_cached(up, down).astype(np.float32).reshape(-1), torch.float32, torch.device(device))
+
+
 def _pinned(array):
     """Host array -> page-locked tensor (what a non-blocking upload needs)."""
     a = torch.as_tensor(np.ascontiguousarray(array))
@@ -452,11 +592,14 @@ def _as_host_wav(y):
     return np.ascontiguousarray(np.asarray(y, dtype=np.float32).reshape(-1))
 
 
-def _resample_groups(sigs, ups_downs, dev):
+def _resample_groups(sigs, ups_downs, dev, rule="scipy", tiling=0):
     """Upload and rate-convert: sigs = float32 host arrays, ups_downs = (up, down) per signal, (1, 1) = as it is.  One upload of all
     samples, one of all offsets, one resample launch per distinct ratio.  Returns (buf, off, order, lens): the converted waveforms lie
     back to back in buf from off[0] on, in the order `order` (indices into sigs), off = device int64 [len + 1] absolute offsets into
-    buf, lens = their lengths (host, in that order)."""
+    buf, lens = their lengths (host, in that order).  rule "librosa": kaiser_best by mstts_wav_resample_fir (lengths by
+    `kaiser_best_out_len`, the valid lengths uploaded with the offsets) instead of resample_poly by mstts_wav_resample."""
+    librosa = rule == "librosa"
+    out_len = (lambda n, up, down: kaiser_best_out_len(n, up, down)[1]) if librosa else resample_out_len
     groups = {}
     for i, ud in enumerate(ups_downs):
         groups.setdefault(ud, []).append(i)
@@ -466,7 +609,7 @@ def _resample_groups(sigs, ups_downs, dev):
     host = np.concatenate([sigs[i] for i in raw_order]) if raw_order else np.zeros(0, np.float32)
     raw_start = dict(zip(raw_order, np.concatenate([[0], np.cumsum([sigs[i].shape[0] for i in raw_order])]).tolist()))
     n_raw = int(host.shape[0])
-    lens = [sigs[i].shape[0] if ups_downs[i] == (1, 1) else resample_out_len(sigs[i].shape[0], *ups_downs[i]) for i in order]
+    lens = [sigs[i].shape[0] if ups_downs[i] == (1, 1) else out_len(sigs[i].shape[0], *ups_downs[i]) for i in order]
     base = raw_start[plain[0]] if plain else n_raw                           # the converted set begins where the unchanged signals lie
     off_host = base + np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
     meta, launches, pos = [off_host], [], len(plain)
@@ -477,12 +620,20 @@ def _resample_groups(sigs, ups_downs, dev):
         launches.append((ud, len(members), cursor, cursor + len(members) + 1, int(max(lens[pos:pos + len(members)]))))
         meta += [in_off, out_off]
         cursor += 2 * (len(members) + 1)
+        if librosa:
+            meta.append(np.asarray([kaiser_best_out_len(sigs[i].shape[0], *ud)[0] for i in members], np.int64))
+            cursor += len(members)
         pos += len(members)
     buf = torch.empty(max(int(off_host[-1]), 1), dtype=torch.float32, device=dev)
     if n_raw:
         buf[:n_raw].copy_(_pinned(host), non_blocking=True)
     meta_dev = _upload(np.concatenate(meta), torch.int64, dev)
     for (up, down), n, a, b, longest in launches:
+        if librosa:
+            L = kaiser_best_step(up, down)[2]
+            lib.call("mstts_wav_resample_fir", lib.ptr(buf), lib.ptr(meta_dev, a), lib.ptr(meta_dev, b), lib.ptr(meta_dev, b + n + 1), n, longest,
+                     lib.ptr(_kaiser_best_device_table(up, down, str(dev))), up, down, 2 * L, L * up, int(tiling), lib.ptr(buf))
+            continue
         lib.call("mstts_wav_resample", lib.ptr(buf), lib.ptr(meta_dev, a), lib.ptr(meta_dev, b), n, longest, lib.ptr(_resample_table(up, down, str(dev))),
                  up, down, lib.ptr(buf))
     return buf, meta_dev[:len(order) + 1], order, lens
@@ -511,31 +662,57 @@ def resample_poly_batch(wavs, up, down, device="cuda", return_tensor=False):
     return out
 
 
-def _trim(buf, off, lens, top_db, frame, hop):
+def resample_kaiser_best_batch(wavs, sr_orig, sr_new, device="cuda", return_tensor=False, tiling=0):
+    """librosa.core.resample(x, sr_orig, sr_new) at res_type="kaiser_best" for a list of waveforms in one launch
+    (mstts_wav_resample_fir), float32 -> list of int(ceil(len ratio))-sample waveforms whose last sample is zero where resampy computes
+    one fewer.  Ratios outside the device envelope (`kaiser_best_supported`) take the host path of the same rule.  tiling: 0 = the
+    library's choice, 1 = row-major, 2 = phase-major (both give the same bits)."""
+    up, down = resample_ratio(sr_orig, sr_new)
+    sigs = [_as_host_wav(y) for y in wavs]
+    if not sigs:
+        return []
+    dev = torch.device(device)
+    if (up, down) == (1, 1) or not kaiser_best_supported(up, down):
+        out = [s.copy() if (up, down) == (1, 1) else resample_kaiser_best(s, up, down).astype(np.float32) for s in sigs]
+        return [torch.as_tensor(o).to(dev) for o in out] if return_tensor else out
+    buf, off, order, lens = _resample_groups(sigs, [(up, down)] * len(sigs), dev, "librosa", tiling)
+    bounds = np.concatenate([[0], np.cumsum(lens)]) + sum(s.shape[0] for s in sigs)
+    res = buf if return_tensor else buf.cpu().numpy()
+    out = [None] * len(sigs)
+    for k, i in enumerate(order):
+        piece = res[int(bounds[k]):int(bounds[k + 1])]
+        out[i] = piece if return_tensor else piece.copy()
+    return out
+
+
+def _trim(buf, off, lens, top_db, frame, hop, rule="scipy"):
     """mstts_wav_trim on waveforms of the (host-known) lengths `lens` at the device offsets `off` into buf -> device (bounds [nw, 2], peak [nw])."""
     nw, total = len(lens), int(sum(lens))
     bounds = torch.empty(nw, 2, dtype=torch.int64, device=buf.device)
     peak = torch.empty(nw, dtype=torch.float32, device=buf.device)
-    ws = torch.empty(max(int(lib.load().mstts_wav_trim_ws_floats(total, nw)), 1), dtype=torch.float32, device=buf.device)
-    lib.call("mstts_wav_trim", lib.ptr(buf), lib.ptr(off), nw, total, int(max(lens)), int(frame), int(hop), float(top_db), lib.ptr(ws),
+    name = "mstts_wav_trim_centred" if rule == "librosa" else "mstts_wav_trim"
+    ws = torch.empty(max(int(getattr(lib.load(), name + "_ws_floats")(total, nw)), 1), dtype=torch.float32, device=buf.device)
+    lib.call(name, lib.ptr(buf), lib.ptr(off), nw, total, int(max(lens)), int(frame), int(hop), float(top_db), lib.ptr(ws),
              lib.ptr(bounds), lib.ptr(peak))
     return bounds, peak
 
 
-def trim_bounds_batch(wavs, top_db=15.0, frame=32, hop=16, device="cuda"):
-    """The silence trim of Feeder.load_wav for a list of waveforms in one launch (mstts_wav_trim) -> (start, end, peak): int64 arrays
-    of the kept range [start, end) of each waveform and float32 max |x| inside it."""
+def trim_bounds_batch(wavs, top_db=15.0, frame=32, hop=16, device="cuda", rule=None):
+    """The silence trim of Feeder.load_wav for a list of waveforms in one launch (mstts_wav_trim; rule "librosa": the centred trim,
+    mstts_wav_trim_centred) -> (start, end, peak): int64 arrays of the kept range [start, end) of each waveform and float32 max |x|
+    inside it."""
+    rule = wav_rule(rule)
     sigs = [_as_host_wav(y) for y in wavs]
     dev = torch.device(device)
     nw = len(sigs)
     cat = _upload(np.concatenate(sigs), torch.float32, dev) if sum(s.shape[0] for s in sigs) else torch.zeros(1, dtype=torch.float32, device=dev)
     off = _upload(np.concatenate([[0], np.cumsum([s.shape[0] for s in sigs])]).astype(np.int64), torch.int64, dev)
-    bounds, peak = _trim(cat, off, [s.shape[0] for s in sigs], top_db, frame, hop)
+    bounds, peak = _trim(cat, off, [s.shape[0] for s in sigs], top_db, frame, hop, rule)
     b = bounds.cpu().numpy()
     return b[:, 0].copy(), b[:, 1].copy(), peak.cpu().numpy()
 
 
-def _front_end_packed(signals, rates, sample_rate, top_db, frame, hop, scale, peak_normalize, stft_hop, dev):
+def _front_end_packed(signals, rates, sample_rate, top_db, frame, hop, scale, peak_normalize, stft_hop, dev, rule="scipy"):
     """Everything of the front end up to (not including) the one host read: returns (packed, offs, order) - packed = the trimmed,
     scaled waveforms back to back, offs = device int64 [2, nw + 1] (sample offsets; frame offsets for an STFT of hop `stft_hop`),
     order = which input each packed waveform is."""
@@ -543,13 +720,16 @@ def _front_end_packed(signals, rates, sample_rate, top_db, frame, hop, scale, pe
     ratios = []
     for i, r in enumerate(rates):
         ud = resample_ratio(r, sample_rate) if int(r) != int(sample_rate) else (1, 1)
-        if ud != (1, 1) and not resample_supported(*ud):              # outside the device envelope: the host's converter
+        if ud != (1, 1) and rule == "librosa":
+            if not kaiser_best_supported(*ud):                        # outside the device envelope: the host path of the same rule
+                sigs[i], ud = resample_kaiser_best(sigs[i], *ud).astype(np.float32), (1, 1)
+        elif ud != (1, 1) and not resample_supported(*ud):            # outside the device envelope: the host's converter
             from scipy.signal import resample_poly
             sigs[i], ud = resample_poly(sigs[i], *ud).astype(np.float32), (1, 1)
         ratios.append(ud)
     nw = len(sigs)
-    buf, off, order, lens = _resample_groups(sigs, ratios, dev)
-    bounds, peak = _trim(buf, off, lens, top_db, frame, hop)
+    buf, off, order, lens = _resample_groups(sigs, ratios, dev, rule)
+    bounds, peak = _trim(buf, off, lens, top_db, frame, hop, rule)
     packed = torch.empty(max(sum(lens), 1), dtype=torch.float32, device=dev)
     offs = torch.empty(2, nw + 1, dtype=torch.int64, device=dev)
     lib.call("mstts_wav_gather_scale", lib.ptr(buf), lib.ptr(off), lib.ptr(bounds), lib.ptr(peak), nw, int(max(lens)), float(scale),
@@ -558,16 +738,18 @@ def _front_end_packed(signals, rates, sample_rate, top_db, frame, hop, scale, pe
 
 
 def wav_front_end(signals, rates, sample_rate, top_db=15.0, frame=32, hop=16, scale=0.99, peak_normalize=False, device="cuda",
-                  return_tensor=False):
+                  return_tensor=False, rule=None):
     """The trimmed, scaled waveforms Feeder.load_wav returns for the same decoded samples, for a batch: signals = float mono arrays,
     rates = their sample rates.  Signals of one source rate are converted in one launch, signals already at sample_rate skip it; one
-    trim, one gather.  peak_normalize: scale / max |x| of the kept range instead of scale.  -> list of float32 waveforms."""
+    trim, one gather.  peak_normalize: scale / max |x| of the kept range instead of scale.  rule: "scipy" (resample_poly, uncentred RMS
+    trim), "librosa" (kaiser_best, centred power trim) or None = `wav_rule`.  -> list of float32 waveforms."""
+    rule = wav_rule(rule)
     if len(signals) != len(rates):
         raise ValueError("one sample rate per signal")
     if not len(signals):
         return []
     dev = torch.device(device)
-    packed, offs, order = _front_end_packed(signals, rates, sample_rate, top_db, frame, hop, scale, peak_normalize, 1, dev)
+    packed, offs, order = _front_end_packed(signals, rates, sample_rate, top_db, frame, hop, scale, peak_normalize, 1, dev, rule)
     o = offs[0].cpu().numpy()                                    # (the one host read: the lengths)
     res = packed if return_tensor else packed[:int(o[-1])].cpu().numpy()
     out = [None] * len(order)
@@ -579,12 +761,13 @@ def wav_front_end(signals, rates, sample_rate, top_db=15.0, frame=32, hop=16, sc
 
 def wav_features(signals, rates, num_freq, frame_shift_ms, frame_length_ms, sample_rate, num_mels=None, max_abs_value=4, ref_level_db=20,
                  want_mel=True, want_spec=False, spectral_subtract=False, top_db=15.0, frame=32, hop=16, scale=0.99, peak_normalize=False,
-                 length_range=None, device="cuda", return_tensor=False, return_lengths=False):
+                 length_range=None, device="cuda", return_tensor=False, return_lengths=False, rule=None):
     """`wav_front_end` followed by the one-launch STFT (mstts_stft_fft) on the packed buffer, without a copy back: list of
     (mel [frames, num_mels] or None, spec [frames, num_freq] or None), the options of `stft_features`.  One host read (the trimmed
     lengths) lies between the upload and the feature launch.  A waveform whose trimmed length is not longer than n_fft / 2 raises the ValueError
     `stft_features` raises.  length_range = (lo, hi) in samples: a waveform whose trimmed length lies outside it gets (None, None) and
-    no transform.  return_lengths: also the list of trimmed lengths in samples."""
+    no transform.  return_lengths: also the list of trimmed lengths in samples.  rule: as in `wav_front_end`."""
+    rule = wav_rule(rule)
     if len(signals) != len(rates):
         raise ValueError("one sample rate per signal")
     if not len(signals):
@@ -592,7 +775,7 @@ def wav_features(signals, rates, num_freq, frame_shift_ms, frame_length_ms, samp
     consts = _fft_constants(num_freq, frame_shift_ms, frame_length_ms, num_mels or 1, sample_rate, str(device))
     n_fft, stft_hop = consts[0], consts[1]
     dev = consts[3].device
-    packed, offs, order = _front_end_packed(signals, rates, sample_rate, top_db, frame, hop, scale, peak_normalize, stft_hop, dev)
+    packed, offs, order = _front_end_packed(signals, rates, sample_rate, top_db, frame, hop, scale, peak_normalize, stft_hop, dev, rule)
     o = offs.cpu().numpy()                                       # (the one host read: sample and frame offsets)
     nw = len(order)
     lens, frames = [int(v) for v in np.diff(o[0])], [int(v) for v in np.diff(o[1])]

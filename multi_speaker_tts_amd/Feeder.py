@@ -4,7 +4,8 @@ plus synthetic train patterns of the benchmark shape.  Mel extraction of speaker
 GPU through ``Audio.melspectrogram``; wav file reading/resampling/trimming is scipy plumbing (the
 reference uses librosa.core.load + librosa.effects.trim, which are not available here); `load_wav_batch` and
 ``Get_Inference_Pattern(front_end="device")`` run resampling, trim and scale on the GPU for all wavs at once
-(``Audio.wav_front_end``), with `load_wav` as their checker.
+(``Audio.wav_front_end``), with `load_wav` as their checker.  ``rule="librosa"`` (or MSTTS_WAV_RULE=librosa) switches all of them
+to a restatement of librosa's own rules - resampy's kaiser_best rate conversion, the centred power-thresholded trim - see `wav_rule`.
 """
 from __future__ import annotations
 
@@ -148,20 +149,48 @@ def read_audio(path):
     return rate, data
 
 
-def load_wav(path, sample_rate=None, top_db=15.0, frame=32, hop=16):
-    """Speaker wav -> float mono at hp.Sound.Sample_Rate, silence-trimmed, scaled by 0.99
-    (Feeder.py:213-215 plumbing: scipy.io.wavfile + polyphase resampling + a frame_length=32 /
-    hop_length=16 RMS trim standing in for librosa.effects.trim)."""
-    from scipy.signal import resample_poly
-    sr = sample_rate or hp.Sound.Sample_Rate
-    rate, data = read_audio(path)
+def wav_rule(rule=None):
+    """"scipy" or "librosa": the argument, else the environment variable MSTTS_WAV_RULE, else "scipy".  "scipy" is the front end as it
+    always was here (resample_poly, uncentred RMS trim), bit for bit; "librosa" restates what the reference's dependency does
+    (librosa.core.load's kaiser_best rate conversion, librosa.effects.trim's centred frames)."""
+    r = rule if rule is not None else os.environ.get("MSTTS_WAV_RULE", "scipy")
+    if r not in ("scipy", "librosa"):
+        raise ValueError("rule must be 'scipy' or 'librosa', not {!r}".format(r))
+    return r
+
+
+def _to_float_mono(data, rule):
+    """Decoded samples -> float32 mono.  Integer PCM of b bits: / (2^(b-1) - 1) under "scipy", / 2^(b-1) under "librosa" (what soundfile and
+    audioread do); uint8: (x - 128) / 128; several channels: their mean."""
     if data.dtype.kind == "i":
-        data = data.astype(np.float32) / float(np.iinfo(data.dtype).max)
+        if rule == "librosa":
+            data = (data.astype(np.float64) / float(2 ** (8 * data.dtype.itemsize - 1))).astype(np.float32)
+        else:
+            data = data.astype(np.float32) / float(np.iinfo(data.dtype).max)
     elif data.dtype.kind == "u":
         data = (data.astype(np.float32) - 128.0) / 128.0
     data = data.astype(np.float32)
     if data.ndim > 1:
         data = data.mean(axis=1)
+    return data
+
+
+def load_wav(path, sample_rate=None, top_db=15.0, frame=32, hop=16, rule=None):
+    """Speaker wav -> float mono at hp.Sound.Sample_Rate, silence-trimmed, scaled by 0.99
+    (Feeder.py:213-215 plumbing: scipy.io.wavfile + polyphase resampling + a frame_length=32 /
+    hop_length=16 RMS trim standing in for librosa.effects.trim).  rule "librosa": the rate conversion and the trim by
+    librosa's own rules instead, in float64 on the host (Audio.resample_kaiser_best, Audio.trim_bounds_centred); None: `wav_rule`."""
+    sr = sample_rate or hp.Sound.Sample_Rate
+    rate, data = read_audio(path)
+    if wav_rule(rule) == "librosa":
+        from . import Audio
+        data = _to_float_mono(data, "librosa")
+        if rate != sr:
+            data = Audio.resample_kaiser_best(data, *Audio.resample_ratio(rate, sr)).astype(np.float32)
+        start, end = Audio.trim_bounds_centred(data, top_db, frame, hop)
+        return data[start:end] * 0.99
+    from scipy.signal import resample_poly
+    data = _to_float_mono(data, "scipy")
     if rate != sr:
         g = np.gcd(int(rate), int(sr))
         data = resample_poly(data, sr // g, rate // g).astype(np.float32)
@@ -176,26 +205,20 @@ def load_wav(path, sample_rate=None, top_db=15.0, frame=32, hop=16):
     return data * 0.99
 
 
-def decode_wav(path):
+def decode_wav(path, rule=None):
     """(sample_rate, float32 mono samples) of an audio file: the decoding and the int / uint / multi-channel conversion of `load_wav`."""
     rate, data = read_audio(path)
-    if data.dtype.kind == "i":
-        data = data.astype(np.float32) / float(np.iinfo(data.dtype).max)
-    elif data.dtype.kind == "u":
-        data = (data.astype(np.float32) - 128.0) / 128.0
-    data = data.astype(np.float32)
-    if data.ndim > 1:
-        data = data.mean(axis=1)
-    return int(rate), data
+    return int(rate), _to_float_mono(data, wav_rule(rule))
 
 
-def load_wav_batch(paths, sample_rate=None, top_db=15.0, frame=32, hop=16, device="cuda"):
+def load_wav_batch(paths, sample_rate=None, top_db=15.0, frame=32, hop=16, device="cuda", rule=None):
     """`load_wav` for a list of files: decoding on the host exactly as there, rate conversion, trim and the 0.99 scale on the GPU for
     the whole list (Audio.wav_front_end: one resample launch per source rate, one trim, one gather) -> list of float32 waveforms."""
     from . import Audio
-    decoded = [decode_wav(p) for p in paths]
+    rule = wav_rule(rule)
+    decoded = [decode_wav(p, rule) for p in paths]
     return Audio.wav_front_end([d for _, d in decoded], [r for r, _ in decoded], sample_rate or hp.Sound.Sample_Rate, top_db=top_db, frame=frame,
-                               hop=hop, scale=0.99, device=device)
+                               hop=hop, scale=0.99, device=device, rule=rule)
 
 
 def wav_front_end_mode(front_end=None):
@@ -222,12 +245,16 @@ def metadata_path():
     return os.path.join(hp.Train.Pattern_Path, hp.Train.Metadata_File.upper()).replace("\\", "/")
 
 
-def check_metadata(md):
-    """Feeder.py:46-56: the pattern set must have been generated with the current hyper parameters."""
+def check_metadata(md, rule=None):
+    """Feeder.py:46-56: the pattern set must have been generated with the current hyper parameters - and under the waveform rule in
+    force (`wav_rule`)."""
     if not all([len(md["Token_Index_Dict"]) == hp.Encoder.Embedding.Token_Size, md["Spectrogram_Dim"] == hp.Sound.Spectrogram_Dim,
                 md["Mel_Dim"] == hp.Sound.Mel_Dim, md["Frame_Shift"] == hp.Sound.Frame_Shift, md["Frame_Length"] == hp.Sound.Frame_Length,
                 md["Sample_Rate"] == hp.Sound.Sample_Rate]):
         raise ValueError("The metadata information and hyper parameter setting are not consistent.")
+    if md.get("Wav_Rule", "scipy") != wav_rule(rule):       # (the key is written only for a rule other than the default)
+        raise ValueError("The pattern set was generated under the waveform rule {!r}, the rule in force is {!r}.".format(
+            md.get("Wav_Rule", "scipy"), wav_rule(rule)))
 
 
 def train_file_order(md, is_Pre_Train=False):
@@ -455,22 +482,24 @@ class Feeder:
     def Speaker_Embedding_Mel(self, mel_List):
         return speaker_windows(mel_List)
 
-    def Get_Inference_Pattern(self, speaker_Wav_Path_List, text_List, speaker_Mel_List=None, front_end=None):
+    def Get_Inference_Pattern(self, speaker_Wav_Path_List, text_List, speaker_Mel_List=None, front_end=None, rule=None):
         """Feeder.py:186-233.  `speaker_Mel_List` ([T,80] arrays) may be given instead of wav paths.  front_end "device": every speaker
         wav through the batched GPU front end (Audio.wav_features: one upload, one resample launch per source rate, one trim, one
-        gather, one mel launch, one copy back); "host": load_wav and one mel launch per wav; None: `wav_front_end_mode`."""
+        gather, one mel launch, one copy back); "host": load_wav and one mel launch per wav; None: `wav_front_end_mode`.  rule: the
+        waveform rule of either path ("scipy", "librosa", None: `wav_rule`)."""
         from . import Audio
+        rule = wav_rule(rule)
         token, length = tokenize(text_List, self.metadata_Dict["Token_Index_Dict"])
         if speaker_Mel_List is None and wav_front_end_mode(front_end) == "device":
-            decoded = [decode_wav(path) for path in speaker_Wav_Path_List]
+            decoded = [decode_wav(path, rule) for path in speaker_Wav_Path_List]
             feats = Audio.wav_features([d for _, d in decoded], [r for r, _ in decoded], num_freq=hp.Sound.Spectrogram_Dim,
                                        frame_shift_ms=hp.Sound.Frame_Shift, frame_length_ms=hp.Sound.Frame_Length, sample_rate=hp.Sound.Sample_Rate,
-                                       num_mels=hp.Sound.Mel_Dim, max_abs_value=hp.Sound.Max_Abs_Mel, device=self.device, return_tensor=True)
+                                       num_mels=hp.Sound.Mel_Dim, max_abs_value=hp.Sound.Max_Abs_Mel, device=self.device, return_tensor=True, rule=rule)
             speaker_Mel_List = mels_to_host([m for m, _ in feats])
         if speaker_Mel_List is None:
             speaker_Mel_List = [
                 np.transpose(Audio.melspectrogram(
-                    y=load_wav(path), num_freq=hp.Sound.Spectrogram_Dim, frame_shift_ms=hp.Sound.Frame_Shift,
+                    y=load_wav(path, rule=rule), num_freq=hp.Sound.Spectrogram_Dim, frame_shift_ms=hp.Sound.Frame_Shift,
                     frame_length_ms=hp.Sound.Frame_Length, num_mels=hp.Sound.Mel_Dim, sample_rate=hp.Sound.Sample_Rate,
                     max_abs_value=hp.Sound.Max_Abs_Mel, device=self.device)).astype(np.float32)
                 for path in speaker_Wav_Path_List]

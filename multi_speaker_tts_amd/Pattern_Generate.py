@@ -35,11 +35,11 @@ def Text_Filtering(text):
     return found[0]
 
 
-def Mel_Generate(path, spectral_Subtract=False, range_Ignore=False, device="cuda"):
+def Mel_Generate(path, spectral_Subtract=False, range_Ignore=False, device="cuda", rule=None):
     """Pattern_Generate.py:33-58 (same positional order): load at hp.Sound.Sample_Rate, trim (top_db 15, librosa's default
-    2048/512 frames), scale by 0.99, reject by duration, mel through the HIP STFT kernel."""
+    2048/512 frames), scale by 0.99, reject by duration, mel through the HIP STFT kernel.  rule: Feeder.load_wav's waveform rule."""
     from . import Audio
-    sig = _Feeder.load_wav(path, frame=2048, hop=512)
+    sig = _Feeder.load_wav(path, frame=2048, hop=512, rule=rule)
     ms = sig.shape[0] / hp.Sound.Sample_Rate * 1000
     if not range_Ignore and (ms < hp.Train.Use_Wav_Length_Range[0] or ms > hp.Train.Use_Wav_Length_Range[1]):
         return None
@@ -49,18 +49,19 @@ def Mel_Generate(path, spectral_Subtract=False, range_Ignore=False, device="cuda
                                              device=device)).astype(np.float32)
 
 
-def Mel_Generate_Batch(paths, spectral_Subtract=False, range_Ignore=False, device="cuda"):
+def Mel_Generate_Batch(paths, spectral_Subtract=False, range_Ignore=False, device="cuda", rule=None):
     """`Mel_Generate` for a list of files through the batched GPU front end (Audio.wav_features with the 2048 / 512 trim): one mel
     [frames, Mel_Dim] or None per path, the hp.Train.Use_Wav_Length_Range filter applied to the trimmed length as there."""
     from . import Audio
-    decoded = [_Feeder.decode_wav(p) for p in paths]
+    rule = _Feeder.wav_rule(rule)
+    decoded = [_Feeder.decode_wav(p, rule) for p in paths]
     if not decoded:
         return []
     sigs, rates = [d for _, d in decoded], [r for r, _ in decoded]
     stft = dict(num_freq=hp.Sound.Spectrogram_Dim, frame_shift_ms=hp.Sound.Frame_Shift, frame_length_ms=hp.Sound.Frame_Length,
                 sample_rate=hp.Sound.Sample_Rate, num_mels=hp.Sound.Mel_Dim, max_abs_value=hp.Sound.Max_Abs_Mel, device=device)
     rng = None if range_Ignore else tuple(v / 1000 * hp.Sound.Sample_Rate for v in hp.Train.Use_Wav_Length_Range)       # ms -> samples
-    feats = Audio.wav_features(sigs, rates, spectral_subtract=spectral_Subtract, frame=2048, hop=512, length_range=rng, return_tensor=True, **stft)
+    feats = Audio.wav_features(sigs, rates, spectral_subtract=spectral_Subtract, frame=2048, hop=512, length_range=rng, return_tensor=True, rule=rule, **stft)
     keep = [i for i, (m, _) in enumerate(feats) if m is not None]
     out = [None] * len(paths)
     if keep:
@@ -81,13 +82,18 @@ def Pattern_File_Write(file_Name, text, mel, token_Index_Dict, dataset, pattern_
 _FROM_FILE = object()
 
 
+def _rule_kw(rule):
+    """The `rule` keyword for a callee, only when a rule was given: without one the call is what it always was."""
+    return {} if rule is None else {"rule": rule}
+
+
 def Pattern_File_Generate(path, text, token_Index_Dict, dataset, spectral_Subtract=False, file_Prefix="", display_Prefix="", range_Ignore=False,
-                          device="cuda", mel=_FROM_FILE):
+                          device="cuda", mel=_FROM_FILE, rule=None):
     """Pattern_Generate.py:60-82 for one (wav, text) pair; returns the pickle name or None when the utterance is skipped.  `mel`: the
     result of Mel_Generate_Batch for this file (None = rejected) instead of a Mel_Generate call."""
     text = Text_Filtering(text)
     if mel is _FROM_FILE:
-        mel = Mel_Generate(path, spectral_Subtract, range_Ignore, device=device) if text is not None else None
+        mel = Mel_Generate(path, spectral_Subtract, range_Ignore, device=device, **_rule_kw(rule)) if text is not None else None
     elif text is None:
         mel = None
     if mel is None:
@@ -97,12 +103,15 @@ def Pattern_File_Generate(path, text, token_Index_Dict, dataset, spectral_Subtra
     return name
 
 
-def Metadata_Generate(token_Index_Dict=None, pattern_path=None):
-    """Pattern_Generate.py:245-274."""
+def Metadata_Generate(token_Index_Dict=None, pattern_path=None, rule=None):
+    """Pattern_Generate.py:245-274.  The waveform rule the set was made under is recorded as 'Wav_Rule' only when it is not the default
+    ("scipy"): an absent key means "scipy", and sets written before the key existed stay valid."""
     root = pattern_path or hp.Train.Pattern_Path
     md = {"Token_Index_Dict": token_Index_Dict or _Feeder.load_token_dict(), "Spectrogram_Dim": hp.Sound.Spectrogram_Dim, "Mel_Dim": hp.Sound.Mel_Dim,
           "Frame_Shift": hp.Sound.Frame_Shift, "Frame_Length": hp.Sound.Frame_Length, "Sample_Rate": hp.Sound.Sample_Rate,
           "File_List": [], "Token_Length_Dict": {}, "Mel_Length_Dict": {}, "Dataset_Dict": {}}
+    if _Feeder.wav_rule(rule) != "scipy":
+        md["Wav_Rule"] = _Feeder.wav_rule(rule)
     meta = hp.Train.Metadata_File.upper()
     for r, _, files in os.walk(root):
         for file in sorted(files):
@@ -247,7 +256,7 @@ def TIMIT_Info_Load(timit_Path):
 
 
 def Pattern_File_Generate_from_SPH(path, text_List, token_Index_Dict, dataset, spectral_Subtract=False, display_Prefix="", range_Ignore=False,
-                                   device="cuda"):
+                                   device="cuda", rule=None):
     """Pattern_Generate.py:80-113: one pattern per (start, end, text) segment of a SPHERE recording, named
     <DATASET>.<basename>.<index>.PICKLE.  Returns the names written.  Two things the reference does here are kept on purpose, so that
     the TEDLIUM pattern set comes out identical: it calls Mel_Generate with its DEFAULTS (`:91` - the spectral_Subtract / range_Ignore
@@ -262,7 +271,7 @@ def Pattern_File_Generate_from_SPH(path, text_List, token_Index_Dict, dataset, s
             tmp = tf.name
         try:
             wavfile.write(tmp, rate, data)
-            mel = Mel_Generate(tmp, device=device)
+            mel = Mel_Generate(tmp, device=device, **_rule_kw(rule))
         finally:
             os.remove(tmp)
         if mel is None:
@@ -285,7 +294,9 @@ def main(argv=None, device="cuda"):
     ap.add_argument("-timit", "--timit_path", required=False)
     ap.add_argument("-all", "--all_save", action="store_true")
     ap.add_argument("-batch", "--batch_size", type=int, default=0)       # N > 0: N files at a time through Mel_Generate_Batch (0: file by file)
+    ap.add_argument("-rule", "--wav_rule", choices=("scipy", "librosa"), default=None)   # the waveform rule (Feeder.wav_rule; default: MSTTS_WAV_RULE, else scipy)
     args = ap.parse_args(argv)
+    rule = _rule_kw(args.wav_rule)                       # (no -rule: every callee resolves the default itself)
     token_Index_Dict = _Feeder.load_token_dict()
     jobs = []                                            # (dataset, path, text or segment list)
     # per corpus, as the reference submits them (Pattern_Generate.py:318-404): LibriSpeech (and TEDLIUM, where the flag is then dropped)
@@ -310,20 +321,20 @@ def main(argv=None, device="cuda"):
                 if jobs[k][0] != dataset or len(ahead) == args.batch_size:
                     break
                 ahead.append(k)
-            mels = Mel_Generate_Batch([jobs[k][1] for k in ahead], spectral[dataset], args.all_save, device=device)
+            mels = Mel_Generate_Batch([jobs[k][1] for k in ahead], spectral[dataset], args.all_save, device=device, **rule)
             batched.update(zip(ahead, mels))
         if dataset == "TL":
-            names = Pattern_File_Generate_from_SPH(path, what, token_Index_Dict, dataset, spectral[dataset], range_Ignore=args.all_save, device=device)
+            names = Pattern_File_Generate_from_SPH(path, what, token_Index_Dict, dataset, spectral[dataset], range_Ignore=args.all_save, device=device, **rule)
         else:
             prefix = "{}.".format(path.split("/")[-2]) if dataset == "TIMIT" else ""
             if args.batch_size > 0:
                 name = Pattern_File_Generate(path, what, token_Index_Dict, dataset, file_Prefix=prefix, mel=batched.pop(i, None))
             else:
-                name = Pattern_File_Generate(path, what, token_Index_Dict, dataset, spectral[dataset], prefix, range_Ignore=args.all_save, device=device)
+                name = Pattern_File_Generate(path, what, token_Index_Dict, dataset, spectral[dataset], prefix, range_Ignore=args.all_save, device=device, **rule)
             names = [name] if name else []
         written += len(names)
         print("[{} {:05d}/{:05d}]".format(dataset, i, len(jobs)), path, "->", ", ".join(names) if names else "Ignored because of length.")
-    Metadata_Generate(token_Index_Dict)
+    Metadata_Generate(token_Index_Dict, **rule)
     return written
 
 

@@ -211,6 +211,10 @@ SIGNATURES = {
     "mstts_wav_trim_ws_floats": (i64, [i64, i32]),
     "mstts_wav_trim": (i32, [vp, vp, i32, i64, i64, i32, i32, f32, vp, vp, vp, vp]),
     "mstts_wav_gather_scale": (i32, [vp, vp, vp, vp, i32, i64, f32, i32, i32, vp, vp, vp, vp]),
+    "mstts_wav_resample_fir_supported": (i32, [i32, i32, i32]),
+    "mstts_wav_resample_fir": (i32, [vp, vp, vp, vp, i32, i64, vp, i32, i32, i32, i64, i32, vp, vp]),
+    "mstts_wav_trim_centred_ws_floats": (i64, [i64, i32]),
+    "mstts_wav_trim_centred": (i32, [vp, vp, i32, i64, i64, i32, i32, f32, vp, vp, vp, vp]),
     "mstts_fold_rows": (i32, [vp, vp, i64, i64, i64, i64, vp]),
     "mstts_decoder_bf16_splits": (i32, [i64, i64, i64, P(i32)]),
     "mstts_skinny_bf16_fwd_splits": (i32, [i64, i64]),
