@@ -271,7 +271,7 @@ int mstts_cell_fwd_pair(const mstts_cell_fwd_desc* a, const mstts_cell_fwd_desc*
  * BahdanauAttention masking/softmax + AttentionWrapper context).  Two launches:
  *   energy : e[b,t] = sum_k w_k tanh(keys[b,t,k] + q[b,k] + (conv31(cum)[b,t,:] . Wd)[k] + b_k)
  *   context: a = softmax(mask(e)); cum_next = cum + a; ctx[b,:] = sum_t a[b,t] values[b,t,:]
- * T <= 512, A == 128, att conv channels == 32. */
+ * T <= 1024, A == 128, att conv channels == 32. */
 typedef struct {
     int64_t B, T, A, M, KS, CH;      /* batch, encoder steps, attention units, memory width, conv taps, conv channels */
     const float* keys; const float* values; const int32_t* lengths;
@@ -351,7 +351,10 @@ int mstts_lsa_step_fwd_qp(const mstts_lsa_const* c, const float* m1, int64_t m1_
  *  dalign : G[t] = G_next[t] + sum_j h_next[t+pad-j][j] ; d_a[b,t] = G[b,t] + values[b,t,:] . d_ctx[b,:]
  *  denergy: d_e = a*(d_a - sum a d_a); g = d_e*w*(1-u^2); dq[b,:] += sum_t g (atomic); h[t,j] = sum_k g[t,k] loc_k[j,k]
  *           (h is [B,T,32], the filter-transpose operand of the previous step's dalign); saves d_e */
-/* d_ctx row b = d_ctx[b*d_ctx_ld ..] (+ d_ctx2[b*d_ctx2_ld ..] when d_ctx2 != NULL) */
+/* d_ctx row b = d_ctx[b*d_ctx_ld ..] (+ d_ctx2[b*d_ctx2_ld ..] when d_ctx2 != NULL).  d_ctx2 is the sum of d_ctx2_parts partial slabs at
+ * stride d_ctx2_pstride floats (parts 0 / 1 = one slab).  Both backward entry points refuse d_ctx2_parts outside [0, 8] (MSTTS_ERR_SHAPE: the
+ * kernels hold eight slab slots) and, with d_ctx2 set, a d_ctx2_pstride that is not a multiple of 4 (MSTTS_ERR_ALIGN: slabs are read as
+ * float4); d_ctx, d_ctx2 16-byte aligned, d_ctx_ld and d_ctx2_ld multiples of 4. */
 int mstts_lsa_dalign_bwd(const mstts_lsa_const* c, const float* d_ctx, int64_t d_ctx_ld, const float* d_ctx2, int64_t d_ctx2_ld,
                          int32_t d_ctx2_parts, int64_t d_ctx2_pstride, const float* G_next, const float* d_f_next, float* G, float* d_align, mstts_stream_t s);
 int mstts_lsa_denergy_bwd(const mstts_lsa_const* c, const float* align, const float* d_align, const float* q, const float* cum,

@@ -1478,6 +1478,8 @@ extern "C" int mstts_lsa_dalign_bwd(const mstts_lsa_const* c, const float* d_ctx
     int rc = check_const(c); if (rc) return rc;
     MSTTS_REQUIRE(aligned16(d_ctx) && aligned16(d_ctx2) && d_ctx_ld % 4 == 0 && d_ctx2_ld % 4 == 0, MSTTS_ERR_ALIGN,
                   "lsa_dalign: d_ctx rows must be 16-byte aligned");
+    MSTTS_REQUIRE(d_ctx2_parts >= 0 && d_ctx2_parts <= 8, MSTTS_ERR_SHAPE, "lsa_dalign: at most 8 d_ctx2 slabs (got %d)", (int)d_ctx2_parts);
+    MSTTS_REQUIRE(!d_ctx2 || d_ctx2_pstride % 4 == 0, MSTTS_ERR_ALIGN, "lsa_dalign: the d_ctx2 slab stride must be a multiple of 4 floats");
     hipLaunchKernelGGL(lsa_dalign_kernel, dim3((unsigned)c->B, cdiv(c->T, TS)), dim3(256), 0, ST(s), *c, d_ctx, (long)d_ctx_ld, d_ctx2,
                        (long)d_ctx2_ld, (int)d_ctx2_parts, (long)d_ctx2_pstride, G_next, d_f_next, G, d_align);
     MSTTS_CHECK_LAUNCH("lsa_dalign_bwd");
@@ -1497,6 +1499,8 @@ extern "C" int mstts_lsa_step_bwd(const mstts_lsa_const* c, const float* d_ctx, 
     int rc = check_const(c); if (rc) return rc;
     MSTTS_REQUIRE(aligned16(d_ctx) && aligned16(d_ctx2) && d_ctx_ld % 4 == 0 && d_ctx2_ld % 4 == 0, MSTTS_ERR_ALIGN,
                   "lsa_step_bwd: d_ctx rows must be 16-byte aligned");
+    MSTTS_REQUIRE(d_ctx2_parts >= 0 && d_ctx2_parts <= 8, MSTTS_ERR_SHAPE, "lsa_step_bwd: at most 8 d_ctx2 slabs (got %d)", (int)d_ctx2_parts);
+    MSTTS_REQUIRE(!d_ctx2 || d_ctx2_pstride % 4 == 0, MSTTS_ERR_ALIGN, "lsa_step_bwd: the d_ctx2 slab stride must be a multiple of 4 floats");
     MSTTS_REQUIRE(ctx_fwd && aligned16(ctx_fwd) && ctx_fwd_ld % 4 == 0, MSTTS_ERR_ALIGN, "lsa_step_bwd: the forward context rows (16-byte aligned) are required");
     MSTTS_REQUIRE(aligned16(c->loc_k), MSTTS_ERR_ALIGN, "lsa_step_bwd: the folded filter loc_k must be 16-byte aligned");
     hipLaunchKernelGGL(lsa_step_bwd_kernel, dim3((unsigned)(cdiv(c->T, TS) * c->B)), dim3(256), 0, ST(s), *c, d_ctx, (long)d_ctx_ld, d_ctx2,
