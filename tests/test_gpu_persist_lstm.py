@@ -1,6 +1,7 @@
 """Persistent BiLSTM launches (csrc/persist_lstm.hip): all T steps of both directions in one launch, forward and BPTT, against the
-launch-per-step pair drivers (mstts_lstm_seq_fwd_pair / mstts_lstm_seq_bwd_pair, themselves checked against the oracle in
-test_gpu_ops.py / test_gpu_model.py) on the same buffers: ragged lengths, reversed direction, zoneout masks, fewer than 32 rows."""
+launch-per-step pair drivers (mstts_lstm_seq_fwd_pair / mstts_lstm_seq_bwd_pair) on the same buffers: ragged lengths, reversed direction,
+zoneout masks, fewer than 32 rows.  The launch-per-step drivers - and the persistent launches at small T - meet the fp64 oracle
+(oracle.model.run_lstm and its autograd, per row and step) in test_gpu_lstm_seq_ref.py; this file carries that base to long sequences."""
 import ctypes as C
 
 import numpy as np
