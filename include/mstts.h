@@ -610,10 +610,25 @@ int mstts_adam_tf_clip(float* p, const float* grad, float* m, float* v, const fl
 /* ---- GE2E loss of the speaker-encoder trainer, forward + backward (Speaker_Embedding/Modules.py:39-98, "Softmax" method):
  * x [N = S*P, D] = last-frame outputs of the LSTM stack, speaker-major (P consecutive rows per speaker), rows ldx apart;
  * wb = {weight, bias} of the scaled cosine similarity.  out[0] = loss, out[1] = d/d weight, out[2] = d/d bias (identically 0);
- * dx [N, D] rows lddx apart = d loss / d x (through tf.nn.l2_normalize(axis=1)).  ws: mstts_ge2e_ws_floats(N, D, S) floats. */
+ * dx [N, D] rows lddx apart = d loss / d x (through tf.nn.l2_normalize(axis=1)).  ws: mstts_ge2e_ws_floats(N, D, S) floats.
+ * mstts_ge2e_contrast_fwd_bwd: the "Contrast" method (Modules.py:93-94) on the same arguments and workspace, with
+ * l0_i = w cosw_i - b and l_ik = w cosb_ik - b: loss = SUM_i [1 - sigmoid(l0_i) + max_{k != s(i)} l_ik] (a sum, not a mean);
+ * of several equal maxima the first (lowest k) takes the gradient; out[2] = SUM_i [sigmoid'(l0_i) - 1] is not zero here. */
 int64_t mstts_ge2e_ws_floats(int64_t N, int64_t D, int64_t S);
 int mstts_ge2e_loss_fwd_bwd(const float* x, int64_t ldx, int64_t S, int64_t P, int64_t D, const float* wb, float* out,
                             float* dx, int64_t lddx, float* ws, mstts_stream_t s);
+int mstts_ge2e_contrast_fwd_bwd(const float* x, int64_t ldx, int64_t S, int64_t P, int64_t D, const float* wb, float* out,
+                                float* dx, int64_t lddx, float* ws, mstts_stream_t s);
+
+/* ---- batch gather out of a device-resident mel bank (the speaker-encoder trainer's feeder; Speaker_Embedding/Feeder.py:66-100):
+ * bank fp32 [total_frames, n_mel] holds every file's mel back to back, file f at frames frame_off[f] .. frame_off[f + 1] (int64
+ * [n_files + 1]); table int32 [N, 4], 16-byte aligned, one row (file, src_start, dst_start, count) per output row:
+ *   out[r, t, :] = bank[frame_off[file] + src_start + (t - dst_start), :]  for dst_start <= t < dst_start + count,  else 0.
+ * Every element of out [N, T, n_mel] is stored exactly once.  A row with file outside [0, n_files), a negative field, src_start + count
+ * beyond the file or dst_start + count beyond T reads nothing, is written as zeros and sets bit 0 of status[0] (int32; the caller
+ * zeroes it once).  All pointers are device pointers. */
+int mstts_mel_bank_gather(const float* bank, const int64_t* frame_off, int64_t n_files, const int32_t* table, int64_t N, int64_t T,
+                          int64_t n_mel, float* out, int32_t* status, mstts_stream_t s);
 
 /* ---- bf16 variants of the skinny products (BASELINE config 3, "bf16 with fp32 master"): the kernel W is a packed bf16 copy made by
  * mstts_pack_bf16_fwd / _bwd from the fp32 master (round to nearest even; lane-consumption order, opaque), the activation block is

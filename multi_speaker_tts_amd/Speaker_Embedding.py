@@ -3,9 +3,13 @@
 .Inference(mel_List)``.  `speaker_embedding.pt` under hp.Speaker_Embedding.Checkpoint_Path is exactly what
 ``MSTTS_SV.Tacotron2.Speaker_Embedding_Load`` reads (MSTTS_SV.py:223-227).  A training pattern is {'Mel': [Batch_Speaker *
 Batch_per_Speaker, frames, 80]} speaker-major with one random frame count from hp.Speaker_Embedding.Train.Frame_Range per batch
-(Speaker_Embedding/Feeder.py:66-100); without one a synthetic pattern of that shape is used.
+(Speaker_Embedding/Feeder.py:66-100).  ``Train()`` feeds itself from the pattern set under hp.Speaker_Embedding.Train.Pattern_Path
+when its metadata file exists (speaker_feeder.MelBank / SpeakerFeeder: the corpus resident on the device, one gather launch per batch;
+Speaker_Embedding_Pattern_Generate writes such a set); without one a synthetic pattern of that shape is used.
 """
 from __future__ import annotations
+
+import os
 
 import numpy as np
 import torch
@@ -17,16 +21,31 @@ from .speaker_trainer import SpeakerTrainEngine, learning_rate
 from .training import DropIn
 
 TRAIN_KEYS = ("Global_Step", "Learning_Rate", "Loss", "Train_OP")
+INFERENCE_IN_TRAIN_FILE = "Speaker_Embedding_Inference_in_Train.txt"       # lines `label<TAB>wav path` (Speaker_Embedding.py:99-102)
+
+
+def Embedding_Value(embeddings, labels):
+    """The figure the reference judges an encoder by (Export_TSNE, Speaker_Embedding.py:155-170): mean distance between the per-label mean
+    embeddings (over ordered pairs of different labels) / mean distance of every embedding to its label's mean."""
+    emb = np.asarray(embeddings)
+    labels = list(labels)
+    means = {lab: np.mean([e for x, e in zip(labels, emb) if x == lab], axis=0) for lab in set(labels)}
+    between = [np.sqrt(np.sum(np.power(m1 - m2, 2))) for l1, m1 in means.items() for l2, m2 in means.items() if l1 != l2]
+    within = [np.sqrt(np.sum(np.power(e - means[lab], 2))) for lab, e in zip(labels, emb)]
+    return np.mean(between) / np.mean(within)
 
 
 class Speaker_Embedding(DropIn):
     HP, FILE, SCOPE = "Speaker_Embedding", "speaker_embedding.pt", "speaker_embedding"
     COLUMNS = (("Learning rate: {:0.6f}", "Learning_Rate"), ("Loss: {:0.5f}", "Loss"))
 
-    def __init__(self, is_Training=True, device="cuda", seed=1234, dims: Dims = None):
+    def __init__(self, is_Training=True, device="cuda", seed=1234, dims: Dims = None, loss_method=None):
         self.is_Training = is_Training
         self.device = device
-        self.engine = SpeakerTrainEngine(dims, device=device, seed=seed)
+        self.seed = seed
+        self.engine = SpeakerTrainEngine(dims, device=device, seed=seed, loss_method=loss_method)
+        self.feeder = None
+        self.embedding_Value = None
         self.params = self.engine.params
         self.train_Tensor_Dict = {k: k for k in TRAIN_KEYS} if is_Training else None
         self.inference_Tensor_Dict = {k: k for k in ("Global_Step", "Embedding")}
@@ -54,12 +73,54 @@ class Speaker_Embedding(DropIn):
         w = self.engine.train_step(mel, int(pattern.get("Batch_per_Speaker", hp.Speaker_Embedding.Train.Batch_per_Speaker)))
         return {"Global_Step": step, "Learning_Rate": learning_rate(step), "Loss": float(w.out3[0]), "Train_OP": None}
 
-    def Inference(self, mel_List):
+    def Train(self, max_steps=None, pattern_fn=None):
+        """Without a pattern_fn, when training and the metadata file of hp.Speaker_Embedding.Train.Pattern_Path exists: the corpus goes
+        into a device mel bank once and every step's batch comes from a SpeakerFeeder on it; otherwise as DropIn.Train."""
+        from . import speaker_feeder as SF
+        if pattern_fn is None and self.is_Training and os.path.exists(SF.metadata_path()):
+            if self.feeder is None:
+                self.feeder = SF.SpeakerFeeder(SF.MelBank.from_patterns(device=self.device), seed=self.seed)
+            pattern_fn = self.feeder.Get_Train_Pattern
+        return super().Train(max_steps, pattern_fn)
+
+    def _after_step(self, result):
+        if self.feeder is not None:
+            self.feeder.check_status()               # right behind the loss read of Train_Step: the stream is already drained
+        if (result["Global_Step"] + 1) % hp.Speaker_Embedding.Train.Inference_Timing == 0 and os.path.exists(INFERENCE_IN_TRAIN_FILE):
+            with open(INFERENCE_IN_TRAIN_FILE, "r") as f:
+                label_List, path_List = list(zip(*[line.strip().split("\t") for line in f.readlines() if line.strip()]))
+            self.Inference(list(path_List), label_List=list(label_List))
+            print("Global step: {}    Embedding value: {:0.5f}".format(result["Global_Step"] + 1, self.embedding_Value))
+
+    def _wav_mels(self, path_List):
+        """Feeder.py:130-144: wav -> trimmed (top_db 15, frames 32 / 16), scaled waveform -> mel [frames, Mel_Dim]."""
+        from . import Audio
+        s = hp.Sound
+        return [np.transpose(Audio.melspectrogram(y=_Feeder.load_wav(path), num_freq=s.Spectrogram_Dim, frame_shift_ms=s.Frame_Shift,
+                                                  frame_length_ms=s.Frame_Length, num_mels=s.Mel_Dim, sample_rate=s.Sample_Rate,
+                                                  max_abs_value=s.Max_Abs_Mel, device=self.device)).astype(np.float32) for path in path_List]
+
+    def Inference(self, path_or_mel_List, export_TSNE=False, label_List=None):
         """Embeddings of whole utterances: 5 windows of 64 frames each, mean of the last-frame outputs, whole-tensor l2
-        normalisation (Speaker_Embedding/Modules.py:127-137; Feeder.py:105-160).  mel_List: [T_i, 80] arrays."""
+        normalisation (Speaker_Embedding/Modules.py:127-137; Feeder.py:105-160).  path_or_mel_List: [T_i, 80] mel arrays - one forward
+        for all, as ever - or wav paths (Speaker_Embedding.py:127-150): hp.Speaker_Embedding.Inference.Max_Embedding_per_Batch files per
+        forward, each batch normalised as a whole like in the reference, the results stacked.  With a label_List the between / within
+        ratio of the result is left in `embedding_Value` (`Embedding_Value`); export_TSNE is accepted, the t-SNE picture is not drawn."""
         from .inference import InferEngine
         if self._infer is None:
             self._infer = InferEngine(self.engine.d, device=self.device, params=self.params)
-        self._infer._keep = []
-        win = torch.as_tensor(_Feeder.speaker_windows(mel_List)).to(torch.device(self.device), torch.float32).contiguous()
-        return self._infer.speaker_embedding(win).cpu().numpy()
+        items = list(path_or_mel_List)
+        if items and all(isinstance(x, str) for x in items):
+            n = hp.Speaker_Embedding.Inference.Max_Embedding_per_Batch
+            batches = [self._wav_mels(items[x:x + n]) for x in range(0, len(items), n)]
+        else:
+            batches = [items]
+        out = []
+        for mel_List in batches:
+            self._infer._keep = []
+            win = torch.as_tensor(_Feeder.speaker_windows(mel_List)).to(torch.device(self.device), torch.float32).contiguous()
+            out.append(self._infer.speaker_embedding(win).cpu().numpy())
+        result = np.vstack(out)
+        if label_List is not None:
+            self.embedding_Value = Embedding_Value(result, label_List)
+        return result

@@ -225,6 +225,8 @@ SIGNATURES = {
     "mstts_skinny_bwd_bf16": (i32, [vp, i64, vp, vp, i64, i64, i64, i64, i32, vp]),
     "mstts_ge2e_ws_floats": (i64, [i64, i64, i64]),
     "mstts_ge2e_loss_fwd_bwd": (i32, [vp, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp]),
+    "mstts_ge2e_contrast_fwd_bwd": (i32, [vp, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp]),
+    "mstts_mel_bank_gather": (i32, [vp, vp, i64, vp, i64, i64, i64, vp, vp, vp]),
     "mstts_wg_overlap_add": (i32, [vp, vp, vp, i64, i64, i64, i64, i64, vp]),
     "mstts_wg_gate": (i32, [vp, i64, vp, i64, i64, vp]),
     "mstts_wg_gate_add": (i32, [vp, i64, vp, vp, i64, i64, vp]),

@@ -3,7 +3,8 @@ Speaker_Embedding/Modules.py:6-98) on the MI355X: dense 80 -> 256, three Zoneout
 two, the last frame l2-normalised per row, scaled-cosine softmax loss against leave-one-out / speaker centroids with trainable
 (weight, bias) = (10, -5), plain TF-Adam (eps 1e-8; the gradient-clipped op of :62-66 is overwritten at :69-72 and never runs),
 learning rate max(exponential_decay, Min).  Python owns buffers and the schedule; arithmetic is libmstts_hip.so
-(mstts_gemm_f32, mstts_lstm_seq_fwd/bwd, mstts_ge2e_loss_fwd_bwd, mstts_adam_tf).
+(mstts_gemm_f32, mstts_lstm_seq_fwd/bwd, mstts_ge2e_loss_fwd_bwd, mstts_adam_tf).  hp.Speaker_Embedding.Train.Loss_Calc_Method
+"Contrast" (Modules.py:93-94) runs mstts_ge2e_contrast_fwd_bwd instead; anything but the two raises, as the reference does.
 """
 from __future__ import annotations
 
@@ -31,9 +32,22 @@ def learning_rate(step):
     return exponential_decay(hp.Speaker_Embedding.Train.Learning_Rate, step)
 
 
+LOSS_CALLS = {"SOFTMAX": "mstts_ge2e_loss_fwd_bwd", "CONTRAST": "mstts_ge2e_contrast_fwd_bwd"}
+
+
+def loss_call(loss_method=None):
+    """Entry point of a Loss_Calc_Method (None: hp.Speaker_Embedding.Train.Loss_Calc_Method), case-insensitive (Modules.py:88-96)."""
+    from . import Hyper_Parameters as hp
+    method = hp.Speaker_Embedding.Train.Loss_Calc_Method if loss_method is None else loss_method
+    if str(method).upper() not in LOSS_CALLS:
+        raise ValueError("Unsupported loss calc method")
+    return LOSS_CALLS[str(method).upper()]
+
+
 class SpeakerTrainEngine(Engine):
-    def __init__(self, dims: Dims = None, device="cuda", seed=1234, values=None, adam=None):
+    def __init__(self, dims: Dims = None, device="cuda", seed=1234, values=None, adam=None, loss_method=None):
         from . import Hyper_Parameters as hp
+        self.loss_call = loss_call(loss_method)
         self.d = dims or Dims()
         self.device = torch.device(device)
         self.seed = seed
@@ -148,7 +162,7 @@ class SpeakerTrainEngine(Engine):
         w.d_out.zero_()
         # loss on the last frame; its gradient lands in the last time row of d_out
         last = (T - 1) * Dm
-        call("mstts_ge2e_loss_fwd_bwd", ptr(w.x[-1], last), T * Dm, S, P_, Dm, ptr(self.wb), ptr(w.out3), ptr(w.d_out, last), T * Dm, ptr(w.loss_ws))
+        call(self.loss_call, ptr(w.x[-1], last), T * Dm, S, P_, Dm, ptr(self.wb), ptr(w.out3), ptr(w.d_out, last), T * Dm, ptr(w.loss_ws))
         d_out = w.d_out
         for i in range(d.spk_lstm_n - 1, -1, -1):
             k, ok = self.P(SPK_CELL % (i, i) + "kernel")

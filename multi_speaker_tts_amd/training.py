@@ -209,7 +209,7 @@ class DropIn:
     """What the drop-in trainer classes share.  The checkpoint file <hp.<HP>.Checkpoint_Path>/<FILE> holds the variables whose names start
     with SCOPE, the Adam slots under `__adam_m__` / `__adam_v__` and the global step under `__global_step__` (Tacotron2.Vocoder_Load and
     Speaker_Embedding_Load read these files).  Train prints the time, the global step and the COLUMNS ((format, result key) pairs) of each
-    step and saves every Checkpoint_Save_Timing steps."""
+    step and saves every Checkpoint_Save_Timing steps; `_after_step(result)` is a class's own per-step hook."""
     HP = FILE = SCOPE = None
     COLUMNS = ()
 
@@ -242,7 +242,9 @@ class DropIn:
         torch.save(state, f)
 
     def _upload(self, a):
-        """A pattern array as a contiguous fp32 tensor on the engine's device."""
+        """A pattern array as a contiguous fp32 tensor on the engine's device (a tensor already there is taken as it is: no host round trip)."""
+        if torch.is_tensor(a):
+            return a.to(self.engine.device, torch.float32).contiguous()
         return torch.as_tensor(np.asarray(a, np.float32)).to(self.engine.device).contiguous()
 
     def Train(self, max_steps=None, pattern_fn=None):
@@ -253,3 +255,7 @@ class DropIn:
                               [fmt.format(r[k]) for fmt, k in self.COLUMNS]))
             if (r["Global_Step"] + 1) % getattr(hp, self.HP).Train.Checkpoint_Save_Timing == 0:
                 self.Save()
+            self._after_step(r)
+
+    def _after_step(self, result):
+        pass
