@@ -841,8 +841,9 @@ int mstts_decoder_train_fwd_persistent(const mstts_decoder_train_desc* d, const 
 int64_t mstts_persist_opk_floats(int64_t S);
 int mstts_persist_unpack_history(const float* opk, const mstts_decoder_train_desc* d, mstts_stream_t s);
 
-/* BPTT through the same S steps.  d_pj [S,B,H+M] holds the projection's input gradient on entry
- * (d_m1 | d_ctx) and is updated in place.  Outputs for the hoisted gradient GEMMs:
+/* BPTT through the same S steps.  d_pj [S,B,H+M] holds the projection's input gradient (d_m1 | d_ctx).  It is an input only: both
+ * mstts_decoder_train_bwd and mstts_decoder_train_bwd_persistent read it and leave it bit-identical (the query path's share of d_m1 and the
+ * next step's share of d_ctx are added on chip or in the workspace, never into d_pj).  Outputs for the hoisted gradient GEMMs:
  *   dg0/dg1 [S,B,4H], dq_hist [S,B,A] (must be zeroed by the caller), de_hist [S,B,T],
  *   d_in0 [parts0,S,B,M+H] = partial slabs of dg0.w0f^T per step (rows of step s are the gradient of in0
  *   slot s; parts0 = mstts_decoder_train_bwd_parts(...); the slabs must be summed by the consumer).

@@ -3,6 +3,8 @@ and _bwd called directly on one engine's descriptors, once as the engine built t
 attention launch, packed BPTT products, query gradient folded into cell 1's pointwise backward) and once on a copy with every optional
 derived-copy pointer nulled (skinny products + pointwise launches, row-major BPTT products).  Same fp32 products in another summation
 order: the bound is the project's figure for that at L <= 20, 5e-5 relative (test_gpu_persist.py::test_persistent_equals_launch_per_step).
+An error both tiers share passes here: each tier on its own against oracle.model.decoder's loop in fp64, per (step, row) slice, is
+tests/test_gpu_decoder_loop_ref.py.
 
 Shapes: the smallest at which the fused tiers exist and both MFMA row tiles are live - the WIDE widths of test_gpu_persist.py (decoder
 1024, memory 768, attention 128), B = 3 (one row tile) and 17 (two), L = 3 ragged - and one MID case (5, 18, 4): fused cells without the

@@ -1,7 +1,9 @@
 """The persistent decoder loop (csrc/persist.hip, mstts_decoder_train_fwd_persistent: all S steps of Modules.py:397-443 in one
 launch) against the launch-per-step loop it replaces (mstts_decoder_train_fwd) on the same engine, inputs and keep-masks: every
-tensor the BPTT reads must agree.  Parity with the oracle at these widths is test_gpu_model.py::test_train_step_parity (its two
-reference-width cases take the persistent path) and tests/test_gpu_depth.py::test_depth_parity_train."""
+tensor the BPTT reads must agree.  Parity of the loop itself with the oracle - every persistent and launch-per-step form on its own against
+oracle.model.decoder's loop in fp64, per (step, row) slice - is tests/test_gpu_decoder_loop_ref.py, the base these comparisons stand on;
+end to end at these widths it is test_gpu_model.py::test_train_step_parity (its two reference-width cases take the persistent path) and
+tests/test_gpu_depth.py::test_depth_parity_train."""
 import numpy as np
 import pytest
 import torch
