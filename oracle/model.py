@@ -521,37 +521,72 @@ def postnet(p, d: Dims, x, training, masks, stats_out=None):
 # --------------------------------------------------------------------------------------------
 # Taco1 mel -> spectrogram, speaker encoder
 # --------------------------------------------------------------------------------------------
-def taco1_convbank(p, d: Dims, x, training, stats_out=None):
-    """ConvBank (Taco1_Mel_to_Spect/Modules.py:8-52; quirks Q12,Q13)."""
+POOL_INJECTED = {"elements": 0, "differ": 0}      # as RELU_INJECTED
+
+
+def pool2_at(y, take_next=None):
+    """max_pooling1d(2, stride 1, 'same') on [B,T,C]: out[t] = max(y[t], y[t+1]), -inf pad on the right.  `take_next` (optional bool tensor of
+    y's shape) fixes which frame every window counts as its maximum - True: t + 1 - like relu_at fixes the side of the ReLU kink: where two
+    neighbouring frames are within rounding distance of each other an fp32 and an fp64 evaluation legitimately choose differently and the
+    gradient moves from one frame to the other.  It may differ from this evaluation's own choice (t + 1 only if strictly larger) only where the
+    two values lie within KINK_BAND of each other (asserted; the last frame has no t + 1), so it cannot hide a wrong pooling."""
+    nxt = torch.cat([y[:, 1:], torch.full_like(y[:, :1], -float("inf"))], dim=1)
+    if take_next is None:
+        return torch.maximum(y, nxt)
+    take_next = torch.as_tensor(take_next).to(torch.bool).reshape(y.shape)
+    differ = take_next != (nxt.detach() > y.detach())
+    POOL_INJECTED["elements"] += int(differ.numel())
+    POOL_INJECTED["differ"] += int(differ.sum())
+    if bool(differ.any()):
+        worst = float((nxt.detach() - y.detach()).abs()[differ].max())
+        assert worst < KINK_BAND, "injected max-pool choice differs outside the kink band: |y[t+1] - y[t]| = %g" % worst
+    return torch.where(take_next, nxt, y)
+
+
+def taco1_convbank(p, d: Dims, x, training, stats_out=None, masks=None, patterns_out=None):
+    """ConvBank (Taco1_Mel_to_Spect/Modules.py:8-52; quirks Q12,Q13).  masks (all optional; nothing given: plain relu / maximum):
+    'relu_bank_%d' (k - 1) and 'relu_p1' [B,T,C] active patterns for relu_at, 'pool_next' [B,T,bank_k bank_ch] for pool2_at.
+    patterns_out: optional dict that receives this evaluation's OWN patterns under those names."""
+    masks = masks or {}
     ys = []
     for k in range(1, d.bank_k + 1):
         sfx = "" if k == 1 else "_%d" % (k - 1)
-        y = torch.relu(conv1d_same(x, p[P_V + "convbank_0/conv1d%s/kernel" % sfx], p[P_V + "convbank_0/conv1d%s/bias" % sfx]))
+        y = relu_at(conv1d_same(x, p[P_V + "convbank_0/conv1d%s/kernel" % sfx], p[P_V + "convbank_0/conv1d%s/bias" % sfx]), masks.get("relu_bank_%d" % (k - 1)))
+        if patterns_out is not None:
+            patterns_out["relu_bank_%d" % (k - 1)] = y.detach() > 0
         ys.append(batch_norm(y, p, P_V + "convbank_0/batch_normalization%s/" % sfx, training, stats_out))
     y = torch.cat(ys, dim=2)
     # max_pooling1d(2, stride 1, 'same'): out[t] = max(y[t], y[t+1]), -inf pad on the right
-    y = torch.maximum(y, torch.cat([y[:, 1:], torch.full_like(y[:, :1], -float("inf"))], dim=1))
-    y = torch.relu(conv1d_same(y, p[P_V + "convbank_0/conv1d_8/kernel"], p[P_V + "convbank_0/conv1d_8/bias"]))
+    if patterns_out is not None:
+        patterns_out["pool_next"] = torch.cat([y.detach()[:, 1:] > y.detach()[:, :-1], torch.zeros_like(y[:, :1], dtype=torch.bool)], dim=1)
+    y = pool2_at(y, masks.get("pool_next"))
+    y = relu_at(conv1d_same(y, p[P_V + "convbank_0/conv1d_8/kernel"], p[P_V + "convbank_0/conv1d_8/bias"]), masks.get("relu_p1"))
+    if patterns_out is not None:
+        patterns_out["relu_p1"] = y.detach() > 0
     y = batch_norm(y, p, P_V + "convbank_0/batch_normalization_8/", training, stats_out)
     y = conv1d_same(y, p[P_V + "convbank_0/conv1d_9/kernel"], p[P_V + "convbank_0/conv1d_9/bias"])
     y = batch_norm(y, p, P_V + "convbank_0/batch_normalization_9/", training, stats_out)
     return x + y
 
 
-def taco1_highway(p, d: Dims, x):
-    """Highway (Taco1_Mel_to_Spect/Modules.py:54-72)."""
+def taco1_highway(p, d: Dims, x, masks=None, patterns_out=None):
+    """Highway (Taco1_Mel_to_Spect/Modules.py:54-72).  masks: optional 'relu_hw_%d' active patterns for relu_at; patterns_out as taco1_convbank's."""
+    masks = masks or {}
     for i in range(d.highway_n):
         pre = P_V + "highway_%d/" % i
-        Hh = torch.relu(x @ p[pre + "dense/kernel"] + p[pre + "dense/bias"])
+        Hh = relu_at(x @ p[pre + "dense/kernel"] + p[pre + "dense/bias"], masks.get("relu_hw_%d" % i))
+        if patterns_out is not None:
+            patterns_out["relu_hw_%d" % i] = Hh.detach() > 0
         Tt = torch.sigmoid(x @ p[pre + "dense_1/kernel"] + p[pre + "dense_1/bias"])
         x = Hh * Tt + x * (1.0 - Tt)
     return x
 
 
-def taco1_forward(p, d: Dims, mel, training, masks=None, stats_out=None):
-    """ConvBank -> Highway -> BiRNN -> Projection as wired at MSTTS_SV.py:100-115."""
+def taco1_forward(p, d: Dims, mel, training, masks=None, stats_out=None, patterns_out=None):
+    """ConvBank -> Highway -> BiRNN -> Projection as wired at MSTTS_SV.py:100-115.  masks: the zoneout keep-masks 'v_zc_fw' ... and, optionally,
+    the kink patterns of taco1_convbank / taco1_highway (injected by the parity tests of the long-sequence cases)."""
     masks = masks or {}
-    x = taco1_highway(p, d, taco1_convbank(p, d, mel, training, stats_out))
+    x = taco1_highway(p, d, taco1_convbank(p, d, mel, training, stats_out, masks, patterns_out), masks, patterns_out)
     outs = []
     for dr in ("fw", "bw"):
         pre = P_V + "birnn/stack_bidirectional_rnn/cell_0/bidirectional_rnn/%s/zoneout_lstm_cell/" % dr

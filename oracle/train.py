@@ -202,14 +202,15 @@ def taco1_in_weight_reg(name):
 def taco1_train_step(params, opt_state, d, mel, spectrogram, masks, global_step, dtype=torch.float64, wr_rate=1e-6,
                      lr_kw=None, return_grads=False):
     """One Mel_to_Spect.Train iteration: loss = mean|pred - spectrogram| (tf.losses.absolute_difference, :58) + wr_rate * sum
-    l2_loss; TF-Adam (eps 1e-6) with the :63-69 learning-rate schedule; BN moving statistics ride along (UPDATE_OPS :80)."""
+    l2_loss; TF-Adam (eps 1e-6) with the :63-69 learning-rate schedule; BN moving statistics ride along (UPDATE_OPS :80).  masks: the zoneout
+    keep-masks and, optionally, the kink patterns of model.taco1_forward and 'l1_sign' (the sign pattern of pred - spectrogram for abs_at)."""
     p = {k: (v.detach().clone().to(dtype) if torch.is_tensor(v) else torch.tensor(np.asarray(v), dtype=dtype)) for k, v in params.items()}
     names = [k for k in p if k.startswith(M.P_V) and not k.endswith(("moving_mean", "moving_variance"))]
     for k in names:
         p[k].requires_grad_(True)
     stats = {}
     pred = M.taco1_forward(p, d, mel.to(dtype), True, masks, stats)
-    l1 = (pred - spectrogram.to(dtype)).abs().mean()
+    l1 = abs_at(pred - spectrogram.to(dtype), masks.get("l1_sign") if masks else None).mean()
     wr = wr_rate * sum(0.5 * (p[k] ** 2).sum() for k in names if taco1_in_weight_reg(k))
     loss = l1 + wr
     grads = dict(zip(names, torch.autograd.grad(loss, [p[k] for k in names])))

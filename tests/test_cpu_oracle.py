@@ -242,3 +242,95 @@ def test_bf16_emulation_sensitivity():
         OM.RECURRENT_BF16 = OM.GEMM_BF16 = False
     assert moved[False][0] < 1e-4 and moved[False][1] < 1e-3          # exact arithmetic: smooth
     assert moved[True][0] > 1e-3 and moved[True][1] > 5e-3            # emulated bf16: the rounding flips dominate
+
+
+def _taco1_forward_before_injection(p, d, mel, masks, stats):
+    """oracle.model.taco1_forward(training=True) as it read before the kink patterns could be injected: plain torch.relu, torch.maximum and
+    (in the caller) abs - kept here so that 'nothing injected' can be held to it bit for bit."""
+    V = OM.P_V
+    ys = []
+    for k in range(1, d.bank_k + 1):
+        sfx = "" if k == 1 else "_%d" % (k - 1)
+        y = torch.relu(OM.conv1d_same(mel, p[V + "convbank_0/conv1d%s/kernel" % sfx], p[V + "convbank_0/conv1d%s/bias" % sfx]))
+        ys.append(OM.batch_norm(y, p, V + "convbank_0/batch_normalization%s/" % sfx, True, stats))
+    y = torch.cat(ys, dim=2)
+    y = torch.maximum(y, torch.cat([y[:, 1:], torch.full_like(y[:, :1], -float("inf"))], dim=1))
+    y = torch.relu(OM.conv1d_same(y, p[V + "convbank_0/conv1d_8/kernel"], p[V + "convbank_0/conv1d_8/bias"]))
+    y = OM.batch_norm(y, p, V + "convbank_0/batch_normalization_8/", True, stats)
+    y = OM.conv1d_same(y, p[V + "convbank_0/conv1d_9/kernel"], p[V + "convbank_0/conv1d_9/bias"])
+    x = mel + OM.batch_norm(y, p, V + "convbank_0/batch_normalization_9/", True, stats)
+    for i in range(d.highway_n):
+        pre = V + "highway_%d/" % i
+        Hh = torch.relu(x @ p[pre + "dense/kernel"] + p[pre + "dense/bias"])
+        Tt = torch.sigmoid(x @ p[pre + "dense_1/kernel"] + p[pre + "dense_1/bias"])
+        x = Hh * Tt + x * (1.0 - Tt)
+    outs = []
+    for dr in ("fw", "bw"):
+        pre = V + "birnn/stack_bidirectional_rnn/cell_0/bidirectional_rnn/%s/zoneout_lstm_cell/" % dr
+        outs.append(OM.run_lstm(x, None, p[pre + "kernel"], p[pre + "bias"], d.birnn, masks["v_zc_" + dr], masks["v_zh_" + dr], d.zoneout, True, reverse=(dr == "bw")))
+    return torch.cat(outs, dim=2) @ p[V + "dense/kernel"] + p[V + "dense/bias"]
+
+
+def test_taco1_oracle_without_injection_is_unchanged():
+    """With no kink pattern given, the Taco1 path (prediction, loss, every gradient, BN statistics) is bit-identical to its earlier statement."""
+    from tests.helpers import taco1_problem, taco1_zoneout_masks
+    B, S = 3, 11
+    _, od, values, mel, spec, g = taco1_problem(B, S, dict(n_mel=80, bank_ch=8, proj1_ch=16, birnn=8, n_spec=20))
+    masks = taco1_zoneout_masks(g, B, S, od)
+    counts = [dict(c) for c in (OM.RELU_INJECTED, OM.POOL_INJECTED, OT.L1_INJECTED)]
+    new_p, _, sc, grads, pred = OT.taco1_train_step(values, None, od, torch.tensor(mel), torch.tensor(spec), masks, 0, return_grads=True)
+    assert counts == [OM.RELU_INJECTED, OM.POOL_INJECTED, OT.L1_INJECTED]                   # nothing went through an injected pattern
+    p = {k: torch.tensor(np.asarray(v), dtype=torch.float64) for k, v in values.items()}
+    names = [k for k in p if k.startswith(OM.P_V) and not k.endswith(("moving_mean", "moving_variance"))]
+    for k in names:
+        p[k].requires_grad_(True)
+    stats = {}
+    pred0 = _taco1_forward_before_injection(p, od, torch.tensor(mel).double(), masks, stats)
+    l1 = (pred0 - torch.tensor(spec).double()).abs().mean()
+    loss = l1 + 1e-6 * sum(0.5 * (p[k] ** 2).sum() for k in names if OT.taco1_in_weight_reg(k))
+    g0 = dict(zip(names, torch.autograd.grad(loss, [p[k] for k in names])))
+    assert torch.equal(pred, pred0.detach()) and sc["Loss"] == float(loss.detach()) and sc["L1_Loss"] == float(l1.detach())
+    assert set(g0) == set(grads) and all(torch.equal(grads[k], g0[k]) for k in g0)
+    assert stats and all(torch.equal(new_p[k], stats[k]) for k in stats)
+
+
+def test_taco1_float32_patterns_stay_inside_the_kink_bands():
+    """The S = 33 parity case of tests/test_gpu_taco1_trainer.py: the kink patterns of the oracle's own float32 evaluation - a correct fp32
+    implementation - injected into its fp64 one are accepted (relu_at, pool2_at and abs_at assert KINK_BAND / L1_KINK_BAND), and with them the
+    fp32 autograd gradients agree with the fp64 ones at the tolerance the GPU test holds the engine to: the inputs of the case respect the bands."""
+    from tests.helpers import TACO1_LONG, rel_err, taco1_problem, taco1_zoneout_masks
+    B, S, kw = TACO1_LONG[0]
+    assert S == 33
+    _, od, values, mel, spec, g = taco1_problem(B, S, kw)
+    masks = taco1_zoneout_masks(g, B, S, od)
+    p32 = {k: torch.tensor(np.asarray(v), dtype=torch.float32) for k, v in values.items()}
+    pat = {}
+    with torch.no_grad():
+        pred32 = OM.taco1_forward(p32, od, torch.tensor(mel), True, masks, {}, patterns_out=pat)
+    pat["l1_sign"] = torch.sign(pred32 - torch.tensor(spec))
+    assert set(pat) == {"relu_bank_%d" % k for k in range(od.bank_k)} | {"relu_hw_%d" % i for i in range(od.highway_n)} | {"relu_p1", "pool_next", "l1_sign"}
+    assert not pat["pool_next"][:, -1].any() and pat["pool_next"].any()
+    before = [dict(c) for c in (OM.RELU_INJECTED, OM.POOL_INJECTED, OT.L1_INJECTED)]
+    _, _, sc, grads, pred = OT.taco1_train_step(values, None, od, torch.tensor(mel), torch.tensor(spec), dict(masks, **pat), 0, return_grads=True)
+    n_relu = sum(int(pat[k].numel()) for k in pat if k.startswith("relu"))
+    for c, b0, n in zip((OM.RELU_INJECTED, OM.POOL_INJECTED, OT.L1_INJECTED), before, (n_relu, int(pat["pool_next"].numel()), int(pat["l1_sign"].numel()))):
+        assert c["elements"] - b0["elements"] == n and c["differ"] - b0["differ"] <= n // 1000           # every element went through; a handful differ
+    assert rel_err(pred32.numpy(), pred.numpy()) < 1e-3
+    _, _, sc32, g32, _ = OT.taco1_train_step(values, None, od, torch.tensor(mel), torch.tensor(spec), dict(masks, **pat), 0, dtype=torch.float32, return_grads=True)
+    bad = [(k, rel_err(g32[k].numpy(), grads[k].numpy())) for k in grads if grads[k].abs().max() > 1e-9 and rel_err(g32[k].numpy(), grads[k].numpy()) > 5e-3]
+    assert not bad, bad
+    # a pattern from outside the bands is refused: a ReLU unit switched on at a clearly negative pre-activation, a pooling window sent to the smaller frame
+    wrong = dict(masks, **pat)
+    wrong["relu_p1"] = torch.ones_like(pat["relu_p1"])
+    try:
+        OT.taco1_train_step(values, None, od, torch.tensor(mel), torch.tensor(spec), wrong, 0)
+        raise RuntimeError("accepted")
+    except AssertionError as e:
+        assert "kink band" in str(e)
+    wrong = dict(masks, **pat)
+    wrong["pool_next"] = ~pat["pool_next"]
+    try:
+        OT.taco1_train_step(values, None, od, torch.tensor(mel), torch.tensor(spec), wrong, 0)
+        raise RuntimeError("accepted")
+    except AssertionError as e:
+        assert "kink band" in str(e)

@@ -6,7 +6,7 @@ import torch
 from multi_speaker_tts_amd import lib
 from multi_speaker_tts_amd.taco1_trainer import Taco1TrainEngine
 from oracle import model as OM, train as OT
-from tests.helpers import dims_pair, rel_err, t2n
+from tests.helpers import TACO1_LONG, rel_err, t2n, taco1_problem, taco1_zoneout_masks
 
 pytestmark = pytest.mark.gpu
 
@@ -43,34 +43,59 @@ def test_small_backward_kernels(dev):
     assert abs(float(loss) - float((p - t).abs().mean())) < 1e-6 and rel_err(t2n(dp), t2n(torch.sign(p - t) / 5000)) < 1e-6
 
 
-@pytest.mark.parametrize("B,S,kw", [(3, 11, {}), (4, 23, dict(bank_ch=16, proj1_ch=32, birnn=16, n_spec=40)), (2, 9, dict(n_mel=80, bank_ch=32, proj1_ch=64, birnn=32, n_spec=129))])
+def _engine_patterns(eng, w, spec, od):
+    """The kink patterns of the engine's step, from its stored tensors, under the names oracle.model.taco1_forward / oracle.train.taco1_train_step
+    take them: ReLU active sets (w.bank_a and w.p1_a hold the ReLU's output, w.hh the highway's pre-activation), the max-pool's choice between
+    frame t and t + 1 (mstts_maxpool2_same_bwd: t + 1 only if strictly larger; w.cat is the tensor it pools) and the L1 sign (mstts_l1_loss_fwd_bwd
+    forms pred - spectrogram from the stored fp32 tensors: one exact fp32 subtraction)."""
+    B, S = w.B, w.S
+    m = {"relu_bank_%d" % k: (w.bank_a[k] > 0).reshape(B, S, -1).cpu() for k in range(od.bank_k)}
+    m["relu_p1"] = (w.p1_a > 0).reshape(B, S, -1).cpu()
+    for i in range(od.highway_n):
+        m["relu_hw_%d" % i] = (w.hh[i] > 0).reshape(B, S, -1).cpu()
+    cat = w.cat.reshape(B, S, -1)
+    m["pool_next"] = torch.cat([cat[:, 1:] > cat[:, :-1], torch.zeros_like(cat[:, :1], dtype=torch.bool)], dim=1).cpu()
+    m["l1_sign"] = torch.sign(w.pred.reshape(B, S, -1) - spec).cpu()
+    return m
+
+
+@pytest.mark.parametrize("B,S,kw", [(3, 11, {}), (4, 23, dict(bank_ch=16, proj1_ch=32, birnn=16, n_spec=40)), (2, 9, dict(n_mel=80, bank_ch=32, proj1_ch=64, birnn=32, n_spec=129))] + TACO1_LONG)
 def test_taco1_train_step_parity(dev, B, S, kw):
-    """Forward, loss, every gradient, parameters after TF-Adam and the BN moving statistics of one trainer step, then a second step."""
-    pd, od = dims_pair(**kw)
-    values = OM.init_params(od, 5)
-    g = np.random.default_rng(6)
-    for k in values:
-        if k.startswith(OM.P_V) and k.endswith(("bias", "beta")) and "highway" not in k:
-            values[k] = g.normal(0, 0.1, values[k].shape)
-        if k.startswith(OM.P_V) and k.endswith("moving_variance"):
-            values[k] = 0.5 + np.abs(g.normal(0, 0.5, values[k].shape))
-    mel = np.clip(g.normal(0, 1.5, (B, S, od.n_mel)), -4, 4).astype(np.float32)
-    spec = g.uniform(0, 1, (B, S, od.n_spec)).astype(np.float32)
+    """Forward, loss, every gradient, parameters after TF-Adam and the BN moving statistics of one trainer step, then a second step.  The
+    TACO1_LONG cases - every convolution on the kernels long sequences reach; the reference's CBHG widths - hand the oracle the engine's kink
+    patterns (ReLU sides, max-pool choices, L1 signs), which it accepts only inside KINK_BAND / L1_KINK_BAND; the short cases inject nothing."""
+    inject = (B, S, kw) in TACO1_LONG
+    pd, od, values, mel, spec, g = taco1_problem(B, S, kw)
     eng = Taco1TrainEngine(pd, device=dev, values=values)
     params, opt = values, None
     for step in range(2):
-        masks = {k: torch.tensor(g.integers(0, 2, (S, B, od.birnn)).astype(np.uint8)) for k in ("v_zc_fw", "v_zh_fw", "v_zc_bw", "v_zh_bw")}
-        params, opt, sc, grads, pred = OT.taco1_train_step(params, opt, od, torch.tensor(mel), torch.tensor(spec), masks, step, return_grads=True)
+        masks = taco1_zoneout_masks(g, B, S, od)
         w = eng.plan(B, S)
         eng.forward(torch.tensor(mel, device=dev), w, masks={k: v.numpy() for k, v in masks.items()})
         eng.loss_and_backward(w, torch.tensor(spec, device=dev))
+        omasks = dict(masks)
+        if inject:
+            seen = [dict(c) for c in (OM.RELU_INJECTED, OM.POOL_INJECTED, OT.L1_INJECTED)]
+            omasks.update(_engine_patterns(eng, w, torch.tensor(spec, device=dev), od))
+        params, opt, sc, grads, pred = OT.taco1_train_step(params, opt, od, torch.tensor(mel), torch.tensor(spec), omasks, step, return_grads=True)
+        if inject:
+            now_ = (OM.RELU_INJECTED, OM.POOL_INJECTED, OT.L1_INJECTED)
+            print("step %d: injected elements / of them on the other side of the kink than the oracle's own: %s" % (
+                step, "  ".join("%s %d / %d" % (n, c["elements"] - s0["elements"], c["differ"] - s0["differ"]) for n, c, s0 in zip(("relu", "pool", "l1"), now_, seen))))
+            assert all(c["elements"] > s0["elements"] for c, s0 in zip(now_, seen))
         got = eng.scalars(w)
         assert rel_err(t2n(w.pred).reshape(B, S, -1), t2n(pred)) < 1e-3
         assert abs(got["Loss"] - sc["Loss"]) < 1e-4 * max(1.0, abs(sc["Loss"])) and abs(got["Weight_Regularization_Loss"] - sc["Weight_Regularization_Loss"]) < 1e-6
-        gexp = eng.params.export(grads=True)
+        # the engine adds the regulariser's gradient inside Adam, the oracle's loss contains the regulariser: add wr_rate x the variable to the
+        # engine's gradient for the comparison, as test_gpu_model.py does.  (Left out, that term IS the difference wherever the L1 gradient is
+        # small: at the reference widths the mean runs over 198 850 terms, a batch-norm gamma's gradient is 2.5e-5 at most and 1e-6 x gamma =
+        # 1e-6 of it reads as an error of 4e-2, a kernel's 1e-6 x 0.15 against 1.5e-4 as 1e-3 - while every bias gradient agrees to 1e-6.)
+        gexp, held = eng.params.export(grads=True), eng.params.export()
+        gexp = {k: v.astype(np.float64) + (eng.wr_rate * held[k].astype(np.float64) if OT.taco1_in_weight_reg(k) else 0.0) for k, v in gexp.items() if k in grads}
         def gerr(k):          # conv1d_9/bias feeds a BatchNorm directly: its true gradient is exactly zero -> absolute test
             ref = t2n(grads[k])
             return rel_err(gexp[k], ref) if np.abs(ref).max() > 1e-9 else float(np.abs(gexp[k]).max() > 1e-5)
+        print("step %d: worst gradient error %.2e (%s)" % ((step,) + max((gerr(k), k) for k in grads)))
         bad = [(k, gerr(k)) for k in grads if gerr(k) > 5e-3]
         assert not bad, bad
         eng.adam_step()
