@@ -886,7 +886,11 @@ typedef struct {
     const float* w0f; const float* w1; const float* b1; const float* wq;
     const float* wproj; const float* bproj; /* [H+M, n_mel+1], [n_mel+1] */
     float zoneout;
-    float* in0; float* in1; float* pj;      /* [2,B,P+M+H] (the generic path uses [2,B,M+H] of it), [2,B,2H], [B,H+M] */
+    /* in0: 2 B (P+M+H) floats.  Weight-streaming path: [2,B,P+M+H], rows [prenet | ctx | h0].  Generic path: its first 2 B (M+H) floats
+     * as [2,B,M+H], rows [ctx | h0].  in1 [2,B,2H], rows [m0 | h1]; pj [B,H+M], rows [m1 | ctx] of the last step run (one slot).
+     * After steps 0 .. n-1 the states are in slot n & 1 of in0, in1, c0, c1, cum - row-major on every path, the fused cell steps'
+     * packed copies (act_p) being extra (tests/test_gpu_decoder_infer_ref.py reads them there). */
+    float* in0; float* in1; float* pj;
     float* c0; float* c1;                   /* [2,B,H] */
     float* cum;                             /* [2,B,T] */
     float* pre_ws;                          /* mstts_decoder_infer_ws_floats(...) floats, 8-byte aligned */

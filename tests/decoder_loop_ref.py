@@ -35,6 +35,9 @@ WIDTHS = {
     "defaults": dict(dec_lstm=32, enc_lstm=16, spk=16, prenet=16),
     "MID": dict(dec_lstm=64, enc_lstm=32, spk=64, prenet=32),
     "WIDE": dict(dec_lstm=1024, enc_lstm=256, spk=256, prenet=256),
+    # tests/decoder_infer_ref.py only: MID's cells with a prenet of 64, the narrowest the free-running driver's weight-streaming path takes
+    # (the name sorts last: the draws of the three above stay what they were)
+    "h64_p64": dict(dec_lstm=64, enc_lstm=32, spk=64, prenet=64),
 }
 # S counts decoder steps.  Row 0 has token length Te, row 1 length 1 (a softmax over one position: d_e = 0), the others anything in 1..Te.
 CASES = {
