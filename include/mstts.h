@@ -768,7 +768,13 @@ typedef struct {
     /* optional bf16 mode of the recurrent products (BASELINE config 3): packed bf16 copies of w0f / w1 / wq made with
      * mstts_pack_bf16_fwd (first three) and mstts_pack_bf16_bwd (last three) using the split counts of
      * mstts_decoder_bf16_splits(H, M, A, out[6]); all six non-NULL -> cell / query products and their data gradients run
-     * as bf(X).bf(W) with fp32 accumulation, everything else stays fp32 */
+     * as bf(X).bf(W) with fp32 accumulation, everything else stays fp32.
+     * ROUNDED (to nearest even, on the way into the product, never in memory): the rows in0[s] / in1[s] / the m1 columns of pj[s] and
+     * the kernels (forward); the gate gradients dg0[s] / dg1[s], the query gradient dq_hist[s] and the kernels (data gradients).
+     * NOT rounded: xw0, b1, the cell states, everything of the attention step.  The stored histories (in0, in1, pj, c0 / c1, acts, craw,
+     * q_hist, align_hist, cum_hist) and gradients (dg0, dg1, dq_hist, de_hist, d_in0) are the UNROUNDED fp32 values - the very arrays the
+     * products round - and the caller's weight-gradient GEMMs read them as such.  tests/test_gpu_decoder_bf16_ref.py holds every stage of
+     * every step to this statement, evaluated in fp64 from the stored arrays. */
     const void* bf_w0f_f; const void* bf_w1_f; const void* bf_wq_f; const void* bf_w0f_b; const void* bf_w1_b; const void* bf_wq_b;
     /* optional fused cell steps (fp32): w0f / w1 packed by mstts_pack_cell_fwd; both non-NULL and
      * mstts_cell_fwd_supported(H, M+H) && (H, 2H) -> each cell is one mstts_cell_fwd launch instead of product + pointwise */
@@ -830,6 +836,14 @@ typedef struct {
                                      data-gradient products take their operands rounded to bf16 (round to nearest even; the kernels when they are loaded into
                                      registers, the activations / gate gradients when they are staged) and run on v_mfma_f32_16x16x32_bf16 with fp32 accumulators;
                                      states, gates, softmax, histories and everything exchanged stay fp32.  The forward launch needs pre / b0 in this mode.
+                                     Rounded operands: pre[s], in0[s], in1[s], the m1 columns of pj[s] (forward); dg0[s], dg1[s], dq_hist[s] (BPTT); b0 and
+                                     b1 are added unrounded.  What is stored - in the row-major tensors and in opk - is the unrounded fp32 value of each,
+                                     the same contract as the bf_* copies of mstts_decoder_train_desc, with ONE difference: every operand but pre and
+                                     dq_hist reaches its product through a ring, and what is rounded is the copy that arrived - the stored value with the
+                                     ring slot's generation, (step >> 2) & 1 counted from the launch's first step, in its last mantissa bit
+                                     (csrc/persist_common.h).  A stored value within one fp32 ulp of a bf16 rounding boundary (2^-17 of all elements)
+                                     therefore rounds the other way than bf(stored value).  tests/test_gpu_decoder_bf16_ref.py holds both launches to
+                                     this statement stage by stage.
                                      (Round 4 had a software-pipelined schedule selector in this slot: removed, tools/persist_pipe.inc.) */
 } mstts_persist_desc;
 int32_t mstts_persist_fwd_supported(int64_t B, int64_t H, int64_t M, int64_t A, int64_t T, int64_t KS);

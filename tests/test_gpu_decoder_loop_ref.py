@@ -9,7 +9,8 @@ loop written out around zoneout_lstm_cell and lsa_step, gradients by autograd), 
     persistent, pre + opk     the same launch forming the prenet rows' product itself (pre / b0) and packing the cell operands (opk), then
                               mstts_persist_unpack_history, then mstts_decoder_train_bwd_persistent behind it (its first d_in0 slab carries only
                               the context columns of slots 1 .. S-1: exactly those are compared)
-This is the base the "A equals B" comparisons of test_gpu_loop_tiers.py and test_gpu_persist.py stand on.  bf16 forms are out of scope.
+This is the base the "A equals B" comparisons of test_gpu_loop_tiers.py and test_gpu_persist.py stand on.  The bf16 forms of the same drivers
+are held stage by stage to the same oracle in tests/test_gpu_decoder_bf16_ref.py, which builds its descriptors with the helpers below.
 
 Inputs: the descriptors are built by hand from the case data of tests/decoder_loop_ref.py (packs through mstts_pack_cell_fwd,
 mstts_pack_skinny_bwd, mstts_transpose01, mstts_persist_pack, mstts_persist_bwd_pack, mstts_lsa_fold_location, mstts_lsa_filter_by_unit, as
@@ -104,9 +105,38 @@ def wcache():
     cache.clear()
 
 
-def _weights(dev, cache, widths):
-    """The variables of a set of widths on the device with every derived copy engine.py makes of them (refresh_derived, _ensure_fallback_packs)."""
+BF_COPIES = ("w0f_f", "w1_f", "wq_f", "w0f_b", "w1_b", "wq_b")
+
+
+def _bf16_copies(dev, w, widths):
+    """The bf16 copies engine.py makes for recurrent_dtype "bf16": the six mstts_pack_bf16_fwd / _bwd copies with the counts of
+    mstts_decoder_bf16_splits (where it admits the widths; zero-filled buffers where it does not - a driver that read them would multiply
+    zeros) and the mstts_pack_cell_fwd_bf16 copies of the fused bf16 cell steps where both cells are supported."""
+    L = lib.load()
+    dm = R.dims_of(widths)
+    H, M = dm["H"], dm["M"]
+    sp = (C.c_int32 * 6)()
+    w["bf_ok"], w["bf_splits"] = bool(L.mstts_decoder_bf16_splits(H, M, A, sp)), list(sp)
+    i16 = lambda n: torch.zeros(n, dtype=torch.int16, device=dev)
+    w["bf"] = {k: i16(n) for k, n in zip(BF_COPIES, ((M + H) * 4 * H, 2 * H * 4 * H, H * A) * 2)}
+    if w["bf_ok"]:
+        for i, (k, src, ld, rows, cols) in enumerate((("w0f_f", "w0f", 4 * H, M + H, 4 * H), ("w1_f", "w1", 4 * H, 2 * H, 4 * H), ("wq_f", "wq", A, H, A),
+                                                      ("w0f_b", "w0f", 4 * H, M + H, 4 * H), ("w1_b", "w1", 4 * H, 2 * H, 4 * H), ("wq_b", "wq", A, H, A))):
+            lib.call("mstts_pack_bf16_fwd" if i < 3 else "mstts_pack_bf16_bwd", lib.ptr(w[src]), ld, lib.ptr(w["bf"][k]), rows, cols, w["bf_splits"][i])
+    w["w0p16"] = w["w1p16"] = None
+    if L.mstts_cell_fwd_bf16_supported(H, M + H) and L.mstts_cell_fwd_bf16_supported(H, 2 * H):
+        w["w0p16"], w["w1p16"] = i16((M + H) * 4 * H), i16(2 * H * 4 * H)
+        lib.call("mstts_pack_cell_fwd_bf16", lib.ptr(w["w0f"]), 4 * H, lib.ptr(w["w0p16"]), M + H, H)
+        lib.call("mstts_pack_cell_fwd_bf16", lib.ptr(w["w1"]), 4 * H, lib.ptr(w["w1p16"]), 2 * H, H)
+    torch.cuda.synchronize()
+
+
+def _weights(dev, cache, widths, bf16=False):
+    """The variables of a set of widths on the device with every derived copy engine.py makes of them (refresh_derived, _ensure_fallback_packs);
+    bf16: also the copies of its config-3 mode (_bf16_copies)."""
     if widths in cache:
+        if bf16 and "bf" not in cache[widths]:
+            _bf16_copies(dev, cache[widths], widths)
         return cache[widths]
     L = lib.load()
     dm = R.dims_of(widths)
@@ -140,6 +170,8 @@ def _weights(dev, cache, widths):
         w["pkb"] = [f(int(L.mstts_persist_bwd_pack_floats(i))) for i in range(3)]
         lib.call("mstts_persist_bwd_pack", lib.ptr(w["w0f"]), lib.ptr(w["w1"]), lib.ptr(w["wq"]), *(lib.ptr(t) for t in w["pkb"]))
     torch.cuda.synchronize()
+    if bf16:
+        _bf16_copies(dev, w, widths)
     cache[widths] = w
     return w
 
@@ -148,10 +180,11 @@ def _upload(dev, cd):
     return {k: cd[k].to(dev).contiguous() for k in ("keys", "values", "lens", "xw0", "pre", "d_pj") + R.MASKS}
 
 
-def _fwd_desc(dev, cd, w, u, tier, packed=False):
+def _fwd_desc(dev, cd, w, u, tier, packed=False, bf16=None):
     """A forward descriptor with output buffers of its own.  tier: "full" (every derived copy engine.py passes), "nulled", "persistent" (the
     launch-per-step path's packed blocks and workspaces are not touched: none given).  Buffers written in full are NaN-filled; in1's slot S
-    has no m0 half and, in the packed persistent form, c0 / c1 have no slot S (decoder_loop_ref.exclude_unwritten): zeroed, as engine.py does."""
+    has no m0 half and, in the packed persistent form, c0 / c1 have no slot S (decoder_loop_ref.exclude_unwritten): zeroed, as engine.py does.
+    bf16 (w from _weights(bf16=True)): "products" = the six bf_* copies, "full" = also the packed bf16 cell kernels where there are any."""
     B, T, S, H, M, P = cd["B"], cd["Te"], cd["S"], cd["H"], cd["M"], cd["P"]
     L = lib.load()
     t = dict(in0=_nan(dev, S + 1, B, M + H), in1=_nan(dev, S + 1, B, 2 * H), pj=_nan(dev, S, B, H + M), c0=_nan(dev, S + 1, B, H), c1=_nan(dev, S + 1, B, H),
@@ -189,6 +222,11 @@ def _fwd_desc(dev, cd, w, u, tier, packed=False):
             d.w0p, d.w1p, d.act_p = lib.ptr(w["w0p"]), lib.ptr(w["w1p"]), lib.ptr(t["act_p"])
     if tier == "nulled":
         assert not any(getattr(d, k) for k in NULLED) and not d.lsa.loc_kt
+    if bf16:
+        for k in BF_COPIES:
+            setattr(d, "bf_" + k, lib.ptr(w["bf"][k]))
+        if bf16 == "full" and w["w0p16"] is not None:
+            d.w0p16, d.w1p16 = lib.ptr(w["w0p16"]), lib.ptr(w["w1p16"])
     return d, t
 
 
@@ -287,6 +325,22 @@ def test_launch_per_step_forms_against_the_oracle(dev, wcache, name):
     assert not failures, failures
 
 
+def _pdesc(dev, packs, xch_bytes, recurrent_bf16=0):
+    """A persistent-launch descriptor with an exchange buffer and control words of its own; opk / pre / b0 are the caller's to set."""
+    t = dict(xch=_zeros(dev, xch_bytes // 4), ctrl=torch.zeros(272, dtype=torch.int32, device=dev))
+    p = lib.PersistDesc()
+    p.w0pk, p.w1pk, p.wqpk, p.xch, p.ctrl = lib.ptr(packs[0]), lib.ptr(packs[1]), lib.ptr(packs[2]), lib.ptr(t["xch"]), lib.ptr(t["ctrl"])
+    p.stamps, p.opk, p.pre, p.b0 = None, None, None, None
+    p.selftest_fail_step, p.near_xcd, p.recurrent_bf16 = 0, near_xcd(), recurrent_bf16
+    return p, t
+
+
+def _ran_to_its_end(t, what):
+    torch.cuda.synchronize()
+    c = t["ctrl"].cpu().numpy()
+    assert c[1] == 0 and c[2] == 256, (what, c[:4])
+
+
 @pytest.mark.parametrize("name", [n for n in R.CASES if R.CASES[n]["widths"] == "WIDE"])
 def test_persistent_forms_against_the_oracle(dev, wcache, name):
     cd = R.case_data(name)
@@ -296,20 +350,8 @@ def test_persistent_forms_against_the_oracle(dev, wcache, name):
         pytest.skip("persistent loop not available on this device (needs 256 CUs and one workgroup per CU)")
     w, u = _weights(dev, wcache, cd["widths"]), _upload(dev, cd)
     failures = []
-
-    def pdesc(packs, xch_bytes):
-        t = dict(xch=_zeros(dev, xch_bytes // 4), ctrl=torch.zeros(272, dtype=torch.int32, device=dev))
-        p = lib.PersistDesc()
-        p.w0pk, p.w1pk, p.wqpk, p.xch, p.ctrl = lib.ptr(packs[0]), lib.ptr(packs[1]), lib.ptr(packs[2]), lib.ptr(t["xch"]), lib.ptr(t["ctrl"])
-        p.stamps, p.opk, p.pre, p.b0 = None, None, None, None
-        p.selftest_fail_step, p.near_xcd, p.recurrent_bf16 = 0, near_xcd(), 0
-        return p, t
-
-    def ran_to_its_end(t, what):
-        torch.cuda.synchronize()
-        c = t["ctrl"].cpu().numpy()
-        assert c[1] == 0 and c[2] == 256, (what, c[:4])
-
+    pdesc = lambda packs, xch_bytes: _pdesc(dev, packs, xch_bytes)
+    ran_to_its_end = _ran_to_its_end
     # ---- forward reading xw0, row-major histories
     d, f = _fwd_desc(dev, cd, w, u, "persistent")
     p, pt = pdesc(w["pk"], int(L.mstts_persist_fwd_ws_bytes()))

@@ -436,7 +436,10 @@ def test_persistent_bf16_equals_launch_per_step_bf16(dev, B, Te, L, ragged):
     TWICE is compared too and its own run-to-run difference is printed next to the cross-path one).  Behind the loop the postnet's five bf16 convolutions + batch norms amplify those flips (measured 2-4e-2 on mel_out, 1-5e-2 in
     relative L2 on the gradient slab - the level at which the emulating oracle's own gradients move under a 1e-6 perturbation,
     tests/test_cpu_oracle.py::test_bf16_emulation_sensitivity): bounded at 8e-2 / 1e-1.  Zero fallbacks, and the persistent launches really
-    ran in bf16 mode."""
+    ran in bf16 mode.  These bounds are the trajectory's flip noise and nothing finer: the accuracy of the kernels of both paths rests on
+    tests/test_gpu_decoder_bf16_ref.py, which holds each form on its own, stage by stage from its own stored history, to ~1e-6 per (step, row)
+    slice - including the one way in which the two paths round different numbers by design (the persistent launches round the exchanged copy,
+    whose last mantissa bit is the ring's generation: tests/decoder_bf16_ref.py, PERSISTENT_SITES)."""
     eng, od = _bf16_engines(dev)
     batch = to_dev(OT.synthetic_batch(od, B, Te, L, seed=5, ragged=ragged), dev)
     seed = OT.step_seed(1234, 0)
