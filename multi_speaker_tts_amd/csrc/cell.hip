@@ -20,6 +20,7 @@
 // round trip, all loads issued before the first MFMA, in consumption order.
 // Exact fp32 arithmetic (v_mfma_f32_16x16x4_f32); deterministic (fixed reduction order).
 #include "common.h"
+#include "lstm_cell.h"
 
 namespace mstts {
 
@@ -176,19 +177,17 @@ __device__ __forceinline__ void cell_fwd_body(const CellFwd& d) {
     for (int q = 0; q < 4; ++q) g4[q] = ((red[0][er][4 * q + ec] + red[1][er][4 * q + ec]) + (red[2][er][4 * q + ec] + red[3][er][4 * q + ec])) + (xwv[q] + bv[q]);
     const float kc = zcv ? d.keep : 0.f, kh = zhv ? d.keep : 0.f;
     // activations through one hardware exp each (v_exp_f32, ~1e-7 relative): the library forms are 3-4x the instructions on the
-    // tail of a latency-bound kernel
-    float si = sigmoidf_(g4[0]), tj = tanhf_(g4[1]), sf = sigmoidf_(g4[2] + 1.0f), so = sigmoidf_(g4[3]);
-    float c = sf * cp + si * tj;
-    float m = so * tanhf_(c);
-    float hn = kh * (m - hp) + hp, cn = kc * (c - cp) + cp;
-    if (SEQ && !rlive) { m = 0.f; hn = hp; cn = cp; si = 0.f; tj = 0.f; sf = 0.f; so = 0.f; c = cp; }
+    // tail of a latency-bound kernel (lstm_cell.h)
+    float hn = hp, cn = cp;
+    CellOut o = lstm_cell_fwd(g4[0], g4[1], g4[2], g4[3], cn, hn, kc, kh);
+    if (SEQ && !rlive) { o = (CellOut){0.f, 0.f, 0.f, 0.f, cp, 0.f}; hn = hp; cn = cp; }
     d.c_next[eb * H + eu] = cn;
     d.h_next[eb * d.h_next_ld + eu] = hn;
-    d.out[eb * d.out_ld + (SEQ ? pos * d.out_st : 0) + eu] = m;
-    if (d.out_p.base) packed_store(d.out_p, eb, eu, m);
+    d.out[eb * d.out_ld + (SEQ ? pos * d.out_st : 0) + eu] = o.m;
+    if (d.out_p.base) packed_store(d.out_p, eb, eu, o.m);
     if (d.h_next_p.base) packed_store(d.h_next_p, eb, eu, hn);
-    if (d.acts) { float* a = d.acts + eb * 4 * H + eu; a[0] = si; a[H] = tj; a[2 * H] = sf; a[3 * H] = so; }
-    if (d.c_raw) d.c_raw[eb * H + eu] = c;
+    if (d.acts) { float* a = d.acts + eb * 4 * H + eu; a[0] = o.si; a[H] = o.tj; a[2 * H] = o.sf; a[3 * H] = o.so; }
+    if (d.c_raw) d.c_raw[eb * H + eu] = o.c;
 }
 
 template <int NIT, bool TWO, bool SEQ>

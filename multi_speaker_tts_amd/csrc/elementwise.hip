@@ -2,7 +2,9 @@
 // Everything here is streaming work: float4 accesses, grid-stride loops capped at 2048 blocks,
 // wave64 shuffles for reductions.
 #include "common.h"
+#include "lstm_cell.h"
 #include <stdarg.h>
+#include <type_traits>
 
 namespace mstts {
 
@@ -412,130 +414,38 @@ __global__ void fold_rows_kernel(const float* __restrict__ src, float* __restric
 }
 
 // ---------------------------------------------------------------------------------------------
-// zoneout LSTM cell: pointwise part, forward and backward
+// zoneout LSTM cell: pointwise part, forward and backward - one body per pass around the cell math of lstm_cell.h.
+// The instantiations with compile-time slab counts are the lean kernels of the step loops: 32-bit indexing, no loop over slabs (with
+// everything general the kernels cost ~1900 instructions per thread in address arithmetic alone, which is what a 32K-element step pays
+// for).  Slab count 0 is the fall-back for every other call: run-time slab counts up to MSTTS_MAX_PARTS, 64-bit indices, `out` may be null.
 // ---------------------------------------------------------------------------------------------
-__global__ void lstm_point_fwd_kernel(mstts_lstm_point_fwd_desc d) {
-    const long n = d.B * d.H;
-    const int H = (int)d.H;
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const int b = (int)(i / H), u = (int)(i % H);
-        int len = d.lengths ? d.lengths[b] : 0x7fffffff;
-        const bool live = d.step < len;
-        const int pos = d.reverse ? (live ? len - 1 - d.step : d.step) : d.step;
-        const long hpl = d.h_prev_ld ? d.h_prev_ld : H, hnl = d.h_next_ld ? d.h_next_ld : H;
-        const float cp = d.c_prev[i], hp = d.h_prev[b * hpl + u];
-        float* outp = d.out ? d.out + b * d.out_sb + pos * d.out_st + u : nullptr;
-        if (!live) {
-            if (outp) *outp = 0.f;
-            d.c_next[i] = cp; d.h_next[b * hnl + u] = hp;
-            if (d.acts_out) { for (int g = 0; g < 4; ++g) d.acts_out[(long)b * 4 * H + g * H + u] = 0.f; }
-            if (d.c_raw) d.c_raw[i] = cp;
-            continue;
-        }
-        float g4[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            float v = sum_parts<MSTTS_MAX_PARTS>(d.gates_h, d.gates_parts, d.gates_pstride, (long)b * 4 * H + g * H + u);
-            if (d.xw) v += d.xw[b * d.xw_sb + pos * d.xw_st + g * H + u];
-            if (d.bias) v += d.bias[g * H + u];
-            g4[g] = v;
-        }
-        const float si = sigmoidf_(g4[0]), tj = tanhf_(g4[1]), sf = sigmoidf_(g4[2] + 1.0f), so = sigmoidf_(g4[3]);
-        const float c = sf * cp + si * tj;
-        const float m = so * tanhf_(c);
-        float dc = c - cp, dm = m - hp;
-        if (d.zc) dc = d.zc[i] ? dc : 0.f;
-        if (d.zh) dm = d.zh[i] ? dm : 0.f;
-        d.c_next[i] = (1.f - d.zoneout) * dc + cp;
-        d.h_next[b * hnl + u] = (1.f - d.zoneout) * dm + hp;
-        if (outp) {
-            float o = m;
-            if (d.residual) o += d.residual[b * d.res_sb + pos * d.res_st + u];
-            *outp = o;
-        }
-        if (d.acts_out) {
-            float* a = d.acts_out + (long)b * 4 * H + u;
-            a[0] = si; a[H] = tj; a[2 * H] = sf; a[3 * H] = so;
-        }
-        if (d.c_raw) d.c_raw[i] = c;
-    }
-}
+template <int PARTS> using point_idx = typename std::conditional<PARTS == 0, long, int>::type;
 
-__global__ void lstm_point_bwd_kernel(mstts_lstm_point_bwd_desc d) {
-    const long n = d.B * d.H;
-    const int H = (int)d.H;
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const int b = (int)(i / H), u = (int)(i % H);
-        int len = d.lengths ? d.lengths[b] : 0x7fffffff;
-        const bool live = d.step < len;
-        const int pos = d.reverse ? (live ? len - 1 - d.step : d.step) : d.step;
-        float dhs = d.d_h_state[i];
-        if (d.d_h_state2) {
-            dhs += sum_parts<MSTTS_MAX_PARTS>(d.d_h_state2, d.dhs2_parts, d.dhs2_pstride, b * d.dhs2_ld + u);
-        }
-        const float dcs = d.d_c_state[i];
-        float* dg = d.dgates + (long)b * 4 * H + u;
-        float* dgp = d.dgates_pos ? d.dgates_pos + b * d.dgp_sb + pos * d.dgp_st + u : nullptr;
-        if (!live) {
-            dg[0] = dg[H] = dg[2 * H] = dg[3 * H] = 0.f;
-            if (dgp) { dgp[0] = dgp[H] = dgp[2 * H] = dgp[3 * H] = 0.f; }
-            d.d_c_prev[i] = dcs; d.d_h_prev[i] = dhs;
-            continue;
-        }
-        float dm = 0.f;
-        if (d.d_out) {
-            dm += sum_parts<MSTTS_MAX_PARTS>(d.d_out, d.dout_parts, d.dout_pstride, b * d.dout_sb + pos * d.dout_st + u);
-        }
-        if (d.d_out2) {
-            dm += sum_parts<MSTTS_MAX_PARTS>(d.d_out2, d.dout2_parts, d.dout2_pstride, i);
-        }
-        const float kz = 1.f - d.zoneout;
-        const float mh = d.zh ? (d.zh[i] ? kz : 0.f) : kz;     // d h'/d m
-        const float mc = d.zc ? (d.zc[i] ? kz : 0.f) : kz;     // d c'/d c
-        dm += mh * dhs;
-        const float* a = d.acts + (long)b * 4 * H + u;
-        const float si = a[0], tj = a[H], sf = a[2 * H], so = a[3 * H];
-        const float c = d.c_raw[i], cp = d.c_prev[i];
-        const float tc = tanhf_(c);
-        const float dc = dm * so * (1.f - tc * tc) + mc * dcs;
-        const float d_o = dm * tc * so * (1.f - so);
-        const float d_i = dc * tj * si * (1.f - si);
-        const float d_j = dc * si * (1.f - tj * tj);
-        const float d_f = dc * cp * sf * (1.f - sf);
-        dg[0] = d_i; dg[H] = d_j; dg[2 * H] = d_f; dg[3 * H] = d_o;
-        if (dgp) { dgp[0] = d_i; dgp[H] = d_j; dgp[2 * H] = d_f; dgp[3 * H] = d_o; }
-        d.d_c_prev[i] = dcs * (1.f - mc) + dc * sf;
-        d.d_h_prev[i] = dhs * (1.f - mh);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// lean decoder-path variants of the two kernels above (no sequence-length masking, no residual, no
-// position indirection, 32-bit indexing, compile-time slab count): the generic kernels cost ~1900
-// instructions per thread in address arithmetic alone, which is what a 32K-element step pays for.
-// ---------------------------------------------------------------------------------------------
-struct PointFwdFast {
-    const float* gates; int pstride;            // [PARTS][B][4H]
-    const float* xw; int xw_ld, xw_st;          // row b, position pos at xw + b*xw_ld + pos*xw_st (or null)
+template <typename I>
+struct PointFwd {
+    const float* gates; int parts; I pstride;   // [parts][B][4H]
+    const float* xw; I xw_ld, xw_st;            // row b, position pos at xw + b*xw_ld + pos*xw_st (or null)
     const float* bias;                          // [4H] or null
-    const float* c_prev; const float* h_prev; int h_prev_ld;
+    const float* c_prev; const float* h_prev; I h_prev_ld;
     const uint8_t* zc; const uint8_t* zh; float keep;
-    float* out; int out_ld, out_st;
-    float* c_next; float* h_next; int h_next_ld;
+    float* out; I out_ld, out_st;               // null in the fall-back only
+    float* c_next; float* h_next; I h_next_ld;
     float* acts; float* c_raw;                  // may be null when SEQ
     const int32_t* lengths; int step, reverse;  // SEQ only
-    const float* residual; int res_ld, res_st;  // SEQ only
-    int B, H;
+    const float* residual; I res_ld, res_st;    // SEQ only
+    I B, H;
 };
 
 // SEQ = dynamic_rnn semantics (length masking, reversed direction, residual wrapper); the decoder uses SEQ = false
 template <int PARTS, bool SEQ>
-__global__ __launch_bounds__(128) void lstm_point_fwd_fast_kernel(PointFwdFast d) {
-    const int i = blockIdx.x * 128 + threadIdx.x;
-    const int H = d.H;
+__global__ __launch_bounds__(128) void lstm_point_fwd_fast_kernel(PointFwd<point_idx<PARTS>> d) {
+    typedef point_idx<PARTS> I;
+    constexpr bool GEN = PARTS == 0;
+    const I i = (I)blockIdx.x * 128 + threadIdx.x;
+    const I H = d.H;
     if (i >= d.B * H) return;
-    const int b = i / H, u = i - b * H;
-    const int g0 = b * 4 * H + u;
+    const I b = i / H, u = i - b * H;
+    const I g0 = b * 4 * H + u;
     int pos = 0;
     bool live = true;
     if (SEQ) {
@@ -543,17 +453,19 @@ __global__ __launch_bounds__(128) void lstm_point_fwd_fast_kernel(PointFwdFast d
         live = d.step < len;
         pos = (d.reverse && live) ? len - 1 - d.step : d.step;
     }
-    const float cp = d.c_prev[i], hp = d.h_prev[b * d.h_prev_ld + u];
+    float cs = d.c_prev[i], hs = d.h_prev[b * d.h_prev_ld + u];
+    float* outp = (!GEN || d.out) ? d.out + b * d.out_ld + pos * d.out_st + u : nullptr;
     if (SEQ && !live) {
-        d.out[b * d.out_ld + pos * d.out_st + u] = 0.f;
-        d.c_next[i] = cp; d.h_next[b * d.h_next_ld + u] = hp;
+        if (!GEN || outp) *outp = 0.f;
+        d.c_next[i] = cs; d.h_next[b * d.h_next_ld + u] = hs;
         if (d.acts) { float* a = d.acts + g0; a[0] = 0.f; a[H] = 0.f; a[2 * H] = 0.f; a[3 * H] = 0.f; }
-        if (d.c_raw) d.c_raw[i] = cp;
+        if (d.c_raw) d.c_raw[i] = cs;
         return;
     }
     float g4[4] = {0.f, 0.f, 0.f, 0.f};
+    const int parts = GEN ? d.parts : PARTS;
 #pragma unroll
-    for (int pp = 0; pp < PARTS; ++pp) {
+    for (int pp = 0; pp < parts; ++pp) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) g4[g] += d.gates[pp * d.pstride + g0 + g * H];
     }
@@ -567,49 +479,63 @@ __global__ __launch_bounds__(128) void lstm_point_fwd_fast_kernel(PointFwdFast d
     }
     const float kc = d.zc ? (d.zc[i] ? d.keep : 0.f) : d.keep;
     const float kh = d.zh ? (d.zh[i] ? d.keep : 0.f) : d.keep;
-    const float si = sigmoidf_(g4[0]), tj = tanhf_(g4[1]), sf = sigmoidf_(g4[2] + 1.0f), so = sigmoidf_(g4[3]);
-    const float c = sf * cp + si * tj;
-    const float m = so * tanhf_(c);
-    d.c_next[i] = kc * (c - cp) + cp;
-    d.h_next[b * d.h_next_ld + u] = kh * (m - hp) + hp;
-    float o = m;
-    if (SEQ && d.residual) o += d.residual[b * d.res_ld + pos * d.res_st + u];
-    d.out[b * d.out_ld + pos * d.out_st + u] = o;
-    if (!SEQ || d.acts) { float* a = d.acts + g0; a[0] = si; a[H] = tj; a[2 * H] = sf; a[3 * H] = so; }
-    if (!SEQ || d.c_raw) d.c_raw[i] = c;
+    const CellOut o = lstm_cell_fwd(g4[0], g4[1], g4[2], g4[3], cs, hs, kc, kh);
+    d.c_next[i] = cs;
+    d.h_next[b * d.h_next_ld + u] = hs;
+    float ov = o.m;
+    if (SEQ && d.residual) ov += d.residual[b * d.res_ld + pos * d.res_st + u];
+    if (!GEN || outp) *outp = ov;
+    if (!SEQ || d.acts) { float* a = d.acts + g0; a[0] = o.si; a[H] = o.tj; a[2 * H] = o.sf; a[3 * H] = o.so; }
+    if (!SEQ || d.c_raw) d.c_raw[i] = o.c;
 }
 
-struct PointBwdFast {
-    const float* d_out; int dout_ld, dout_st, dout_parts, dout_pstride;     // may be null
-    const float* d_out2; int dout2_parts, dout2_pstride;           // [parts][B][H] or null
+template <typename I>
+struct PointBwd {
+    const float* d_out; I dout_ld, dout_st; int dout_parts; I dout_pstride;        // may be null
+    const float* d_out2; int dout2_parts; I dout2_pstride;         // [parts][B][H] or null
     const float* d_c_state; const float* d_h_state;
-    const float* dhs2; int dhs2_ld, dhs2_parts; long dhs2_pstride; // or null
+    const float* dhs2; I dhs2_ld; int dhs2_parts; long dhs2_pstride; // or null
     const float* acts; const float* c_raw; const float* c_prev;
     const uint8_t* zc; const uint8_t* zh; float keep;
     float* dgates; float* d_c_prev; float* d_h_prev;
     const int32_t* lengths; int step, reverse;                     // SEQ only
-    float* dgates_pos; int dgp_ld, dgp_st;                         // SEQ only (or null)
+    float* dgates_pos; I dgp_ld, dgp_st;                           // SEQ only (or null)
     const float* dq; const float* wq_t;                            // FUSE_Q only: [B][QA], [QA/4][H][4]
-    int B, H;
+    I B, H;
     int row2d;                                                     // grid (H / 128, B): the row is blockIdx.y - no division in front of the loads
 };
 constexpr int QA = 128;        // attention units of the fused query-layer gradient (hp.Attention.Memory_Size)
 __device__ const float pb_zero[1] = {0.f};        // stand-ins for optional operands of the pointwise kernels (see the load block below)
 __device__ const uint8_t pb_one[1] = {1};
 
-// FUSE_Q: the output gradient also gets dq[b,:] . Wq[u,:] (the attention query layer's data gradient, q = m1 . Wq), computed here from
-// the transposed kernel instead of by a product launch of its own; all QA loads of a thread are issued before the first FMA
-struct PointBwdFastPair { PointBwdFast d[2]; };      // two independent cells per launch (blockIdx.y): the two BiLSTM directions
+struct PointBwdPair { PointBwd<int> d[2]; };      // two independent cells per launch (blockIdx.y): the two BiLSTM directions
 
-template <int P_OUT, int P_OUT2, int P_DHS, bool SEQ, int FUSE_Q = 0>        // FUSE_Q: 0 off, 1 fp32, 2 bf16-rounded operands
-__device__ __forceinline__ void lstm_point_bwd_fast_body(const PointBwdFast& d) {
-    const int H = d.H;
+// the sum of an operand's slabs, as the fall-back forms it before it adds the operand (the order of sum_parts)
+template <int N>
+__device__ __forceinline__ float slab_sum(const float (&r)[N]) {
+    float s = r[0];
+#pragma unroll
+    for (int pp = 1; pp < N; ++pp) s += r[pp];
+    return s;
+}
+
+// P_OUT / P_OUT2 / P_DHS: slabs of d_out / d_out2 / d_h_state2, all three 0 in the fall-back (then the descriptor's counts hold).
+// FUSE_Q (0 off, 1 fp32, 2 bf16-rounded operands): the output gradient also gets dq[b,:] . Wq[u,:] (the attention query layer's data
+// gradient, q = m1 . Wq), computed here from the transposed kernel instead of by a product launch of its own; all QA loads of a thread are
+// issued before the first FMA
+template <int P_OUT, int P_OUT2, int P_DHS, bool SEQ, int FUSE_Q = 0>
+__device__ __forceinline__ void lstm_point_bwd_fast_body(const PointBwd<point_idx<P_OUT>>& d) {
+    typedef point_idx<P_OUT> I;
+    constexpr bool GEN = P_OUT == 0;
+    static_assert(GEN ? (P_OUT2 == 0 && P_DHS == 0 && SEQ && !FUSE_Q) : (P_OUT2 > 0 && P_DHS > 0), "the fall-back is <0, 0, 0, true>");
+    constexpr int N_OUT = GEN ? MSTTS_MAX_PARTS : P_OUT, N_OUT2 = GEN ? MSTTS_MAX_PARTS : P_OUT2, N_DHS = GEN ? MSTTS_MAX_PARTS : P_DHS;
+    const I H = d.H;
     // fused form: H % 128 == 0 (checked by the host), so the 128 threads of a block share one row - a block-uniform index lets the dq
     // row come through scalar loads
-    int i, b, u;
+    I i, b, u;
     if (d.row2d) { b = blockIdx.y; u = blockIdx.x * 128 + threadIdx.x; i = b * H + u; }
     else {
-        i = blockIdx.x * 128 + threadIdx.x;
+        i = (I)blockIdx.x * 128 + threadIdx.x;
         if (i >= d.B * H) return;
         b = FUSE_Q ? (int)(blockIdx.x * 128) / H : i / H; u = i - b * H;
     }
@@ -631,7 +557,8 @@ __device__ __forceinline__ void lstm_point_bwd_fast_body(const PointBwdFast& d) 
     }
     // ---- every operand of the element, requested back to back.  Optional operands (absent slabs, absent masks) are read from a
     // constant block through a selected pointer rather than skipped: a null check is a branch, and the kernel used to be seven basic
-    // blocks each ending in its own wait - seven dependent memory round trips for 30 floats.
+    // blocks each ending in its own wait - seven dependent memory round trips for 30 floats.  (Fall-back: MSTTS_MAX_PARTS slots per
+    // operand, those past the descriptor's count hold zero.)
     const float* p_dhs2 = d.dhs2 ? d.dhs2 + b * d.dhs2_ld + u : pb_zero;
     const long s_dhs2 = d.dhs2 ? d.dhs2_pstride : 0;
     const float* p_do = d.d_out ? d.d_out + b * d.dout_ld + pos * d.dout_st + u : pb_zero;
@@ -640,22 +567,26 @@ __device__ __forceinline__ void lstm_point_bwd_fast_body(const PointBwdFast& d) 
     const long s_do2 = d.d_out2 ? d.dout2_pstride : 0;
     const uint8_t* p_zh = d.zh ? d.zh + i : pb_one;
     const uint8_t* p_zc = d.zc ? d.zc + i : pb_one;
-    const float r_dhs = d.d_h_state[i], dcs = d.d_c_state[i];
-    float r_dhs2[P_DHS], r_do[P_OUT], r_do2[P_OUT2];
+    const float r_dhs = d.d_h_state[i];
+    float dcs = d.d_c_state[i];
+    float r_dhs2[N_DHS], r_do[N_OUT], r_do2[N_OUT2];
 #pragma unroll
-    for (int pp = 0; pp < P_DHS; ++pp) r_dhs2[pp] = p_dhs2[pp * s_dhs2];
+    for (int pp = 0; pp < N_DHS; ++pp) r_dhs2[pp] = (!GEN || pp < d.dhs2_parts) ? p_dhs2[pp * s_dhs2] : 0.f;
 #pragma unroll
-    for (int pp = 0; pp < P_OUT; ++pp) r_do[pp] = p_do[pp * s_do];
+    for (int pp = 0; pp < N_OUT; ++pp) r_do[pp] = (!GEN || pp < d.dout_parts) ? p_do[pp * s_do] : 0.f;
 #pragma unroll
-    for (int pp = 0; pp < P_OUT2; ++pp) r_do2[pp] = p_do2[pp * s_do2];
+    for (int pp = 0; pp < N_OUT2; ++pp) r_do2[pp] = (!GEN || pp < d.dout2_parts) ? p_do2[pp * s_do2] : 0.f;
     const uint8_t r_zh = *p_zh, r_zc = *p_zc;
     const float* a = d.acts + b * 4 * H + u;
     const float si = a[0], tj = a[H], sf = a[2 * H], so = a[3 * H];
     const float c = d.c_raw[i], cp = d.c_prev[i];
     __builtin_amdgcn_sched_barrier(0);
     float dhs = r_dhs;
+    if (GEN) { if (d.dhs2) dhs += slab_sum(r_dhs2); }
+    else {
 #pragma unroll
-    for (int pp = 0; pp < P_DHS; ++pp) dhs += r_dhs2[pp];
+        for (int pp = 0; pp < N_DHS; ++pp) dhs += r_dhs2[pp];
+    }
     float* dg = d.dgates + b * 4 * H + u;
     float* dgp = (SEQ && d.dgates_pos) ? d.dgates_pos + b * d.dgp_ld + pos * d.dgp_st + u : nullptr;
     if (SEQ && !live) {
@@ -665,10 +596,13 @@ __device__ __forceinline__ void lstm_point_bwd_fast_body(const PointBwdFast& d) 
         return;
     }
     float dm = 0.f;
+    if (GEN) { dm += slab_sum(r_do); dm += slab_sum(r_do2); }
+    else {
 #pragma unroll
-    for (int pp = 0; pp < P_OUT; ++pp) dm += r_do[pp];
+        for (int pp = 0; pp < N_OUT; ++pp) dm += r_do[pp];
 #pragma unroll
-    for (int pp = 0; pp < P_OUT2; ++pp) dm += r_do2[pp];
+        for (int pp = 0; pp < N_OUT2; ++pp) dm += r_do2[pp];
+    }
     if (FUSE_Q) {
         __syncthreads();
         float q0 = 0.f, q1 = 0.f, q2 = 0.f, q3 = 0.f;
@@ -682,21 +616,17 @@ __device__ __forceinline__ void lstm_point_bwd_fast_body(const PointBwdFast& d) 
         }
         dm += (q0 + q1) + (q2 + q3);
     }
-    const float mh = r_zh ? d.keep : 0.f;
-    const float mc = r_zc ? d.keep : 0.f;
-    dm += mh * dhs;
-    const float tc = tanhf_(c);
-    const float dc = dm * so * (1.f - tc * tc) + mc * dcs;
-    const float d_i = dc * tj * si * (1.f - si), d_j = dc * si * (1.f - tj * tj), d_f = dc * cp * sf * (1.f - sf), d_o = dm * tc * so * (1.f - so);
-    dg[0] = d_i; dg[H] = d_j; dg[2 * H] = d_f; dg[3 * H] = d_o;
-    if (dgp) { dgp[0] = d_i; dgp[H] = d_j; dgp[2 * H] = d_f; dgp[3 * H] = d_o; }
-    d.d_c_prev[i] = dcs * (1.f - mc) + dc * sf;
-    d.d_h_prev[i] = dhs * (1.f - mh);
+    const CellGrad g = lstm_cell_bwd(dm, dhs, dcs, si, tj, sf, so, c, cp, r_zh ? d.keep : 0.f, r_zc ? d.keep : 0.f);
+    dg[0] = g.i; dg[H] = g.j; dg[2 * H] = g.f; dg[3 * H] = g.o;
+    // the state gradients are stored in the block that computes them, in front of the dgates_pos branch: how the compiler forms
+    // dcs (1 - mc) + dc sf (two rounded products and a sum, or one product and an FMA) has followed the block the store sits in
+    d.d_c_prev[i] = dcs; d.d_h_prev[i] = dhs;
+    if (dgp) { dgp[0] = g.i; dgp[H] = g.j; dgp[2 * H] = g.f; dgp[3 * H] = g.o; }
 }
 template <int P_OUT, int P_OUT2, int P_DHS, bool SEQ, int FUSE_Q = 0>
-__global__ __launch_bounds__(128) void lstm_point_bwd_fast_kernel(PointBwdFast d) { lstm_point_bwd_fast_body<P_OUT, P_OUT2, P_DHS, SEQ, FUSE_Q>(d); }
+__global__ __launch_bounds__(128) void lstm_point_bwd_fast_kernel(PointBwd<point_idx<P_OUT>> d) { lstm_point_bwd_fast_body<P_OUT, P_OUT2, P_DHS, SEQ, FUSE_Q>(d); }
 template <int P_DHS>
-__global__ __launch_bounds__(128) void lstm_point_bwd_fast_pair_kernel(PointBwdFastPair p) { lstm_point_bwd_fast_body<1, 1, P_DHS, true, 0>(p.d[blockIdx.y]); }
+__global__ __launch_bounds__(128) void lstm_point_bwd_fast_pair_kernel(PointBwdPair p) { lstm_point_bwd_fast_body<1, 1, P_DHS, true, 0>(p.d[blockIdx.y]); }
 
 // ---------------------------------------------------------------------------------------------
 // losses
@@ -1121,50 +1051,81 @@ extern "C" int mstts_fold_rows(const float* src, float* dst, int64_t rows, int64
     return MSTTS_OK;
 }
 
-extern "C" int mstts_lstm_point_fwd(const mstts_lstm_point_fwd_desc* d, mstts_stream_t s) {
-    MSTTS_REQUIRE(d && d->gates_h && d->c_prev && d->h_prev && d->c_next && d->h_next, MSTTS_ERR_SHAPE, "lstm_point_fwd: null pointer");
-    if (d->B * d->H == 0) return MSTTS_OK;
-    const int parts = d->gates_parts > 1 ? d->gates_parts : 1;
-    const bool seq = d->lengths || d->residual || d->reverse || d->xw_st != 0 || d->out_st != 0 || !d->acts_out || !d->c_raw;
-    const long span = (d->B + 1) * (d->out_sb > d->xw_sb ? d->out_sb : d->xw_sb);
-    const bool fast = d->out && d->B * d->H * 4 < (1LL << 30) && (parts == 1 || parts == 2 || parts == 4 || parts == 7 || parts == 8 || parts == 16) &&
-                      (long)parts * d->gates_pstride < (1LL << 30) && span < (1LL << 30);
-    if (fast) {
-        PointFwdFast f;
-        f.gates = d->gates_h; f.pstride = (int)d->gates_pstride; f.xw = d->xw; f.xw_ld = (int)d->xw_sb; f.xw_st = (int)d->xw_st; f.bias = d->bias;
-        f.c_prev = d->c_prev; f.h_prev = d->h_prev; f.h_prev_ld = (int)(d->h_prev_ld ? d->h_prev_ld : d->H);
-        f.zc = d->zc; f.zh = d->zh; f.keep = 1.f - d->zoneout;
-        f.out = d->out; f.out_ld = (int)d->out_sb; f.out_st = (int)d->out_st; f.c_next = d->c_next; f.h_next = d->h_next;
-        f.h_next_ld = (int)(d->h_next_ld ? d->h_next_ld : d->H); f.acts = d->acts_out; f.c_raw = d->c_raw;
-        f.lengths = d->lengths; f.step = d->step; f.reverse = d->reverse;
-        f.residual = d->residual; f.res_ld = (int)d->res_sb; f.res_st = (int)d->res_st;
-        f.B = (int)d->B; f.H = (int)d->H;
-        dim3 grid((unsigned)((d->B * d->H + 127) / 128));
-#define MSTTS_PF(P)                                                                                        \
-        if (seq) hipLaunchKernelGGL((lstm_point_fwd_fast_kernel<P, true>), grid, dim3(128), 0, ST(s), f);    \
-        else hipLaunchKernelGGL((lstm_point_fwd_fast_kernel<P, false>), grid, dim3(128), 0, ST(s), f)
-        if (parts == 16) { MSTTS_PF(16); } else if (parts == 8) { MSTTS_PF(8); } else if (parts == 7) { MSTTS_PF(7); } else if (parts == 4) { MSTTS_PF(4); }
-        else if (parts == 2) { MSTTS_PF(2); } else { MSTTS_PF(1); }
-#undef MSTTS_PF
-        MSTTS_CHECK_LAUNCH("lstm_point_fwd_fast");
-        return MSTTS_OK;
-    }
-    hipLaunchKernelGGL(lstm_point_fwd_kernel, dim3(grid_for(d->B * d->H, 256)), dim3(256), 0, ST(s), *d);
-    MSTTS_CHECK_LAUNCH("lstm_point_fwd");
-    return MSTTS_OK;
+// ---- pointwise cell entries: descriptor translation (one fill per descriptor pair) and the instantiations, each listed once
+template <typename I>
+static PointFwd<I> point_fwd_fill(const mstts_lstm_point_fwd_desc* d) {
+    PointFwd<I> f;
+    f.gates = d->gates_h; f.parts = d->gates_parts > 1 ? d->gates_parts : 1; f.pstride = (I)d->gates_pstride;
+    f.xw = d->xw; f.xw_ld = (I)d->xw_sb; f.xw_st = (I)d->xw_st; f.bias = d->bias;
+    f.c_prev = d->c_prev; f.h_prev = d->h_prev; f.h_prev_ld = (I)(d->h_prev_ld ? d->h_prev_ld : d->H);
+    f.zc = d->zc; f.zh = d->zh; f.keep = 1.f - d->zoneout;
+    f.out = d->out; f.out_ld = (I)d->out_sb; f.out_st = (I)d->out_st; f.c_next = d->c_next; f.h_next = d->h_next;
+    f.h_next_ld = (I)(d->h_next_ld ? d->h_next_ld : d->H); f.acts = d->acts_out; f.c_raw = d->c_raw;
+    f.lengths = d->lengths; f.step = d->step; f.reverse = d->reverse;
+    f.residual = d->residual; f.res_ld = (I)d->res_sb; f.res_st = (I)d->res_st;
+    f.B = (I)d->B; f.H = (I)d->H;
+    return f;
 }
-static void point_bwd_fill(const mstts_lstm_point_bwd_desc* d, PointBwdFast& f) {
-    const int po = d->dout_parts > 1 ? d->dout_parts : 1, po2 = d->dout2_parts > 1 ? d->dout2_parts : 1, ph = d->dhs2_parts > 1 ? d->dhs2_parts : 1;
+template <typename I>
+static PointBwd<I> point_bwd_fill(const mstts_lstm_point_bwd_desc* d, int row2d) {
+    PointBwd<I> f;
     f.dq = d->dq; f.wq_t = d->wq_t;
-    f.d_out = d->d_out; f.dout_ld = (int)d->dout_sb; f.dout_st = (int)d->dout_st; f.dout_parts = po; f.dout_pstride = (int)d->dout_pstride;
-    f.d_out2 = d->d_out2; f.dout2_parts = po2; f.dout2_pstride = (int)d->dout2_pstride;
+    f.d_out = d->d_out; f.dout_ld = (I)d->dout_sb; f.dout_st = (I)d->dout_st; f.dout_parts = d->dout_parts > 1 ? d->dout_parts : 1; f.dout_pstride = (I)d->dout_pstride;
+    f.d_out2 = d->d_out2; f.dout2_parts = d->dout2_parts > 1 ? d->dout2_parts : 1; f.dout2_pstride = (I)d->dout2_pstride;
     f.d_c_state = d->d_c_state; f.d_h_state = d->d_h_state;
-    f.dhs2 = d->d_h_state2; f.dhs2_ld = (int)d->dhs2_ld; f.dhs2_parts = ph; f.dhs2_pstride = (long)d->dhs2_pstride;
+    f.dhs2 = d->d_h_state2; f.dhs2_ld = (I)d->dhs2_ld; f.dhs2_parts = d->dhs2_parts > 1 ? d->dhs2_parts : 1; f.dhs2_pstride = (long)d->dhs2_pstride;
     f.acts = d->acts; f.c_raw = d->c_raw; f.c_prev = d->c_prev; f.zc = d->zc; f.zh = d->zh; f.keep = 1.f - d->zoneout;
     f.dgates = d->dgates; f.d_c_prev = d->d_c_prev; f.d_h_prev = d->d_h_prev;
     f.lengths = d->lengths; f.step = d->step; f.reverse = d->reverse;
-    f.dgates_pos = d->dgates_pos; f.dgp_ld = (int)d->dgp_sb; f.dgp_st = (int)d->dgp_st;
-    f.B = (int)d->B; f.H = (int)d->H; f.row2d = 0;
+    f.dgates_pos = d->dgates_pos; f.dgp_ld = (I)d->dgp_sb; f.dgp_st = (I)d->dgp_st;
+    f.B = (I)d->B; f.H = (I)d->H; f.row2d = row2d;
+    return f;
+}
+
+// forward: the slab counts with a kernel of their own, [0] plain / [1] sequence form
+struct PointFwdRow { int parts; void (*k[2])(PointFwd<int>); };
+template <int P> static PointFwdRow point_fwd_row() { return {P, {lstm_point_fwd_fast_kernel<P, false>, lstm_point_fwd_fast_kernel<P, true>}}; }
+static const PointFwdRow point_fwd_table[] = {point_fwd_row<1>(), point_fwd_row<2>(), point_fwd_row<4>(), point_fwd_row<7>(), point_fwd_row<8>(), point_fwd_row<16>()};
+
+// backward: the (d_out, d_out2, d_h_state2) slab triples with kernels of their own, [0] plain / [1] sequence form; Q rows also have the
+// fused query gradient ([0] fp32, [1] bf16-rounded operands) and the pair form, both for (1, 1, PH) only
+struct PointBwdRow { int po, po2, ph; void (*k[2])(PointBwd<int>); void (*q[2])(PointBwd<int>); void (*pair)(PointBwdPair); };
+template <int PO, int PO2, int PH, bool Q = false>
+static PointBwdRow point_bwd_row() {
+    PointBwdRow r = {PO, PO2, PH, {lstm_point_bwd_fast_kernel<PO, PO2, PH, false>, lstm_point_bwd_fast_kernel<PO, PO2, PH, true>}, {nullptr, nullptr}, nullptr};
+    if constexpr (Q) {
+        static_assert(PO == 1 && PO2 == 1, "fused query gradient / pair form: single d_out and d_out2 slabs");
+        r.q[0] = lstm_point_bwd_fast_kernel<1, 1, PH, false, 1>; r.q[1] = lstm_point_bwd_fast_kernel<1, 1, PH, false, 2>;
+        r.pair = lstm_point_bwd_fast_pair_kernel<PH>;
+    }
+    return r;
+}
+static const PointBwdRow point_bwd_table[] = {point_bwd_row<1, 1, 1, true>(), point_bwd_row<1, 1, 4, true>(), point_bwd_row<4, 1, 4>(), point_bwd_row<1, 1, 8, true>(),
+                                              point_bwd_row<8, 1, 8>(), point_bwd_row<8, 1, 1>(), point_bwd_row<1, 1, 2, true>()};
+static const PointBwdRow* point_bwd_find(int po, int po2, int ph) {
+    for (const PointBwdRow& r : point_bwd_table)
+        if (r.po == po && r.po2 == po2 && r.ph == ph) return &r;
+    return nullptr;
+}
+static int parts_of(int32_t n) { return n > 1 ? n : 1; }
+
+extern "C" int mstts_lstm_point_fwd(const mstts_lstm_point_fwd_desc* d, mstts_stream_t s) {
+    MSTTS_REQUIRE(d && d->gates_h && d->c_prev && d->h_prev && d->c_next && d->h_next, MSTTS_ERR_SHAPE, "lstm_point_fwd: null pointer");
+    if (d->B * d->H == 0) return MSTTS_OK;
+    const int parts = parts_of(d->gates_parts);
+    const bool seq = d->lengths || d->residual || d->reverse || d->xw_st != 0 || d->out_st != 0 || !d->acts_out || !d->c_raw;
+    const long span = (d->B + 1) * (d->out_sb > d->xw_sb ? d->out_sb : d->xw_sb);
+    const bool small = d->out && d->B * d->H * 4 < (1LL << 30) && (long)parts * d->gates_pstride < (1LL << 30) && span < (1LL << 30);
+    const dim3 grid((unsigned)((d->B * d->H + 127) / 128));
+    for (const PointFwdRow& r : point_fwd_table)
+        if (small && r.parts == parts) {
+            hipLaunchKernelGGL(r.k[seq], grid, dim3(128), 0, ST(s), point_fwd_fill<int>(d));
+            MSTTS_CHECK_LAUNCH("lstm_point_fwd_fast");
+            return MSTTS_OK;
+        }
+    hipLaunchKernelGGL((lstm_point_fwd_fast_kernel<0, true>), grid, dim3(128), 0, ST(s), point_fwd_fill<long>(d));
+    MSTTS_CHECK_LAUNCH("lstm_point_fwd");
+    return MSTTS_OK;
 }
 
 /* the pointwise backward of two independent cells of the same shape in ONE launch (the two directions of a BiLSTM step, sequence
@@ -1172,19 +1133,16 @@ static void point_bwd_fill(const mstts_lstm_point_bwd_desc* d, PointBwdFast& f) 
  * MSTTS_ERR_SHAPE when the pair form is not available for the geometry - the caller then issues two single calls. */
 extern "C" int mstts_lstm_point_bwd_pair(const mstts_lstm_point_bwd_desc* a, const mstts_lstm_point_bwd_desc* b, mstts_stream_t s) {
     MSTTS_REQUIRE(a && b && a->B == b->B && a->H == b->H, MSTTS_ERR_SHAPE, "lstm_point_bwd_pair: the two cells must have the same shape");
-    const int ph = a->dhs2_parts > 1 ? a->dhs2_parts : 1, phb = b->dhs2_parts > 1 ? b->dhs2_parts : 1;
-    const bool ok = ph == phb && (ph == 1 || ph == 2 || ph == 4 || ph == 8) && a->dout_parts <= 1 && b->dout_parts <= 1 && !a->d_out2 && !b->d_out2 &&
+    const PointBwdRow* r = point_bwd_find(1, 1, parts_of(a->dhs2_parts));
+    const bool ok = parts_of(a->dhs2_parts) == parts_of(b->dhs2_parts) && r && r->pair && a->dout_parts <= 1 && b->dout_parts <= 1 && !a->d_out2 && !b->d_out2 &&
                     !a->dq && !b->dq && a->B * a->H * 4 < (1LL << 30) && (a->B + 1) * a->dout_sb < (1LL << 30) && (a->B + 1) * a->dgp_sb < (1LL << 30) &&
                     (!a->d_h_state2) == (!b->d_h_state2);
     MSTTS_REQUIRE(ok, MSTTS_ERR_SHAPE, "lstm_point_bwd_pair: geometry not covered by the pair kernel");
-    PointBwdFastPair p;
-    point_bwd_fill(a, p.d[0]);
-    point_bwd_fill(b, p.d[1]);
+    PointBwdPair p;
+    p.d[0] = point_bwd_fill<int>(a, 0);
+    p.d[1] = point_bwd_fill<int>(b, 0);
     dim3 grid((unsigned)((a->B * a->H + 127) / 128), 2);
-    if (ph == 8) hipLaunchKernelGGL((lstm_point_bwd_fast_pair_kernel<8>), grid, dim3(128), 0, ST(s), p);
-    else if (ph == 4) hipLaunchKernelGGL((lstm_point_bwd_fast_pair_kernel<4>), grid, dim3(128), 0, ST(s), p);
-    else if (ph == 2) hipLaunchKernelGGL((lstm_point_bwd_fast_pair_kernel<2>), grid, dim3(128), 0, ST(s), p);
-    else hipLaunchKernelGGL((lstm_point_bwd_fast_pair_kernel<1>), grid, dim3(128), 0, ST(s), p);
+    hipLaunchKernelGGL(r->pair, grid, dim3(128), 0, ST(s), p);
     MSTTS_CHECK_LAUNCH("lstm_point_bwd_pair");
     return MSTTS_OK;
 }
@@ -1193,67 +1151,26 @@ extern "C" int mstts_lstm_point_bwd(const mstts_lstm_point_bwd_desc* d, mstts_st
     MSTTS_REQUIRE(d && d->d_c_state && d->d_h_state && d->acts && d->c_raw && d->c_prev && d->dgates && d->d_c_prev && d->d_h_prev,
                   MSTTS_ERR_SHAPE, "lstm_point_bwd: null pointer");
     if (d->B * d->H == 0) return MSTTS_OK;
-    {
-        const int po = d->dout_parts > 1 ? d->dout_parts : 1, po2 = d->dout2_parts > 1 ? d->dout2_parts : 1;
-        const int ph = d->dhs2_parts > 1 ? d->dhs2_parts : 1;
-        const bool seq = d->lengths || d->reverse || d->dgates_pos || d->dout_st != 0;
-        const bool small = d->B * d->H * 4 < (1LL << 30) && (long)po * d->dout_pstride < (1LL << 30) && (d->B + 1) * d->dout_sb < (1LL << 30) &&
-                           (d->B + 1) * d->dgp_sb < (1LL << 30);
-        const bool fuse_q = d->dq && d->wq_t;
-        MSTTS_REQUIRE(!fuse_q || (aligned16(d->dq) && aligned16(d->wq_t)), MSTTS_ERR_ALIGN, "lstm_point_bwd: dq / wq_t must be 16-byte aligned");
-        MSTTS_REQUIRE(!fuse_q || d->H % 128 == 0, MSTTS_ERR_SHAPE, "lstm_point_bwd: the fused query-layer gradient needs H %% 128 == 0");
-        MSTTS_REQUIRE(!fuse_q || (d->A == QA && !d->d_out2 && !d->lengths && !d->reverse && !d->dgates_pos && d->dout_st == 0), MSTTS_ERR_SHAPE,
-                      "lstm_point_bwd: the fused query-layer gradient needs A == %d, no d_out2 and the plain (non-sequence) form", QA);
-        int shape = -1;      // (P_OUT, P_OUT2, P_DHS)
-        if (fuse_q) shape = (po == 1 && ph == 8) ? 10 : (po == 1 && ph == 1) ? 11 : (po == 1 && ph == 4) ? 12 : (po == 1 && ph == 2) ? 13 : -2;
-        else if (po == 1 && po2 == 1 && ph == 1) shape = 0;
-        else if (po == 1 && po2 == 1 && ph == 4) shape = 1;
-        else if (po == 4 && po2 == 1 && ph == 4) shape = 2;
-        else if (po == 1 && po2 == 1 && ph == 8) shape = 3;
-        else if (po == 8 && po2 == 1 && ph == 8) shape = 4;
-        else if (po == 8 && po2 == 1 && ph == 1) shape = 5;
-        else if (po == 1 && po2 == 1 && ph == 2) shape = 6;
-        MSTTS_REQUIRE(!fuse_q || (small && shape >= 10), MSTTS_ERR_SHAPE, "lstm_point_bwd: fused query-layer gradient not available for this slab geometry");
-        if (small && shape >= 0) {
-            PointBwdFast f;
-            f.dq = d->dq; f.wq_t = d->wq_t;
-            f.d_out = d->d_out; f.dout_ld = (int)d->dout_sb; f.dout_st = (int)d->dout_st; f.dout_parts = po; f.dout_pstride = (int)d->dout_pstride;
-            f.d_out2 = d->d_out2; f.dout2_parts = po2; f.dout2_pstride = (int)d->dout2_pstride;
-            f.d_c_state = d->d_c_state; f.d_h_state = d->d_h_state;
-            f.dhs2 = d->d_h_state2; f.dhs2_ld = (int)d->dhs2_ld; f.dhs2_parts = ph; f.dhs2_pstride = (long)d->dhs2_pstride;
-            f.acts = d->acts; f.c_raw = d->c_raw; f.c_prev = d->c_prev; f.zc = d->zc; f.zh = d->zh; f.keep = 1.f - d->zoneout;
-            f.dgates = d->dgates; f.d_c_prev = d->d_c_prev; f.d_h_prev = d->d_h_prev;
-            f.lengths = d->lengths; f.step = d->step; f.reverse = d->reverse;
-            f.dgates_pos = d->dgates_pos; f.dgp_ld = (int)d->dgp_sb; f.dgp_st = (int)d->dgp_st;
-            f.B = (int)d->B; f.H = (int)d->H;
-            f.row2d = (d->H % 128 == 0 && d->B <= 65535) ? 1 : 0;
-            dim3 grid((unsigned)((d->B * d->H + 127) / 128));
-            if (f.row2d) grid = dim3((unsigned)(d->H / 128), (unsigned)d->B);
-#define MSTTS_PB(A1, A2, A3)                                                                                          \
-            if (seq) hipLaunchKernelGGL((lstm_point_bwd_fast_kernel<A1, A2, A3, true>), grid, dim3(128), 0, ST(s), f);   \
-            else hipLaunchKernelGGL((lstm_point_bwd_fast_kernel<A1, A2, A3, false>), grid, dim3(128), 0, ST(s), f)
-            switch (shape) {
-                case 0: MSTTS_PB(1, 1, 1); break;
-                case 1: MSTTS_PB(1, 1, 4); break;
-                case 2: MSTTS_PB(4, 1, 4); break;
-                case 3: MSTTS_PB(1, 1, 8); break;
-                case 4: MSTTS_PB(8, 1, 8); break;
-                case 5: MSTTS_PB(8, 1, 1); break;
-#define MSTTS_PBQ(PH) do { if (d->dq_bf16) hipLaunchKernelGGL((lstm_point_bwd_fast_kernel<1, 1, PH, false, 2>), grid, dim3(128), 0, ST(s), f);     \
-                           else hipLaunchKernelGGL((lstm_point_bwd_fast_kernel<1, 1, PH, false, 1>), grid, dim3(128), 0, ST(s), f); } while (0)
-                case 10: MSTTS_PBQ(8); break;
-                case 11: MSTTS_PBQ(1); break;
-                case 12: MSTTS_PBQ(4); break;
-                case 13: MSTTS_PBQ(2); break;
-#undef MSTTS_PBQ
-                default: MSTTS_PB(1, 1, 2); break;
-            }
-#undef MSTTS_PB
-            MSTTS_CHECK_LAUNCH("lstm_point_bwd_fast");
-            return MSTTS_OK;
-        }
+    const int po = parts_of(d->dout_parts), po2 = parts_of(d->dout2_parts), ph = parts_of(d->dhs2_parts);
+    const bool seq = d->lengths || d->reverse || d->dgates_pos || d->dout_st != 0;
+    const bool small = d->B * d->H * 4 < (1LL << 30) && (long)po * d->dout_pstride < (1LL << 30) && (d->B + 1) * d->dout_sb < (1LL << 30) &&
+                       (d->B + 1) * d->dgp_sb < (1LL << 30);
+    const bool fuse_q = d->dq && d->wq_t;
+    MSTTS_REQUIRE(!fuse_q || (aligned16(d->dq) && aligned16(d->wq_t)), MSTTS_ERR_ALIGN, "lstm_point_bwd: dq / wq_t must be 16-byte aligned");
+    MSTTS_REQUIRE(!fuse_q || d->H % 128 == 0, MSTTS_ERR_SHAPE, "lstm_point_bwd: the fused query-layer gradient needs H %% 128 == 0");
+    MSTTS_REQUIRE(!fuse_q || (d->A == QA && !d->d_out2 && !d->lengths && !d->reverse && !d->dgates_pos && d->dout_st == 0), MSTTS_ERR_SHAPE,
+                  "lstm_point_bwd: the fused query-layer gradient needs A == %d, no d_out2 and the plain (non-sequence) form", QA);
+    const PointBwdRow* r = point_bwd_find(po, fuse_q ? 1 : po2, ph);          // (the fused form has no d_out2: its slab count does not matter)
+    MSTTS_REQUIRE(!fuse_q || (small && r && r->q[0]), MSTTS_ERR_SHAPE, "lstm_point_bwd: fused query-layer gradient not available for this slab geometry");
+    if (small && r) {
+        const int row2d = (d->H % 128 == 0 && d->B <= 65535) ? 1 : 0;
+        const dim3 grid = row2d ? dim3((unsigned)(d->H / 128), (unsigned)d->B) : dim3((unsigned)((d->B * d->H + 127) / 128));
+        void (*const kernel)(PointBwd<int>) = fuse_q ? r->q[d->dq_bf16 ? 1 : 0] : r->k[seq];
+        hipLaunchKernelGGL(kernel, grid, dim3(128), 0, ST(s), point_bwd_fill<int>(d, row2d));
+        MSTTS_CHECK_LAUNCH("lstm_point_bwd_fast");
+        return MSTTS_OK;
     }
-    hipLaunchKernelGGL(lstm_point_bwd_kernel, dim3(grid_for(d->B * d->H, 256)), dim3(256), 0, ST(s), *d);
+    hipLaunchKernelGGL((lstm_point_bwd_fast_kernel<0, 0, 0, true>), dim3((unsigned)((d->B * d->H + 127) / 128)), dim3(128), 0, ST(s), point_bwd_fill<long>(d, 0));
     MSTTS_CHECK_LAUNCH("lstm_point_bwd");
     return MSTTS_OK;
 }

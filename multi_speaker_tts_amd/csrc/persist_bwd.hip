@@ -105,22 +105,11 @@ struct PersistBwd {
     float* xch; unsigned* ctrl; unsigned long long* stamps; int fail_step; int near_xcd;
 };
 
-// zoneout-LSTM cell backward for one (row, unit) (the pointwise part of mstts_lstm_point_bwd): dm = gradient of the cell output m
-// (without the zoned-state path), dhs / dcs = gradients of the zoned states h' / c'.  Returns the four gate gradients, updates the carried
-// state gradients to those of the PREVIOUS step's states (direct zoneout paths only; the product part is added by the caller).
+// zoneout-LSTM cell backward for one (row, unit) (lstm_cell.h), the four gate gradients as the vector the exchange publishes
 __device__ __forceinline__ pf32x4 cell_bwd(float dm, float& dhs, float& dcs, float si, float tj, float sf, float so, float c, float cp,
                                            float mh, float mc) {
-    dm += mh * dhs;
-    const float tc = tanhf_(c);
-    const float dc = dm * so * (1.f - tc * tc) + mc * dcs;
-    pf32x4 dg;
-    dg[0] = dc * tj * si * (1.f - si);
-    dg[1] = dc * si * (1.f - tj * tj);
-    dg[2] = dc * cp * sf * (1.f - sf);
-    dg[3] = dm * tc * so * (1.f - so);
-    dcs = dcs * (1.f - mc) + dc * sf;
-    dhs = dhs * (1.f - mh);
-    return dg;
+    const CellGrad g = lstm_cell_bwd(dm, dhs, dcs, si, tj, sf, so, c, cp, mh, mc);
+    return (pf32x4){g.i, g.j, g.f, g.o};
 }
 
 // BF16 (BASELINE config 3): the data-gradient products d[g] . W^T of both cells and of the query layer take their operands rounded to bf16

@@ -12,6 +12,7 @@
 // One barrier and one hand-off per step.  Every wait is bounded; a time-out raises the abort word in ctrl[1] and the caller re-runs the
 // launch-per-step form (mstts_lstm_seq_fwd_pair / mstts_lstm_seq_bwd_pair), which reads and writes the same buffers.
 #include "persist_common.h"
+#include "lstm_cell.h"
 
 namespace mstts {
 
@@ -164,12 +165,9 @@ __global__ __launch_bounds__(ETH) void persist_lstm_fwd_kernel(EncFwd p) {
 #pragma unroll
             for (int k4 = 0; k4 < 4; ++k4) gs += *reinterpret_cast<const pf32x4*>(rb + ((((k4 * 2 + o_rt) * 2 + o_ut) * 64) + lane) * 4);
             // ZoneoutLSTMCell.py:228-271 (gates i, j, f, o; forget bias 1; training-mode zoneout) under dynamic_rnn's length rule
-            float si = sigmoidf_(gs[0]), tj = tanhf_(gs[1]), sf = sigmoidf_(gs[2] + 1.0f), so = sigmoidf_(gs[3]);
-            float c = sf * cs + si * tj;
-            float m = so * tanhf_(c);
-            const float kc = zcv ? p.keep : 0.f, kh = zhv ? p.keep : 0.f;
-            float hn = kh * (m - hs) + hs, cn = kc * (c - cs) + cs;
-            if (!live) { m = 0.f; hn = hs; cn = cs; si = 0.f; tj = 0.f; sf = 0.f; so = 0.f; c = cs; }
+            float hn = hs, cn = cs;
+            CellOut o = lstm_cell_fwd(gs[0], gs[1], gs[2], gs[3], cn, hn, zcv ? p.keep : 0.f, zhv ? p.keep : 0.f);
+            if (!live) { o = (CellOut){0.f, 0.f, 0.f, 0.f, cs, 0.f}; hn = hs; cn = cs; }
             hs = hn; cs = cn;
             // publish h_t: the piece of (row, 4 consecutive units) is the four unit lanes of this row
             pf32x4 pv;
@@ -180,8 +178,8 @@ __global__ __launch_bounds__(ETH) void persist_lstm_fwd_kernel(EncFwd p) {
             LSTAMP(4);
             // history of this (row, unit) for the BPTT and for the row-major tensors (persist_lstm_unpack_fwd_kernel): two contiguous KB per wave
             pf32x4* eo = p.epk + epk_index(t, G, g, wave, 0, lane);
-            eo[0] = (pf32x4){si, tj, sf, so};
-            eo[64] = (pf32x4){m, hn, cn, __uint_as_float((zcv ? 1u : 0u) | (zhv ? 2u : 0u) | (live ? 4u : 0u))};
+            eo[0] = (pf32x4){o.si, o.tj, o.sf, o.so};
+            eo[64] = (pf32x4){o.m, hn, cn, __uint_as_float((zcv ? 1u : 0u) | (zhv ? 2u : 0u) | (live ? 4u : 0u))};
             LSTAMP(5);
         }
     }
@@ -272,23 +270,14 @@ __global__ __launch_bounds__(ETH) void persist_lstm_bwd_kernel(EncBwd p) {
         } else {
             LSTM_BWD_OPERANDS(k + 1, ob)
         }
-        // zoneout-cell backward of (row b, unit u) at step t (elementwise.hip: lstm_point_bwd_kernel)
-        const float dhs = dhc + dh_rec;
+        // zoneout-cell backward of (row b, unit u) at step t (lstm_cell.h); a dead row hands its state gradients on and publishes zeros
+        dhc += dh_rec;
         pf32x4 dg = {0.f, 0.f, 0.f, 0.f};
         if (live) {
-            const float mh = zhv ? p.keep : 0.f, mc = zcv ? p.keep : 0.f;
-            dm += mh * dhs;
             const float si = av[0], tj = av[1], sf = av[2], so = av[3];
-            const float tc = tanhf_(sf * cp + si * tj);            // the raw cell state of the step, as the forward kernel formed it
-            const float dc = dm * so * (1.f - tc * tc) + mc * dcs;
-            dg[3] = dm * tc * so * (1.f - so);
-            dg[0] = dc * tj * si * (1.f - si);
-            dg[1] = dc * si * (1.f - tj * tj);
-            dg[2] = dc * cp * sf * (1.f - sf);
-            dcs = dcs * (1.f - mc) + dc * sf;
-            dhc = dhs * (1.f - mh);
-        } else {
-            dhc = dhs;
+            const float c = sf * cp + si * tj;                    // the raw cell state of the step, as the forward kernel formed it
+            const CellGrad gr = lstm_cell_bwd(dm, dhc, dcs, si, tj, sf, so, c, cp, zhv ? p.keep : 0.f, zcv ? p.keep : 0.f);
+            dg = (pf32x4){gr.i, gr.j, gr.f, gr.o};
         }
         LSTM_BWD_LAND();                                    // next step's operands have landed before this step's stores go out (see the forward kernel)
         // the piece of (row b, unit u) = its four gate gradients: ring column 4 u + gate

@@ -806,3 +806,225 @@ def test_lstm_point_bwd_pair(dev, B, H):
     assert not np.array_equal(t2n(ta["dg"]), t2n(tb["dg"]))
     bb.H = H + 4                                                    # members of different shape: a host-side rejection
     assert lib.load().mstts_lstm_point_bwd_pair(C.byref(ba), C.byref(bb), lib.stream()) != 0
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# every dispatch arm of mstts_lstm_point_fwd / _bwd / _bwd_pair (csrc/elementwise.hip; the cell math is csrc/lstm_cell.h), each against the
+# zoneout cell in fp64 (ZoneoutLSTMCell.py:228-271) at the tolerances of tests/test_gpu_model.py::test_lstm_point_fwd_bwd: 1e-5 forward,
+# 2e-5 backward.  (5, 24): flat grid, ragged last block; (3, 128): the backward's grid of (H / 128, B) blocks.
+# ---------------------------------------------------------------------------------------------------------------------------------
+POINT_SHAPES = [(5, 24), (3, 128)]
+POINT_T, POINT_STEP = 4, 2
+POINT_LEN = [4, 3, 2, 1, 3]         # at step 2: rows 2 and 3 are dead, step 2 is the last live step of rows 1 and 4
+
+
+def _point_rows(B, form):
+    """(lengths or None, live [B], pos [B]) of a case: 'plain' has no lengths and position 0, 'seq' / 'rev' are dynamic_rnn's two directions."""
+    if form == "plain":
+        return None, np.ones(B, bool), np.zeros(B, np.int64)
+    lengths = np.array(POINT_LEN[:B], np.int32)
+    live = POINT_STEP < lengths
+    pos = np.where(live & (form == "rev"), lengths - 1 - POINT_STEP, POINT_STEP).astype(np.int64)
+    return lengths, live, pos
+
+
+def _only_at(what, got, ref, tol):
+    """`ref` holds NaN wherever the call must not write: those elements of `got` still hold their NaN filling, the others meet `tol`."""
+    got, w = t2n(got), ~np.isnan(ref)
+    assert np.isnan(got[~w]).all(), what + ": written outside its region"
+    _chk(what, got[w], ref[w], tol)
+
+
+def _point_fwd_run(dev, B, H, parts, mode, form, wide, out_null=False, saves=None, seed=0):
+    T, seq = POINT_T, form != "plain"
+    lengths, live, pos = _point_rows(B, form)
+    saves = (not seq) if saves is None else saves
+    hpl, hnl, old = (H + 4, H + 8, H + 12) if wide else (H, H, H)
+    gates = _r(dev, parts, B, 4 * H, seed=seed + 1, scale=1.0 / np.sqrt(parts))
+    add = _r(dev, *((B, T, 4 * H) if seq else (B, 4 * H)), seed=seed + 2) if mode == "xw" else _r(dev, 4 * H, seed=seed + 2, scale=0.1)
+    cp, hp = _r(dev, B, H, seed=seed + 3), _r(dev, B, hpl, seed=seed + 4)
+    zc, zh = _bits(dev, B, H, seed=seed + 5), _bits(dev, B, H, seed=seed + 6)
+    res = _r(dev, B, T, H, seed=seed + 7) if seq else None
+    out = None if out_null else _nan(dev, *((B, T, old) if seq else (B, old)))
+    cn, hn = _nan(dev, B, H), _nan(dev, B, hnl)
+    acts, craw = (_nan(dev, B, 4 * H), _nan(dev, B, H)) if saves else (None, None)
+    d = lib.LstmPointFwd()
+    d.B, d.H, d.gates_h, d.gates_parts, d.gates_pstride = B, H, lib.ptr(gates), parts, B * 4 * H
+    if mode == "xw":
+        d.xw, d.xw_sb, d.xw_st = lib.ptr(add), (T * 4 * H if seq else 4 * H), (4 * H if seq else 0)
+    else:
+        d.bias = lib.ptr(add)
+    d.c_prev, d.h_prev, d.h_prev_ld, d.zc, d.zh, d.zoneout = lib.ptr(cp), lib.ptr(hp), (hpl if wide else 0), lib.ptr(zc), lib.ptr(zh), 0.1
+    if seq:
+        lens = torch.tensor(lengths, device=dev)
+        d.lengths, d.step, d.reverse, d.residual, d.res_sb, d.res_st = lib.ptr(lens), POINT_STEP, int(form == "rev"), lib.ptr(res), T * H, H
+    d.out, d.out_sb, d.out_st = lib.ptr(out), (T * old if seq else old), (old if seq else 0)
+    d.c_next, d.h_next, d.h_next_ld, d.acts_out, d.c_raw = lib.ptr(cn), lib.ptr(hn), (hnl if wide else 0), lib.ptr(acts), lib.ptr(craw)
+    lib.call("mstts_lstm_point_fwd", C.byref(d))
+    rows = np.arange(B)
+    g = _f64(gates).sum(0) + (_f64(add)[rows, pos] if (mode == "xw" and seq) else _f64(add))
+    i, j, f, o = np.split(g, 4, axis=1)
+    si, tj, sf, so = _sg(i), np.tanh(j), _sg(f + 1.0), _sg(o)
+    cp64, hp64, lv = _f64(cp), _f64(hp)[:, :H], live[:, None]
+    c = sf * cp64 + si * tj
+    m = so * np.tanh(c)
+    tag = "fwd %s parts %d %s%s: " % (form, parts, mode, " wide" if wide else "")
+    if not out_null:
+        ref = np.full(tuple(out.shape), np.nan)
+        o_ref = np.where(lv, m + (_f64(res)[rows, pos] if seq else 0.0), 0.0)
+        if seq:
+            ref[rows, pos, :H] = o_ref
+        else:
+            ref[:, :H] = o_ref
+        _only_at(tag + "out", out, ref, 1e-5)
+    _chk(tag + "c_next", cn, np.where(lv, 0.9 * t2n(zc) * (c - cp64) + cp64, cp64), 1e-5)
+    ref = np.full((B, hnl), np.nan)
+    ref[:, :H] = np.where(lv, 0.9 * t2n(zh) * (m - hp64) + hp64, hp64)
+    _only_at(tag + "h_next", hn, ref, 1e-5)
+    if saves:
+        _chk(tag + "acts", acts, np.where(lv, np.concatenate([si, tj, sf, so], 1), 0.0), 1e-5)
+        _chk(tag + "c_raw", craw, np.where(lv, c, cp64), 1e-5)
+
+
+@pytest.mark.parametrize("mode", ["bias", "xw"])            # the bias alone / a hoisted input product with the bias folded in
+@pytest.mark.parametrize("parts", [1, 2, 3, 4, 7, 8, 16])    # 3: no instantiation of its own, the run-time slab count
+@pytest.mark.parametrize("B,H", POINT_SHAPES)
+def test_lstm_point_fwd_arms(dev, B, H, parts, mode):
+    """mstts_lstm_point_fwd for every slab count it has a kernel for and one it has none for, in the plain form and in the sequence form
+    (lengths with a dead row and a row at its last live step, both directions, residual, nonzero out_st / xw_st, no saves), with default
+    and with wider state / output row strides (columns behind H keep their NaN)."""
+    for form in ("plain", "seq", "rev"):
+        for wide in (False, True):
+            _point_fwd_run(dev, B, H, parts, mode, form, wide)
+
+
+@pytest.mark.parametrize("form", ["plain", "seq", "rev"])
+@pytest.mark.parametrize("B,H", POINT_SHAPES)
+def test_lstm_point_fwd_without_out_and_with_saves(dev, B, H, form):
+    """out == NULL (states and saves only) and the sequence form with the BPTT saves: a dead row saves zero activations and c_raw = c_prev."""
+    for parts in (1, 3):
+        _point_fwd_run(dev, B, H, parts, "bias", form, True, out_null=True, saves=True)
+        _point_fwd_run(dev, B, H, parts, "xw", form, False, saves=True)
+
+
+def _point_bwd_run(dev, B, H, po, po2, ph, form, masks=True, dout=True, dout2=False, dhs2=False, fuse=None, seed=0, launch=True):
+    """One backward case: (descriptor, checker).  po / po2 / ph: slabs of d_out / d_out2 / d_h_state2; fuse: None or dq_bf16 (0 / 1)."""
+    T, seq, A = POINT_T, form != "plain", 128
+    lengths, live, pos = _point_rows(B, form)
+    rows, lv = np.arange(B), torch.tensor(live)[:, None]
+    ld2 = H + 4
+    g64 = torch.tensor(np.random.default_rng(seed + 1).normal(size=(B, 4 * H)), dtype=torch.float64, requires_grad=True)
+    cp, hp = _r(dev, B, H, seed=seed + 3), _r(dev, B, H, seed=seed + 4)
+    zc, zh = (_bits(dev, B, H, seed=seed + 5), _bits(dev, B, H, seed=seed + 6)) if masks else (None, None)
+    cp64, hp64 = cp.double().cpu().requires_grad_(True), hp.double().cpu().requires_grad_(True)
+    i, j, f, o = g64.chunk(4, 1)
+    si, tj, sf, so = torch.sigmoid(i), torch.tanh(j), torch.sigmoid(f + 1.0), torch.sigmoid(o)
+    c = sf * cp64 + si * tj
+    m = so * torch.tanh(c)
+    kc, kh = (0.9 * zc.cpu().double(), 0.9 * zh.cpu().double()) if masks else (0.9, 0.9)
+    c2, h2 = torch.where(lv, kc * (c - cp64) + cp64, cp64), torch.where(lv, kh * (m - hp64) + hp64, hp64)
+    acts, craw = torch.cat([si, tj, sf, so], 1).detach().float().to(dev), c.detach().float().to(dev)
+    d_o = _r(dev, *((po, B, T, H) if seq else (po, B, H)), seed=seed + 7) if dout else None
+    d_o2 = _r(dev, po2, B, H, seed=seed + 8) if dout2 else None
+    dcs, dhs = _r(dev, B, H, seed=seed + 9), _r(dev, B, H, seed=seed + 10)
+    d_h2 = _r(dev, ph, B, ld2, seed=seed + 11) if dhs2 else None
+    dm64 = torch.zeros(B, H, dtype=torch.float64)
+    if dout:
+        dm64 = dm64 + torch.tensor(_f64(d_o).sum(0)[rows, pos] if seq else _f64(d_o).sum(0))
+    if dout2:
+        dm64 = dm64 + d_o2.double().cpu().sum(0)
+    dhs64 = dhs.double().cpu() + (d_h2.double().cpu().sum(0)[:, :H] if dhs2 else 0.0)
+    dq = wq = wq_t = None
+    if fuse is not None:
+        dq, wq = _r(dev, B, A, seed=seed + 12), _r(dev, H, A, seed=seed + 13, scale=0.2)
+        wq_t = wq.view(H, A // 4, 4).permute(1, 0, 2).contiguous()           # [A/4][H][4] (mstts_transpose01(Wq, wq_t, H, A/4, 4))
+        rnd = (lambda t: t.bfloat16().double().cpu()) if fuse else (lambda t: t.double().cpu())
+        dm64 = dm64 + rnd(dq) @ rnd(wq).T
+    ((torch.where(lv, m, torch.zeros_like(m)) * dm64).sum() + (c2 * dcs.double().cpu()).sum() + (h2 * dhs64).sum()).backward()
+    dg, dcp, dhp = _nan(dev, B, 4 * H), _nan(dev, B, H), _nan(dev, B, H)
+    dgp = _nan(dev, B, T, 4 * H) if seq else None
+    b = lib.LstmPointBwd()
+    b.B, b.H = B, H
+    if dout:
+        b.d_out, b.dout_sb, b.dout_st, b.dout_parts, b.dout_pstride = lib.ptr(d_o), (T * H if seq else H), (H if seq else 0), po, d_o[0].numel()
+    if dout2:
+        b.d_out2, b.dout2_parts, b.dout2_pstride = lib.ptr(d_o2), po2, B * H
+    b.d_c_state, b.d_h_state = lib.ptr(dcs), lib.ptr(dhs)
+    if dhs2:
+        b.d_h_state2, b.dhs2_ld, b.dhs2_parts, b.dhs2_pstride = lib.ptr(d_h2), ld2, ph, B * ld2
+    b.acts, b.c_raw, b.c_prev, b.zc, b.zh, b.zoneout = lib.ptr(acts), lib.ptr(craw), lib.ptr(cp), lib.ptr(zc), lib.ptr(zh), 0.1
+    lens = torch.tensor(lengths, device=dev) if seq else None
+    if seq:
+        b.lengths, b.step, b.reverse, b.dgates_pos, b.dgp_sb, b.dgp_st = lib.ptr(lens), POINT_STEP, int(form == "rev"), lib.ptr(dgp), T * 4 * H, 4 * H
+    b.dgates, b.d_c_prev, b.d_h_prev = lib.ptr(dg), lib.ptr(dcp), lib.ptr(dhp)
+    if fuse is not None:
+        b.dq, b.wq_t, b.A, b.dq_bf16 = lib.ptr(dq), lib.ptr(wq_t), A, fuse
+    keep = (cp, hp, zc, zh, acts, craw, d_o, d_o2, dcs, dhs, d_h2, dq, wq_t, lens)
+    tag = "bwd %s (%d,%d,%d)%s%s%s%s: " % (form, po, po2, ph, "" if masks else " no masks", "" if dout else " no d_out", " d_out2" if dout2 else "",
+                                           " dhs2" if dhs2 else "")
+
+    def check(tol=2e-5):
+        errs = [_chk(tag + "dgates", dg, t2n(g64.grad), tol), _chk(tag + "d_c_prev", dcp, t2n(cp64.grad), tol),
+                _chk(tag + "d_h_prev", dhp, t2n(hp64.grad), tol)]
+        if seq:
+            ref = np.full((B, T, 4 * H), np.nan)
+            ref[rows, pos] = t2n(g64.grad)
+            _only_at(tag + "dgates_pos", dgp, ref, tol)
+        return max(errs), keep
+
+    if launch:
+        lib.call("mstts_lstm_point_bwd", C.byref(b))
+    return b, check
+
+
+# (form, masks, d_out, d_out2, d_h_state2) - a slab count above 1 needs its operand whatever the row says
+POINT_BWD_VARIANTS = [("plain", True, True, True, True), ("plain", False, True, False, False), ("seq", True, True, False, True),
+                      ("seq", True, False, True, False), ("rev", False, True, True, True), ("rev", True, True, False, False)]
+
+
+@pytest.mark.parametrize("po,po2,ph", [(1, 1, 1), (1, 1, 4), (4, 1, 4), (1, 1, 8), (8, 1, 8), (8, 1, 1), (1, 1, 2),      # the instantiated triples
+                                       (2, 1, 1), (1, 3, 1)])                                                        # none of them: run-time slab counts
+@pytest.mark.parametrize("B,H", POINT_SHAPES)
+def test_lstm_point_bwd_arms(dev, B, H, po, po2, ph):
+    """mstts_lstm_point_bwd for every (d_out, d_out2, d_h_state2) slab triple it has a kernel for and two it has none for (one of them
+    d_out2 in 3 slabs), plain and sequence form (dead row, reverse, dgates_pos written at the row's position only), with and without
+    keep masks, d_out, d_out2 and d_h_state2 (row stride wider than H)."""
+    for form, masks, dout, dout2, dhs2 in POINT_BWD_VARIANTS:
+        _point_bwd_run(dev, B, H, po, po2, ph, form, masks, dout or po > 1, dout2 or po2 > 1, dhs2 or ph > 1)[1]()
+
+
+@pytest.mark.parametrize("bf16", [0, 1])
+@pytest.mark.parametrize("ph", [1, 2, 4, 8])
+def test_lstm_point_bwd_fused_query(dev, ph, bf16):
+    """The query layer's data gradient dq . Wq^T folded into the output gradient (B, H, A = 3, 128, 128), fp32 and with both operands
+    rounded to bf16 (the reference rounds them the same way before its fp64 product)."""
+    for masks, dhs2 in ((True, True), (False, ph > 1)):
+        _point_bwd_run(dev, 3, 128, 1, 1, ph, "plain", masks, True, False, dhs2, fuse=bf16)[1]()
+
+
+def test_lstm_point_bwd_fused_query_refusals(dev):
+    """What the fused query gradient does not cover is refused on the host, nothing is launched (the outputs keep their NaN)."""
+    L = lib.load()
+    b, check = _point_bwd_run(dev, 5, 24, 1, 1, 1, "plain", fuse=0, launch=False)              # H % 128 != 0
+    assert L.mstts_lstm_point_bwd(C.byref(b), lib.stream()) != 0
+    b, check = _point_bwd_run(dev, 3, 128, 1, 1, 1, "plain", dout2=True, fuse=0, launch=False)  # with d_out2
+    assert L.mstts_lstm_point_bwd(C.byref(b), lib.stream()) != 0
+    b, check = _point_bwd_run(dev, 3, 128, 1, 1, 1, "plain", fuse=0, launch=False)
+    b.A = 64                                                                                  # A != 128
+    assert L.mstts_lstm_point_bwd(C.byref(b), lib.stream()) != 0
+    b.A, b.wq_t = 128, b.wq_t + 4                                                             # wq_t off its 16-byte alignment
+    assert L.mstts_lstm_point_bwd(C.byref(b), lib.stream()) != 0
+    b.wq_t -= 4
+    lib.call("mstts_lstm_point_bwd", C.byref(b))                                              # the same descriptor, repaired, runs
+    check()
+
+
+@pytest.mark.parametrize("ph", [1, 2, 4, 8])
+@pytest.mark.parametrize("B,H", POINT_SHAPES)
+def test_lstm_point_bwd_pair_arms(dev, B, H, ph):
+    """mstts_lstm_point_bwd_pair for each d_h_state2 slab count it covers: the two directions of a BiLSTM step (lengths, dgates_pos, the
+    second member reversed), each member against fp64 autograd of its own cell."""
+    for dhs2 in ((True, False) if ph == 1 else (True,)):
+        (ba, ca), (bb, cb) = (_point_bwd_run(dev, B, H, 1, 1, ph, form, dhs2=dhs2, seed=seed, launch=False) for form, seed in (("seq", 0), ("rev", 50)))
+        lib.call("mstts_lstm_point_bwd_pair", C.byref(ba), C.byref(bb))
+        ca(); cb()
