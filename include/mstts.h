@@ -630,6 +630,20 @@ int mstts_ge2e_contrast_fwd_bwd(const float* x, int64_t ldx, int64_t S, int64_t 
 int mstts_mel_bank_gather(const float* bank, const int64_t* frame_off, int64_t n_files, const int32_t* table, int64_t N, int64_t T,
                           int64_t n_mel, float* out, int32_t* status, mstts_stream_t s);
 
+/* ---- batch features out of a device-resident bank of waveforms (the Taco1 vocoder trainer's feeder; Taco1_Mel_to_Spect/Feeder.py:46-105;
+ * csrc/stft_bank.hip): bank fp32 holds every file's trimmed waveform back to back, file f at samples sig_off[f] .. sig_off[f + 1] (int64
+ * [n_files + 1]); files int32 [N] = the file of each output row; window, twiddle, mel_basis, mel_rng and the scalars exactly as
+ * mstts_stft_fft takes them.  With F_r = 1 + len_r / hop:
+ *   mel_out[r, t, :] / spec_out[r, t, :] = frame t of mstts_stft_fft on waveform files[r], bit for bit   for t < F_r,   0 for t >= F_r
+ * (the symmetric mel normalisation and the [0, 1] spectrogram; no flags).  mel_out [N, T, n_mel], spec_out [N, T, n_fft/2+1]; either may
+ * be NULL, not both; every element is stored exactly once.  A row with files[r] outside [0, n_files), len_r <= n_fft / 2 or F_r > T reads
+ * nothing from the bank, is written as zeros and sets bit 0 of status[0] (int32; the caller zeroes it once).  N * T < 2^31.  All pointers
+ * are device pointers. */
+int mstts_stft_bank_batch(const float* bank, const int64_t* sig_off, int64_t n_files, const int32_t* files, int64_t N, int64_t T,
+                          float preemph, const float* window, const float* twiddle, const float* mel_basis, const int32_t* mel_rng,
+                          int32_t n_fft, int32_t hop, int32_t win, int32_t n_mel, float max_abs, float ref_level_db,
+                          float* mel_out, float* spec_out, int32_t* status, mstts_stream_t s);
+
 /* ---- bf16 variants of the skinny products (BASELINE config 3, "bf16 with fp32 master"): the kernel W is a packed bf16 copy made by
  * mstts_pack_bf16_fwd / _bwd from the fp32 master (round to nearest even; lane-consumption order, opaque), the activation block is
  * rounded to bf16 on the way into LDS, accumulation and the partial slabs are fp32:

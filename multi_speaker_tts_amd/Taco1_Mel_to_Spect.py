@@ -4,10 +4,15 @@
 The saved file (`mel_to_spectrogram.pt` under hp.Taco1_Mel_to_Spect.Checkpoint_Path) is exactly what
 ``MSTTS_SV.Tacotron2.Vocoder_Load`` reads, as in the reference where the TTS model restores the vocoder scope from the
 vocoder trainer's checkpoint directory (MSTTS_SV.py:229-234).  Patterns are dicts {'Mel': [B,T,80], 'Spectrogram': [B,T,1025]}
-(the reference's Taco1 feeder pads pickled (mel, spectrogram) pairs to the batch maximum); without one a synthetic pattern
-of the trainer's batch shape is used.
+(the reference's Taco1 feeder pads pickled (mel, spectrogram) pairs to the batch maximum).  ``Train()`` feeds itself from the pattern
+set under hp.Taco1_Mel_to_Spect.Train.Pattern_Path when its metadata file exists: from a device bank of the set's waveforms
+(taco1_feeder.SignalBank / Taco1Feeder: one STFT launch per batch; Taco1_Mel_to_Spect_Pattern_Generate writes such a set) when every
+file carries its 'Signal' and the bank fits its budget, else from the reference's host loop (taco1_feeder.PatternFeeder); without a
+metadata file a synthetic pattern of the trainer's batch shape is used.
 """
 from __future__ import annotations
+
+import os
 
 import numpy as np
 
@@ -17,6 +22,7 @@ from .taco1_trainer import Taco1TrainEngine, learning_rate
 from .training import DropIn
 
 TRAIN_KEYS = ("Global_Step", "Learning_Rate", "Loss", "Train_OP")
+INFERENCE_IN_TRAIN_FILE = "Mel_to_Spect_Inference_in_Train.txt"           # one wav path per line (Taco1_Mel_to_Spect.py:111-116)
 
 
 class Mel_to_Spect(DropIn):
@@ -25,6 +31,8 @@ class Mel_to_Spect(DropIn):
 
     def __init__(self, device="cuda", seed=1234, dims: Dims = None):
         self.device = device
+        self.seed = seed
+        self.feeder = None
         self.engine = Taco1TrainEngine(dims, device=device, seed=seed)
         self.params = self.engine.params
         self.train_Tensor_Dict = {k: k for k in TRAIN_KEYS}
@@ -45,6 +53,43 @@ class Mel_to_Spect(DropIn):
         res = self.engine.scalars(w)
         res.update({"Global_Step": step, "Learning_Rate": learning_rate(step), "Train_OP": None})
         return res
+
+    def _make_feeder(self):
+        """The device feeder when every file of the pattern set carries its 'Signal' and the bank fits its budget; else one line saying
+        which of the two failed, and the host feeder."""
+        from . import taco1_feeder as TF
+        md = TF.load_metadata()
+        names, signals = md["File_List"], md.get("Signal_Length_Dict", {})
+        missing = sum(1 for n in names if n not in signals)
+        if missing:
+            print("{} of {} pattern files carry no 'Signal': feeding from the host (PatternFeeder).".format(missing, len(names)))
+            return TF.PatternFeeder(seed=self.seed, md=md)
+        try:
+            bank = TF.SignalBank.from_patterns(device=self.device, md=md)
+        except TF.BankBudgetError as e:
+            print("The signal bank does not fit ({}): feeding from the host (PatternFeeder).".format(e))
+            return TF.PatternFeeder(seed=self.seed, md=md)
+        return TF.Taco1Feeder(bank, seed=self.seed)
+
+    def Train(self, max_steps=None, pattern_fn=None):
+        """Without a pattern_fn, when the metadata file of hp.Taco1_Mel_to_Spect.Train.Pattern_Path exists: every step's batch comes from
+        the pattern set (`_make_feeder`); otherwise as DropIn.Train."""
+        from . import taco1_feeder as TF
+        if pattern_fn is None and os.path.exists(TF.metadata_path()):
+            if self.feeder is None:
+                self.feeder = self._make_feeder()
+            pattern_fn = self.feeder.Get_Train_Pattern
+        return super().Train(max_steps, pattern_fn)
+
+    def _after_step(self, result):
+        """Taco1_Mel_to_Spect.py:108-135: the periodic inference on the wav paths of Mel_to_Spect_Inference_in_Train.txt."""
+        if hasattr(self.feeder, "check_status"):
+            self.feeder.check_status()               # right behind the loss read of Train_Step: the stream is already drained
+        if (result["Global_Step"] + 1) % hp.Taco1_Mel_to_Spect.Train.Inference_Timing == 0 and os.path.exists(INFERENCE_IN_TRAIN_FILE):
+            with open(INFERENCE_IN_TRAIN_FILE, "r") as f:
+                paths = [line.strip() for line in f.readlines() if line.strip()]
+            if paths:
+                self.Inference(paths)
 
     def Inference(self, speaker_Wav_Paths, export=True, griffin_lim_seed=0):
         """Taco1_Mel_to_Spect.py:137-178 (the feeder's Get_Inference_Pattern, Feeder.py:114-147, included): wav files -> trimmed

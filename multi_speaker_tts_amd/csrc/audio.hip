@@ -4,7 +4,7 @@
 // fp32 MFMA GEMM (overlapping frames are just rows with stride hop), followed by the 1025 -> 80 mel
 // filterbank GEMM and a fused dB / normalise pass.
 #include "common.h"
-#include "fft_stages.h"
+#include "stft_frame.h"
 
 namespace mstts {
 
@@ -37,12 +37,7 @@ __global__ void db_normalize_kernel(float* __restrict__ mel, long n, float max_a
 }
 
 // ---------------------------------------------------------------------------------------------
-// The same transform as ONE launch: a workgroup per frame, real FFT in LDS.
-//   x[i] = window[i - off] * preemph(reflect(f*hop + i - n_fft/2))   (0 outside the window)       Audio.py:42-48,62-64
-//   z[m] = x[2m] + i x[2m+1]  ->  Stockham radix-4 FFT of n_fft/2 complex points (ping-pong LDS buffers, twiddles from a table
-//   built in fp64 on the host)  ->  X[k] = E[k] + e^{-2 pi i k / n_fft} O[k]  ->  |X[k]|, k = 0 .. n_fft/2
-//   spec_out = clip((20 log10(max(1e-5, |X|)) - ref_db + 100) / 100, 0, 1)                          Audio.py:19-22,91-92
-//   mel_out  = symmetric-normalised dB of mel_basis . |X| over each filter's non-zero bin range     Audio.py:29-32,78-80,94-96
+// The same transform as ONE launch: a workgroup per frame, real FFT in LDS (the frame's arithmetic: stft_frame_body, csrc/stft_frame.h).
 // Several waveforms per launch: frame g belongs to waveform w with frame_off[w] <= g < frame_off[w + 1].
 // Algorithmic bytes per frame: hop new samples in, n_mel (+ n_fft/2 + 1) floats out; 5 N log2 N flops - the kernel is bound by
 // LDS round trips (log4(N/2) stages), a few microseconds per workgroup, 4+ workgroups resident per CU.
@@ -55,9 +50,6 @@ __global__ __launch_bounds__(256) void stft_fft_kernel(const float* __restrict__
                                                        float* __restrict__ spec_out, const float* __restrict__ mag_in,
                                                        const float* __restrict__ sub, float sub_scale, int flags) {
     extern __shared__ __attribute__((aligned(16))) float2 fft_lds[];
-    const int N2 = n_fft >> 1, tid = threadIdx.x;
-    float2* bufa = fft_lds;
-    float2* bufb = fft_lds + N2;
     const long g = blockIdx.x;
     int w = 0;
     for (int lo = 0, hi = nw; hi - lo > 1;) {            // uniform binary search: frame_off[w] <= g
@@ -66,85 +58,10 @@ __global__ __launch_bounds__(256) void stft_fft_kernel(const float* __restrict__
         w = lo;
     }
     const long f = g - frame_off[w], n = wav_off[w + 1] - wav_off[w];
-    const float* x = wav + wav_off[w];
-    const int off = (n_fft - win) >> 1, pad = n_fft >> 1;
-    auto sample = [&](int i) -> float {                  // windowed, pre-emphasised, reflect-padded sample i of this frame
-        if (i < off || i >= off + win) return 0.f;
-        long j = f * hop + i - pad;
-        if (j < 0) j = -j;
-        if (j >= n) j = 2 * (n - 1) - j;
-        if (j < 0) j = 0;
-        const float prev = j > 0 ? x[j - 1] : 0.f;
-        return window[i - off] * (x[j] - coef * prev);
-    };
-    const int NB = N2 + 1;
-    float* mag = reinterpret_cast<float*>(bufb);
-    if (mag_in) {
-        // second pass of the spectral-subtraction form (Audio.py:45-46): magnitudes of the first pass minus sub[k], clipped at 0
-        for (int k = tid; k < NB; k += 256) {
-            const float m = fmaxf(mag_in[g * NB + k] - (sub ? sub[k] * sub_scale : 0.f), 0.f);
-            mag[k] = m;
-            if (spec_out) {
-                const float db = 20.f * log10f(fmaxf(1e-5f, m)) - ref_db;
-                spec_out[g * NB + k] = fminf(fmaxf((db + 100.f) * 0.01f, 0.f), 1.f);
-            }
-        }
-        __syncthreads();
-    } else {
-    for (int m = tid; m < N2; m += 256) bufa[m] = make_float2(sample(2 * m), sample(2 * m + 1));
-    __syncthreads();
-    // Stockham radix-4 stages (csrc/fft_stages.h); the spectrum ends up in bufa, bufb is the other buffer
-    {
-        float2* z = fft_stockham_stages(bufa, bufb, tw, N2, n_fft, tid);
-        if (z != bufa) { bufb = bufa; bufa = z; }
-    }
-    // real-input post-processing -> magnitudes in LDS (bufb is free)
-    mag = reinterpret_cast<float*>(bufb);
-    for (int k = tid; k < NB; k += 256) {
-        const float2 zk = bufa[k & (N2 - 1)], zc = bufa[(N2 - k) & (N2 - 1)];
-        const float er = 0.5f * (zk.x + zc.x), ei = 0.5f * (zk.y - zc.y);           // E = (Z[k] + conj(Z[N2-k])) / 2
-        const float orr = 0.5f * (zk.y + zc.y), oi = -0.5f * (zk.x - zc.x);         // O = -i (Z[k] - conj(Z[N2-k])) / 2
-        const float2 t = k < N2 ? tw[k] : make_float2(-1.f, 0.f);
-        const float re = er + orr * t.x - oi * t.y, im = ei + orr * t.y + oi * t.x;
-        const float m = sqrtf(re * re + im * im);
-        mag[k] = m;
-        if (spec_out) {
-            if (flags & 2) spec_out[g * NB + k] = m;                    // raw magnitudes (first pass of the spectral-subtraction form)
-            else {
-                const float db = 20.f * log10f(fmaxf(1e-5f, m)) - ref_db;
-                spec_out[g * NB + k] = fminf(fmaxf((db + 100.f) * 0.01f, 0.f), 1.f);
-            }
-        }
-    }
-    __syncthreads();
-    }
-    if (!mel_out) return;
-    // mel: three threads per filter, each sums every third bin of the filter's non-zero range; the three partial sums are
-    // combined in fixed order (bit-reproducible).  No wave reductions: twenty dependent shuffle chains per wave cost more than
-    // the transform itself.
-    float* part = reinterpret_cast<float*>(bufa);             // the spectrum has been consumed
-    for (int c0 = 0; c0 < n_mel; c0 += 85) {                   // 85 filters x 3 threads per pass
-        const int c = c0 + tid / 3, q = tid - (tid / 3) * 3;
-        if (tid < 255 && c < n_mel) {
-            const int lo = mel_rng[2 * c], hi = mel_rng[2 * c + 1];
-            const float* row = mel_basis + (long)c * NB;
-            float acc = 0.f;
-            for (int b = lo + q; b < hi; b += 3) acc = fmaf(row[b], mag[b], acc);
-            part[tid] = acc;
-        }
-        __syncthreads();
-        if (tid < 85 && c0 + tid < n_mel) {
-            const int cc = c0 + tid;
-            const float m = (part[3 * tid] + part[3 * tid + 1]) + part[3 * tid + 2];
-            const float db = 20.f * log10f(fmaxf(1e-5f, m));
-            if (flags & 1) mel_out[g * n_mel + cc] = fminf(fmaxf((db + 100.f) * 0.01f, 0.f), 1.f);          // Audio._normalize
-            else {
-                const float v = (2.f * max_abs) * ((db + 100.f) * 0.01f) - max_abs;                        // Audio._symmetric_normalize
-                mel_out[g * n_mel + cc] = fminf(fmaxf(v, -max_abs), max_abs);
-            }
-        }
-        __syncthreads();
-    }
+    const long NB = (n_fft >> 1) + 1;
+    stft_frame_body(fft_lds, wav + wav_off[w], n, f, coef, window, tw, mel_basis, mel_rng, n_fft, hop, win, n_mel, max_abs, ref_db,
+                    mel_out ? mel_out + g * n_mel : nullptr, spec_out ? spec_out + g * NB : nullptr, mag_in ? mag_in + g * NB : nullptr, sub,
+                    sub_scale, flags);
 }
 
 }  // namespace mstts
