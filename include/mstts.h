@@ -476,8 +476,9 @@ int mstts_griffin_lim(const float* spec, const float* phase_u, const uint64_t* s
  * waveform w's ceil(n_w up / down) outputs at out + out_off[w].  phase_table [up][T], T = mstts_wav_resample_taps(up, down) =
  * ceil((2 half + 1) / up) made odd: phase_table[p][i] = h[p + (T - 1 - i) up], 0 beyond the filter - an output reads one row
  * against T consecutive inputs.  max_out = the longest output (sizes the grid).  One sum per output in ascending j by one thread: a
- * waveform gives the same bits alone or in any batch.  mstts_wav_resample_supported: the table and a tile's input span fit in LDS
- * (every pair of 8000 / 16000 / 22050 / 24000 / 44100 / 48000 Hz -> 16000 / 22050 Hz does).
+ * waveform gives the same bits alone or in any batch - and the bits of mstts_wav_resample_fir (below) at taps = T, origin = half and
+ * every output valid.  mstts_wav_resample_supported: the table and a tile's input span fit in LDS (every pair of 8000 / 16000 / 22050 /
+ * 24000 / 44100 / 48000 Hz -> 16000 / 22050 Hz does).
  *
  * mstts_wav_trim: the silence trim of Feeder.load_wav.  Frames [i hop, i hop + frame), i < 1 + (len - frame) / hop, are kept when
  * 20 log10(max(rms_i, 1e-10) / max(max_i rms_i, 1e-10)) > -top_db; bounds[w] = (start, end) = (first hop, min(len, (last + 1) hop))
@@ -500,9 +501,8 @@ int mstts_wav_gather_scale(const float* wav, const int64_t* in_off, const int64_
                            int64_t max_len, float scale, int32_t peak_normalize, int32_t stft_hop, float* out, int64_t* out_off,
                            int64_t* frame_off, mstts_stream_t s);
 
-/* The same front end by librosa's rules (Feeder.load_wav(rule="librosa"); csrc/wav_front_end_librosa.hip): resampy's kaiser_best as a
- * polyphase FIR, librosa.effects.trim's centred frames.  Layout, stream and checking conventions as above; mstts_wav_gather_scale
- * serves both rule sets.  Parity with the packages is unpinned.
+/* The same front end by librosa's rules (Feeder.load_wav(rule="librosa"); the same file, the same trim kernels under a second rule):
+ * resampy's kaiser_best as a polyphase FIR, librosa.effects.trim's centred frames.  Layout, stream and checking conventions as above; mstts_wav_gather_scale serves both rule sets.  Parity with the packages is unpinned.
  *
  * mstts_wav_resample_fir: a polyphase FIR with a host-supplied table [up][taps], an explicit origin and a valid length per waveform.
  * With q = origin + m down, p = q mod up, jm = q div up:

@@ -7,6 +7,7 @@ computation itself is ``mstts_stft_mel`` in libmstts_hip.so.
 from __future__ import annotations
 
 import functools
+from typing import Callable, NamedTuple
 
 import numpy as np
 import torch
@@ -384,7 +385,7 @@ def Griffin_Lim_Batch(spectrograms, phase=None, rng=None, seed=0, device="cuda",
 # Waveform front end on the GPU (csrc/wav_front_end.hip): what Feeder.load_wav does to decoded samples - polyphase rate conversion
 # (scipy.signal.resample_poly's arithmetic), the frame-RMS silence trim, the 0.99 scale - for a batch of waveforms, packed so that
 # the result feeds mstts_stft_fft without a copy back.  Feeder.load_wav stays what it is and is the checker.  rule="librosa" selects
-# the second rule set (kaiser_best, centred trim; csrc/wav_front_end_librosa.hip) in every function that takes `rule`.
+# the second rule set (kaiser_best, centred trim) in every function that takes `rule`: what the two differ in is the table `_rule` reads.
 # ---------------------------------------------------------------------------------------------------------------------
 def resample_ratio(rate, sample_rate):
     """(up, down) of a conversion rate -> sample_rate in lowest terms, as load_wav forms them."""
@@ -428,15 +429,9 @@ def resample_supported(up, down):
     return int(up) >= 1 and int(down) >= 1 and bool(lib.load().mstts_wav_resample_supported(int(up), int(down)))
 
 
-@functools.lru_cache(maxsize=16)
-def _resample_table(up, down, device):
-    assert lib.load().mstts_wav_resample_taps(up, down) == resample_taps(up, down)
-    return _upload(resample_phase_table(up, down).astype(np.float32).reshape(-1), torch.float32, torch.device(device))
-
-
 # --- the second rule set, rule = "librosa": librosa.core.load (resampy 0.2.x's kaiser_best) and librosa.effects.trim, restated from the
-# published algorithms in float64 (parity with the packages is unpinned).  The host functions are the checkers of
-# csrc/wav_front_end_librosa.hip.
+# published algorithms in float64 (parity with the packages is unpinned).  The host functions are the checkers of the
+# device path under that rule.
 KAISER_BEST = dict(num_zeros=64, precision=9, rolloff=0.9475937167399596, beta=14.769656459379492)
 
 
@@ -568,11 +563,6 @@ def kaiser_best_supported(up, down):
     return int(up) <= 4096 and int(down) <= 4096 and bool(lib.load().mstts_wav_resample_fir_supported(int(up), int(down), 2 * L))
 
 
-@functools.lru_cache(maxsize=16)
-def _kaiser_best_device_table(up, down, device):
-    return _upload(_kaiser_best_table_cached(up, down).astype(np.float32).reshape(-1), torch.float32, torch.device(device))
-
-
 def _pinned(array):
     """Host array -> page-locked tensor (what a non-blocking upload needs)."""
     a = torch.as_tensor(np.ascontiguousarray(array))
@@ -592,14 +582,48 @@ def _as_host_wav(y):
     return np.ascontiguousarray(np.asarray(y, dtype=np.float32).reshape(-1))
 
 
+class _Rule(NamedTuple):
+    """What one rule set of the front end is made of; everything else below is shared."""
+    out_len: Callable        # (n, up, down) -> (n_valid, n_out): computed samples, samples returned (the rest are zeros)
+    supported: Callable      # (up, down) -> the device resampler serves this ratio
+    host: Callable           # (x, up, down) -> float32: the host converter, for ratios outside the device envelope
+    table: Callable          # (up, down) -> (float64 phase table [up, taps], origin) of the device resampler
+    valid: bool              # n_valid is uploaded, for mstts_wav_resample_fir; else every output is valid: mstts_wav_resample
+    trim: str                # the trim entry's name
+
+
+def _host_resample_poly(x, up, down):
+    from scipy.signal import resample_poly
+    return resample_poly(x, up, down).astype(np.float32)
+
+
+_RULES = {
+    "scipy": _Rule(out_len=lambda n, up, down: (resample_out_len(n, up, down),) * 2, supported=resample_supported, host=_host_resample_poly,
+                   table=lambda up, down: (resample_phase_table(up, down), 10 * max(up, down)), valid=False, trim="mstts_wav_trim"),
+    "librosa": _Rule(out_len=kaiser_best_out_len, supported=kaiser_best_supported,
+                     host=lambda x, up, down: resample_kaiser_best(x, up, down).astype(np.float32),
+                     table=lambda up, down: (_kaiser_best_table_cached(up, down), kaiser_best_step(up, down)[2] * up),
+                     valid=True, trim="mstts_wav_trim_centred"),
+}
+
+
+def _rule(name):
+    return _RULES[name]
+
+
+@functools.lru_cache(maxsize=32)
+def _device_table(rule, up, down, device):
+    """(the rule's phase table on the device as float32, taps, origin)."""
+    table, origin = _rule(rule).table(up, down)
+    return _upload(table.astype(np.float32).reshape(-1), torch.float32, torch.device(device)), table.shape[1], origin
+
+
 def _resample_groups(sigs, ups_downs, dev, rule="scipy", tiling=0):
     """Upload and rate-convert: sigs = float32 host arrays, ups_downs = (up, down) per signal, (1, 1) = as it is.  One upload of all
-    samples, one of all offsets, one resample launch per distinct ratio.  Returns (buf, off, order, lens): the converted waveforms lie
-    back to back in buf from off[0] on, in the order `order` (indices into sigs), off = device int64 [len + 1] absolute offsets into
-    buf, lens = their lengths (host, in that order).  rule "librosa": kaiser_best by mstts_wav_resample_fir (lengths by
-    `kaiser_best_out_len`, the valid lengths uploaded with the offsets) instead of resample_poly by mstts_wav_resample."""
-    librosa = rule == "librosa"
-    out_len = (lambda n, up, down: kaiser_best_out_len(n, up, down)[1]) if librosa else resample_out_len
+    samples, one of all offsets (and of the valid lengths, where the rule has them), one resample launch per distinct ratio.  Returns
+    (buf, off, order, lens): the converted waveforms lie back to back in buf from off[0] on, in the order `order` (indices into sigs),
+    off = device int64 [len + 1] absolute offsets into buf, lens = their lengths (host, in that order)."""
+    r = _rule(rule)
     groups = {}
     for i, ud in enumerate(ups_downs):
         groups.setdefault(ud, []).append(i)
@@ -609,7 +633,7 @@ def _resample_groups(sigs, ups_downs, dev, rule="scipy", tiling=0):
     host = np.concatenate([sigs[i] for i in raw_order]) if raw_order else np.zeros(0, np.float32)
     raw_start = dict(zip(raw_order, np.concatenate([[0], np.cumsum([sigs[i].shape[0] for i in raw_order])]).tolist()))
     n_raw = int(host.shape[0])
-    lens = [sigs[i].shape[0] if ups_downs[i] == (1, 1) else out_len(sigs[i].shape[0], *ups_downs[i]) for i in order]
+    lens = [sigs[i].shape[0] if ups_downs[i] == (1, 1) else r.out_len(sigs[i].shape[0], *ups_downs[i])[1] for i in order]
     base = raw_start[plain[0]] if plain else n_raw                           # the converted set begins where the unchanged signals lie
     off_host = base + np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
     meta, launches, pos = [off_host], [], len(plain)
@@ -620,8 +644,8 @@ def _resample_groups(sigs, ups_downs, dev, rule="scipy", tiling=0):
         launches.append((ud, len(members), cursor, cursor + len(members) + 1, int(max(lens[pos:pos + len(members)]))))
         meta += [in_off, out_off]
         cursor += 2 * (len(members) + 1)
-        if librosa:
-            meta.append(np.asarray([kaiser_best_out_len(sigs[i].shape[0], *ud)[0] for i in members], np.int64))
+        if r.valid:
+            meta.append(np.asarray([r.out_len(sigs[i].shape[0], *ud)[0] for i in members], np.int64))
             cursor += len(members)
         pos += len(members)
     buf = torch.empty(max(int(off_host[-1]), 1), dtype=torch.float32, device=dev)
@@ -629,30 +653,26 @@ def _resample_groups(sigs, ups_downs, dev, rule="scipy", tiling=0):
         buf[:n_raw].copy_(_pinned(host), non_blocking=True)
     meta_dev = _upload(np.concatenate(meta), torch.int64, dev)
     for (up, down), n, a, b, longest in launches:
-        if librosa:
-            L = kaiser_best_step(up, down)[2]
+        table, taps, origin = _device_table(rule, up, down, str(dev))
+        if r.valid:
             lib.call("mstts_wav_resample_fir", lib.ptr(buf), lib.ptr(meta_dev, a), lib.ptr(meta_dev, b), lib.ptr(meta_dev, b + n + 1), n, longest,
-                     lib.ptr(_kaiser_best_device_table(up, down, str(dev))), up, down, 2 * L, L * up, int(tiling), lib.ptr(buf))
-            continue
-        lib.call("mstts_wav_resample", lib.ptr(buf), lib.ptr(meta_dev, a), lib.ptr(meta_dev, b), n, longest, lib.ptr(_resample_table(up, down, str(dev))),
-                 up, down, lib.ptr(buf))
+                     lib.ptr(table), up, down, taps, origin, int(tiling), lib.ptr(buf))
+        else:                                                    # (the entry restates this rule's taps and origin)
+            assert lib.load().mstts_wav_resample_taps(up, down) == taps and origin == 10 * max(up, down)
+            lib.call("mstts_wav_resample", lib.ptr(buf), lib.ptr(meta_dev, a), lib.ptr(meta_dev, b), n, longest, lib.ptr(table), up, down, lib.ptr(buf))
     return buf, meta_dev[:len(order) + 1], order, lens
 
 
-def resample_poly_batch(wavs, up, down, device="cuda", return_tensor=False):
-    """scipy.signal.resample_poly(x, up, down) for a list of waveforms in one launch (mstts_wav_resample), float32 ->
-    list of ceil(len up / down)-sample waveforms.  Ratios outside the device envelope (`resample_supported`) take the host path."""
-    g = int(np.gcd(int(up), int(down))) if up >= 1 and down >= 1 else 1
-    up, down = int(up) // g, int(down) // g
+def _resample_batch(rule, wavs, up, down, device, return_tensor, tiling=0):
+    """A list of waveforms at one ratio (lowest terms) under `rule`: one launch, or the rule's host converter outside its device envelope."""
     sigs = [_as_host_wav(y) for y in wavs]
     if not sigs:
         return []
     dev = torch.device(device)
-    if not resample_supported(up, down):
-        from scipy.signal import resample_poly
-        out = [resample_poly(s, up, down).astype(np.float32) for s in sigs]
+    if not _rule(rule).supported(up, down):
+        out = [_rule(rule).host(s, up, down) for s in sigs]
         return [torch.as_tensor(o).to(dev) for o in out] if return_tensor else out
-    buf, off, order, lens = _resample_groups(sigs, [(up, down)] * len(sigs), dev)
+    buf, off, order, lens = _resample_groups(sigs, [(up, down)] * len(sigs), dev, rule, tiling)
     bounds = np.concatenate([[0], np.cumsum(lens)]) + (0 if (up, down) == (1, 1) else sum(s.shape[0] for s in sigs))
     res = buf if return_tensor else buf.cpu().numpy()
     out = [None] * len(sigs)
@@ -662,35 +682,27 @@ def resample_poly_batch(wavs, up, down, device="cuda", return_tensor=False):
     return out
 
 
+def resample_poly_batch(wavs, up, down, device="cuda", return_tensor=False):
+    """scipy.signal.resample_poly(x, up, down) for a list of waveforms in one launch (mstts_wav_resample), float32 ->
+    list of ceil(len up / down)-sample waveforms.  Ratios outside the device envelope (`resample_supported`) take the host path."""
+    g = int(np.gcd(int(up), int(down))) if up >= 1 and down >= 1 else 1
+    return _resample_batch("scipy", wavs, int(up) // g, int(down) // g, device, return_tensor)
+
+
 def resample_kaiser_best_batch(wavs, sr_orig, sr_new, device="cuda", return_tensor=False, tiling=0):
     """librosa.core.resample(x, sr_orig, sr_new) at res_type="kaiser_best" for a list of waveforms in one launch
     (mstts_wav_resample_fir), float32 -> list of int(ceil(len ratio))-sample waveforms whose last sample is zero where resampy computes
     one fewer.  Ratios outside the device envelope (`kaiser_best_supported`) take the host path of the same rule.  tiling: 0 = the
     library's choice, 1 = row-major, 2 = phase-major (both give the same bits)."""
-    up, down = resample_ratio(sr_orig, sr_new)
-    sigs = [_as_host_wav(y) for y in wavs]
-    if not sigs:
-        return []
-    dev = torch.device(device)
-    if (up, down) == (1, 1) or not kaiser_best_supported(up, down):
-        out = [s.copy() if (up, down) == (1, 1) else resample_kaiser_best(s, up, down).astype(np.float32) for s in sigs]
-        return [torch.as_tensor(o).to(dev) for o in out] if return_tensor else out
-    buf, off, order, lens = _resample_groups(sigs, [(up, down)] * len(sigs), dev, "librosa", tiling)
-    bounds = np.concatenate([[0], np.cumsum(lens)]) + sum(s.shape[0] for s in sigs)
-    res = buf if return_tensor else buf.cpu().numpy()
-    out = [None] * len(sigs)
-    for k, i in enumerate(order):
-        piece = res[int(bounds[k]):int(bounds[k + 1])]
-        out[i] = piece if return_tensor else piece.copy()
-    return out
+    return _resample_batch("librosa", wavs, *resample_ratio(sr_orig, sr_new), device, return_tensor, tiling)
 
 
 def _trim(buf, off, lens, top_db, frame, hop, rule="scipy"):
-    """mstts_wav_trim on waveforms of the (host-known) lengths `lens` at the device offsets `off` into buf -> device (bounds [nw, 2], peak [nw])."""
+    """The rule's trim entry on waveforms of the (host-known) lengths `lens` at the device offsets `off` into buf -> device (bounds [nw, 2], peak [nw])."""
     nw, total = len(lens), int(sum(lens))
     bounds = torch.empty(nw, 2, dtype=torch.int64, device=buf.device)
     peak = torch.empty(nw, dtype=torch.float32, device=buf.device)
-    name = "mstts_wav_trim_centred" if rule == "librosa" else "mstts_wav_trim"
+    name = _rule(rule).trim
     ws = torch.empty(max(int(getattr(lib.load(), name + "_ws_floats")(total, nw)), 1), dtype=torch.float32, device=buf.device)
     lib.call(name, lib.ptr(buf), lib.ptr(off), nw, total, int(max(lens)), int(frame), int(hop), float(top_db), lib.ptr(ws),
              lib.ptr(bounds), lib.ptr(peak))
@@ -720,12 +732,8 @@ def _front_end_packed(signals, rates, sample_rate, top_db, frame, hop, scale, pe
     ratios = []
     for i, r in enumerate(rates):
         ud = resample_ratio(r, sample_rate) if int(r) != int(sample_rate) else (1, 1)
-        if ud != (1, 1) and rule == "librosa":
-            if not kaiser_best_supported(*ud):                        # outside the device envelope: the host path of the same rule
-                sigs[i], ud = resample_kaiser_best(sigs[i], *ud).astype(np.float32), (1, 1)
-        elif ud != (1, 1) and not resample_supported(*ud):            # outside the device envelope: the host's converter
-            from scipy.signal import resample_poly
-            sigs[i], ud = resample_poly(sigs[i], *ud).astype(np.float32), (1, 1)
+        if ud != (1, 1) and not _rule(rule).supported(*ud):           # outside the device envelope: the host path of the same rule
+            sigs[i], ud = _rule(rule).host(sigs[i], *ud), (1, 1)
         ratios.append(ud)
     nw = len(sigs)
     buf, off, order, lens = _resample_groups(sigs, ratios, dev, rule)

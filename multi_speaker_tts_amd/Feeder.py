@@ -152,7 +152,7 @@ def read_audio(path):
 def wav_rule(rule=None):
     """"scipy" or "librosa": the argument, else the environment variable MSTTS_WAV_RULE, else "scipy".  "scipy" is the front end as it
     always was here (resample_poly, uncentred RMS trim), bit for bit; "librosa" restates what the reference's dependency does
-    (librosa.core.load's kaiser_best rate conversion, librosa.effects.trim's centred frames; DESIGN 4.10.1)."""
+    (librosa.core.load's kaiser_best rate conversion, librosa.effects.trim's centred frames; DESIGN 4.10)."""
     r = rule if rule is not None else os.environ.get("MSTTS_WAV_RULE", "scipy")
     if r not in ("scipy", "librosa"):
         raise ValueError("rule must be 'scipy' or 'librosa', not {!r}".format(r))

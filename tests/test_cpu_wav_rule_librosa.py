@@ -1,5 +1,5 @@
 """The waveform front end by librosa's rules (rule="librosa": resampy's kaiser_best rate conversion, librosa.effects.trim's centred
-frames; csrc/wav_front_end_librosa.hip), the parts that need no GPU: entry points and defaults, the filter against an
+frames; csrc/wav_front_end.hip), the parts that need no GPU: entry points and defaults, the filter against an
 independent restatement, the polyphase table form against a literal transcription of resampy's sequential loop, an analytic signal,
 hand-derived trim cases and the metadata key.  Neither resampy nor librosa is installed where this was written: the transcription and
 the restatements below are made from the published algorithms, parity with the packages themselves is unpinned.  The helpers here are
@@ -161,8 +161,8 @@ def test_entry_points_defaults_and_refusals(tmp_path, monkeypatch):
     for name in ENTRY_POINTS:
         assert name in declared and name in lib.SIGNATURES and hasattr(cdll, name), name
     assert lib.ABI_VERSION == 5 and lib.load().mstts_abi_version() == 5                    # additions only
-    assert "wav_front_end_librosa.hip" in build.SOURCES
-    src = open(os.path.join(ROOT, "multi_speaker_tts_amd", "csrc", "wav_front_end_librosa.hip")).read()
+    assert "wav_front_end.hip" in build.SOURCES                                             # both rule sets live in the one file
+    src = open(os.path.join(ROOT, "multi_speaker_tts_amd", "csrc", "wav_front_end.hip")).read()
     assert "hipStreamSynchronize" not in src and "hipDeviceSynchronize" not in src and "hipMemcpy" not in src
     L = lib.load()
     one = ctypes.c_void_p(16)                                                              # dummies, never dereferenced

@@ -67,6 +67,37 @@ def test_resampler_batch_independence(dev):
         assert same_run and all(same_alone)
 
 
+def test_default_resampler_is_the_fir_at_a_fixed_origin(dev):
+    """mstts_wav_resample gives the bits of mstts_wav_resample_fir fed the float32 `resample_phase_table`, taps = `resample_taps`,
+    origin = 10 max(up, down) and n_valid = the output lengths, under the row-major and the phase-major tiling: the default rule IS that
+    FIR at a fixed origin, and keeps a kernel of its own only for speed.  One batch of 1 (shorter than a filter row), 700
+    (shorter than a tile) and 5 000 samples (several workgroups)."""
+    from multi_speaker_tts_amd import Audio, lib
+    lens = (1, 700, 5000)
+    x = torch.as_tensor(np.concatenate([_signal(n, 500 + i) for i, n in enumerate(lens)]))
+    for up, down in ((1, 3), (320, 441), (2, 1)):
+        assert (up, down) in envelope_ratios() and Audio.resample_supported(up, down)
+        out_lens = [Audio.resample_out_len(n, up, down) for n in lens]
+        in_off = np.concatenate([[0], np.cumsum(lens)])
+        out_off = in_off[-1] + np.concatenate([[0], np.cumsum(out_lens)])
+        meta = torch.as_tensor(np.concatenate([in_off, out_off, out_lens]).astype(np.int64)).to(dev)      # 4 + 4 + 3 words
+        table = torch.as_tensor(Audio.resample_phase_table(up, down).astype(np.float32).reshape(-1)).to(dev)
+        taps, origin = Audio.resample_taps(up, down), 10 * max(up, down)
+        got = []
+        for tiling in (None, 1, 2):                                                        # None: mstts_wav_resample
+            buf = torch.cat([x, torch.full((sum(out_lens),), float("nan"))]).to(dev)
+            if tiling is None:
+                lib.call("mstts_wav_resample", lib.ptr(buf), lib.ptr(meta, 0), lib.ptr(meta, 4), 3, max(out_lens), lib.ptr(table), up, down, lib.ptr(buf))
+            else:
+                assert lib.load().mstts_wav_resample_fir_supported(up, down, taps) == 2
+                lib.call("mstts_wav_resample_fir", lib.ptr(buf), lib.ptr(meta, 0), lib.ptr(meta, 4), lib.ptr(meta, 8), 3, max(out_lens), lib.ptr(table),
+                         up, down, taps, origin, tiling, lib.ptr(buf))
+            got.append(buf[in_off[-1]:].cpu().numpy())
+        same = [bool(np.array_equal(got[0].view(np.uint32), g.view(np.uint32))) for g in got[1:]]
+        print("resample %d/%d: %d outputs, mstts_wav_resample == FIR row-major %s, == FIR phase-major %s" % (up, down, got[0].shape[0], *same))
+        assert np.isfinite(got[0]).all() and all(same)
+
+
 @pytest.mark.parametrize("frame,hop", ((32, 16), (2048, 512)))
 def test_trim_against_fp64_restatement(dev, frame, hop):
     """trim_bounds_batch on the float32 arrays load_wav trims (host rate conversion, uploaded as they are): start and end of the fp64

@@ -1,4 +1,4 @@
-"""The waveform front end by librosa's rules on the MI355X (csrc/wav_front_end_librosa.hip; Audio.resample_kaiser_best_batch,
+"""The waveform front end by librosa's rules on the MI355X (csrc/wav_front_end.hip; Audio.resample_kaiser_best_batch,
 trim_bounds_batch / wav_front_end / wav_features with rule="librosa", Feeder.load_wav_batch and Get_Inference_Pattern) against the
 float64 host rules of tests/test_cpu_wav_rule_librosa.py.
 
