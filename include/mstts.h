@@ -859,6 +859,9 @@ typedef struct {
                                      therefore rounds the other way than bf(stored value).  tests/test_gpu_decoder_bf16_ref.py holds both launches to
                                      this statement stage by stage.
                                      (Round 4 had a software-pipelined schedule selector in this slot: removed, tools/persist_pipe.inc.) */
+    int32_t ctx_dead;             /* BPTT launch only (the forward launch ignores it): 0 or 256 = the value of mstts_decoder_train_bwd_desc.ctx_dead, see
+                                     there; w0pk must then be the mstts_persist_bwd_pack_live(..., ctx_dead) copy.  (It takes the place of the struct's
+                                     tail padding: sizeof is unchanged, a zero-initialised descriptor is the earlier behaviour.) */
 } mstts_persist_desc;
 int32_t mstts_persist_fwd_supported(int64_t B, int64_t H, int64_t M, int64_t A, int64_t T, int64_t KS);
 int64_t mstts_persist_fwd_ws_bytes(void);
@@ -880,6 +883,16 @@ typedef struct {
     const mstts_decoder_train_desc* fwd;
     float* d_pj; float* dg0; float* dg1; float* dq_hist; float* de_hist; float* d_in0;
     float* ws;
+    int32_t ctx_dead;             /* 0 or 256 (anything else: MSTTS_ERR_SHAPE).  The caller's promise about the LAST ctx_dead context columns (values
+                                     columns M - ctx_dead .. M - 1): they are constant over the positions t < lengths[b] of each row and zero past
+                                     the length - the tiled speaker embedding of memory = [encoder | speaker] - and nobody reads their gradient.  The
+                                     context is then that constant at every step; its gradient adds the same number to d_alignment at every position
+                                     of the row, which the softmax backward a (d_a - sum a d_a) removes, and its share of d_values is the gradient of
+                                     a frozen input.  With ctx_dead > 0 both drivers leave the dead columns of every d_in0 slab zero (given a
+                                     zero-initialised buffer: the launch-per-step loop clears them behind its last step, the persistent launch never
+                                     writes them), and the persistent launch never reads the dead columns of d_pj.  dg0, dg1, dq_hist, de_hist and the
+                                     live d_in0 columns are the same gradient, summed without a term that is zero in exact arithmetic.
+                                     0: every column is computed, bit for bit the earlier behaviour. */
 } mstts_decoder_train_bwd_desc;
 int mstts_decoder_train_bwd(const mstts_decoder_train_bwd_desc* d, mstts_stream_t s);
 int64_t mstts_decoder_train_bwd_ws_floats(int64_t B, int64_t H, int64_t M, int64_t A, int64_t T, int64_t CH);
@@ -891,13 +904,17 @@ int32_t mstts_decoder_train_bwd_parts(int64_t H, int64_t M);   /* number of d_in
  *                        mstts_persist_bwd_pack_floats(0 / 1 / 2) floats),  xch = mstts_persist_bwd_ws_bytes() bytes,  ctrl = 272 uint32.
  * It reads the forward history of bd->fwd and bd->d_pj and writes what mstts_decoder_train_bwd writes - dg0, dg1 [S,B,4H], dq_hist
  * (no pre-zeroing needed), de_hist - with ONE difference: d_in0 receives, in its FIRST slab only, the complete gradient of the
- * context rows (columns 0..M-1 of slots 1..S-1; the h0 columns are not written), so a consumer sums 1 slab instead of
+ * context rows (columns 0..M-ctx_dead-1 of slots 1..S-1; the h0 columns are not written), so a consumer sums 1 slab instead of
  * mstts_decoder_train_bwd_parts().  ctrl[1] == 0 and ctrl[2] == 256 after the launch <=> complete; otherwise re-run
  * mstts_decoder_train_bwd (it overwrites everything). */
 int32_t mstts_persist_bwd_supported(int64_t B, int64_t H, int64_t M, int64_t A, int64_t T, int64_t KS);
 int64_t mstts_persist_bwd_ws_bytes(void);
 int64_t mstts_persist_bwd_pack_floats(int32_t which);
 int mstts_persist_bwd_pack(const float* w0f, const float* w1, const float* wq, float* w0t, float* w1t, float* wqt, mstts_stream_t s);
+/* The same for a launch with ctx_dead (0 or 256): the on-chain half of the cell-0 kernel is cut into 32 slices of (M - ctx_dead) / 32 context
+ * columns (24 as above, or 16 = exactly one MFMA output tile).  Same buffer sizes. */
+int mstts_persist_bwd_pack_live(const float* w0f, const float* w1, const float* wq, float* w0t, float* w1t, float* wqt, int32_t ctx_dead,
+                                mstts_stream_t s);
 int mstts_decoder_train_bwd_persistent(const mstts_decoder_train_bwd_desc* bd, const mstts_persist_desc* p, mstts_stream_t s);
 
 /* ---- free-running decoder steps (inference branch of Decoder_Helper.next_inputs,

@@ -460,6 +460,7 @@ extern "C" int mstts_decoder_train_bwd(const mstts_decoder_train_bwd_desc* bd, m
                   MSTTS_ERR_SHAPE, "decoder_train_bwd: null pointer");
     const mstts_decoder_train_desc* d = bd->fwd;
     const long B = d->B, S = d->S, H = d->H, M = d->lsa.M, A = d->lsa.A, T = d->lsa.T, CH = d->lsa.CH;
+    MSTTS_REQUIRE((bd->ctx_dead == 0 || bd->ctx_dead == 256) && bd->ctx_dead <= M, MSTTS_ERR_SHAPE, "decoder_train_bwd: ctx_dead must be 0 or 256");
     const long BH = B * H, BT = B * T, W0 = M + H, W1 = 2 * H, WP = H + M;
     const int sp1 = mstts_skinny_bwd_splits(W1, 4 * H), sp0 = mstts_skinny_bwd_splits(W0, 4 * H), spq = mstts_skinny_bwd_splits(H, A);
     const int np1 = sp1 > 0 ? sp1 : 1, npq = spq > 0 ? spq : 1;
@@ -522,6 +523,13 @@ extern "C" int mstts_decoder_train_bwd(const mstts_decoder_train_bwd_desc* bd, m
         RC(mstts_lstm_point_bwd(&p, s));
         // [d_ctx_{st-1} | d_h0 state] = dg0 . w0f^T   (slabs at stride S*B*W0)
         PROBED(MSTTS_PROBE_CELL0_DGEMM, s, recurrent_bwd(w0, p.dgates, 4 * H, bd->d_in0 + st * B * W0, d_in0_slab, B, &parts0, s));
+    }
+    if (bd->ctx_dead > 0 && S * B > 0) {
+        // the dead context columns of every slab: computed above like the others (the attention backward read them, where their constant
+        // cancels), handed to the caller as the zeros the persistent launch leaves there
+        const long slabs = mstts_decoder_train_bwd_parts(H, M);
+        MSTTS_REQUIRE(hipMemset2DAsync(bd->d_in0 + (M - bd->ctx_dead), (size_t)W0 * 4, 0, (size_t)bd->ctx_dead * 4, (size_t)(slabs * S * B), (hipStream_t)s) == hipSuccess,
+                      MSTTS_ERR_LAUNCH, "decoder_train_bwd: clearing the dead context columns failed");
     }
     return MSTTS_OK;
 }

@@ -19,6 +19,15 @@
 //   * attention: row j, unit / column slice i as in the forward kernel: 96 value columns (LDS), 16 key / query units, its slice of
 //     the query kernel (LDS), and the part of G = dL/d(cumulative alignment) that its own 16 units contribute - the row's
 //     d_alignment = sum over the 8 slices of (values_i . d_ctx_i + G_i), so ONE exchange per step carries both.
+// Live context width (template parameter MC = PM - ctx_dead).  memory = [encoder 512 | speaker embedding 256, tiled over the row's
+// positions and zero past its length], so context columns 512 .. 767 are the same per-row constant at every step.  Their gradient has two
+// destinations and both discard it: in d_alignment[t] = values[t] . d_ctx + G[t] they add ONE number c to every position inside the length, and
+// the softmax backward a (d_a - sum a d_a) removes a constant (c - c sum a = 0; both terms are formed from the same gathered d_alignment);
+// in d_values they are the gradient of a frozen input.  With ctx_dead = 256 the numbers above become: context columns 16 j .. 16 j + 15 per
+// product workgroup - exactly ONE MFMA output tile, 32 instead of 64 f32-input MFMAs per wave on the chain and 16 instead of 32 kernel
+// registers per lane -, 64 value columns per attention slice (LDS 48 -> 32 KB), 128 instead of 192 four-column blocks per row in the
+// partial-d_ctx ring, two instead of four tiles in the reduction; d_in0 is stored and d_pj is read for the live columns only.  The shadow half
+// (h0 rows) and everything of cell 1 are unchanged.  ctx_dead = 0 instantiates the full width: the earlier kernel.
 // Exact fp32, fixed summation order (deterministic).  Bounded waits / abort word / start rendezvous as in the forward kernel; on
 // abort the host re-runs mstts_decoder_train_bwd.
 #include "persist_fwd_parts.h"        // (the bf16 operand types and the 16x16x32 bf16 MFMA macro; persist_common.h through it)
@@ -48,7 +57,10 @@
 #define BPTT_LATE_OP0 0         // 1 = the cell-0 update's packed operands requested behind the cell-1 shadow product (in front of the d_m0 wait) instead of in front of it
 #endif
 #ifndef BSPLIT_C0
-#define BSPLIT_C0 0             // like BSPLIT_C1 for the on-chain half of the cell-0 product (context columns)
+#define BSPLIT_C0 1             // like BSPLIT_C1 for the on-chain half of the cell-0 product (context columns), in the instantiations with ctx_dead = 256 only: their ONE
+                                // remaining output tile as three planes is 24 registers against 16 fp32 (24 bf16 MFMAs per wave for 32 f32-input ones), which fits in
+                                // what the second tile left (247 - 252 VGPRs, no scratch); at the full width the same split spills 10 - 16 registers and stays off
+                                // (profiles/persist_bwd_ctx_dead_codegen.txt, profiles/ab_bptt_ctx_dead.txt: step -0.17 ms, 3.7 x the spread)
 #endif
 namespace mstts {
 
@@ -72,7 +84,7 @@ constexpr long BO_DG1 = 0, BO_DG0 = BO_DG1 + PRING * BDG, BO_PM0 = BO_DG0 + PRIN
                BO_DA = BO_DM1 + PRING * BDM1, BXCH_FLOATS = BO_DA + PRING * BDA;
 // LDS layout (floats); small arrays first (DS immediate offsets reach 64 KB).  TT = 128 or 256 encoder positions (the kernel's instantiations);
 // the transposed value slice in LDS always covers positions 0 .. 127, with TT = 256 the positions from 128 on are read from memory (L2 hits).
-template <int TT> struct BL {
+template <int TT, int MC = PM> struct BL {
     static constexpr int B_RED = 0,                  // [8 waves][4 tiles][64 lanes][4]: product partials; the attention phases use it as scratch
               B_G = B_RED,                           //   [TT + 32 padded positions][16 units] energy gradients of this slice (attention only)
               B_PC = B_G + (TT + 32) * 16,           //   [192 pieces][4] partial d_ctx as fetched
@@ -83,8 +95,8 @@ template <int TT> struct BL {
               B_GP = B_TR + 3 * 128 + 512,           // [TT] this slice's part of G
               B_A = B_GP + TT, B_CUM = B_A + TT, B_DE = B_CUM + TT + 48, B_DC = B_DE + TT, B_DPJ = B_DC + 96, B_QF = B_DPJ + 96,
               B_DQ = B_QF + 16, B_DQF = B_DQ + 512, B_LK = B_DQF + 16, B_FLAG = B_LK + 32 * 16, B_STAMP = B_FLAG + 4,
-              B_VALT = B_STAMP + 2 * 16,             // [96 columns][128 positions] values slice, transposed
-              B_WQT = B_VALT + 96 * PT,              // [(k4 * 4 + e) * 256 + l][4]: Wq[4 l + e][16 i + 4 k4 ..]   (BPTT_QOWN: [32 registers][512 threads] cell-0 kernel, half 1)
+              B_VALT = B_STAMP + 2 * 16,             // [MC / 8 columns][128 positions] values slice, transposed (MC = the live context width: 96 or 64 columns)
+              B_WQT = B_VALT + (MC / 8) * PT,              // [(k4 * 4 + e) * 256 + l][4]: Wq[4 l + e][16 i + 4 k4 ..]   (BPTT_QOWN: [32 registers][512 threads] cell-0 kernel, half 1)
               B_WQO = B_WQT + 16 * 256 * 4,          // BPTT_QOWN: [4 units e][128 k] Wq rows of this owner's units
               B_FLOATS = B_WQO + (BPTT_QOWN ? 4 * 128 : 0);
     static_assert(B_FLOATS * 4 <= 160 * 1024, "LDS budget");
@@ -116,9 +128,14 @@ __device__ __forceinline__ pf32x4 cell_bwd(float dm, float& dhs, float& dcs, flo
 // (the transposed kernels once, when they are loaded into registers; the gate / query gradients when they are fetched) and run on
 // v_mfma_f32_16x16x32_bf16 with fp32 accumulators; the cell-update backward, the attention backward and everything exchanged stay fp32, and
 // the gate gradients written for the hoisted weight-gradient products are the unrounded ones (those products round for themselves).
-template <bool PROF, int TT, bool BF16 = false>
+// MC: the live context width, PM or PM - ctx_dead (mstts_persist_desc.ctx_dead): the context columns from MC on have no consumer for their gradient, so
+// the on-chain cell-0 product, the partial-d_ctx ring, values . d_ctx and the d_in0 rows cover columns 0 .. MC - 1 only.
+template <bool PROF, int TT, bool BF16 = false, int MC = PM>
 __global__ __launch_bounds__(PTH) void persist_bwd_kernel(PersistBwd d) {
-    typedef BL<TT> Y;
+    typedef BL<TT, MC> Y;
+    static_assert(MC == PM || MC == PM - 256, "live context width");
+    constexpr int CS = MC / 8, CQ = CS / 4, CJ = MC / 32, NB = MC / 4;      // columns per attention slice / per column quarter / per product workgroup; 4-column blocks per row
+    constexpr int NKT0 = CJ > 16 ? 2 : 1;                                   // output tiles of the on-chain cell-0 half (24 columns: the second tile is half padding; 16: exactly one)
     constexpr int B_RED = Y::B_RED, B_G = Y::B_G, B_PC = Y::B_PC, B_DA = Y::B_DA, B_PD = Y::B_PD, B_TR = Y::B_TR, B_GP = Y::B_GP, B_A = Y::B_A, B_CUM = Y::B_CUM,
                   B_DE = Y::B_DE, B_DC = Y::B_DC, B_DPJ = Y::B_DPJ, B_QF = Y::B_QF, B_DQ = Y::B_DQ, B_DQF = Y::B_DQF, B_LK = Y::B_LK, B_FLAG = Y::B_FLAG,
                   B_STAMP = Y::B_STAMP, B_VALT = Y::B_VALT, B_WQT = Y::B_WQT, B_WQO = Y::B_WQO;
@@ -148,10 +165,10 @@ __global__ __launch_bounds__(PTH) void persist_bwd_kernel(PersistBwd d) {
 
     // ---------------- once: the transposed kernels of this workgroup / wave -> registers.  w1t[h * 32 + kt * 16 + ks]: half h (0 = the
     // rows on the chain: m0 units, 1 = h1 units), output tile kt, contraction step ks of this wave's eighth; w0t likewise (context / h0)
-    constexpr bool BS1 = BSPLIT_C1 != 0 && !BF16 && BPTT_QOWN != 0 && BPTT_W0LDS != 0, BS0 = BSPLIT_C0 != 0 && !BF16;
+    constexpr bool BS1 = BSPLIT_C1 != 0 && !BF16 && BPTT_QOWN != 0 && BPTT_W0LDS != 0, BS0 = BSPLIT_C0 != 0 && !BF16 && MC < PM;    // (at the full width there are no registers for it: 10 - 16 spilled)
     // BS1 / BS0: half 0 lives as planes (w1s / w0s), the fp32 array holds half 1 only; W0L: half 1 of cell 0 lives in LDS
-    constexpr int NW0 = BF16 ? 1 : ((BS0 ? 0 : 32) + (W0L ? 0 : 32)) > 0 ? ((BS0 ? 0 : 32) + (W0L ? 0 : 32)) : 1;
-    constexpr int W0H1 = BS0 ? 0 : 32;                           // where half 1 starts in w0t (unused with W0L)
+    constexpr int W0H1 = BS0 ? 0 : 16 * NKT0;
+    constexpr int NW0 = BF16 ? 1 : (W0H1 + (W0L ? 0 : 32)) > 0 ? (W0H1 + (W0L ? 0 : 32)) : 1;                           // where half 1 starts in w0t (unused with W0L)
     float w1t[BF16 ? 1 : (BS1 ? 32 : 64)], w0t[NW0];
     pbf16x8 wb1t[BF16 ? 8 : 1], wb0t[BF16 ? 8 : 1];              // BF16: the same values as packed octets (contraction steps 8 j .. 8 j + 7 of a (half, tile))
     pbf16x8 w1s[3][BS1 ? 4 : 1];                                 // BS1: half 0 of the cell-1 kernel as three planes, [plane][kt * 2 + j]
@@ -179,7 +196,7 @@ __global__ __launch_bounds__(PTH) void persist_bwd_kernel(PersistBwd d) {
             }
             if constexpr (BS0) {
 #pragma unroll
-                for (int o = 0; o < 4; ++o) {
+                for (int o = 0; o < 2 * NKT0; ++o) {
                     float x[8];
 #pragma unroll
                     for (int e = 0; e < 8; ++e) x[e] = p0[((o >> 1) * 16 + 8 * (o & 1) + e) * 64];
@@ -187,7 +204,7 @@ __global__ __launch_bounds__(PTH) void persist_bwd_kernel(PersistBwd d) {
                 }
             } else {
 #pragma unroll
-                for (int r = 0; r < 32; ++r) w0t[r] = p0[r * 64];
+                for (int r = 0; r < 16 * NKT0; ++r) w0t[r] = p0[r * 64];
             }
             if constexpr (W0L) {
 #pragma unroll
@@ -217,9 +234,9 @@ __global__ __launch_bounds__(PTH) void persist_bwd_kernel(PersistBwd d) {
         asb += asb2;
 #endif
         for (int x = tid; x < 32 * 16; x += PTH) sm[B_LK + x] = (x < PKS * 16) ? d.loc_k[(x >> 4) * PA + 16 * gi + (x & 15)] : 0.f;
-        for (int x = tid; x < 96 * PT; x += PTH) {
+        for (int x = tid; x < CS * PT; x += PTH) {
             const int c = x >> 7, t = x & 127;
-            sm[B_VALT + x] = (arow && t < alen && t < T) ? d.values[((long)ab * T + t) * PM + 96 * gi + c] : 0.f;
+            sm[B_VALT + x] = (arow && t < alen && t < T) ? d.values[((long)ab * T + t) * PM + CS * gi + c] : 0.f;
         }
         for (int x = tid; x < TT + 48; x += PTH) sm[B_CUM + x] = 0.f;
         for (int x = tid; x < TT; x += PTH) { sm[B_GP + x] = 0.f; sm[B_A + x] = 0.f; sm[B_DE + x] = 0.f; }
@@ -256,10 +273,10 @@ __global__ __launch_bounds__(PTH) void persist_bwd_kernel(PersistBwd d) {
     const int abc = arow ? ab : 0;
 #define LOAD_ROWS(ST) do { const long r__ = (long)(ST) * B + abc; const int t__ = tid & (TT - 1);                                   \
         rav = (d.align_hist + r__ * T)[t__ < T ? t__ : 0]; rcv = (d.cum_hist + r__ * T)[t__ < T ? t__ : 0];                     \
-        rqv = (d.q_hist + r__ * PA + 16 * (g & 7))[tid & 15]; rdv = (d.d_pj + r__ * (PH + PM) + PH + 96 * (g & 7))[tid < 96 ? tid : 0]; } while (0)
+        rqv = (d.q_hist + r__ * PA + 16 * (g & 7))[tid & 15]; rdv = (d.d_pj + r__ * (PH + PM) + PH + CS * (g & 7))[tid < CS ? tid : 0]; } while (0)
 #define STORE_ROWS() do { const int t__ = tid & (TT - 1);                                                                           \
         sm[B_A + t__] = t__ < T ? rav : 0.f; sm[B_CUM + 15 + t__] = t__ < T ? rcv : 0.f;                                        \
-        sm[B_QF + (tid & 15)] = rqv; sm[B_DPJ + (tid < 96 ? tid : 0)] = rdv; } while (0)
+        sm[B_QF + (tid & 15)] = rqv; sm[B_DPJ + (tid < CS ? tid : 0)] = rdv; } while (0)
     // operands of the cell-1 update backward (saved activations, cell states, keep-masks, the projection's d_m1): HBM-cold, requested ONE STEP
     // AHEAD (here for the first step, at the bottom of the loop body for the next) by every wave outside any condition - see persist.hip
     float a1v[4], cr1, cp1, dpm1;
@@ -327,8 +344,8 @@ __global__ __launch_bounds__(PTH) void persist_bwd_kernel(PersistBwd d) {
             sm[B_G + (tid < 240 ? tid : (15 + TT) * 16 + (tid - 240))] = 0.f;
             pf32x4 pc[1] = {{0.f, 0.f, 0.f, 0.f}};
             unsigned pcoff[1];
-            pcoff[0] = (unsigned)((BO_PCTX + nslot * BPCTX + ((long)ab * 192 + 24 * gi) * 32) * 4 + 16 * (tid < 192 ? tid : 0));
-            if (!first && tid < 192) issue<1>(xr, pcoff, pc);       // requested now, it travels under the tanh terms
+            pcoff[0] = (unsigned)((BO_PCTX + nslot * BPCTX + ((long)ab * NB + (CS / 4) * gi) * 32) * 4 + 16 * (tid < 2 * CS ? tid : 0));
+            if (!first && tid < 2 * CS) issue<1>(xr, pcoff, pc);       // requested now, it travels under the tanh terms
             __syncthreads();
             PSTAMP(15);
             // tanh terms of this slice (independent of everything that arrives): fac = w_k (1 - tanh^2(keys + q + location filter))
@@ -349,46 +366,46 @@ __global__ __launch_bounds__(PTH) void persist_bwd_kernel(PersistBwd d) {
                 }
             }
             PSTAMP(0);
-            // d_ctx of this slice's 96 columns: projection part + the 8 partial tiles of the next step's cell-0 product
+            // d_ctx of this slice's CS columns: projection part + the 8 partial tiles of the next step's cell-0 product
             if (!first) {
-                if (tid < 192) {
+                if (tid < 2 * CS) {
                     { const unsigned g1[1] = {ngen}; if (!complete<1>(xr, pcoff, pc, d.ctrl, g1)) PFAIL(); }
                     *reinterpret_cast<pf32x4*>(sm + B_PC + 4 * tid) = pc[0];
                 }
             }
             PABORT_CHECK();
             PSTAMP(1);
-            if (tid < 24) {
+            if (tid < CS / 4) {
                 pf32x4 acc = {0.f, 0.f, 0.f, 0.f};
                 if (!first) {
 #pragma unroll
                     for (int src = 0; src < 8; ++src) acc += *reinterpret_cast<const pf32x4*>(sm + B_PC + (tid * 8 + src) * 4);
-                    reinterpret_cast<pf32x4*>(d.d_in0 + (sB1 + ab) * (PM + PH) + 96 * gi)[tid] = acc;       // gradient of ctx_s from cell 0 of step s+1 (d_values)
+                    reinterpret_cast<pf32x4*>(d.d_in0 + (sB1 + ab) * (PM + PH) + CS * gi)[tid] = acc;       // gradient of ctx_s from cell 0 of step s+1 (d_values)
                 }
                 *reinterpret_cast<pf32x4*>(sm + B_DC + 4 * tid) = acc + *reinterpret_cast<const pf32x4*>(sm + B_DPJ + 4 * tid);
             }
             __syncthreads();
             {   // values_i . d_ctx_i: thread (position t, column quarter cq)
                 const int t = tid & 127, cq = tid >> 7;
-                pf32x4 vg[6];
-                if (NH > 1) {       // position 128 + t: this thread's 24 value columns from memory (zero past the row's length there; L2 hits after the first step)
+                pf32x4 vg[CQ / 4];
+                if (NH > 1) {       // position 128 + t: this thread's CQ value columns from memory (zero past the row's length there; L2 hits after the first step)
                     const int tt = 128 + t < T ? 128 + t : 0;
-                    const pf32x4* vp4 = reinterpret_cast<const pf32x4*>(d.values + ((long)ab * T + tt) * PM + 96 * gi + 24 * cq);
+                    const pf32x4* vp4 = reinterpret_cast<const pf32x4*>(d.values + ((long)ab * T + tt) * PM + CS * gi + CQ * cq);
 #pragma unroll
-                    for (int c4 = 0; c4 < 6; ++c4) vg[c4] = vp4[c4];
+                    for (int c4 = 0; c4 < CQ / 4; ++c4) vg[c4] = vp4[c4];
                 }
                 float acc = 0.f, acc2 = 0.f;
 #pragma unroll 2
-                for (int c4 = 0; c4 < 6; ++c4) {
-                    const pf32x4 dcv = *reinterpret_cast<const pf32x4*>(sm + B_DC + 24 * cq + 4 * c4);
+                for (int c4 = 0; c4 < CQ / 4; ++c4) {
+                    const pf32x4 dcv = *reinterpret_cast<const pf32x4*>(sm + B_DC + CQ * cq + 4 * c4);
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) acc += sm[B_VALT + (24 * cq + 4 * c4 + e) * PT + t] * dcv[e];
+                    for (int e = 0; e < 4; ++e) acc += sm[B_VALT + (CQ * cq + 4 * c4 + e) * PT + t] * dcv[e];
                 }
                 sm[B_PD + cq * TT + t] = acc;
                 if (NH > 1) {
 #pragma unroll
-                    for (int c4 = 0; c4 < 6; ++c4) {
-                        const pf32x4 dcv = *reinterpret_cast<const pf32x4*>(sm + B_DC + 24 * cq + 4 * c4);
+                    for (int c4 = 0; c4 < CQ / 4; ++c4) {
+                        const pf32x4 dcv = *reinterpret_cast<const pf32x4*>(sm + B_DC + CQ * cq + 4 * c4);
 #pragma unroll
                         for (int e = 0; e < 4; ++e) acc2 += vg[c4][e] * dcv[e];
                     }
@@ -597,12 +614,13 @@ __global__ __launch_bounds__(PTH) void persist_bwd_kernel(PersistBwd d) {
 // six-product split; ALDS: the fp32 kernel values of this half come from LDS ([register][thread], B_WQT region) instead of registers
 #define PROD_HALF(half, WT, WBASE, WB, WS, OFF_OUT, IS_CTX, SPL, ALDS)                                                                \
         {                                                                                                                            \
+            constexpr int NKT__ = (IS_CTX) ? NKT0 : 2;               /* output tiles of this half */                                 \
             pf32x4 acc[2][2];                                                                                                        \
             _Pragma("unroll") for (int kt = 0; kt < 2; ++kt)                                                                         \
                 _Pragma("unroll") for (int t = 0; t < 2; ++t) acc[kt][t] = (pf32x4){0.f, 0.f, 0.f, 0.f};                             \
             if constexpr (BF16) {                                                                                                    \
                 _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                                        \
-                    _Pragma("unroll") for (int kt = 0; kt < 2; ++kt) {                                                               \
+                    _Pragma("unroll") for (int kt = 0; kt < NKT__; ++kt) {                                                           \
                         acc[kt][0] = PMFMA_BF16(WB[(half) * 4 + kt * 2 + j], bqh[j], acc[kt][0]);                                     \
                         acc[kt][1] = PMFMA_BF16(WB[(half) * 4 + kt * 2 + j], bqh[2 + j], acc[kt][1]);                                 \
                     }                                                                                                                \
@@ -617,7 +635,7 @@ __global__ __launch_bounds__(PTH) void persist_bwd_kernel(PersistBwd d) {
                         _Pragma("unroll") for (int e = 0; e < 8; ++e) f__[e] = bq[t * 4 + 2 * j + (e >> 2)][e & 3];                  \
                         bsp_split8(f__, bp__[0][j], bp__[1][j], bp__[2][j]);                                                         \
                     }                                                                                                                \
-                    _Pragma("unroll") for (int kt = 0; kt < 2; ++kt) {                                                               \
+                    _Pragma("unroll") for (int kt = 0; kt < NKT__; ++kt) {                                                           \
                         pf32x4 a__ = {0.f, 0.f, 0.f, 0.f};                                                                           \
                         _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                                              \
                             a__ = PMFMA_BF16(WS[2][kt * 2 + j], bp__[0][j], a__);                                                    \
@@ -633,7 +651,7 @@ __global__ __launch_bounds__(PTH) void persist_bwd_kernel(PersistBwd d) {
                 }                                                                                                                    \
             } else {                                                                                                                 \
                 _Pragma("unroll") for (int ks = 0; ks < 16; ++ks)                                                                    \
-                    _Pragma("unroll") for (int kt = 0; kt < 2; ++kt) {                                                               \
+                    _Pragma("unroll") for (int kt = 0; kt < NKT__; ++kt) {                                                           \
                         float a__;                                                                                                   \
                         if constexpr (ALDS) a__ = sm[B_WQT + (kt * 16 + ks) * PTH + tid]; else a__ = WT[(WBASE) + kt * 16 + ks];     \
                         acc[kt][0] = PMFMA(a__, bq[ks >> 2][ks & 3], acc[kt][0]);                                                    \
@@ -642,19 +660,19 @@ __global__ __launch_bounds__(PTH) void persist_bwd_kernel(PersistBwd d) {
             }                                                                                                                        \
             if ((half) == 1) __syncthreads();                        /* the first tile's readers are done */                         \
             if constexpr (BF16 || !(SPL)) {                          /* (the split form has stored its tiles already; it is used for half 0 only) */ \
-                _Pragma("unroll") for (int kt = 0; kt < 2; ++kt)                                                                     \
+                _Pragma("unroll") for (int kt = 0; kt < NKT__; ++kt)                                                                 \
                     _Pragma("unroll") for (int t = 0; t < 2; ++t)                                                                    \
                         *reinterpret_cast<pf32x4*>(sm + B_RED + ((wave * 4 + kt * 2 + t) * 64 + lane) * 4) = acc[kt][t];             \
             }                                                                                                                        \
             PABORT_CHECK();                                                                                                          \
-            if (tid < 256) {                                                                                                         \
+            if (tid < 128 * NKT__) {                                 /* (tile = kt * 2 + row tile) */                                \
                 const int tile = tid >> 6, l = tid & 63, kt = tile >> 1, t = tile & 1;                                               \
                 pf32x4 r = {0.f, 0.f, 0.f, 0.f};                                                                                     \
                 _Pragma("unroll") for (int w = 0; w < 8; ++w) r += *reinterpret_cast<const pf32x4*>(sm + B_RED + ((w * 4 + tile) * 64 + l) * 4); \
                 const int blk = 4 * kt + (l >> 4), row = 16 * t + (l & 15);                                                          \
                 if (IS_CTX) {                                                                                                        \
-                    if (blk < 6) {                                                                                                   \
-                        const long o = (((long)row * 192 + 6 * gj + blk) * 8 + gi) * 4;                                              \
+                    if (blk < CJ / 4) {                                                                                              \
+                        const long o = (((long)row * NB + (CJ / 4) * gj + blk) * 8 + gi) * 4;                                        \
                         xpublish(xr, (unsigned)((BO_PCTX + slot * BPCTX + o) * 4), r, gen);                                                 \
                     }                                                                                                                \
                 } else {                                                                                                             \
@@ -770,8 +788,9 @@ __global__ __launch_bounds__(PTH) void persist_bwd_kernel(PersistBwd d) {
 // ---- packers.  Contraction step ks of wave w's eighth: group mm = ks >> 2 -> producer column slice j' = 4 w + mm, unit 32 j' + 4 i + (ks & 3); the
 // MFMA's inner index (lane >> 4) is the gate.  Output tile kt, row m = lane & 15 of the A operand: cell 1 half 0 = m0 unit 32 j + 16 kt + m
 // (kernel row = that), half 1 = h1 unit (row H + ...); cell 0 half 0 = context column 24 j + 16 kt + m when 16 kt + m < 24 (else a zero
-// row), half 1 = h0 unit (row M + ...).
-__global__ void persist_pack_bwd_kernel(const float* __restrict__ w0f, const float* __restrict__ w1, float* __restrict__ w0t, float* __restrict__ w1t) {
+// row), half 1 = h0 unit (row M + ...).  cj = context columns per workgroup: 24, or 16 with ctx_dead == 256 (tile 0 is then column 16 j + m,
+// tile 1 all zero rows that the kernel never loads).
+__global__ void persist_pack_bwd_kernel(const float* __restrict__ w0f, const float* __restrict__ w1, float* __restrict__ w0t, float* __restrict__ w1t, int cj) {
     const long n = 256L * 8 * 64 * 64;
     for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < 2 * n; p += (long)gridDim.x * blockDim.x) {
         const bool c1 = p >= n;
@@ -790,7 +809,7 @@ __global__ void persist_pack_bwd_kernel(const float* __restrict__ w0f, const flo
             const long row = (half == 0 ? 0 : PH) + 32 * gj + ok;
             v = w1[row * 4 * PH + col];
         } else if (half == 0) {
-            v = ok < 24 ? w0f[(long)(24 * gj + ok) * 4 * PH + col] : 0.f;
+            v = ok < cj ? w0f[(long)(cj * gj + ok) * 4 * PH + col] : 0.f;
         } else {
             v = w0f[(long)(PM + 32 * gj + ok) * 4 * PH + col];
         }
@@ -839,13 +858,16 @@ extern "C" int mstts_persist_unpack_history(const float* opk, const mstts_decode
 
 // Every instantiation, once: 128 or 256 encoder positions (beyond 128 the positions from 128 on are read from memory); fp32 or bf16
 // recurrent products; with or without the stage stamps.  bwd_index() is the row's place in the table.
-#define PBW_INST(P_, T_, B16_) {persist_bwd_kernel<P_, T_, B16_>, (int)(BL<T_>::B_FLOATS * 4)}
-static const PersistInst<PersistBwd> BWD_TABLE[] = {
-    PBW_INST(false, 128, false), PBW_INST(true, 128, false), PBW_INST(false, 128, true), PBW_INST(true, 128, true),
-    PBW_INST(false, 256, false), PBW_INST(true, 256, false), PBW_INST(false, 256, true), PBW_INST(true, 256, true)};
+// The same eight again for the live context width PM - 256 (ctx_dead == 256).
+#define PBW_INST(P_, T_, B16_, MC_) {persist_bwd_kernel<P_, T_, B16_, MC_>, (int)(BL<T_, MC_>::B_FLOATS * 4)}
+#define PBW_EIGHT(MC_)                                                                                                                     \
+    PBW_INST(false, 128, false, MC_), PBW_INST(true, 128, false, MC_), PBW_INST(false, 128, true, MC_), PBW_INST(true, 128, true, MC_),   \
+    PBW_INST(false, 256, false, MC_), PBW_INST(true, 256, false, MC_), PBW_INST(false, 256, true, MC_), PBW_INST(true, 256, true, MC_)
+static const PersistInst<PersistBwd> BWD_TABLE[] = {PBW_EIGHT(PM), PBW_EIGHT(PM - 256)};
+#undef PBW_EIGHT
 #undef PBW_INST
-constexpr int bwd_index(bool t256, bool bf16, bool stamps) { return (t256 * 2 + bf16) * 2 + stamps; }
-static_assert(sizeof(BWD_TABLE) / sizeof(BWD_TABLE[0]) == bwd_index(true, true, true) + 1, "one table row per (positions, bf16, stamps)");
+constexpr int bwd_index(bool dead, bool t256, bool bf16, bool stamps) { return ((dead * 2 + t256) * 2 + bf16) * 2 + stamps; }
+static_assert(sizeof(BWD_TABLE) / sizeof(BWD_TABLE[0]) == bwd_index(true, true, true, true) + 1, "one table row per (live width, positions, bf16, stamps)");
 
 extern "C" int64_t mstts_persist_bwd_ws_bytes(void) { return BXCH_FLOATS * 4; }
 extern "C" int64_t mstts_persist_bwd_pack_floats(int32_t which) { return which < 2 ? 256L * 8 * 64 * 64 : 8L * 16 * 256 * 4; }
@@ -857,8 +879,14 @@ extern "C" int32_t mstts_persist_bwd_supported(int64_t B, int64_t H, int64_t M, 
 }
 
 extern "C" int mstts_persist_bwd_pack(const float* w0f, const float* w1, const float* wq, float* w0t, float* w1t, float* wqt, mstts_stream_t s) {
+    return mstts_persist_bwd_pack_live(w0f, w1, wq, w0t, w1t, wqt, 0, s);
+}
+
+extern "C" int mstts_persist_bwd_pack_live(const float* w0f, const float* w1, const float* wq, float* w0t, float* w1t, float* wqt, int32_t ctx_dead,
+                                           mstts_stream_t s) {
     MSTTS_REQUIRE(w0f && w1 && wq && w0t && w1t && wqt, MSTTS_ERR_SHAPE, "persist_bwd_pack: null pointer");
-    hipLaunchKernelGGL(persist_pack_bwd_kernel, dim3(4096), dim3(256), 0, (hipStream_t)s, w0f, w1, w0t, w1t);
+    MSTTS_REQUIRE(ctx_dead == 0 || ctx_dead == 256, MSTTS_ERR_SHAPE, "persist_bwd_pack: ctx_dead must be 0 or 256");
+    hipLaunchKernelGGL(persist_pack_bwd_kernel, dim3(4096), dim3(256), 0, (hipStream_t)s, w0f, w1, w0t, w1t, (int)((PM - ctx_dead) / 32));
     MSTTS_CHECK_LAUNCH("persist_pack_bwd");
     hipLaunchKernelGGL(persist_pack_wqt_kernel, dim3(8 * 16 * 4), dim3(256), 0, (hipStream_t)s, wq, wqt);
     MSTTS_CHECK_LAUNCH("persist_pack_wqt");
@@ -870,6 +898,8 @@ extern "C" int mstts_decoder_train_bwd_persistent(const mstts_decoder_train_bwd_
                   p->xch && p->ctrl, MSTTS_ERR_SHAPE, "decoder_train_bwd_persistent: null pointer");
     const mstts_decoder_train_desc* d = bd->fwd;
     const long B = d->B, S = d->S, H = d->H, M = d->lsa.M, A = d->lsa.A, T = d->lsa.T;
+    MSTTS_REQUIRE((p->ctx_dead == 0 || p->ctx_dead == 256) && bd->ctx_dead == p->ctx_dead, MSTTS_ERR_SHAPE,
+                  "decoder_train_bwd_persistent: ctx_dead must be 0 or 256, the same in both descriptors (the packed cell-0 kernel is cut for it)");
     MSTTS_REQUIRE(d->lsa.B == B && mstts_persist_bwd_supported(B, H, M, A, T, d->lsa.KS), MSTTS_ERR_SHAPE,
                   "decoder_train_bwd_persistent: shape or device not supported (see mstts_persist_bwd_supported)");
     MSTTS_REQUIRE(d->zc0 && d->zh0 && d->zc1 && d->zh1, MSTTS_ERR_SHAPE, "decoder_train_bwd_persistent: the four zoneout keep-masks are required");
@@ -890,7 +920,7 @@ extern "C" int mstts_decoder_train_bwd_persistent(const mstts_decoder_train_bwd_
     a.dg0 = bd->dg0; a.dg1 = bd->dg1; a.dq_hist = bd->dq_hist; a.de_hist = bd->de_hist; a.d_in0 = bd->d_in0;
     a.xch = p->xch; a.ctrl = p->ctrl; a.stamps = (unsigned long long*)p->stamps;
     persist_knobs(a, p->selftest_fail_step, p->near_xcd);
-    const PersistInst<PersistBwd>& k = BWD_TABLE[bwd_index(T > 128, p->recurrent_bf16 != 0, p->stamps != nullptr)];
+    const PersistInst<PersistBwd>& k = BWD_TABLE[bwd_index(p->ctx_dead != 0, T > 128, p->recurrent_bf16 != 0, p->stamps != nullptr)];
     hipLaunchKernelGGL(k.kernel, dim3(PWG), dim3(PTH), (size_t)k.lds_bytes, hs, a);
     MSTTS_CHECK_LAUNCH("persist_bwd");
     return MSTTS_OK;

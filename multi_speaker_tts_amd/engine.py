@@ -190,6 +190,10 @@ class TrainEngine(Engine):
         self.persist_stamps = None           # bench: 256 x 16 int64 tensor -> per-stage ticks of the next persistent launch
         self.persist_bwd = self.persist and os.environ.get("MSTTS_PERSIST_BWD", "1") != "0" and bool(lb.mstts_persist_bwd_supported(1, H, M, d.att, 1, d.att_k))
         self.persist_bwd_fallbacks = 0
+        # mstts_decoder_train_bwd_desc.ctx_dead: the engine builds values = [encoder | tiled speaker embedding, zero past the length] itself
+        # (mstts_speaker_tile) and the speaker stack is frozen, so the speaker columns of the context gradient have no reader (0 / 256 are
+        # the widths the library takes)
+        self.ctx_dead = d.spk if d.spk == 256 and M == 2 * d.enc_lstm + d.spk else 0
         self.speaker_ticket_redos = 0        # forward passes re-run because a persistent launch of the speaker stack in front of them gave up
         self.trace_events, self.bptt_end_event = False, None
         self.collective_redos = 0            # data parallel: backward passes re-run because ANOTHER rank's persistent launch gave up
@@ -315,7 +319,7 @@ class TrainEngine(Engine):
         if self.persist:
             call("mstts_persist_pack", ptr(self.w0f), ptr(k1, o1), ptr(wq_, oq_), ptr(k0, o0), ptr(self.pk[0]), ptr(self.pk[1]), ptr(self.pk[2]))
         if self.persist_bwd:
-            call("mstts_persist_bwd_pack", ptr(self.w0f), ptr(k1, o1), ptr(wq_, oq_), ptr(self.pkb[0]), ptr(self.pkb[1]), ptr(self.pkb[2]))
+            call("mstts_persist_bwd_pack_live", ptr(self.w0f), ptr(k1, o1), ptr(wq_, oq_), ptr(self.pkb[0]), ptr(self.pkb[1]), ptr(self.pkb[2]), self.ctx_dead)
         wp, owp = self.P("decoder/decoder/linear_projection/dense/kernel")
         bp, obp = self.P("decoder/decoder/linear_projection/dense/bias")
         nm1 = d.n_mel + 1
@@ -473,17 +477,17 @@ class TrainEngine(Engine):
         w.post_dx = f(B * S, max(d.post_ch, d.n_mel))
         w.post_dx2 = f(B * S, max(d.post_ch, d.n_mel))
         w.d_proj = f(S, B, self.proj_ld)
-        w.d_pj = f(S, B, H + M)
+        w.d_pj = f(S, B, H + M, zero=bool(self.ctx_dead))          # (ctx_dead: the dead columns of these three are never written - they read as the zeros of the activation)
         w.dg0, w.dg1 = f(S, B, 4 * H), f(S, B, 4 * H)
         w.dq_hist, w.de_hist = f(S, B, A), f(S, B, Te)
         w.d_in0_parts = int(lb.mstts_decoder_train_bwd_parts(H, M))
-        w.d_in0 = f(w.d_in0_parts, S, B, M + H)
+        w.d_in0 = f(w.d_in0_parts, S, B, M + H, zero=bool(self.ctx_dead))
         w.dec_bwd_ws = f(int(lb.mstts_decoder_train_bwd_ws_floats(B, H, M, A, Te, d.att_ch)), zero=True)
         w.lsa_param_ws = f((int(lb.mstts_lsa_param_bwd_ws_floats(B, Te, S)) + 3) // 4 * 4)   # partial blocks of the attention parameter gradients
         w.d_pre = f(S * B, Pn)
         w.d_pre2 = f(S * B, Pn)
         w.d_keys = f(B, Te, A)
-        w.d_values = f(B, Te, M)
+        w.d_values = f(B, Te, M, zero=bool(self.ctx_dead))
         w.enc_dgs = {dr: f(Te, B, 4 * He) for dr in ("fw", "bw")}
         w.enc_dgp = {dr: f(B, Te, 4 * He) for dr in ("fw", "bw")}
         w.enc_bwd_ws = {dr: f(int(lb.mstts_lstm_seq_ws_floats(B, He, 1))) for dr in ("fw", "bw")}
@@ -495,6 +499,9 @@ class TrainEngine(Engine):
         w.job_flag_host = self._pin("job_flag_host", 1)
         w.dec = lib.DecoderTrain()
         w.dec_b = lib.DecoderTrainBwd()
+        w.dec_b.ctx_dead = self.ctx_dead
+        if w.persist_bwd:
+            w.pdesc_b.ctx_dead = self.ctx_dead
         w.zero_on_activate = cv.zero
         w.extent_bytes = cv.off
         w.arena_generation = self._arena.generation
@@ -844,7 +851,8 @@ class TrainEngine(Engine):
         gbp, ogbp = self.G("decoder/decoder/linear_projection/dense/bias")
         call("mstts_copy2d", ptr(self.dwp_pad), self.proj_ld, ptr(gwp, ogwp), d.n_mel + 1, H + M, d.n_mel + 1, 1)
         call("mstts_colsum", ptr(w.d_proj), S * B, d.n_mel + 1, self.proj_ld, ptr(gbp, ogbp), 1)
-        self._gemm(w.d_proj, self.wp_pad, w.d_pj, S * B, H + M, self.proj_ld, self.proj_ld, self.proj_ld, H + M, trans_b=True)
+        Ml = M - self.ctx_dead      # the live context columns: nobody reads the gradient of the speaker columns (mstts_decoder_train_bwd_desc.ctx_dead)
+        self._gemm(w.d_proj, self.wp_pad, w.d_pj, S * B, H + Ml, self.proj_ld, self.proj_ld, self.proj_ld, H + M, trans_b=True)
         # ---- decoder loop backward (its persistent launch needs every CU: the vocoder side chain of the forward pass, which ran under the
         # loss and the postnet's backward pass, has to be off the chip)
         self._join_vocoder(w)
@@ -912,16 +920,16 @@ class TrainEngine(Engine):
 
         def memory_gradient():
             # d_values[b] = sum_s align[s,b,:]^T (d_ctx from projection + d_ctx from next step's cell 0)
-            self._gemm(w.align_hist, w.d_pj, w.d_values, Te, M, S, B * Te, B * (H + M), M, trans_a=True, batch=B,
+            self._gemm(w.align_hist, w.d_pj, w.d_values, Te, Ml, S, B * Te, B * (H + M), M, trans_a=True, batch=B,
                        strides=(Te, H + M, Te * M), b_off=H, exact=True)
             if S > 1:
                 for part in range(parts):
-                    self._gemm(w.align_hist, w.d_in0, w.d_values, Te, M, S - 1, B * Te, B * (M + H), M, trans_a=True, batch=B,
+                    self._gemm(w.align_hist, w.d_in0, w.d_values, Te, Ml, S - 1, B * Te, B * (M + H), M, trans_a=True, batch=B,
                                strides=(Te, M + H, Te * M), b_off=(part * S + 1) * B * (M + H), accumulate=True, exact=True)
             # memory layer
             wm, owm = self.P("attention/memory_layer/kernel"); gwm, ogwm = self.G("attention/memory_layer/kernel")
             self._gemm(w.values, w.d_keys, gwm, M, A, B * Te, M, A, A, trans_a=True, split_k=max(2, _split_k(M, A, B * Te)), c_off=ogwm)
-            self._gemm(w.d_keys, wm, w.d_values, B * Te, M, A, A, A, M, trans_b=True, accumulate=True, b_off=owm)
+            self._gemm(w.d_keys, wm, w.d_values, B * Te, Ml, A, A, A, M, trans_b=True, accumulate=True, b_off=owm)
 
         # ---- encoder BiLSTM backward: descriptors
         x_in, cin = w.enc_y[-1], d.enc_conv_ch

@@ -99,7 +99,8 @@ class WgWnDesc(C.Structure):
 
 
 class PersistDesc(C.Structure):
-    _fields_ = [("w0pk", vp), ("w1pk", vp), ("wqpk", vp), ("xch", vp), ("ctrl", vp), ("stamps", vp), ("opk", vp), ("selftest_fail_step", i32), ("near_xcd", i32), ("pre", vp), ("b0", vp), ("recurrent_bf16", i32)]
+    _fields_ = [("w0pk", vp), ("w1pk", vp), ("wqpk", vp), ("xch", vp), ("ctrl", vp), ("stamps", vp), ("opk", vp), ("selftest_fail_step", i32), ("near_xcd", i32), ("pre", vp), ("b0", vp), ("recurrent_bf16", i32),
+                ("ctx_dead", i32)]
 
 
 class PersistInferDesc(C.Structure):
@@ -109,7 +110,7 @@ class PersistInferDesc(C.Structure):
 
 class DecoderTrainBwd(C.Structure):
     _fields_ = [("fwd", C.POINTER(DecoderTrain)), ("d_pj", vp), ("dg0", vp), ("dg1", vp), ("dq_hist", vp),
-                ("de_hist", vp), ("d_in0", vp), ("ws", vp)]
+                ("de_hist", vp), ("d_in0", vp), ("ws", vp), ("ctx_dead", i32)]
 
 
 class DecoderInfer(C.Structure):
@@ -280,6 +281,7 @@ SIGNATURES = {
     "mstts_persist_bwd_ws_bytes": (i64, []),
     "mstts_persist_bwd_pack_floats": (i64, [i32]),
     "mstts_persist_bwd_pack": (i32, [vp, vp, vp, vp, vp, vp, vp]),
+    "mstts_persist_bwd_pack_live": (i32, [vp, vp, vp, vp, vp, vp, i32, vp]),
     "mstts_decoder_train_bwd_persistent": (i32, [P(DecoderTrainBwd), P(PersistDesc), vp]),
     "mstts_decoder_train_bwd_ws_floats": (i64, [i64, i64, i64, i64, i64, i64]),
     "mstts_decoder_train_bwd_parts": (i32, [i64, i64]),
