@@ -644,6 +644,27 @@ int mstts_stft_bank_batch(const float* bank, const int64_t* sig_off, int64_t n_f
                           int32_t n_fft, int32_t hop, int32_t win, int32_t n_mel, float max_abs, float ref_level_db,
                           float* mel_out, float* spec_out, int32_t* status, mstts_stream_t s);
 
+/* ---- training batches of the WaveGlow trainer out of the same kind of bank (WaveGlow/Feeder.py:55-105; csrc/wg_crop.hip): bank and sig_off as
+ * mstts_stft_bank_batch takes them (every file's trimmed waveform at the export rate, scaled to a peak of 0.99); table int32 [N][2] = (file,
+ * start) per output row; phase_table [up][taps], up, down as mstts_wav_resample takes them (taps = mstts_wav_resample_taps; the table may be
+ * NULL when up = down = 1); window, twiddle, mel_basis, mel_rng and the scalars as mstts_stft_fft takes them.  For row r, with len = sig_off[file
+ * + 1] - sig_off[file] and c = min(L, len - start):
+ *   audio_out[r, i] = bank[sig_off[file] + start + i]  for i < c,   +0.0 for c <= i < L                   (x = this row, 0 outside [0, L))
+ *   y[m], m < Lr = ceil(L up / down) = mstts_wav_resample's sum on x (q = 10 max(up, down) + m down, one fmaf chain over the taps ascending
+ *           against phase_table[q mod up], out-of-range inputs as 0.f); y = x when up = down = 1
+ *   mel_out[r, t, :] = frame t of mstts_stft_fft on y, bit for bit   for t < F = 1 + Lr / hop,   +0.0 for F <= t < T
+ * audio_out [N, L], mel_out [N, T, n_mel]; every element is stored exactly once; bank samples before start or behind the crop are never
+ * read.  A row with file outside [0, n_files), start < 0 or start >= len reads nothing from the bank, is written as zeros and sets bit 0 of
+ * status[0] (int32; the caller zeroes it once).  MSTTS_ERR_SHAPE before any launch: a null pointer, N, L, T or n_files < 1, N * T >= 2^31,
+ * a transform mstts_stft_fft_supported refuses, Lr <= n_fft / 2, F > T, up / down not in lowest terms or not served.
+ * mstts_wg_crop_supported: 1 when mstts_wav_resample serves the ratio, mstts_stft_fft the transform and the workgroup's LDS plan (8 n_fft
+ * + 4 (win + 1) bytes) fits 64 KB.  All pointers are device pointers; nothing synchronises. */
+int mstts_wg_crop_supported(int32_t up, int32_t down, int32_t n_fft, int32_t win);
+int mstts_wg_crop_batch(const float* bank, const int64_t* sig_off, int64_t n_files, const int32_t* table, int64_t N, int64_t L, int64_t T,
+                        const float* phase_table, int32_t up, int32_t down, float preemph, const float* window, const float* twiddle,
+                        const float* mel_basis, const int32_t* mel_rng, int32_t n_fft, int32_t hop, int32_t win, int32_t n_mel, float max_abs,
+                        float* audio_out, float* mel_out, int32_t* status, mstts_stream_t s);
+
 /* ---- bf16 variants of the skinny products (BASELINE config 3, "bf16 with fp32 master"): the kernel W is a packed bf16 copy made by
  * mstts_pack_bf16_fwd / _bwd from the fp32 master (round to nearest even; lane-consumption order, opaque), the activation block is
  * rounded to bf16 on the way into LDS, accumulation and the partial slabs are fp32:

@@ -4,7 +4,8 @@
 The saved file (`waveglow.pt` under hp.WaveGlow.Checkpoint_Path) holds the variables under their `waveglow/...` names - exactly
 what ``MSTTS_SV.Tacotron2.Vocoder_Load`` reads - plus the Adam slots and the global step under `__...__` keys, which the inference
 engine ignores.  Patterns are dicts {'Audio': [N, L], 'Mel': [N, T, 80]}; without one a synthetic pattern of the reference's batch
-shape is used.  The wav feeder follows WaveGlow/Feeder.py:30-114 (Feeder.load_wav's trim stands in for librosa's).
+shape is used.  The wav feeder follows WaveGlow/Feeder.py:30-114 (Feeder.load_wav's trim stands in for librosa's); with
+feeder="device" the batches come from a device-resident bank of the corpus instead (waveglow_feeder.py).
 """
 from __future__ import annotations
 
@@ -122,14 +123,25 @@ class WavFeeder:
         self._stop = True
 
 
+def feeder_mode(feeder=None):
+    """"device" or "host": the argument, else the environment variable MSTTS_WG_FEEDER, else "host" (WavFeeder resamples with scipy in
+    fp64; the device resampler cannot promise its last bit, so the bank path is opt-in as front_end="device" is)."""
+    mode = feeder if feeder is not None else os.environ.get("MSTTS_WG_FEEDER", "host")
+    if mode not in ("device", "host"):
+        raise ValueError("feeder must be 'device' or 'host', not {!r}".format(mode))
+    return mode
+
+
 # ---- the trainer class ----------------------------------------------------------------------------------------------------------------
 class WaveGlow(DropIn):
     HP, FILE, SCOPE = "WaveGlow", "waveglow.pt", P_WG
     COLUMNS = (("Learning rate: {:0.5f}", "Learning_Rate"), ("Log S Loss: {:0.5f}", "Log_S_Loss"),
                ("Log Det W Loss: {:0.5f}", "Log_Det_W_Loss"), ("Audio Loss: {:0.5f}", "Audio_Loss"))
 
-    def __init__(self, device="cuda", seed=1234, dims: WGDims = None, values=None):
+    def __init__(self, device="cuda", seed=1234, dims: WGDims = None, values=None, feeder=None):
         self.device = device
+        self.seed = seed
+        self.feeder_mode = feeder_mode(feeder)
         self.engine = WaveGlowTrainEngine(dims or WGDims.from_hp(hp), device=device, seed=seed, values=values)
         self.params = self.engine.params
         self.feeder = None
@@ -155,11 +167,31 @@ class WaveGlow(DropIn):
         res.update({"Global_Step": step, "Learning_Rate": learning_rate(step), "Train_OP": None})
         return res
 
+    def _make_feeder(self):
+        """"host": the reference's loop (WavFeeder).  "device": the signal bank of the wavs under hp.WaveGlow.Train.Pattern_Path and the
+        one-launch feeder on it; when the bank does not fit its budget, one line saying so and the host feeder."""
+        if self.feeder_mode == "host":
+            return WavFeeder(device=self.device)
+        from . import waveglow_feeder as WF
+        paths = wav_paths(hp.WaveGlow.Train.Pattern_Path)
+        if not paths:
+            raise ValueError("no .wav files under '%s'" % hp.WaveGlow.Train.Pattern_Path)
+        try:
+            bank = WF.bank_from_wavs(paths, device=self.device)
+        except WF.BankBudgetError as e:
+            print("The signal bank does not fit ({}): feeding from the host (WavFeeder).".format(e))
+            return WavFeeder(device=self.device)
+        return WF.WaveGlowFeeder(bank, seed=self.seed, dims=self.engine.d)
+
     def Train(self, max_steps=None, pattern_fn=None):
         if pattern_fn is None:
-            self.feeder = self.feeder or WavFeeder(device=self.device)
+            self.feeder = self.feeder or self._make_feeder()
             pattern_fn = self.feeder.Get_Train_Pattern
         super().Train(max_steps, pattern_fn)
+
+    def _after_step(self, result):
+        if hasattr(self.feeder, "check_status"):
+            self.feeder.check_status()               # right behind the loss read of Train_Step: the stream is already drained
 
     def Inference(self, path_List, file_Prefix=None):
         """wav -> mel -> WaveGlowEngine (built from the current values) -> WAV files under hp.WaveGlow.Inference.Path/WAV (WaveGlow.py:144-205)."""

@@ -229,6 +229,8 @@ SIGNATURES = {
     "mstts_ge2e_contrast_fwd_bwd": (i32, [vp, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp]),
     "mstts_mel_bank_gather": (i32, [vp, vp, i64, vp, i64, i64, i64, vp, vp, vp]),
     "mstts_stft_bank_batch": (i32, [vp, vp, i64, vp, i64, i64, f32, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp]),
+    "mstts_wg_crop_supported": (i32, [i32, i32, i32, i32]),
+    "mstts_wg_crop_batch": (i32, [vp, vp, i64, vp, i64, i64, i64, vp, i32, i32, f32, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp]),
     "mstts_wg_overlap_add": (i32, [vp, vp, vp, i64, i64, i64, i64, i64, vp]),
     "mstts_wg_gate": (i32, [vp, i64, vp, i64, i64, vp]),
     "mstts_wg_gate_add": (i32, [vp, i64, vp, vp, i64, i64, vp]),
