@@ -34,7 +34,8 @@ enum { MSTTS_OK = 0, MSTTS_ERR_SHAPE = -1, MSTTS_ERR_DTYPE = -2, MSTTS_ERR_ALIGN
 enum { MSTTS_ACT_NONE = 0, MSTTS_ACT_RELU = 1, MSTTS_ACT_TANH = 2, MSTTS_ACT_SIGMOID = 3 };
 
 const char* mstts_last_error(void);
-/* Bumped whenever a descriptor struct or an entry point's signature changes (4: round 4; 5: round 5 - mstts_persist_desc.recurrent_bf16 in the slot of round 4's schedule selector); the Python binding checks it at load. */
+/* Bumped whenever a descriptor struct or an entry point's signature changes (4: round 4; 5: round 5 - mstts_persist_desc.recurrent_bf16 in the slot of round 4's schedule selector); the Python binding checks it at load.  A new entry point or descriptor alone (mstts_bn_train_fwd_seg,
+ * mstts_convbank_pack) does not bump it: the binding's symbol check finds a library that lacks one. */
 int mstts_abi_version(void);
 /* Diagnostic (tests of the persistent launches' co-residency handling; no reference counterpart - MSTTS_SV.py:24 is a single session on one
  * device): n_workgroups workgroups that each hold 96 KB of LDS - a whole CU as far as a persistent workgroup is concerned - for
@@ -140,6 +141,32 @@ int mstts_bn_infer_fwd(const float* x, const float* gamma, const float* beta, co
 int mstts_bn_train_bwd(const float* dy, const float* x, const float* gamma, const float* save_mean, const float* save_rstd,
                        const uint8_t* keep_mask, float keep_prob, int32_t act, float* dz, float* dgamma, float* dbeta,
                        float* dbias, int64_t rows, int64_t C, float* ws, mstts_stream_t s);
+
+/* The training-mode forward for nseg batch-norm layers that sit side by side in one block: x[rows, C] with row stride ld >= C, segment i
+ * = columns [i*C/nseg, (i+1)*C/nseg) with the parameters segs->seg[i] (the table is HOST memory, read before the call returns; it is handed to
+ * the kernels by value, so the layers need not be contiguous anywhere).  One column-sum launch over all C columns and one finalize launch
+ * update every segment's moving statistics by mstts_bn_train_fwd's arithmetic (same fixed-order form under mstts_gemm_deterministic);
+ * save_mean / save_rstd [C] receive the batch statistics.  moving_mean / moving_var of a segment may both be NULL.
+ *   y == NULL: statistics only (gamma / beta are not read).
+ *   y != NULL: y[rows, C] (dense, row stride C) = (x-mean)*rstd*gamma+beta;  with pool_T > 0 (rows = whole runs of pool_T frames) the
+ *   tf max_pooling1d(2,1,'same') of mstts_maxpool2_same along each run is applied on the way out: y[t] = max(z[t], z[t+1]), y[pool_T-1] =
+ *   z[pool_T-1] (Taco1_Mel_to_Spect/Modules.py:22-33: the bank's batch norms, the concatenation, the pool) - z itself is never stored.
+ * 16-byte accesses when C, ld and the pointers allow, scalar ones otherwise.  ws: 4*C floats of scratch (2*C when y == NULL). */
+#define MSTTS_BN_SEG_MAX 16
+typedef struct { const float* gamma; const float* beta; float* moving_mean; float* moving_var; } mstts_bn_seg;
+typedef struct { mstts_bn_seg seg[MSTTS_BN_SEG_MAX]; } mstts_bn_seg_table;
+int mstts_bn_train_fwd_seg(const float* x, int64_t ld, const mstts_bn_seg_table* segs, int32_t nseg, float* y, float* save_mean,
+                           float* save_rstd, float momentum, float eps, int64_t rows, int64_t C, int64_t pool_T, float* ws, mstts_stream_t s);
+/* The conv bank of Taco1_Mel_to_Spect/Modules.py:15-27 (bank_k 'same' convolutions of widths 1..bank_k over one input, concatenated) as at
+ * most two window products: src (HOST table; [k-1] = the conv of width k, kernel [k, cin, cout], bias [cout]) is packed, zero-padded, into
+ * one weight matrix per group.  Width k reads the time offsets -(k-1)/2 .. k-1-(k-1)/2, so the widths lo..hi fit one window of hi taps
+ * with left pad (hi-1)/2: the group's matrix is [hi*cin, (hi-lo+1)*cout], conv k's tap j at window tap j + (hi-1)/2 - (k-1)/2, its columns
+ * at (k-lo)*cout, zeros elsewhere (exact zeros in the product).  Group 0 = widths 1..k_split at w, group 1 = widths k_split+1..bank_k behind
+ * it (k_split == bank_k: one group); bias [bank_k*cout] in bank order.  One launch; a derived copy of frozen variables - pack once. */
+#define MSTTS_BANK_MAX 16
+typedef struct { const float* kernel[MSTTS_BANK_MAX]; const float* bias[MSTTS_BANK_MAX]; } mstts_convbank_src;
+int mstts_convbank_pack(const mstts_convbank_src* src, int32_t bank_k, int32_t k_split, int64_t cin, int64_t cout, float* w, float* bias,
+                        mstts_stream_t s);
 
 /* ---- small fused elementwise pieces ---------------------------------------------------------
  * dropout fwd/bwd on flat arrays: y = x * mask / keep  (prenet, Modules.py:248-253)

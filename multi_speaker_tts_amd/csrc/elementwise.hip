@@ -360,6 +360,108 @@ __global__ void maxpool2_kernel(const float* __restrict__ x, float* __restrict__
         y[i] = v;
     }
 }
+// ---- segmented batch norm (mstts_bn_train_fwd_seg): nseg layers side by side in one [rows, C] block of row stride ld --------------------
+// finalize: bn_finalize_kernel's arithmetic per column (the variance uncontracted - see there).  Block row blockIdx.y is one segment, whose
+// parameter pointers arrive by value; gb (null: statistics only) receives the segments' gamma | beta as dense C-wide vectors, so the apply
+// pass needs no table.
+__global__ void bn_seg_finalize_kernel(const float* __restrict__ ws, float inv_rows, float eps, float momentum, mstts_bn_seg_table tab,
+                                       float* __restrict__ save_mean, float* __restrict__ save_rstd, float* __restrict__ gb, int cseg, int C) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= cseg) return;
+    const mstts_bn_seg p = tab.seg[blockIdx.y];
+    const int c = blockIdx.y * cseg + j;
+    const float mean = ws[c] * inv_rows;
+    float var;
+    {
+#pragma clang fp contract(off)
+        const float msq = mean * mean;
+        var = ws[C + c] * inv_rows - msq;
+    }
+    var = fmaxf(var, 0.f);
+    save_mean[c] = mean;
+    save_rstd[c] = rsqrtf(var + eps);
+    if (gb) { gb[c] = p.gamma[j]; gb[C + c] = p.beta[j]; }
+    if (p.moving_mean) {
+        p.moving_mean[j] = p.moving_mean[j] * momentum + mean * (1.f - momentum);
+        p.moving_var[j] = p.moving_var[j] * momentum + var * (1.f - momentum);
+    }
+}
+
+template <int W> __device__ __forceinline__ void load_w(const float* __restrict__ p, float (&v)[W]) {
+    if constexpr (W == 4) { const float4 q = *reinterpret_cast<const float4*>(p); v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w; }
+    else v[0] = *p;
+}
+template <int W> __device__ __forceinline__ void store_w(float* __restrict__ p, const float (&v)[W]) {
+    if constexpr (W == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    else *p = v[0];
+}
+
+// apply: z = (x - mean) * rstd * gamma + beta (bn_apply_kernel's expression) into the dense y[rows, C]; pool_T > 0 fuses
+// max_pooling1d(2, 1, 'same') over rows of pool_T frames by maxpool2_kernel's rule, y[t] = max(z[t], z[t + 1]), y[T - 1] = z[T - 1].
+// The 256 threads are 2^qshift column lanes of W adjacent columns x 256 >> qshift row lanes; a thread walks `sub` consecutive rows, so the
+// z[t + 1] it formed for y[t] is the next row's own value: x is read once, z is never stored.  I: the index type (int where rows * ld < 2^31).
+template <int W, typename I>
+__global__ __launch_bounds__(256) void bn_seg_apply_kernel(const float* __restrict__ x, I ld, const float* __restrict__ mean,
+                                                           const float* __restrict__ rstd, const float* __restrict__ gb,
+                                                           float* __restrict__ y, I rows, int C, int qshift, int sub, int pool_T) {
+    const int col = (int)((blockIdx.y << qshift) + (threadIdx.x & ((1u << qshift) - 1u))) * W;
+    const I r0 = (I)(blockIdx.x * (256u >> qshift) + (threadIdx.x >> qshift)) * (I)sub;
+    if (col >= C || r0 >= rows) return;
+    const I r1 = r0 + sub < rows ? r0 + (I)sub : rows;
+    float mu[W], rs[W], ga[W], be[W];
+    load_w<W>(mean + col, mu); load_w<W>(rstd + col, rs); load_w<W>(gb + col, ga); load_w<W>(gb + C + col, be);
+    auto norm = [&](I r, float (&z)[W]) {
+        float xv[W];
+        load_w<W>(x + r * ld + col, xv);
+#pragma unroll
+        for (int j = 0; j < W; ++j) z[j] = (xv[j] - mu[j]) * rs[j] * ga[j] + be[j];
+    };
+    if (pool_T <= 0) {
+#pragma unroll 4
+        for (I r = r0; r < r1; ++r) {
+            float z[W];
+            norm(r, z);
+            store_w<W>(y + r * (I)C + col, z);
+        }
+        return;
+    }
+    float zc[W], zn[W] = {};
+    norm(r0, zc);
+    int t = (int)(r0 % (I)pool_T);
+#pragma unroll 4
+    for (I r = r0; r < r1; ++r) {
+        const bool pair = t + 1 < pool_T;            // (frame t + 1 of the same batch row: r + 1 < rows then, rows being whole batch rows)
+        if (r + 1 < r1 || pair) norm(r + 1, zn);
+        float o[W];
+#pragma unroll
+        for (int j = 0; j < W; ++j) { o[j] = pair ? fmaxf(zc[j], zn[j]) : zc[j]; zc[j] = zn[j]; }
+        store_w<W>(y + r * (I)C + col, o);
+        if (++t == pool_T) t = 0;
+    }
+}
+
+// mstts_convbank_pack: block row blockIdx.y packs the conv of width k = blockIdx.y + 1 ([k, cin, cout] + bias) into its group's matrix.
+// Group 0 holds the widths 1..k_split, group 1 (behind it in w) the widths k_split + 1..bank_k; a group of widths lo..hi is
+// [hi * cin, (hi - lo + 1) * cout]: window hi, left pad (hi - 1) / 2, conv k's tap j at window tap j + (hi - 1) / 2 - (k - 1) / 2, zeros elsewhere.
+__global__ void convbank_pack_kernel(mstts_convbank_src src, int bank_k, int k_split, int cin, int cout, float* __restrict__ w,
+                                     float* __restrict__ bias) {
+    const int k = blockIdx.y + 1;
+    const bool g1 = k > k_split;
+    const int lo = g1 ? k_split + 1 : 1, hi = g1 ? bank_k : k_split;
+    const long ncol = (long)(hi - lo + 1) * cout;
+    const long base = g1 ? (long)k_split * cin * k_split * cout : 0;
+    const int shift = (hi - 1) / 2 - (k - 1) / 2;
+    const float* __restrict__ kk = src.kernel[blockIdx.y];
+    const float* __restrict__ bb = src.bias[blockIdx.y];
+    const long n = (long)hi * cin * cout;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n + cout; i += (long)gridDim.x * blockDim.x) {
+        if (i >= n) { bias[(long)(k - 1) * cout + (i - n)] = bb[i - n]; continue; }
+        const long row = i / cout;
+        const int co = (int)(i - row * cout), tap = (int)(row / cin), ci = (int)(row - (long)tap * cin), j = tap - shift;
+        w[base + row * ncol + (long)(k - lo) * cout + co] = (j >= 0 && j < k) ? kk[((long)j * cin + ci) * cout + co] : 0.f;
+    }
+}
+
 __global__ void highway_kernel(const float* __restrict__ hp, const float* __restrict__ tp, const float* __restrict__ x,
                                float* __restrict__ y, long n) {
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
@@ -1017,6 +1119,59 @@ extern "C" int mstts_maxpool2_same(const float* x, float* y, int64_t B, int64_t 
     MSTTS_CHECK_LAUNCH("maxpool2_same");
     return MSTTS_OK;
 }
+template <int W, typename I>
+static void launch_bn_seg_apply(const float* x, long ld, const float* mean, const float* rstd, const float* gb, float* y, long rows, int C,
+                                int pool_T, hipStream_t st) {
+    const int cq = cdiv(C, W), sub = 16;
+    int qshift = 0;
+    while (qshift < 8 && (1 << qshift) < cq) ++qshift;           // column lanes: the power of two that covers C / W, 256 at the most
+    const long rows_per_block = (long)(256 >> qshift) * sub;
+    dim3 grid((unsigned)cdiv(rows, rows_per_block), (unsigned)cdiv(cq, 1 << qshift));
+    hipLaunchKernelGGL((bn_seg_apply_kernel<W, I>), grid, dim3(256), 0, st, x, (I)ld, mean, rstd, gb, y, (I)rows, C, qshift, sub, pool_T);
+}
+
+extern "C" int mstts_bn_train_fwd_seg(const float* x, int64_t ld, const mstts_bn_seg_table* segs, int32_t nseg, float* y, float* save_mean,
+                                      float* save_rstd, float momentum, float eps, int64_t rows, int64_t C, int64_t pool_T, float* ws,
+                                      mstts_stream_t s) {
+    MSTTS_REQUIRE(segs != nullptr && nseg >= 1 && nseg <= MSTTS_BN_SEG_MAX, MSTTS_ERR_SHAPE, "bn_seg: 1..%d segments", MSTTS_BN_SEG_MAX);
+    MSTTS_REQUIRE(rows > 0 && C > 0 && C % nseg == 0 && ld >= C && C < (1LL << 30), MSTTS_ERR_SHAPE, "bn_seg: rows > 0, C a multiple of nseg, ld >= C");
+    MSTTS_REQUIRE(pool_T >= 0 && pool_T < (1LL << 31) && (pool_T == 0 || rows % pool_T == 0), MSTTS_ERR_SHAPE, "bn_seg: rows must be whole runs of pool_T frames");
+    MSTTS_REQUIRE(x && save_mean && save_rstd && ws, MSTTS_ERR_SHAPE, "bn_seg: null pointer");
+    for (int i = 0; i < nseg; ++i)
+        MSTTS_REQUIRE((!y || (segs->seg[i].gamma && segs->seg[i].beta)) && (!segs->seg[i].moving_mean == !segs->seg[i].moving_var), MSTTS_ERR_SHAPE,
+                      "bn_seg: segment %d lacks a parameter", i);
+    const int cseg = (int)(C / nseg);
+    hipMemsetAsync(ws, 0, 2 * C * sizeof(float), ST(s));
+    launch_col_stats(x, nullptr, nullptr, 1.f, nullptr, nullptr, (long)rows, (int)C, (long)ld, 0, ws, ws + C, ST(s));
+    float* gb = y ? ws + 2 * C : nullptr;
+    hipLaunchKernelGGL(bn_seg_finalize_kernel, dim3(cdiv(cseg, 256), nseg), dim3(256), 0, ST(s), (const float*)ws, 1.f / (float)rows, eps, momentum,
+                       *segs, save_mean, save_rstd, gb, cseg, (int)C);
+    if (y) {
+        const bool v4 = C % 4 == 0 && ld % 4 == 0 && aligned16(x) && aligned16(y) && aligned16(save_mean) && aligned16(save_rstd) && aligned16(ws);
+        const bool i32 = (rows + 4096) * ld < (1LL << 31);      // (a block's first row may lie up to 4 096 rows past the end)
+        const float *m = save_mean, *r = save_rstd;
+        if (v4 && i32) launch_bn_seg_apply<4, int>(x, ld, m, r, gb, y, rows, (int)C, (int)pool_T, ST(s));
+        else if (v4) launch_bn_seg_apply<4, long>(x, ld, m, r, gb, y, rows, (int)C, (int)pool_T, ST(s));
+        else if (i32) launch_bn_seg_apply<1, int>(x, ld, m, r, gb, y, rows, (int)C, (int)pool_T, ST(s));
+        else launch_bn_seg_apply<1, long>(x, ld, m, r, gb, y, rows, (int)C, (int)pool_T, ST(s));
+    }
+    MSTTS_CHECK_LAUNCH("bn_train_fwd_seg");
+    return MSTTS_OK;
+}
+
+extern "C" int mstts_convbank_pack(const mstts_convbank_src* src, int32_t bank_k, int32_t k_split, int64_t cin, int64_t cout, float* w,
+                                   float* bias, mstts_stream_t s) {
+    MSTTS_REQUIRE(src != nullptr && w && bias, MSTTS_ERR_SHAPE, "convbank_pack: null pointer");
+    MSTTS_REQUIRE(bank_k >= 1 && bank_k <= MSTTS_BANK_MAX && k_split >= 1 && k_split <= bank_k, MSTTS_ERR_SHAPE,
+                  "convbank_pack: 1 <= k_split <= bank_k <= %d", MSTTS_BANK_MAX);
+    MSTTS_REQUIRE(cin > 0 && cout > 0 && cin * cout < (1LL << 24), MSTTS_ERR_SHAPE, "convbank_pack: cin, cout out of range");
+    for (int i = 0; i < bank_k; ++i) MSTTS_REQUIRE(src->kernel[i] && src->bias[i], MSTTS_ERR_SHAPE, "convbank_pack: conv %d missing", i + 1);
+    hipLaunchKernelGGL(convbank_pack_kernel, dim3(grid_for((long)bank_k * cin * cout + cout, 256), bank_k), dim3(256), 0, ST(s), *src, (int)bank_k,
+                       (int)k_split, (int)cin, (int)cout, w, bias);
+    MSTTS_CHECK_LAUNCH("convbank_pack");
+    return MSTTS_OK;
+}
+
 extern "C" int mstts_highway_combine(const float* h_pre, const float* t_pre, const float* x, float* y, int64_t n, mstts_stream_t s) {
     if (n == 0) return MSTTS_OK;
     hipLaunchKernelGGL(highway_kernel, dim3(grid_for(n, 256)), dim3(256), 0, ST(s), h_pre, t_pre, x, y, (long)n);

@@ -20,10 +20,10 @@ import torch
 from . import lib
 from .lib import ACT_NONE, ACT_RELU, ACT_TANH, gemm, ptr, call
 from .masks import MaskSet, step_seed
-from .params import CELL, ENC_CELL, LSA, LSA_VARS, VOC, Dims, ParamStore, bank_suffix
+from .params import CELL, ENC_CELL, LSA, LSA_VARS, VOC, Dims, ParamStore, bank_groups, bank_suffix
 from .persist import PERSIST_COOLDOWN, PERSIST_STRIKES, CoolDown, Ticket, decoder_workgroups, lstm_bwd_workgroups, lstm_fwd_workgroups, near_xcd
-from .training import (Engine, _split_k, _split_k_big, bn_train_fwd, conv_bn_bwd, conv_fwd, exponential_decay, lstm_layer_grads, lstm_seq_bwd,
-                       lstm_seq_fwd)
+from .training import (BN_EPS, BN_MOM, Engine, _split_k, _split_k_big, bn_train_fwd, conv_bn_bwd, conv_fwd, exponential_decay, lstm_layer_grads,
+                       lstm_seq_bwd, lstm_seq_fwd)
 
 MAX_PLANS = 64     # cached workspace sets (one per batch shape): views into ONE arena, a set owns no device memory
 
@@ -36,6 +36,7 @@ def learning_rate(step):
 
 
 VOC_OVERLAP = os.environ.get("MSTTS_VOC_OVERLAP", "1") != "0"    # the vocoder conv-bank's statistics side effect (quirk Q20) on its own stream, under the loss and the postnet's backward pass
+VOC_FUSED = os.environ.get("MSTTS_VOC_FUSED", "1") != "0"        # ... as two packed bank products and segmented batch norms with the pool fused (15 launches; 0: one product, BN chain and copy per bank width, 59); read when a batch shape is planned
 POSTNET_WGRAD_OVERLAP = os.environ.get("MSTTS_POSTNET_WGRAD_OVERLAP", "1") != "0"   # ... and the postnet's weight-gradient products, beside its data-gradient chain
 ENC_TAIL_OVERLAP = os.environ.get("MSTTS_ENC_TAIL_OVERLAP", "1") != "0"   # ... and what follows the encoder's BPTT launch on that stream too, beside the decoder's weight-gradient products
 ENC_OVERLAP = os.environ.get("MSTTS_ENC_OVERLAP", "1") != "0"    # the encoder's persistent launches on their own stream, under decoder-side products that do not depend on them
@@ -217,6 +218,13 @@ class TrainEngine(Engine):
         if self.persist_bwd:
             self.pkb = [self._f(int(lb.mstts_persist_bwd_pack_floats(i))) for i in range(3)]
         self.flip = {}
+        # the vocoder conv bank as two window products (mstts_convbank_pack): packed, zero-padded copies of the FROZEN bank kernels, rebuilt when
+        # the non-trainable slab changes (params.frozen_version) - never per step; None: these dims keep the product per bank width
+        self.voc_bank = None
+        if update_vocoder_bn and d.bank_ch % 4 == 0 and d.n_mel % 4 == 0 and 1 <= d.bank_k <= lib.BANK_MAX:
+            groups = bank_groups(d.bank_k, max(1, d.bank_k // 2))
+            n = sum(win * d.n_mel * (hi - lo + 1) * d.bank_ch for lo, hi, win, _ in groups)
+            self.voc_bank = {"groups": groups, "w": self._f(n), "bias": self._f(d.bank_k * d.bank_ch), "version": None, "tables": None}
         self.big_tiles = os.environ.get("MSTTS_SPLIT_K_BIG", "1") != "0"      # weight-gradient splits chosen for the 256 x 256-tile kernels
         self._derived_stale = True
         self.gemm_dtype = (gemm_dtype or "f32").lower()
@@ -459,16 +467,19 @@ class TrainEngine(Engine):
         w.bn_ws = f(2 * max(d.post_ch, d.enc_conv_ch, d.bank_k * d.bank_ch, d.proj1_ch, d.n_mel, d.emb))
         # vocoder conv-bank (BN update side effect)
         if self.update_vocoder_bn:
-            w.v_tmp = f(B * S, d.bank_ch)
-            w.v_tmp2 = f(B * S, d.bank_ch)
+            w.voc_fused = VOC_FUSED and self.voc_bank is not None
+            if not w.voc_fused:              # (the chain per bank width: one width's product and its normalised copy, the last BN's unread output)
+                w.v_tmp = f(B * S, d.bank_ch)
+                w.v_tmp2 = f(B * S, d.bank_ch)
+                w.v_p2y = f(B * S, d.n_mel)
             w.v_cat = f(B * S, d.bank_k * d.bank_ch)
             w.v_pool = f(B * S, d.bank_k * d.bank_ch)
             w.v_p1 = f(B * S, d.proj1_ch)
             w.v_p1y = f(B * S, d.proj1_ch)
             w.v_p2 = f(B * S, d.n_mel)
-            w.v_p2y = f(B * S, d.n_mel)
-            w.v_stat = f(2 * max(d.bank_ch, d.proj1_ch, d.n_mel))
-            w.v_bn_ws = f(2 * max(d.bank_ch, d.proj1_ch, d.n_mel))          # (its own column-sum workspace: the chain may run beside the main stream's BN calls)
+            widest = max(d.bank_k * d.bank_ch if w.voc_fused else d.bank_ch, d.proj1_ch, d.n_mel)
+            w.v_stat = f(2 * widest)
+            w.v_bn_ws = f(4 * widest)        # (its own column-sum workspace: the chain may run beside the main stream's BN calls)
         # losses
         w.scalars = f(4)
         w.d_linear, w.d_post, w.d_stop = f(B, S, d.n_mel), f(B, S, d.n_mel), f(B, S)
@@ -514,7 +525,7 @@ class TrainEngine(Engine):
         are put back to their state at the start of the pass and the whole pass is run again with the launch-per-step loops (_redo).
         allowed: the fallback policy's decision for this optimizer step (train_step takes it ONCE per step with _persist_begin_step and
         hands it down); None = a forward pass driven on its own (tests, tools) advances the policy itself.
-        overlap_vocoder: train_step only - the vocoder conv-bank's statistics side effect (quirk Q20: ~50 small launches, 1.0 ms, read by nothing in
+        overlap_vocoder: train_step only - the vocoder conv-bank's statistics side effect (quirk Q20: _vocoder_bn_update, read by nothing in
         the step) goes to its own stream and loss_and_backward joins it in front of the decoder's BPTT launch (which needs every CU); a forward
         pass driven on its own keeps it on the caller's stream."""
         d, ps = self.d, self.params
@@ -766,11 +777,60 @@ class TrainEngine(Engine):
             torch.cuda.current_stream().wait_event(done)
             w.side_wgrads = False
 
+    def _ensure_bank_pack(self):
+        """The packed bank kernels and bias (self.voc_bank) and the chain's three batch-norm pointer tables, rebuilt when the frozen slab has
+        changed since they were made (load, broadcast: params.frozen_version); an optimizer step does not touch the vocoder's variables."""
+        vb, ps, d = self.voc_bank, self.params, self.d
+        cb = VOC + "convbank_0/"
+        names = [cb + "conv1d%s/" % bank_suffix(k) for k in range(1, d.bank_k + 1)]
+        version = ps.frozen_version          # (the vocoder is frozen in this trainer: params.is_trainable)
+        if vb["version"] == version:
+            return
+        src = lib.ConvBankSrc()
+        for i, n in enumerate(names):
+            src.kernel[i], src.bias[i] = ptr(*self.P(n + "kernel")), ptr(*self.P(n + "bias"))
+        call("mstts_convbank_pack", C.byref(src), d.bank_k, vb["groups"][0][1], d.n_mel, d.bank_ch, ptr(vb["w"]), ptr(vb["bias"]))
+
+        def table(scopes):
+            t = lib.BnSegTable()
+            for i, bn in enumerate(scopes):
+                t.seg[i].gamma, t.seg[i].beta = ptr(*self.P(bn + "gamma")), ptr(*self.P(bn + "beta"))
+                t.seg[i].moving_mean, t.seg[i].moving_var = ptr(*self.P(bn + "moving_mean")), ptr(*self.P(bn + "moving_variance"))
+            return t
+        vb["tables"] = (table([cb + "batch_normalization%s/" % bank_suffix(k) for k in range(1, d.bank_k + 1)]),
+                        table([cb + "batch_normalization_8/"]), table([cb + "batch_normalization_9/"]))
+        vb["version"] = version
+
     def _vocoder_bn_update(self, w):
-        """Quirk Q20: the train op also runs the vocoder conv-bank's BN update ops on the predicted mel."""
+        """Quirk Q20: the train op also runs the vocoder conv-bank's BN update ops on the predicted mel.  Only the ten layers' moving statistics
+        come out of it.  Fused form (VOC_FUSED, dims the packed bank takes): the bank as two window products that write the concatenation
+        directly, one segmented batch norm over it with the max-pool on its way out, the two projections, the last layer's statistics alone."""
         d = self.d
         B, S = w.B, w.S
         rows = B * S
+        if w.voc_fused:
+            C1 = d.bank_k * d.bank_ch
+            vb = self.voc_bank
+            self._ensure_bank_pack()
+            t_bank, t_p1, t_p2 = vb["tables"]
+            off = 0
+            for lo, hi, win, pad in vb["groups"]:
+                n, c0 = (hi - lo + 1) * d.bank_ch, (lo - 1) * d.bank_ch
+                self._gemm(w.mel_out, vb["w"], w.v_cat, rows, n, win * d.n_mel, d.n_mel, n, C1, bias=vb["bias"], act=ACT_RELU,
+                           win=(S, d.n_mel, pad), b_off=off, bias_off=c0, c_off=c0, exact=True)
+                off += win * d.n_mel * n
+            bn_seg = lambda tab, nseg, x, y, cols, pool: call("mstts_bn_train_fwd_seg", ptr(x), cols, C.byref(tab), nseg, ptr(y), ptr(w.v_stat),
+                                                              ptr(w.v_stat, cols), BN_MOM, BN_EPS, rows, cols, pool, ptr(w.v_bn_ws))
+            bn_seg(t_bank, d.bank_k, w.v_cat, w.v_pool, C1, S)
+            kk, ok = self.P(VOC + "convbank_0/conv1d_8/kernel"); b, ob = self.P(VOC + "convbank_0/conv1d_8/bias")
+            self._gemm(w.v_pool, kk, w.v_p1, rows, d.proj1_ch, d.proj1_k * C1, C1, d.proj1_ch, d.proj1_ch, bias=b, act=ACT_RELU,
+                 win=(S, C1, (d.proj1_k - 1) // 2), b_off=ok, bias_off=ob, exact=True)
+            bn_seg(t_p1, 1, w.v_p1, w.v_p1y, d.proj1_ch, 0)
+            kk, ok = self.P(VOC + "convbank_0/conv1d_9/kernel"); b, ob = self.P(VOC + "convbank_0/conv1d_9/bias")
+            self._gemm(w.v_p1y, kk, w.v_p2, rows, d.n_mel, d.proj2_k * d.proj1_ch, d.proj1_ch, d.n_mel, d.n_mel, bias=b,
+                 win=(S, d.proj1_ch, (d.proj2_k - 1) // 2), b_off=ok, bias_off=ob, exact=True)
+            bn_seg(t_p2, 1, w.v_p2, None, d.n_mel, 0)
+            return
         for k in range(1, d.bank_k + 1):
             sfx = bank_suffix(k)
             kk, ok = self.P(VOC + "convbank_0/conv1d%s/kernel" % sfx); b, ob = self.P(VOC + "convbank_0/conv1d%s/bias" % sfx)

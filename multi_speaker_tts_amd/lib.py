@@ -121,6 +121,21 @@ class DecoderInfer(C.Structure):
                 ("pre_ws", vp), ("linear", vp), ("stop", vp), ("align_hist", vp), ("w0s", vp), ("wp_pad", vp), ("w0sp", vp), ("w1p", vp), ("act_p", vp), ("wp_own", vp), ("vp", vp)]
 
 
+BN_SEG_MAX = BANK_MAX = 16     # MSTTS_BN_SEG_MAX / MSTTS_BANK_MAX
+
+
+class BnSeg(C.Structure):
+    _fields_ = [("gamma", vp), ("beta", vp), ("moving_mean", vp), ("moving_var", vp)]
+
+
+class BnSegTable(C.Structure):
+    _fields_ = [("seg", BnSeg * BN_SEG_MAX)]
+
+
+class ConvBankSrc(C.Structure):
+    _fields_ = [("kernel", vp * BANK_MAX), ("bias", vp * BANK_MAX)]
+
+
 P = C.POINTER
 # name -> (restype, argtypes); every symbol include/mstts.h declares
 SIGNATURES = {
@@ -142,6 +157,8 @@ SIGNATURES = {
     "mstts_embedding_fwd": (i32, [vp, vp, vp, i64, i64, i64, vp]),
     "mstts_embedding_bwd": (i32, [vp, vp, vp, i64, i64, i64, vp]),
     "mstts_bn_train_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, i64, i64, vp, vp]),
+    "mstts_bn_train_fwd_seg": (i32, [vp, i64, P(BnSegTable), i32, vp, vp, vp, f32, f32, i64, i64, i64, vp, vp]),
+    "mstts_convbank_pack": (i32, [P(ConvBankSrc), i32, i32, i64, i64, vp, vp, vp]),
     "mstts_bn_infer_fwd": (i32, [vp, vp, vp, vp, vp, vp, f32, i64, i64, vp]),
     "mstts_bn_train_bwd": (i32, [vp, vp, vp, vp, vp, vp, f32, i32, vp, vp, vp, vp, i64, i64, vp, vp]),
     "mstts_dropout": (i32, [vp, vp, f32, vp, i64, vp]),

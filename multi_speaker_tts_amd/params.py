@@ -78,6 +78,14 @@ def bank_suffix(k):
     return "" if k == 1 else "_%d" % (k - 1)
 
 
+def bank_groups(bank_k, k_split):
+    """The window products that replace the conv bank's bank_k 'same' convolutions (mstts_convbank_pack): [(lo, hi, window, pad)] for the
+    widths 1..k_split and k_split + 1..bank_k (k_split == bank_k: one group).  Width k reads the time offsets -(k-1)//2 .. k-1-(k-1)//2,
+    so the widths lo..hi fit a window of hi taps with left pad (hi-1)//2."""
+    g = [(1, k_split)] + ([(k_split + 1, bank_k)] if k_split < bank_k else [])
+    return [(lo, hi, hi, (hi - 1) // 2) for lo, hi in g]
+
+
 def variable_table(d: Dims):
     """[(name, shape, init)] in graph-construction order."""
     t = []
@@ -245,6 +253,7 @@ class ParamStore:
                 wd[o:o + int(np.prod(shape))] = 1
         self.wd_mask = torch.from_numpy(wd).to(device)
         self.version = 0          # bumped whenever the variables change (load, optimizer step): engines key their packed / folded copies on it
+        self.frozen_version = 0   # ... whenever the non-trainable slab may have (load, broadcast; not an optimizer step): copies derived from frozen variables alone
         self.load(values if values is not None else initial_values(d, seed))
 
     def _slab(self, name, grad=False):
@@ -263,10 +272,15 @@ class ParamStore:
     def g(self, name):
         return self.grad, self.offset[name]
 
-    def touch(self):
+    def touch(self, frozen=True):
         """The variables were written (optimizer step, broadcast, load): every cache keyed on `version` (packed / folded kernels of the
-        inference engines, the train engine's derived copies) is stale from here on.  Every code path that writes `train` / `frozen` calls this."""
+        inference engines, the train engine's derived copies) is stale from here on.  Every code path that writes `train` / `frozen` calls this.
+        frozen=False: the writer touched the trainable slab only (the optimizer step) - copies derived from frozen variables alone, keyed on
+        `frozen_version` (the train engine's packed vocoder conv bank), stay valid.  The BN moving statistics, which every step rewrites in
+        the non-trainable slab, are not variables in this sense: nothing derives a copy from them."""
         self.version += 1
+        if frozen:
+            self.frozen_version += 1
 
     def load(self, values):
         self.touch()

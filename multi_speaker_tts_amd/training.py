@@ -124,7 +124,7 @@ class Engine:
             call("mstts_adam_tf_clip", ptr(ps.train), ptr(ps.grad), ptr(ps.adam_m), ptr(ps.adam_v), clip[0], 2.0, clip[1],
                  float(lr_t), b1, b2, eps, ps.n_train)
         self.global_step += 1
-        ps.touch()                           # (an InferEngine sharing this store keys its packed / folded kernels on the version)
+        ps.touch(frozen=False)               # (an InferEngine sharing this store keys its packed / folded kernels on the version; Adam writes `train` only)
         return lr_t
 
 
