@@ -44,7 +44,6 @@ class Speaker_Embedding(DropIn):
         self.device = device
         self.seed = seed
         self.engine = SpeakerTrainEngine(dims, device=device, seed=seed, loss_method=loss_method)
-        self.feeder = None
         self.embedding_Value = None
         self.params = self.engine.params
         self.train_Tensor_Dict = {k: k for k in TRAIN_KEYS} if is_Training else None
@@ -73,19 +72,15 @@ class Speaker_Embedding(DropIn):
         w = self.engine.train_step(mel, int(pattern.get("Batch_per_Speaker", hp.Speaker_Embedding.Train.Batch_per_Speaker)))
         return {"Global_Step": step, "Learning_Rate": learning_rate(step), "Loss": float(w.out3[0]), "Train_OP": None}
 
-    def Train(self, max_steps=None, pattern_fn=None):
-        """Without a pattern_fn, when training and the metadata file of hp.Speaker_Embedding.Train.Pattern_Path exists: the corpus goes
-        into a device mel bank once and every step's batch comes from a SpeakerFeeder on it; otherwise as DropIn.Train."""
+    def _corpus_feeder(self):
+        """When training and the metadata file of hp.Speaker_Embedding.Train.Pattern_Path exists: the corpus goes into a device mel bank
+        once and every step's batch comes from a SpeakerFeeder on it."""
         from . import speaker_feeder as SF
-        if pattern_fn is None and self.is_Training and os.path.exists(SF.metadata_path()):
-            if self.feeder is None:
-                self.feeder = SF.SpeakerFeeder(SF.MelBank.from_patterns(device=self.device), seed=self.seed)
-            pattern_fn = self.feeder.Get_Train_Pattern
-        return super().Train(max_steps, pattern_fn)
+        if self.is_Training and os.path.exists(SF.metadata_path()):
+            return SF.SpeakerFeeder(SF.MelBank.from_patterns(device=self.device), seed=self.seed)
 
     def _after_step(self, result):
-        if self.feeder is not None:
-            self.feeder.check_status()               # right behind the loss read of Train_Step: the stream is already drained
+        super()._after_step(result)
         if (result["Global_Step"] + 1) % hp.Speaker_Embedding.Train.Inference_Timing == 0 and os.path.exists(INFERENCE_IN_TRAIN_FILE):
             with open(INFERENCE_IN_TRAIN_FILE, "r") as f:
                 label_List, path_List = list(zip(*[line.strip().split("\t") for line in f.readlines() if line.strip()]))

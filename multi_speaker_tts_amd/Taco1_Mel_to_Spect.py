@@ -32,7 +32,6 @@ class Mel_to_Spect(DropIn):
     def __init__(self, device="cuda", seed=1234, dims: Dims = None):
         self.device = device
         self.seed = seed
-        self.feeder = None
         self.engine = Taco1TrainEngine(dims, device=device, seed=seed)
         self.params = self.engine.params
         self.train_Tensor_Dict = {k: k for k in TRAIN_KEYS}
@@ -54,10 +53,12 @@ class Mel_to_Spect(DropIn):
         res.update({"Global_Step": step, "Learning_Rate": learning_rate(step), "Train_OP": None})
         return res
 
-    def _make_feeder(self):
-        """The device feeder when every file of the pattern set carries its 'Signal' and the bank fits its budget; else one line saying
-        which of the two failed, and the host feeder."""
+    def _corpus_feeder(self):
+        """When the metadata file of hp.Taco1_Mel_to_Spect.Train.Pattern_Path exists: the device feeder when every file of the pattern set
+        carries its 'Signal' and the bank fits its budget; else one line saying which of the two failed, and the host feeder."""
         from . import taco1_feeder as TF
+        if not os.path.exists(TF.metadata_path()):
+            return None
         md = TF.load_metadata()
         names, signals = md["File_List"], md.get("Signal_Length_Dict", {})
         missing = sum(1 for n in names if n not in signals)
@@ -71,20 +72,9 @@ class Mel_to_Spect(DropIn):
             return TF.PatternFeeder(seed=self.seed, md=md)
         return TF.Taco1Feeder(bank, seed=self.seed)
 
-    def Train(self, max_steps=None, pattern_fn=None):
-        """Without a pattern_fn, when the metadata file of hp.Taco1_Mel_to_Spect.Train.Pattern_Path exists: every step's batch comes from
-        the pattern set (`_make_feeder`); otherwise as DropIn.Train."""
-        from . import taco1_feeder as TF
-        if pattern_fn is None and os.path.exists(TF.metadata_path()):
-            if self.feeder is None:
-                self.feeder = self._make_feeder()
-            pattern_fn = self.feeder.Get_Train_Pattern
-        return super().Train(max_steps, pattern_fn)
-
     def _after_step(self, result):
         """Taco1_Mel_to_Spect.py:108-135: the periodic inference on the wav paths of Mel_to_Spect_Inference_in_Train.txt."""
-        if hasattr(self.feeder, "check_status"):
-            self.feeder.check_status()               # right behind the loss read of Train_Step: the stream is already drained
+        super()._after_step(result)
         if (result["Global_Step"] + 1) % hp.Taco1_Mel_to_Spect.Train.Inference_Timing == 0 and os.path.exists(INFERENCE_IN_TRAIN_FILE):
             with open(INFERENCE_IN_TRAIN_FILE, "r") as f:
                 paths = [line.strip() for line in f.readlines() if line.strip()]

@@ -144,7 +144,6 @@ class WaveGlow(DropIn):
         self.feeder_mode = feeder_mode(feeder)
         self.engine = WaveGlowTrainEngine(dims or WGDims.from_hp(hp), device=device, seed=seed, values=values)
         self.params = self.engine.params
-        self.feeder = None
         self.train_Tensor_Dict = {k: k for k in TRAIN_KEYS}
         self.inference_Tensor_Dict = {k: k for k in ("Global_Step", "Audio")}
 
@@ -167,7 +166,7 @@ class WaveGlow(DropIn):
         res.update({"Global_Step": step, "Learning_Rate": learning_rate(step), "Train_OP": None})
         return res
 
-    def _make_feeder(self):
+    def _corpus_feeder(self):
         """"host": the reference's loop (WavFeeder).  "device": the signal bank of the wavs under hp.WaveGlow.Train.Pattern_Path and the
         one-launch feeder on it; when the bank does not fit its budget, one line saying so and the host feeder."""
         if self.feeder_mode == "host":
@@ -182,16 +181,6 @@ class WaveGlow(DropIn):
             print("The signal bank does not fit ({}): feeding from the host (WavFeeder).".format(e))
             return WavFeeder(device=self.device)
         return WF.WaveGlowFeeder(bank, seed=self.seed, dims=self.engine.d)
-
-    def Train(self, max_steps=None, pattern_fn=None):
-        if pattern_fn is None:
-            self.feeder = self.feeder or self._make_feeder()
-            pattern_fn = self.feeder.Get_Train_Pattern
-        super().Train(max_steps, pattern_fn)
-
-    def _after_step(self, result):
-        if hasattr(self.feeder, "check_status"):
-            self.feeder.check_status()               # right behind the loss read of Train_Step: the stream is already drained
 
     def Inference(self, path_List, file_Prefix=None):
         """wav -> mel -> WaveGlowEngine (built from the current values) -> WAV files under hp.WaveGlow.Inference.Path/WAV (WaveGlow.py:144-205)."""

@@ -17,24 +17,15 @@ from collections import namedtuple
 import numpy as np
 
 from . import Hyper_Parameters as hp
+from .device_bank import MAX_WORKERS, DeviceBank, TableFeeder, _Epochs, check_metadata, file_lengths, load_chunked
 
 # lengths: int64 [n_files] frames per file; speaker_files: one int array of file indices per speaker
 BankIndex = namedtuple("BankIndex", ["lengths", "speaker_files"])
-
-MAX_WORKERS = 16
 
 
 def metadata_path(pattern_path=None):
     tr = hp.Speaker_Embedding.Train
     return os.path.join(pattern_path or tr.Pattern_Path, tr.Metadata_File.upper()).replace("\\", "/")
-
-
-def check_metadata(md):
-    """Feeder.py:37-45: the pattern set must have been made with the current sound hyper parameters."""
-    s = hp.Sound
-    if not all([md["Spectrogram_Dim"] == s.Spectrogram_Dim, md["Mel_Dim"] == s.Mel_Dim, md["Frame_Shift"] == s.Frame_Shift,
-                md["Frame_Length"] == s.Frame_Length, md["Sample_Rate"] == s.Sample_Rate]):
-        raise ValueError("The metadata information and hyper parameter setting are not consistent.")
 
 
 def epoch_groups(rng, bank_index, batch_speaker, batch_per_speaker):
@@ -82,13 +73,11 @@ def check_table(table, lengths, T):
     if t.ndim != 2 or t.shape[1] != 4:
         raise ValueError("the table must be [N, 4], not %s" % (t.shape,))
     t = t.astype(np.int64)
-    lengths = np.asarray(lengths, np.int64)
-    bad = (t < 0).any(axis=1) | (t[:, 0] >= lengths.shape[0])
-    file_len = lengths[np.where(bad, 0, t[:, 0])] if lengths.shape[0] else np.zeros(t.shape[0], np.int64)
-    bad |= (t[:, 1] + t[:, 3] > file_len) | (t[:, 2] + t[:, 3] > T)
+    bad, file_len = file_lengths(t[:, 0], lengths)
+    bad |= (t < 0).any(axis=1) | (t[:, 1] + t[:, 3] > file_len) | (t[:, 2] + t[:, 3] > T)
     if bad.any():
         r = int(np.nonzero(bad)[0][0])
-        raise ValueError("table row %d %s is invalid for %d files and T = %d" % (r, tuple(int(v) for v in t[r]), lengths.shape[0], T))
+        raise ValueError("table row %d %s is invalid for %d files and T = %d" % (r, tuple(int(v) for v in t[r]), len(lengths), T))
 
 
 def _load_pattern(args):
@@ -100,40 +89,16 @@ def _load_pattern(args):
     return np.ascontiguousarray(d["Mel"], np.float32)
 
 
-class MelBank:
-    """Every utterance's mel on the device: `bank` fp32 [total_frames, n_mel], `frame_off` int64 [n_files + 1] (device), `lengths`
-    (host int64), `speakers` (names) and `index` (BankIndex: host lengths and speaker -> file lists).  bank_bytes is a budget (default:
-    half of the free device memory at construction); a corpus over it raises ValueError."""
+class MelBank(DeviceBank):
+    """Every utterance's mel on the device: a DeviceBank of width n_mel (`bank` fp32 [total_frames, n_mel], `frame_off` = its offsets)
+    with `speakers` (names) and `index` (BankIndex: host lengths and speaker -> file lists)."""
+    NAME, UNIT = "mel bank", "frames"
 
     def __init__(self, lengths, speakers, speaker_files, n_mel, device="cuda", bank_bytes=None):
-        import torch
-        self.device = torch.device(device)
-        self.lengths = np.asarray(lengths, np.int64)
+        super().__init__(lengths, n_mel, device, bank_bytes)
         self.speakers = list(speakers)
         self.index = BankIndex(self.lengths, [np.asarray(f, np.int64) for f in speaker_files])
-        self.n_mel = int(n_mel)
-        offsets = np.concatenate([[0], np.cumsum(self.lengths)]).astype(np.int64)
-        self.total_frames = int(offsets[-1])
-        need = self.total_frames * self.n_mel * 4
-        if bank_bytes is None:
-            bank_bytes = torch.cuda.mem_get_info(self.device)[0] // 2
-        if need > bank_bytes:
-            raise ValueError("the corpus needs %d bytes of device memory, the mel bank's budget is %d bytes" % (need, bank_bytes))
-        if self.total_frames < 1:
-            raise ValueError("the corpus holds no frames")
-        self.bank_bytes = int(bank_bytes)
-        self.bank = torch.empty(self.total_frames, self.n_mel, dtype=torch.float32, device=self.device)
-        self.frame_off = torch.as_tensor(offsets).to(self.device)
-        self._offsets = offsets
-
-    def _fill(self, first, mels):
-        """mels: host arrays of files first, first + 1, ...: one upload."""
-        import torch
-        for k, m in enumerate(mels):
-            if m.shape != (self.lengths[first + k], self.n_mel):
-                raise ValueError("file %d: mel of shape %s, expected %s" % (first + k, m.shape, (int(self.lengths[first + k]), self.n_mel)))
-        a, b = int(self._offsets[first]), int(self._offsets[first + len(mels)])
-        self.bank[a:b].copy_(torch.as_tensor(np.concatenate(mels, axis=0)))
+        self.n_mel, self.frame_off, self.total_frames = self.width, self.offsets, self.total
 
     @classmethod
     def from_mels(cls, speaker_to_mel_list, device="cuda", bank_bytes=None):
@@ -150,9 +115,8 @@ class MelBank:
 
     @classmethod
     def from_patterns(cls, pattern_path=None, device="cuda", bank_bytes=None, workers=MAX_WORKERS, chunk=1024):
-        """Read METADATA.PICKLE and every pattern pickle under pattern_path (default hp.Speaker_Embedding.Train.Pattern_Path) once, with at
-        most 16 worker threads, `chunk` files per upload.  Speakers and their files in sorted order."""
-        from concurrent.futures import ThreadPoolExecutor
+        """Read METADATA.PICKLE and every pattern pickle under pattern_path (default hp.Speaker_Embedding.Train.Pattern_Path) once
+        (`load_chunked`).  Speakers and their files in sorted order."""
         root = pattern_path or hp.Speaker_Embedding.Train.Pattern_Path
         with open(metadata_path(root), "rb") as f:
             md = pickle.load(f)
@@ -165,58 +129,36 @@ class MelBank:
             jobs += [(root, name, s) for name in names]
         self = cls([md["Mel_Length_Dict"][name] for _, name, _ in jobs], speakers, files, md["Mel_Dim"], device, bank_bytes)
         self.names = [name for _, name, _ in jobs]
-        with ThreadPoolExecutor(max_workers=max(1, min(int(workers), MAX_WORKERS))) as pool:
-            for first in range(0, len(jobs), chunk):
-                self._fill(first, list(pool.map(_load_pattern, jobs[first:first + chunk])))
+        load_chunked(self, jobs, _load_pattern, workers, chunk)
         return self
 
 
-class SpeakerFeeder:
-    """`Get_Train_Pattern()` -> {'Mel': device tensor [N, T, n_mel], 'Batch_per_Speaker': P}: per batch one pinned upload of the table and
-    one gather launch, into a ring of `ring` output buffers (a returned 'Mel' stays valid until `ring` - 1 further batches were drawn).
-    The same seed gives the same batches bit for bit.  `status` (device int32 [1]) has bit 0 set once the kernel met an invalid row;
-    `check_status()` reads it (a synchronisation) and raises."""
+class SpeakerFeeder(TableFeeder):
+    """`Get_Train_Pattern()` -> {'Mel': device tensor [N, T, n_mel], 'Batch_per_Speaker': P}: a TableFeeder (ring of 3) whose table is
+    `plan_batch`'s and whose launch is mstts_mel_bank_gather.  The same seed gives the same batches bit for bit."""
+    KERNEL = "mstts_mel_bank_gather"
 
     def __init__(self, bank, seed=1234, batch_speaker=None, batch_per_speaker=None, frame_range=None, ring=3):
-        import torch
         tr = hp.Speaker_Embedding.Train
         self.bank = bank
         self.S = int(batch_speaker or tr.Batch_Speaker)
         self.P = int(batch_per_speaker or tr.Batch_per_Speaker)
         self.frame_range = tuple(int(v) for v in (frame_range or tr.Frame_Range))
-        self.rng = np.random.default_rng(seed)
-        self._groups = []
+        self._epochs = _Epochs(seed, lambda rng: epoch_groups(rng, bank.index, self.S, self.P))
         n_max = self.S * self.P
-        dev = bank.device
-        self.status = torch.zeros(1, dtype=torch.int32, device=dev)
-        self._slots = [(torch.empty(n_max, 4, dtype=torch.int32, pin_memory=True), torch.empty(n_max, 4, dtype=torch.int32, device=dev),
-                        torch.empty(n_max * self.frame_range[1] * bank.n_mel, dtype=torch.float32, device=dev), torch.cuda.Event())
-                       for _ in range(max(2, int(ring)))]
-        self._next = 0
-        epoch_groups(np.random.default_rng(0), bank.index, self.S, self.P)          # (raises now when no batch can be formed)
+        self._make_ring(bank.device, n_max, 4, [n_max * self.frame_range[1] * bank.n_mel], ring)
 
     def plan(self):
         """The next batch of the epoch as (T, table); a new epoch's groups are drawn when the last one is used up."""
-        if not self._groups:
-            self._groups = epoch_groups(self.rng, self.bank.index, self.S, self.P)
-        return plan_batch(self.rng, self.bank.index, self.S, self.P, self.frame_range, speakers=self._groups.pop(0))
+        return plan_batch(self._epochs.rng, self.bank.index, self.S, self.P, self.frame_range, speakers=self._epochs.next())
 
-    def Get_Train_Pattern(self):
-        import torch
+    def table(self, plan):
+        check_table(plan[1], self.bank.lengths, plan[0])
+        return plan[1]
+
+    def batch(self, plan, table_dev, N, bufs):
         from .lib import call, ptr
-        T, table = self.plan()
-        check_table(table, self.bank.lengths, T)
-        N, b = table.shape[0], self.bank
-        host, dev, out, done = self._slots[self._next]
-        self._next = (self._next + 1) % len(self._slots)
-        done.synchronize()                                   # the slot's previous upload and launch (ring batches ago)
-        host[:N].copy_(torch.from_numpy(table))
-        dev[:N].copy_(host[:N], non_blocking=True)
-        mel = out[:N * T * b.n_mel].view(N, T, b.n_mel)
-        call("mstts_mel_bank_gather", ptr(b.bank), ptr(b.frame_off), b.lengths.shape[0], ptr(dev), N, T, b.n_mel, ptr(mel), ptr(self.status))
-        done.record()
+        T, b = plan[0], self.bank
+        mel = bufs[0][:N * T * b.n_mel].view(N, T, b.n_mel)
+        call(self.KERNEL, ptr(b.bank), ptr(b.frame_off), b.lengths.shape[0], ptr(table_dev), N, T, b.n_mel, ptr(mel), ptr(self.status))
         return {"Mel": mel, "Batch_per_Speaker": self.P}
-
-    def check_status(self):
-        if int(self.status.item()) != 0:
-            raise RuntimeError("mstts_mel_bank_gather met an invalid table row (status %d)" % int(self.status.item()))

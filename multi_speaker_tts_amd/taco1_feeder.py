@@ -17,8 +17,8 @@ import threading
 import numpy as np
 
 from . import Hyper_Parameters as hp
+from .device_bank import MAX_WORKERS, BankBudgetError, DeviceBank, TableFeeder, _Epochs, check_metadata, file_lengths, load_chunked  # noqa: F401
 
-MAX_WORKERS = 16
 PREEMPHASIS, REF_LEVEL_DB = 0.97, 20.0          # Audio.stft_features' constants
 
 
@@ -32,14 +32,6 @@ def load_metadata(pattern_path=None):
         md = pickle.load(f)
     check_metadata(md)
     return md
-
-
-def check_metadata(md):
-    """Feeder.py:36-44: the pattern set must have been made with the current sound hyper parameters."""
-    s = hp.Sound
-    if not all([md["Spectrogram_Dim"] == s.Spectrogram_Dim, md["Mel_Dim"] == s.Mel_Dim, md["Frame_Shift"] == s.Frame_Shift,
-                md["Frame_Length"] == s.Frame_Length, md["Sample_Rate"] == s.Sample_Rate]):
-        raise ValueError("The metadata information and hyper parameter setting are not consistent.")
 
 
 def epoch_batches(rng, file_list, mel_lengths, batch_size, sort_by_length):
@@ -63,34 +55,20 @@ def check_files(files, lengths, T, n_fft, hop):
     f = np.asarray(files)
     if f.ndim != 1:
         raise ValueError("files must be [N], not %s" % (f.shape,))
-    f = f.astype(np.int64)
-    lengths = np.asarray(lengths, np.int64)
-    bad = (f < 0) | (f >= lengths.shape[0])
-    n = lengths[np.where(bad, 0, f)] if lengths.shape[0] else np.zeros(f.shape[0], np.int64)
+    bad, n = file_lengths(f, lengths)
     bad |= (n <= n_fft // 2) | (1 + n // hop > T)
     if bad.any():
         r = int(np.nonzero(bad)[0][0])
-        raise ValueError("row %d (file %d) is invalid for %d files, n_fft = %d, hop = %d and T = %d" % (r, int(f[r]), lengths.shape[0], n_fft, hop, T))
+        raise ValueError("row %d (file %d) is invalid for %d files, n_fft = %d, hop = %d and T = %d" % (r, int(f[r]), len(lengths), n_fft, hop, T))
 
 
-class _Epochs:
-    """The endless sequence of batches both feeders draw from: a new epoch's plan when the last one is used up."""
-
-    def __init__(self, seed, file_list, mel_lengths, batch_size, sort_by_length):
-        self.rng = np.random.default_rng(seed)
-        self.args = (list(file_list), np.asarray(mel_lengths, np.int64), int(batch_size), bool(sort_by_length))
-        self._groups = []
-        epoch_batches(np.random.default_rng(0), *self.args)                 # (raises now when no batch can be formed)
-
-    def next(self):
-        if not self._groups:
-            self._groups = epoch_batches(self.rng, *self.args)
-        return self._groups.pop(0)
-
-
-def _train_hp(batch_size, sort_by_length):
+def _train_epochs(seed, mel_lengths, batch_size, sort_by_length):
+    """(batch size, the epochs of `epoch_batches` over files 0 .. len(mel_lengths) - 1 that both feeders draw from); None: the
+    trainer's hyper parameter."""
     tr = hp.Taco1_Mel_to_Spect.Train
-    return int(batch_size or tr.Batch_Size), bool(tr.Pattern_Sorting_by_Length if sort_by_length is None else sort_by_length)
+    B, sort = int(batch_size or tr.Batch_Size), bool(tr.Pattern_Sorting_by_Length if sort_by_length is None else sort_by_length)
+    lengths = np.asarray(mel_lengths, np.int64)
+    return B, _Epochs(seed, lambda rng: epoch_batches(rng, range(len(lengths)), lengths, B, sort))
 
 
 def pad_batch(mels, specs):
@@ -113,8 +91,7 @@ class PatternFeeder:
         md = md if md is not None else load_metadata(self.root)
         check_metadata(md)
         self.names = list(md["File_List"])
-        B, sort = _train_hp(batch_size, sort_by_length)
-        self._epochs = _Epochs(seed, self.names, [md["Mel_Length_Dict"][n] for n in self.names], B, sort)
+        self._epochs = _train_epochs(seed, [md["Mel_Length_Dict"][n] for n in self.names], batch_size, sort_by_length)[1]
         self.max_queue = int(max_queue or hp.Taco1_Mel_to_Spect.Train.Max_Pattern_Queue)
         self.queue = queue.Queue(maxsize=self.max_queue)
         self.max_queued = 0
@@ -164,42 +141,14 @@ def _load_signal(args):
     return sig
 
 
-class BankBudgetError(ValueError):
-    """The corpus does not fit the signal bank's budget."""
-
-
-class SignalBank:
-    """Every file's trimmed waveform on the device: `bank` fp32 [total_samples], `sig_off` int64 [n_files + 1] (device), `lengths` (host
-    int64, samples) and `names`.  bank_bytes is a budget (default: half of the free device memory at construction); a corpus over it
-    raises BankBudgetError (a ValueError)."""
+class SignalBank(DeviceBank):
+    """Every file's trimmed waveform on the device: a DeviceBank of width 1 (`bank` fp32 [total_samples], `sig_off` = its offsets,
+    `lengths` in samples)."""
+    NAME, UNIT = "signal bank", "samples"
 
     def __init__(self, lengths, device="cuda", bank_bytes=None, names=None):
-        import torch
-        self.device = torch.device(device)
-        self.lengths = np.asarray(lengths, np.int64)
-        self.names = list(names) if names is not None else None
-        offsets = np.concatenate([[0], np.cumsum(self.lengths)]).astype(np.int64)
-        self.total_samples = int(offsets[-1])
-        need = self.total_samples * 4
-        if bank_bytes is None:
-            bank_bytes = torch.cuda.mem_get_info(self.device)[0] // 2
-        if need > bank_bytes:
-            raise BankBudgetError("the corpus needs %d bytes of device memory, the signal bank's budget is %d bytes" % (need, bank_bytes))
-        if self.total_samples < 1:
-            raise ValueError("the corpus holds no samples")
-        self.bank_bytes = int(bank_bytes)
-        self.bank = torch.empty(self.total_samples, dtype=torch.float32, device=self.device)
-        self.sig_off = torch.as_tensor(offsets).to(self.device)
-        self._offsets = offsets
-
-    def _fill(self, first, sigs):
-        """sigs: host arrays of files first, first + 1, ...: one upload."""
-        import torch
-        for k, x in enumerate(sigs):
-            if x.shape != (self.lengths[first + k],):
-                raise ValueError("file %d: signal of shape %s, expected (%d,)" % (first + k, x.shape, int(self.lengths[first + k])))
-        a, b = int(self._offsets[first]), int(self._offsets[first + len(sigs)])
-        self.bank[a:b].copy_(torch.as_tensor(np.concatenate(sigs)))
+        super().__init__(lengths, 1, device, bank_bytes, names)
+        self.sig_off, self.total_samples = self.offsets, self.total
 
     @classmethod
     def from_signals(cls, signals, device="cuda", bank_bytes=None):
@@ -212,8 +161,7 @@ class SignalBank:
     @classmethod
     def from_patterns(cls, pattern_path=None, device="cuda", bank_bytes=None, workers=MAX_WORKERS, chunk=1024, md=None):
         """Read METADATA.PICKLE and the 'Signal' of every pattern pickle under pattern_path (default hp.Taco1_Mel_to_Spect.Train.Pattern_Path)
-        once, with at most 16 worker threads, `chunk` files per upload.  Files in 'File_List' order."""
-        from concurrent.futures import ThreadPoolExecutor
+        once (`load_chunked`).  Files in 'File_List' order."""
         root = pattern_path or hp.Taco1_Mel_to_Spect.Train.Pattern_Path
         md = md if md is not None else load_metadata(root)
         check_metadata(md)
@@ -223,22 +171,17 @@ class SignalBank:
             raise ValueError("%d of %d pattern files carry no 'Signal' (the first: %s)" % (len(missing), len(names), missing[0]))
         self = cls([md["Signal_Length_Dict"][n] for n in names], device, bank_bytes, names)
         self.mel_lengths = np.asarray([md["Mel_Length_Dict"][n] for n in names], np.int64)
-        jobs = [(root, n, int(k)) for n, k in zip(names, self.lengths)]
-        with ThreadPoolExecutor(max_workers=max(1, min(int(workers), MAX_WORKERS))) as pool:
-            for first in range(0, len(jobs), chunk):
-                self._fill(first, list(pool.map(_load_signal, jobs[first:first + chunk])))
+        load_chunked(self, [(root, n, int(k)) for n, k in zip(names, self.lengths)], _load_signal, workers, chunk)
         return self
 
 
-class Taco1Feeder:
+class Taco1Feeder(TableFeeder):
     """`Get_Train_Pattern()` -> {'Mel': device tensor [N, T, n_mel], 'Spectrogram': device tensor [N, T, n_spec]}, T = the group's longest:
-    per batch one pinned upload of the `files` table and one mstts_stft_bank_batch launch on the current stream, into one of two
-    alternating pairs of output buffers allocated once for the largest possible group (a returned batch stays valid until the next but one
-    is drawn; a new batch shape allocates nothing).  The same seed gives the same batches as PatternFeeder's, bit for bit.  `status`
-    (device int32 [1]) has bit 0 set once the kernel met an invalid row; `check_status()` reads it (a synchronisation) and raises."""
+    a TableFeeder (ring of 2, its buffers sized for the largest possible group) whose table is the group's `files` and whose launch is
+    mstts_stft_bank_batch.  The same seed gives the same batches as PatternFeeder's, bit for bit."""
+    KERNEL = "mstts_stft_bank_batch"
 
-    def __init__(self, bank, seed=1234, batch_size=None, sort_by_length=None):
-        import torch
+    def __init__(self, bank, seed=1234, batch_size=None, sort_by_length=None, ring=2):
         from . import Audio
         s = hp.Sound
         self.bank = bank
@@ -249,15 +192,10 @@ class Taco1Feeder:
         mel_lengths = getattr(bank, "mel_lengths", None)
         if mel_lengths is not None and not np.array_equal(mel_lengths, self.frames):
             raise ValueError("the metadata's mel lengths are not 1 + signal length / hop: the pattern set was not made from these signals")
-        B, sort = _train_hp(batch_size, sort_by_length)
-        self._epochs = _Epochs(seed, range(len(self.frames)), self.frames, B, sort)
-        n_max, dev = min(B, len(self.frames)), bank.device
+        B, self._epochs = _train_epochs(seed, self.frames, batch_size, sort_by_length)
+        n_max = min(B, len(self.frames))
         rows = n_max * int(self.frames.max())
-        self.status = torch.zeros(1, dtype=torch.int32, device=dev)
-        self._slots = [(torch.empty(n_max, dtype=torch.int32, pin_memory=True), torch.empty(n_max, dtype=torch.int32, device=dev),
-                        torch.empty(rows * self.n_mel, dtype=torch.float32, device=dev),
-                        torch.empty(rows * self.n_spec, dtype=torch.float32, device=dev), torch.cuda.Event()) for _ in range(2)]
-        self._next = 0
+        self._make_ring(bank.device, n_max, 1, [rows * self.n_mel, rows * self.n_spec], ring)
 
     def check_files(self, files, T):
         check_files(files, self.bank.lengths, T, self.n_fft, self.hop)
@@ -267,32 +205,23 @@ class Taco1Feeder:
         files = self._epochs.next().astype(np.int32)
         return int(self.frames[files].max()), files
 
+    def table(self, plan):
+        self.check_files(plan[1], plan[0])
+        return plan[1]
+
     def launch(self, files_dev, N, T, mel, spec):
         """One mstts_stft_bank_batch launch on the current stream: files_dev device int32 [N] -> mel [N, T, n_mel], spec [N, T, n_spec]
         (either may be None)."""
         from .lib import call, ptr
         _, _, _, hann, tw, fb, rng = self.consts
         b = self.bank
-        call("mstts_stft_bank_batch", ptr(b.bank), ptr(b.sig_off), b.lengths.shape[0], ptr(files_dev), N, T, PREEMPHASIS, ptr(hann), ptr(tw),
+        call(self.KERNEL, ptr(b.bank), ptr(b.sig_off), b.lengths.shape[0], ptr(files_dev), N, T, PREEMPHASIS, ptr(hann), ptr(tw),
              ptr(fb), ptr(rng), self.n_fft, self.hop, self.win, self.n_mel, self.max_abs, REF_LEVEL_DB,
              ptr(mel) if mel is not None else None, ptr(spec) if spec is not None else None, ptr(self.status))
 
-    def Get_Train_Pattern(self):
-        import torch
-        T, files = self.plan()
-        self.check_files(files, T)
-        N = files.shape[0]
-        host, dev, mel_buf, spec_buf, done = self._slots[self._next]
-        self._next = (self._next + 1) % len(self._slots)
-        done.synchronize()                                   # the slot's previous upload and launch (two batches ago)
-        host[:N].copy_(torch.from_numpy(files))
-        dev[:N].copy_(host[:N], non_blocking=True)
-        mel = mel_buf[:N * T * self.n_mel].view(N, T, self.n_mel)
-        spec = spec_buf[:N * T * self.n_spec].view(N, T, self.n_spec)
-        self.launch(dev, N, T, mel, spec)
-        done.record()
+    def batch(self, plan, files_dev, N, bufs):
+        T = plan[0]
+        mel = bufs[0][:N * T * self.n_mel].view(N, T, self.n_mel)
+        spec = bufs[1][:N * T * self.n_spec].view(N, T, self.n_spec)
+        self.launch(files_dev, N, T, mel, spec)
         return {"Mel": mel, "Spectrogram": spec}
-
-    def check_status(self):
-        if int(self.status.item()) != 0:
-            raise RuntimeError("mstts_stft_bank_batch met an invalid row (status %d)" % int(self.status.item()))

@@ -209,9 +209,11 @@ class DropIn:
     """What the drop-in trainer classes share.  The checkpoint file <hp.<HP>.Checkpoint_Path>/<FILE> holds the variables whose names start
     with SCOPE, the Adam slots under `__adam_m__` / `__adam_v__` and the global step under `__global_step__` (Tacotron2.Vocoder_Load and
     Speaker_Embedding_Load read these files).  Train prints the time, the global step and the COLUMNS ((format, result key) pairs) of each
-    step and saves every Checkpoint_Save_Timing steps; `_after_step(result)` is a class's own per-step hook."""
+    step and saves every Checkpoint_Save_Timing steps; `_after_step(result)` is the per-step hook: here the status check of a device
+    corpus feeder (`feeder`, from `_corpus_feeder`), a class adds its own."""
     HP = FILE = SCOPE = None
     COLUMNS = ()
+    feeder = None
 
     def _file(self):
         return os.path.join(getattr(hp, self.HP).Checkpoint_Path.replace("\\", "/"), self.FILE)
@@ -247,7 +249,17 @@ class DropIn:
             return a.to(self.engine.device, torch.float32).contiguous()
         return torch.as_tensor(np.asarray(a, np.float32)).to(self.engine.device).contiguous()
 
+    def _corpus_feeder(self):
+        """The feeder Train() draws its patterns from when it is given no pattern_fn, made once; None: Train_Step(None), a class's
+        synthetic pattern."""
+        return None
+
     def Train(self, max_steps=None, pattern_fn=None):
+        if pattern_fn is None:
+            if self.feeder is None:
+                self.feeder = self._corpus_feeder()
+            if self.feeder is not None:
+                pattern_fn = self.feeder.Get_Train_Pattern
         while max_steps is None or self.engine.global_step < max_steps:
             t0 = time.time()
             r = self.Train_Step(pattern_fn() if pattern_fn else None)
@@ -258,4 +270,5 @@ class DropIn:
             self._after_step(r)
 
     def _after_step(self, result):
-        pass
+        if hasattr(self.feeder, "check_status"):
+            self.feeder.check_status()               # right behind the loss read of Train_Step: the stream is already drained

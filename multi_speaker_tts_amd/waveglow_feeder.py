@@ -15,7 +15,8 @@ from typing import NamedTuple
 import numpy as np
 
 from . import Hyper_Parameters as hp
-from .taco1_feeder import MAX_WORKERS, BankBudgetError, SignalBank, _Epochs
+from .device_bank import MAX_WORKERS, BankBudgetError, TableFeeder, _Epochs, default_bank_bytes, file_lengths, pooled_chunks
+from .taco1_feeder import SignalBank, epoch_batches
 
 PREEMPHASIS = 0.97                               # Audio.stft_features' constant
 
@@ -47,36 +48,32 @@ def bank_from_wavs(paths, device="cuda", bank_bytes=None, chunk=256, workers=MAX
     to nothing is left out with one printed line.  bank_bytes: the bank's budget (default: half of the free device memory now); the
     corpus going over it raises BankBudgetError as soon as it does."""
     import torch
-    from concurrent.futures import ThreadPoolExecutor
     from . import Audio
     dev = torch.device(device)
     paths = list(paths)
     if bank_bytes is None:
-        bank_bytes = torch.cuda.mem_get_info(dev)[0] // 2
+        bank_bytes = default_bank_bytes(dev)
     pieces, lengths, names, total = [], [], [], 0
-    with ThreadPoolExecutor(max_workers=max(1, min(int(workers), MAX_WORKERS))) as pool:
-        for first in range(0, len(paths), max(1, int(chunk))):
-            part = paths[first:first + max(1, int(chunk))]
-            decoded = list(pool.map(_decode, part))
-            sigs = Audio.wav_front_end([d for _, d in decoded], [r for r, _ in decoded], hp.WaveGlow.Export_Sample_Rate, top_db=15, frame=32,
-                                       hop=16, scale=0.99, peak_normalize=True, device=dev, return_tensor=True, rule="scipy")
-            kept = []
-            for p, x in zip(part, sigs):
-                if x.numel() == 0:
-                    print("'{}' trims to nothing: left out of the signal bank.".format(p))
-                    continue
-                kept.append(x)
-                names.append(p)
-                lengths.append(int(x.numel()))
-            total += sum(int(x.numel()) for x in kept)
-            if total * 4 > bank_bytes:
-                raise BankBudgetError("the corpus needs more than %d bytes of device memory, the signal bank's budget is %d bytes" % (total * 4, bank_bytes))
-            if kept:
-                pieces.append(torch.cat(kept))                       # (a copy: the front end's packed buffer, untrimmed, is let go)
+    for first, decoded in pooled_chunks(paths, _decode, workers, chunk):
+        sigs = Audio.wav_front_end([d for _, d in decoded], [r for r, _ in decoded], hp.WaveGlow.Export_Sample_Rate, top_db=15, frame=32,
+                                   hop=16, scale=0.99, peak_normalize=True, device=dev, return_tensor=True, rule="scipy")
+        kept = []
+        for p, x in zip(paths[first:first + len(sigs)], sigs):
+            if x.numel() == 0:
+                print("'{}' trims to nothing: left out of the signal bank.".format(p))
+                continue
+            kept.append(x)
+            names.append(p)
+            lengths.append(int(x.numel()))
+        total += sum(int(x.numel()) for x in kept)
+        if total * 4 > bank_bytes:
+            raise BankBudgetError("the corpus needs more than %d bytes of device memory, the signal bank's budget is %d bytes" % (total * 4, bank_bytes))
+        if kept:
+            pieces.append(torch.cat(kept))                           # (a copy: the front end's packed buffer, untrimmed, is let go)
     bank = SignalBank(lengths, dev, bank_bytes, names)
     at = 0
     for x in pieces:
-        bank.bank[at:at + x.numel()].copy_(x)
+        bank._fill_device(at, x)
         at += int(x.numel())
     return bank
 
@@ -97,14 +94,11 @@ def check_table(table, lengths):
     t = np.asarray(table)
     if t.ndim != 2 or t.shape[1] != 2:
         raise ValueError("table must be [N, 2], not %s" % (t.shape,))
-    t = t.astype(np.int64)
-    lengths = np.asarray(lengths, np.int64)
-    bad = (t[:, 0] < 0) | (t[:, 0] >= lengths.shape[0])
-    n = lengths[np.where(bad, 0, t[:, 0])] if lengths.shape[0] else np.zeros(t.shape[0], np.int64)
+    bad, n = file_lengths(t[:, 0], lengths)
     bad |= (t[:, 1] < 0) | (t[:, 1] >= n)
     if bad.any():
         r = int(np.nonzero(bad)[0][0])
-        raise ValueError("row %d (file %d, start %d) is invalid for %d files" % (r, int(t[r, 0]), int(t[r, 1]), lengths.shape[0]))
+        raise ValueError("row %d (file %d, start %d) is invalid for %d files" % (r, int(t[r, 0]), int(t[r, 1]), len(lengths)))
 
 
 def crop_frames(L, up, down, transform):
@@ -157,17 +151,15 @@ def crop_batch_host(bank_host, offsets, table, L, up, down, T=None, transform=No
     return audio, mel
 
 
-class WaveGlowFeeder:
+class WaveGlowFeeder(TableFeeder):
     """`Get_Train_Pattern()` -> {'Audio': device tensor [N, L], 'Mel': device tensor [N, F, Mel_Dim]}, L = Max_Signal_Length, F = the mel
-    frames of L samples after the conversion Export_Sample_Rate -> Sound.Sample_Rate: per batch one pinned upload of the (file, start)
-    table and one mstts_wg_crop_batch launch on the current stream, into one of two alternating pairs of output buffers allocated once (a
-    returned batch stays valid until the next but one is drawn).  The plan is the reference's: files shuffled, grouped by Batch_Size, the
-    groups shuffled, then a crop per row as each batch is drawn, all from one Generator(seed).  `status` (device int32 [1]) has bit 0 set
-    once the kernel met an invalid row; `check_status()` reads it (a synchronisation) and raises.  dims: the trainer's WGDims, whose
-    `restructure` must accept (L, F)."""
+    frames of L samples after the conversion Export_Sample_Rate -> Sound.Sample_Rate: a TableFeeder (ring of 2) whose table is the
+    (file, start) pairs of `crop_plan` and whose launch is mstts_wg_crop_batch.  The plan is the reference's: files shuffled, grouped by
+    Batch_Size, the groups shuffled, then a crop per row as each batch is drawn, all from one Generator(seed).  dims: the trainer's
+    WGDims, whose `restructure` must accept (L, F)."""
+    KERNEL = "mstts_wg_crop_batch"
 
-    def __init__(self, bank, seed=1234, batch_size=None, max_length=None, dims=None, transform=None):
-        import torch
+    def __init__(self, bank, seed=1234, batch_size=None, max_length=None, dims=None, transform=None, ring=2):
         from . import Audio
         from .waveglow import WGDims
         from .waveglow_trainer import restructure
@@ -186,38 +178,24 @@ class WaveGlowFeeder:
         B = int(batch_size or tr.Batch_Size)
         restructure(dims or WGDims.from_hp(hp), B, self.L, self.F)                 # (raises what the train step would)
         n = len(bank.lengths)
-        self._epochs = _Epochs(seed, range(n), bank.lengths, B, False)
-        n_max, dev, n_mel = min(B, n), bank.device, int(self.transform.num_mels)
-        self.status = torch.zeros(1, dtype=torch.int32, device=dev)
-        self._slots = [(torch.empty(n_max, 2, dtype=torch.int32, pin_memory=True), torch.empty(n_max, 2, dtype=torch.int32, device=dev),
-                        torch.empty(n_max * self.L, dtype=torch.float32, device=dev),
-                        torch.empty(n_max * self.F * n_mel, dtype=torch.float32, device=dev), torch.cuda.Event()) for _ in range(2)]
-        self._next = 0
+        self._epochs = _Epochs(seed, lambda rng: epoch_batches(rng, range(n), bank.lengths, B, False))
+        n_max = min(B, n)
+        self._make_ring(bank.device, n_max, 2, [n_max * self.L, n_max * self.F * int(self.transform.num_mels)], ring)
 
     def plan(self):
         """The next batch as its table, int32 [N, 2]."""
         return crop_plan(self._epochs.rng, self.bank.lengths, self._epochs.next(), self.L)
 
+    def table(self, plan):
+        check_table(plan, self.bank.lengths)
+        return plan
+
     def launch(self, table_dev, N, audio, mel):
         b = self.bank
         crop_batch(b.bank, b.sig_off, b.lengths.shape[0], table_dev, N, self.L, self.F, self.up, self.down, self.transform, audio, mel, self.status)
 
-    def Get_Train_Pattern(self):
-        import torch
-        table = self.plan()
-        check_table(table, self.bank.lengths)
-        N = table.shape[0]
-        host, dev, audio_buf, mel_buf, done = self._slots[self._next]
-        self._next = (self._next + 1) % len(self._slots)
-        done.synchronize()                                   # the slot's previous upload and launch (two batches ago)
-        host[:N].copy_(torch.from_numpy(table))
-        dev[:N].copy_(host[:N], non_blocking=True)
-        audio = audio_buf[:N * self.L].view(N, self.L)
-        mel = mel_buf[:N * self.F * self.transform.num_mels].view(N, self.F, self.transform.num_mels)
-        self.launch(dev, N, audio, mel)
-        done.record()
+    def batch(self, plan, table_dev, N, bufs):
+        audio = bufs[0][:N * self.L].view(N, self.L)
+        mel = bufs[1][:N * self.F * self.transform.num_mels].view(N, self.F, self.transform.num_mels)
+        self.launch(table_dev, N, audio, mel)
         return {"Audio": audio, "Mel": mel}
-
-    def check_status(self):
-        if int(self.status.item()) != 0:
-            raise RuntimeError("mstts_wg_crop_batch met an invalid row (status %d)" % int(self.status.item()))
