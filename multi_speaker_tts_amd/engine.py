@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import types
 import warnings
 
 import numpy as np
@@ -28,7 +29,6 @@ from .training import (BN_EPS, BN_MOM, Engine, _split_k, _split_k_big, bn_train_
 MAX_PLANS = 64     # cached workspace sets (one per batch shape): views into ONE arena, a set owns no device memory
 
 
-
 def learning_rate(step):
     """MSTTS_SV.py:163-169."""
     from . import Hyper_Parameters as hp
@@ -43,7 +43,21 @@ ENC_OVERLAP = os.environ.get("MSTTS_ENC_OVERLAP", "1") != "0"    # the encoder's
 
 
 class _WS:
-    """Attribute bag of device buffers for one (B, T_enc, L) shape: views into the engine's workspace arena."""
+    """Device buffers for one (B, T_enc, L) shape - views into the engine's workspace arena, named in _build_plan - and the flags below."""
+    persist = persist_bwd = persist_enc = False      # the shape admits the persistent decoder forward / decoder BPTT / encoder launches (tests clear them)
+    persist_now = persist_bwd_now = False            # ... and the fallback policy allowed them in the forward pass that ran last
+    opk_valid = enc_hist_valid = False               # that pass left the decoder's packed BPTT operands / the encoder's packed history
+    fold_prenet = False                              # ... and formed the cell-0 input product inside the decoder launch
+    voc_fused = False                                # the vocoder chain's fused form (VOC_FUSED when the shape was planned)
+    voc_done = None                                  # the vocoder side chain's event until it is joined
+    side_wgrads = False                              # postnet weight-gradient products are on the encoder's stream, not joined yet
+
+
+def _loss_dict(s, wr_rate):
+    """The step's loss report from the four loss words."""
+    wr = float(s[3]) * wr_rate
+    return {"Linear_Loss": float(s[0]), "Postnet_Loss": float(s[1]), "Stop_Loss": float(s[2]),
+            "Weight_Regularization_Loss": wr, "Loss": float(s[0] + s[1] + s[2]) + wr}
 
 
 class _LateScalars:
@@ -55,10 +69,7 @@ class _LateScalars:
     def get(self):
         if self._res is None:
             self.event.synchronize()
-            s = self.slot.numpy().copy()
-            wr = float(s[3]) * self.wr_rate
-            self._res = {"Linear_Loss": float(s[0]), "Postnet_Loss": float(s[1]), "Stop_Loss": float(s[2]),
-                         "Weight_Regularization_Loss": wr, "Loss": float(s[0] + s[1] + s[2]) + wr}
+            self._res = _loss_dict(self.slot.numpy().copy(), self.wr_rate)
         return self._res
 
 
@@ -120,7 +131,12 @@ class TrainEngine(Engine):
         the attention parameter gradients in their one-add-per-element forms - so two runs from the same state end bit-identical
         (tests/test_gpu_model.py::test_deterministic_training_is_bit_reproducible) where the persistent launches run (the reference widths); the
         launch-per-step fallback loops keep K-cuts with atomics of their own.  A debugging mode: 121 ms per step at the headline shape (2.9 x)."""
-        lib.load()
+        self.recurrent_dtype, self.gemm_dtype = (recurrent_dtype or "f32").lower(), (gemm_dtype or "f32").lower()
+        if self.gemm_dtype not in ("f32", "bf16"):
+            raise ValueError("gemm_dtype must be 'f32' or 'bf16'")
+        if self.recurrent_dtype not in ("f32", "bf16"):
+            raise ValueError("recurrent_dtype must be 'f32' or 'bf16'")
+        lb = lib.load()
         self.d = dims or Dims()
         self.device = torch.device(device)
         self.seed, self.rank, self.world = seed, rank, world
@@ -151,7 +167,6 @@ class TrainEngine(Engine):
         self.loc_k, self.loc_b, self.d_loc_k = self._f(d.att_k, d.att), self._f(d.att), self._f(d.att_k, d.att)
         self.loc_kt = self._f(d.att, 36) if d.att_k <= 31 else None       # the folded filter by unit (forward attention step)
         # fused cell steps (csrc/cell.hip): the two decoder cell kernels in the lanes' consumption order
-        lb = lib.load()
         self.fused_cells = bool(lb.mstts_cell_fwd_supported(H, M + H)) and bool(lb.mstts_cell_fwd_supported(H, 2 * H))
         self.w0p = self._f((M + H) * 4 * H) if self.fused_cells else None
         self.w1p = self._f(2 * H * 4 * H) if self.fused_cells else None
@@ -169,7 +184,7 @@ class TrainEngine(Engine):
         # (BASELINE config 2), or - round 5 - bf16 ones when the whole step runs config-3 arithmetic (recurrent_dtype AND gemm_dtype "bf16":
         # the bf16 instantiation forms the prenet rows' product itself, as a bf16 product like the hoisted one it replaces; with fp32
         # contractions around bf16 loops that product would have to stay fp32, and that combination keeps the launch-per-step loops)
-        rdt, gdt = (recurrent_dtype or "f32").lower(), (gemm_dtype or "f32").lower()
+        rdt, gdt = self.recurrent_dtype, self.gemm_dtype
         self.persist_bf16 = rdt == "bf16" and gdt == "bf16" and d.prenet == 256 and os.environ.get("MSTTS_PERSIST_BF16", "1") != "0"
         self.persist = (os.environ.get("MSTTS_PERSIST", "1") != "0" and (rdt == "f32" or self.persist_bf16)
                         and bool(lb.mstts_persist_fwd_supported(1, H, M, d.att, 1, d.att_k)))
@@ -180,14 +195,17 @@ class TrainEngine(Engine):
         # consecutive steps with a fallback the persistent plans are switched off for PERSIST_COOLDOWN steps (warned once), then probed
         # again.  persist_disabled_steps counts the steps run that way; non_persistent_plans the shapes planned without them although
         # the widths are the reference's (the T_enc / batch cliff of the persistent kernels).
-        self._moving_snapshot = None
+        self._moving_snapshot = torch.empty(self.params.n_moving, dtype=torch.float32, device=self.device)   # (forward: the BN moving statistics at the start of a speculative pass)
         self._persist_cool = CoolDown()
         self._persist_warned = False
+        self._step_fell_back = self._step_was_persistent = False      # this optimizer step: a persistent launch gave up / the policy admitted them
+        self.persist_last_status = None      # the control words of the decoder launch that gave up last
         self.persist_disabled_steps = 0
         self.non_persistent_plans = 0
         self._warned_shapes = set()
         self.persist_selftest = 0            # tests: k > 0 makes the persistent forward launch abort at step k - 1
         self.persist_bwd_selftest = 0        # ... and the persistent BPTT launch at its k-th step
+        self.persist_enc_selftest = 0        # ... and the next k encoder launches read "gave up"
         self.persist_stamps = None           # bench: 256 x 16 int64 tensor -> per-stage ticks of the next persistent launch
         self.persist_bwd = self.persist and os.environ.get("MSTTS_PERSIST_BWD", "1") != "0" and bool(lb.mstts_persist_bwd_supported(1, H, M, d.att, 1, d.att_k))
         self.persist_bwd_fallbacks = 0
@@ -208,6 +226,7 @@ class TrainEngine(Engine):
         if self.persist_enc:
             n = int(lb.mstts_persist_lstm_pack_floats())
             self.enc_pk = {dr: (self._f(n), self._f(n)) for dr in ("fw", "bw")}          # (forward order, BPTT order)
+        self._side = self._enc_stream = self._voc_stream = None
         if self.device.type == "cuda":
             self._side = torch.cuda.Stream(device=self.device)                # status words -> pinned host memory, the job-wide verdict's exchange
             self._enc_stream = torch.cuda.Stream(device=self.device)          # the encoder's persistent launches (forward / loss_and_backward)
@@ -226,13 +245,8 @@ class TrainEngine(Engine):
             n = sum(win * d.n_mel * (hi - lo + 1) * d.bank_ch for lo, hi, win, _ in groups)
             self.voc_bank = {"groups": groups, "w": self._f(n), "bias": self._f(d.bank_k * d.bank_ch), "version": None, "tables": None}
         self.big_tiles = os.environ.get("MSTTS_SPLIT_K_BIG", "1") != "0"      # weight-gradient splits chosen for the 256 x 256-tile kernels
-        self._derived_stale = True
-        self.gemm_dtype = (gemm_dtype or "f32").lower()
-        if self.gemm_dtype not in ("f32", "bf16"):
-            raise ValueError("gemm_dtype must be 'f32' or 'bf16'")
-        self.recurrent_dtype = (recurrent_dtype or "f32").lower()
-        if self.recurrent_dtype not in ("f32", "bf16"):
-            raise ValueError("recurrent_dtype must be 'f32' or 'bf16'")
+        self._derived_stale = self._fallback_packs_stale = True
+        self._scalar_ring, self._scalar_next, self._scalar_avg, self._scalar_handles = None, 0, None, [None] * 4     # scalars_async
         self.bf = None
         if self.recurrent_dtype == "bf16" and lb.mstts_cell_fwd_bf16_supported(H, M + H) and lb.mstts_cell_fwd_bf16_supported(H, 2 * H):
             self.w0p16 = torch.zeros((M + H) * 4 * H, dtype=torch.int16, device=self.device)
@@ -271,7 +285,7 @@ class TrainEngine(Engine):
     def _ensure_fallback_packs(self):
         """Packed kernels of the launch-per-step loops (decoder cells forward / data-gradient products backward, encoder cells, the
         transposed query kernel of the fused query gradient), refreshed at most once per optimizer step."""
-        if not getattr(self, "_fallback_packs_stale", True):
+        if not self._fallback_packs_stale:
             return
         self._fallback_packs_stale = False
         d = self.d
@@ -297,14 +311,10 @@ class TrainEngine(Engine):
         if self.wq_t is not None:
             call("mstts_transpose01", ptr(wq_, oq_), ptr(self.wq_t), H, d.att // 4, 4)      # [H, A/4, 4] -> [A/4, H, 4]
         if self.bf is not None:              # bf16 copies of the master weights for the launch-per-step bf16 loops, in the lanes' consumption order
-            A_ = d.att
-            f0, f1, fq, b0, b1, bq = self.bf["splits"]
-            call("mstts_pack_bf16_fwd", ptr(self.w0f), 4 * H, ptr(self.bf["w0f_f"]), M + H, 4 * H, f0)
-            call("mstts_pack_bf16_fwd", ptr(k1, o1), 4 * H, ptr(self.bf["w1_f"]), 2 * H, 4 * H, f1)
-            call("mstts_pack_bf16_fwd", ptr(wq_, oq_), A_, ptr(self.bf["wq_f"]), H, A_, fq)
-            call("mstts_pack_bf16_bwd", ptr(self.w0f), 4 * H, ptr(self.bf["w0f_b"]), M + H, 4 * H, b0)
-            call("mstts_pack_bf16_bwd", ptr(k1, o1), 4 * H, ptr(self.bf["w1_b"]), 2 * H, 4 * H, b1)
-            call("mstts_pack_bf16_bwd", ptr(wq_, oq_), A_, ptr(self.bf["wq_b"]), H, A_, bq)
+            mats = (("w0f", ptr(self.w0f), M + H, 4 * H), ("w1", ptr(k1, o1), 2 * H, 4 * H), ("wq", ptr(wq_, oq_), H, d.att))
+            for way, cuts in (("fwd", self.bf["splits"][:3]), ("bwd", self.bf["splits"][3:])):
+                for (nm, src, rows, cols), cut in zip(mats, cuts):
+                    call("mstts_pack_bf16_" + way, src, cols, ptr(self.bf[nm + "_" + way[0]]), rows, cols, cut)
 
     def refresh_derived(self):
         """Folded cell-0 kernel (context rows appear twice) and the 4-column padded
@@ -392,23 +402,17 @@ class TrainEngine(Engine):
         w.masks = MaskSet(d, B, Te, S, True, self.device, rank=self.rank, alloc=lambda n: cv.take(n, dtype=torch.uint8))
         # encoder
         w.emb = f(B * Te, d.emb)
-        w.enc_a = [f(B * Te, d.enc_conv_ch) for _ in range(d.enc_conv_n)]
-        w.enc_y = [f(B * Te, d.enc_conv_ch) for _ in range(d.enc_conv_n)]
-        w.enc_mean = [f(d.enc_conv_ch) for _ in range(d.enc_conv_n)]
-        w.enc_rstd = [f(d.enc_conv_ch) for _ in range(d.enc_conv_n)]
+        w.enc_a, w.enc_y = ([f(B * Te, d.enc_conv_ch) for _ in range(d.enc_conv_n)] for _ in range(2))
+        w.enc_mean, w.enc_rstd = ([f(d.enc_conv_ch) for _ in range(d.enc_conv_n)] for _ in range(2))
         w.enc_xw = {dr: f(B * Te, 4 * He) for dr in ("fw", "bw")}
-        w.enc_c = {dr: f(Te + 1, B, He) for dr in ("fw", "bw")}
-        w.enc_h = {dr: f(Te + 1, B, He) for dr in ("fw", "bw")}
-        w.enc_acts = {dr: f(Te, B, 4 * He) for dr in ("fw", "bw")}
-        w.enc_craw = {dr: f(Te, B, He) for dr in ("fw", "bw")}
+        w.enc_c, w.enc_h = ({dr: f(Te + 1, B, He) for dr in ("fw", "bw")} for _ in range(2))
+        w.enc_acts, w.enc_craw = {dr: f(Te, B, 4 * He) for dr in ("fw", "bw")}, {dr: f(Te, B, He) for dr in ("fw", "bw")}
         w.enc_gates = {dr: f(int(lib.load().mstts_lstm_seq_ws_floats(B, He, 0))) for dr in ("fw", "bw")}
         w.enc_hp = {dr: f(2 * int(lib.load().mstts_cell_act_floats(B, He))) for dr in ("fw", "bw")} if self.enc_whp is not None else None
-        w.values = f(B, Te, M)
-        w.keys = f(B, Te, A)
+        w.values, w.keys = f(B, Te, M), f(B, Te, A)
         # decoder
         w.frames = f(S, B, d.n_mel)
-        w.pre_a = [f(S * B, Pn) for _ in range(d.prenet_n)]      # relu outputs
-        w.pre_d = [f(S * B, Pn) for _ in range(d.prenet_n)]      # after dropout
+        w.pre_a, w.pre_d = ([f(S * B, Pn) for _ in range(d.prenet_n)] for _ in range(2))      # relu outputs, after dropout
         w.xw0 = f(S, B, 4 * H)
         w.in0, w.in1, w.pj = f(S + 1, B, M + H), f(S + 1, B, 2 * H), f(S, B, H + M)
         w.c0, w.c1 = f(S + 1, B, H), f(S + 1, B, H)
@@ -429,11 +433,9 @@ class TrainEngine(Engine):
         if w.persist_enc:
             w.enc_xch = f(int(lb.mstts_persist_lstm_ws_bytes()) // 4)
             w.enc_ctrl = cv.take(16, dtype=torch.int32)
-            w.enc_ctrl_host = self._pin("enc_ctrl_host", 16)
-            w.enc_ctrl_host_b = self._pin("enc_ctrl_host_b", 16)
+            w.enc_ctrl_host, w.enc_ctrl_host_b = self._pin("enc_ctrl_host", 16), self._pin("enc_ctrl_host_b", 16)
             w.enc_hist = f(int(lb.mstts_persist_lstm_hist_floats(Te)))        # packed per-step inputs + history of the persistent forward
             w.enc_bws = f(int(lb.mstts_persist_lstm_bwd_floats(Te)))
-            w.enc_hist_valid = False
         w.persist = self.persist and bool(lb.mstts_persist_fwd_supported(B, H, M, A, Te, d.att_k))
         if self.persist and not w.persist and not cv.count and not cv.overflow:
             # the device and the widths admit the persistent launches, this batch shape does not: ~1.7x slower loop - say so, once per shape
@@ -444,39 +446,27 @@ class TrainEngine(Engine):
                               "(mstts_persist_fwd_supported); this shape runs the launch-per-step loops" % (B, Te), RuntimeWarning, stacklevel=3)
         if w.persist:
             w.xch = f(int(lb.mstts_persist_fwd_ws_bytes()) // 4)
-            w.pctrl = cv.take(272, dtype=torch.int32)
-            w.pctrl_host = self._pin("pctrl_host", 272)
-            w.pdesc = lib.PersistDesc()
+            w.pctrl, w.pctrl_host, w.pdesc = cv.take(272, dtype=torch.int32), self._pin("pctrl_host", 272), lib.PersistDesc()
         w.persist_bwd = w.persist and self.persist_bwd and bool(lb.mstts_persist_bwd_supported(B, H, M, A, Te, d.att_k))
         if w.persist_bwd:
             w.xch_b = f(int(lb.mstts_persist_bwd_ws_bytes()) // 4)
-            w.pctrl_b = cv.take(272, dtype=torch.int32)
-            w.pctrl_b_host = self._pin("pctrl_b_host", 272)
-            w.pdesc_b = lib.PersistDesc()
+            w.pctrl_b, w.pctrl_b_host, w.pdesc_b = cv.take(272, dtype=torch.int32), self._pin("pctrl_b_host", 272), lib.PersistDesc()
             w.opk = f(int(lb.mstts_persist_opk_floats(S)))         # the cell updates' BPTT operands, packed by owner (instead of acts / craw / c)
-        w.opk_valid = False
         w.proj = f(S, B, self.proj_ld)
         w.linear, w.stop = f(B, S, d.n_mel), f(B, S)
         # postnet
         chans = [d.post_ch] * (d.post_n - 1) + [d.n_mel]
-        w.post_a = [f(B * S, c) for c in chans]
-        w.post_y = [f(B * S, c) for c in chans]
-        w.post_mean = [f(c) for c in chans]
-        w.post_rstd = [f(c) for c in chans]
+        w.post_a, w.post_y = ([f(B * S, c) for c in chans] for _ in range(2))
+        w.post_mean, w.post_rstd = ([f(c) for c in chans] for _ in range(2))
         w.mel_out = f(B, S, d.n_mel)
         w.bn_ws = f(2 * max(d.post_ch, d.enc_conv_ch, d.bank_k * d.bank_ch, d.proj1_ch, d.n_mel, d.emb))
         # vocoder conv-bank (BN update side effect)
         if self.update_vocoder_bn:
             w.voc_fused = VOC_FUSED and self.voc_bank is not None
             if not w.voc_fused:              # (the chain per bank width: one width's product and its normalised copy, the last BN's unread output)
-                w.v_tmp = f(B * S, d.bank_ch)
-                w.v_tmp2 = f(B * S, d.bank_ch)
-                w.v_p2y = f(B * S, d.n_mel)
-            w.v_cat = f(B * S, d.bank_k * d.bank_ch)
-            w.v_pool = f(B * S, d.bank_k * d.bank_ch)
-            w.v_p1 = f(B * S, d.proj1_ch)
-            w.v_p1y = f(B * S, d.proj1_ch)
-            w.v_p2 = f(B * S, d.n_mel)
+                w.v_tmp, w.v_tmp2, w.v_p2y = f(B * S, d.bank_ch), f(B * S, d.bank_ch), f(B * S, d.n_mel)
+            w.v_cat, w.v_pool = f(B * S, d.bank_k * d.bank_ch), f(B * S, d.bank_k * d.bank_ch)
+            w.v_p1, w.v_p1y, w.v_p2 = f(B * S, d.proj1_ch), f(B * S, d.proj1_ch), f(B * S, d.n_mel)
             widest = max(d.bank_k * d.bank_ch if w.voc_fused else d.bank_ch, d.proj1_ch, d.n_mel)
             w.v_stat = f(2 * widest)
             w.v_bn_ws = f(4 * widest)        # (its own column-sum workspace: the chain may run beside the main stream's BN calls)
@@ -485,8 +475,7 @@ class TrainEngine(Engine):
         w.d_linear, w.d_post, w.d_stop = f(B, S, d.n_mel), f(B, S, d.n_mel), f(B, S)
         # backward
         w.post_dz = [f(B * S, c) for c in chans]
-        w.post_dx = f(B * S, max(d.post_ch, d.n_mel))
-        w.post_dx2 = f(B * S, max(d.post_ch, d.n_mel))
+        w.post_dx, w.post_dx2 = f(B * S, max(d.post_ch, d.n_mel)), f(B * S, max(d.post_ch, d.n_mel))
         w.d_proj = f(S, B, self.proj_ld)
         w.d_pj = f(S, B, H + M, zero=bool(self.ctx_dead))          # (ctx_dead: the dead columns of these three are never written - they read as the zeros of the activation)
         w.dg0, w.dg1 = f(S, B, 4 * H), f(S, B, 4 * H)
@@ -495,74 +484,83 @@ class TrainEngine(Engine):
         w.d_in0 = f(w.d_in0_parts, S, B, M + H, zero=bool(self.ctx_dead))
         w.dec_bwd_ws = f(int(lb.mstts_decoder_train_bwd_ws_floats(B, H, M, A, Te, d.att_ch)), zero=True)
         w.lsa_param_ws = f((int(lb.mstts_lsa_param_bwd_ws_floats(B, Te, S)) + 3) // 4 * 4)   # partial blocks of the attention parameter gradients
-        w.d_pre = f(S * B, Pn)
-        w.d_pre2 = f(S * B, Pn)
-        w.d_keys = f(B, Te, A)
-        w.d_values = f(B, Te, M, zero=bool(self.ctx_dead))
-        w.enc_dgs = {dr: f(Te, B, 4 * He) for dr in ("fw", "bw")}
-        w.enc_dgp = {dr: f(B, Te, 4 * He) for dr in ("fw", "bw")}
+        w.d_pre, w.d_pre2 = f(S * B, Pn), f(S * B, Pn)
+        w.d_keys, w.d_values = f(B, Te, A), f(B, Te, M, zero=bool(self.ctx_dead))
+        w.enc_dgs, w.enc_dgp = {dr: f(Te, B, 4 * He) for dr in ("fw", "bw")}, {dr: f(B, Te, 4 * He) for dr in ("fw", "bw")}
         w.enc_bwd_ws = {dr: f(int(lb.mstts_lstm_seq_ws_floats(B, He, 1))) for dr in ("fw", "bw")}
-        w.enc_dy = f(B * Te, max(d.enc_conv_ch, d.emb))
-        w.enc_dz = f(B * Te, d.enc_conv_ch)
-        w.enc_dx = f(B * Te, max(d.enc_conv_ch, d.emb))
+        w.enc_dy, w.enc_dz, w.enc_dx = f(B * Te, max(d.enc_conv_ch, d.emb)), f(B * Te, d.enc_conv_ch), f(B * Te, max(d.enc_conv_ch, d.emb))
         # descriptors with stable addresses
-        w.job_flag = cv.take(1, dtype=torch.int32)
-        w.job_flag_host = self._pin("job_flag_host", 1)
-        w.dec = lib.DecoderTrain()
-        w.dec_b = lib.DecoderTrainBwd()
+        w.job_flag, w.job_flag_host = cv.take(1, dtype=torch.int32), self._pin("job_flag_host", 1)
+        w.dec, w.dec_b = lib.DecoderTrain(), lib.DecoderTrainBwd()
         w.dec_b.ctx_dead = self.ctx_dead
         if w.persist_bwd:
             w.pdesc_b.ctx_dead = self.ctx_dead
-        w.zero_on_activate = cv.zero
-        w.extent_bytes = cv.off
-        w.arena_generation = self._arena.generation
+        w.zero_on_activate, w.extent_bytes, w.arena_generation = cv.zero, cv.off, self._arena.generation
         return (None if (cv.count or cv.overflow) else w), cv.off
 
     # ------------------------------------------------------------------ forward
+    def _forward_plan(self, w, batch, masks, allowed, overlap_vocoder, redo):
+        """What this forward pass will use, decided once.  The persistent launches are speculative (enqueued without waiting for their control
+        words); a re-run (redo) is the plan with everything speculative switched off.  The set's flags are read here, when the pass starts."""
+        allowed = False if redo else (self._persist_begin_step() if allowed is None else bool(allowed))
+        decoder, bptt, encoder = bool(w.persist) and allowed, bool(w.persist_bwd) and allowed, bool(w.persist_enc) and allowed
+        return types.SimpleNamespace(
+            decoder=decoder,                         # the decoder loop as ONE persistent launch
+            bptt=bptt,                               # the policy's word for the backward pass of this step (w.persist_bwd_now)
+            packed_bptt=decoder and bptt,            # ... whose launch reads the cell updates' operands packed by owner (w.opk), written by this one
+            encoder=encoder,                         # the BiLSTM as one persistent launch
+            encoder_forked=encoder and ENC_OVERLAP,  # ... on the encoder's stream
+            late_masks=masks is None and encoder and ENC_OVERLAP,    # the decoder-side masks are drawn under that launch
+            side_chains=overlap_vocoder and VOC_OVERLAP and self.device.type == "cuda",
+            # the pass runs on the persistent launches' outputs before their status words are known; a launch that gave up leaves junk there,
+            # and the BN layers would fold that junk into their MOVING statistics - one update per train step is the reference's behaviour
+            # (Modules.py:37-40 update ops), so the whole range (one contiguous slice of the non-trainable slab) is put back before the re-run
+            snapshot=decoder or encoder or (not redo and "_speaker_ticket" in batch))
+
     def forward(self, batch, w, seed=None, masks=None, _redo=False, allowed=None, overlap_vocoder=False):
         """Forward pass.  The persistent launches (encoder BiLSTM, decoder loop) are enqueued WITHOUT waiting for their control words; the
-        words of both are read once, behind the rest of the pass (one host sync per pass).  If either launch gave up, the BN moving statistics
-        are put back to their state at the start of the pass and the whole pass is run again with the launch-per-step loops (_redo).
+        words of both are read once, behind the rest of the pass (one host sync per pass: _forward_verdict).  If either launch gave up, the
+        whole pass is run again with the launch-per-step loops (_redo).
         allowed: the fallback policy's decision for this optimizer step (train_step takes it ONCE per step with _persist_begin_step and
         hands it down); None = a forward pass driven on its own (tests, tools) advances the policy itself.
         overlap_vocoder: train_step only - the vocoder conv-bank's statistics side effect (quirk Q20: _vocoder_bn_update, read by nothing in
         the step) goes to its own stream and loss_and_backward joins it in front of the decoder's BPTT launch (which needs every CU); a forward
         pass driven on its own keeps it on the caller's stream."""
-        d, ps = self.d, self.params
-        B, Te, L, S = w.B, w.Te, w.L, w.S
-        H, M, A, Pn, He = d.dec_lstm, d.mem, d.att, d.prenet, d.enc_lstm
-        w.voc_done = None
         if self._active_plan is not w and not _redo:         # (a set planned earlier, while a set of another shape has used the arena since)
             self._activate(w)
         if self._derived_stale:
             self.refresh_derived()
-        allowed = False if _redo else (self._persist_begin_step() if allowed is None else bool(allowed))
-        w.persist_now = bool(w.persist) and allowed
-        w.persist_bwd_now = bool(getattr(w, "persist_bwd", False)) and allowed
-        speculative = (allowed and (w.persist_now or bool(getattr(w, "persist_enc", False)))) or (not _redo and "_speaker_ticket" in batch)
-        if speculative:
-            # the pass runs on the persistent launches' outputs before their status words are known; a launch that gave up leaves junk there,
-            # and the BN layers would fold that junk into their MOVING statistics - one update per train step is the reference's behaviour
-            # (Modules.py:37-40 update ops), so the whole range (one contiguous slice of the non-trainable slab) is put back before the re-run
-            n_mov = self.params.n_moving
-            if self._moving_snapshot is None or self._moving_snapshot.numel() != n_mov:
-                self._moving_snapshot = torch.empty(n_mov, dtype=torch.float32, device=self.device)
-            self._moving_snapshot.copy_(self.params.frozen[:n_mov])
-        # (the decoder-side masks are drawn under the encoder's persistent launch when that runs on its own stream)
-        late_masks = masks is None and bool(getattr(w, "persist_enc", False)) and allowed and ENC_OVERLAP
+        p = self._forward_plan(w, batch, masks, allowed, overlap_vocoder, _redo)
+        w.persist_now, w.persist_bwd_now, w.enc_hist_valid, w.opk_valid = p.decoder, p.bptt, p.encoder, p.packed_bptt
+        w.voc_done, w.batch = None, batch
+        if p.snapshot:
+            self._moving_snapshot.copy_(self.params.frozen[:self.params.n_moving])
         mask_seed = seed if seed is not None else step_seed(self.seed, self.global_step)
         if masks is not None:
             w.masks.load(masks)
         else:
-            w.masks.draw(mask_seed, only=(lambda n: n.startswith("enc_")) if late_masks else None)
-        mk = w.masks
-        self._bnws = w.bn_ws
-        tok, tlen = batch["Token"], batch["Token_Length"]
-        mel, mlen, spk = batch["Mel"], batch["Mel_Length"], batch["Speaker_Embedding"]
-        w.batch = batch
-        # ---- encoder (Modules.py:15-73)
+            w.masks.draw(mask_seed, only=(lambda n: n.startswith("enc_")) if p.late_masks else None)
+        x, cin = self._encoder_convs(w, batch)
+        enc_ticket, enc_done = self._encoder_bilstm(w, p, batch, x, cin)
+        if p.late_masks:
+            w.masks.draw(mask_seed, only=lambda n: not n.startswith("enc_"))
+        pre = self._hoisted_prenet(w, batch)
+        if enc_done is not None:
+            lib.join(enc_done)
+        self._memory_and_keys(w, batch)
+        self._fill_decoder(w, p, batch, pre)
+        dec_ticket = self._decoder_loop(w, p, pre)
+        self._forward_tail(w, overlap_vocoder=p.side_chains)
+        spk_ticket = None if _redo else batch.pop("_speaker_ticket", None)
+        if self._forward_verdict(w, batch, dec_ticket, enc_ticket, spk_ticket):
+            return w
+        return self.forward(batch, w, seed=seed, masks=masks, _redo=True, overlap_vocoder=overlap_vocoder)
+
+    def _encoder_convs(self, w, batch):
+        """Embedding and the convolution blocks (Modules.py:15-73); returns the last block's output and its width."""
+        d, mk, B, Te = self.d, w.masks, w.B, w.Te
         emb, oe = self.P("encoder/embedding_variable")
-        call("mstts_embedding_fwd", ptr(tok), ptr(emb, oe), ptr(w.emb), B * Te, d.n_tok, d.emb)
+        call("mstts_embedding_fwd", ptr(batch["Token"]), ptr(emb, oe), ptr(w.emb), B * Te, d.n_tok, d.emb)
         x, cin = w.emb, d.emb
         for i in range(d.enc_conv_n):
             pre = "encoder/conv_%d/" % i
@@ -570,6 +568,12 @@ class TrainEngine(Engine):
             bn_train_fwd(self, pre + "batch_normalization/", w.enc_a[i], w.enc_y[i], w.enc_mean[i], w.enc_rstd[i],
                          mk["enc_conv_drop_%d" % i], 1 - d.conv_drop, B * Te, d.enc_conv_ch, w.bn_ws)
             x, cin = w.enc_y[i], d.enc_conv_ch
+        return x, cin
+
+    def _encoder_bilstm(self, w, p, batch, x, cin):
+        """The input products of both directions, then all steps: one persistent launch on the encoder's stream, the same in line, or the
+        launch-per-step pair driver.  Returns (ticket of the launch, event to join before the memory is read); either may be None."""
+        d, mk, tlen, B, Te, M, He = self.d, w.masks, batch["Token_Length"], w.B, w.Te, self.d.mem, self.d.enc_lstm
         seqs = []
         for di, dr in enumerate(("fw", "bw")):
             k, ok = self.P(ENC_CELL % dr + "kernel"); b, ob = self.P(ENC_CELL % dr + "bias")
@@ -579,53 +583,53 @@ class TrainEngine(Engine):
             if self.enc_whp is not None:                 # fused steps: packed recurrent kernel + packed h blocks
                 q.wh_p, q.h_p = ptr(self.enc_whp[dr]), ptr(w.enc_hp[dr])
             seqs.append(q)
-        enc_ticket, enc_done = None, None
-        w.enc_hist_valid = bool(getattr(w, "persist_enc", False)) and allowed
-        if w.enc_hist_valid and ENC_OVERLAP:
+        if p.encoder_forked:
             # (the persistent launch occupies 64 of the 256 CUs for 0.34 ms: on its own stream, under the decoder's hoisted prenet, which does not depend on it)
-            ready = torch.cuda.Event()
-            ready.record()
-            with torch.cuda.stream(self._enc_stream):
-                self._enc_stream.wait_event(ready)
-                enc_ticket = self._enc_persistent(w, "mstts_lstm_seq_fwd_pair_persistent", seqs, 0)   # (status read at the end of the pass)
-                enc_done = torch.cuda.Event()
-                enc_done.record()
-        elif w.enc_hist_valid:
-            enc_ticket = self._enc_persistent(w, "mstts_lstm_seq_fwd_pair_persistent", seqs, 0)
-        if not w.enc_hist_valid:
-            self._ensure_fallback_packs()
-            call("mstts_lstm_seq_fwd_pair", C.byref(seqs[0]), C.byref(seqs[1]))     # both directions advance together: one launch per step
-        if late_masks:
-            w.masks.draw(mask_seed, only=lambda n: not n.startswith("enc_"))
-        # ---- hoisted prenet over all S frames (Modules.py:239-255) and cell-0 input product
-        call("mstts_shift_frames", ptr(mel), ptr(w.frames), B, L, d.n_mel)
+            with lib.fork(self._enc_stream) as side:
+                ticket = self._enc_persistent(w, "mstts_lstm_seq_fwd_pair_persistent", seqs, 0)      # (status read at the end of the pass)
+            return ticket, side.done
+        if p.encoder:
+            return self._enc_persistent(w, "mstts_lstm_seq_fwd_pair_persistent", seqs, 0), None
+        self._ensure_fallback_packs()
+        call("mstts_lstm_seq_fwd_pair", C.byref(seqs[0]), C.byref(seqs[1]))     # both directions advance together: one launch per step
+        return None, None
+
+    def _hoisted_prenet(self, w, batch):
+        """The prenet over all S frames at once (Modules.py:239-255); returns its output."""
+        d, mk, B, S, Pn = self.d, w.masks, w.B, w.S, self.d.prenet
+        call("mstts_shift_frames", ptr(batch["Mel"]), ptr(w.frames), B, w.L, d.n_mel)
         x, cin = w.frames, d.n_mel
         for i in range(d.prenet_n):
             k, ok = self.P("decoder/decoder/prenet_%d/dense/kernel" % i); b, ob = self.P("decoder/decoder/prenet_%d/dense/bias" % i)
             self._gemm(x, k, w.pre_a[i], S * B, Pn, cin, cin, Pn, Pn, bias=b, act=ACT_RELU, b_off=ok, bias_off=ob)
             call("mstts_dropout", ptr(w.pre_a[i]), ptr(mk["prenet_drop_%d" % i]), 1 - d.prenet_drop, ptr(w.pre_d[i]), S * B * Pn)
             x, cin = w.pre_d[i], Pn
-        if enc_done is not None:
-            torch.cuda.current_stream().wait_event(enc_done)
-        # ---- memory = [encoder | speaker], masked past Token_Length; keys = values . W_mem
+        return x
+
+    def _memory_and_keys(self, w, batch):
+        """memory = [encoder | speaker], masked past Token_Length; keys = values . W_mem"""
+        d, B, Te, M, A = self.d, w.B, w.Te, self.d.mem, self.d.att
         if batch.get("_speaker_event") is not None:          # (the product surface forms the embedding on another stream, beside everything above)
-            torch.cuda.current_stream().wait_event(batch["_speaker_event"])
-        call("mstts_speaker_tile", ptr(spk), ptr(tlen), ptr(w.values), B, Te, M, 2 * He, d.spk)
+            lib.join(batch["_speaker_event"])
+        call("mstts_speaker_tile", ptr(batch["Speaker_Embedding"]), ptr(batch["Token_Length"]), ptr(w.values), B, Te, M, 2 * d.enc_lstm, d.spk)
         wm, owm = self.P("attention/memory_layer/kernel")
         self._gemm(w.values, wm, w.keys, B * Te, A, M, M, A, A, b_off=owm)
+
+    def _fill_decoder(self, w, p, batch, x):
+        """The cell-0 input product where it is hoisted, and the decoder loop's descriptor (both forms of the loop read it)."""
+        d, mk, B, Te, S = self.d, w.masks, w.B, w.Te, w.S
+        H, M, A, Pn = d.dec_lstm, d.mem, d.att, d.prenet
         k0, o0 = self.P(CELL % 0 + "kernel"); b0, ob0 = self.P(CELL % 0 + "bias")
         # cell-0 input product xw0 = prenet . W0[:P] + b0: inside the persistent launch (fp32 mode, 256-wide prenet), else hoisted here
         # (exact_f32_products: every product of the loop on the f32-input MFMA - the launch's round-4 form, which keeps the prenet rows' product
         #  hoisted; selected together with mstts_gemm_split3(0) by whoever wants IEEE fp32 products everywhere, e.g. bench.py's strict leg)
-        w.fold_prenet = w.persist_now and Pn == 256 and (self.persist_bf16 or (self.gemm_dtype == "f32" and not self.exact_f32_products
-                                                                                and os.environ.get("MSTTS_PERSIST_FOLD", "1") != "0"))
-        xw0_product = lambda: self._gemm(x, k0, w.xw0, S * B, 4 * H, Pn, Pn, 4 * H, 4 * H, bias=b0, b_off=o0, bias_off=ob0)
+        w.fold_prenet = p.decoder and Pn == 256 and (self.persist_bf16 or (self.gemm_dtype == "f32" and not self.exact_f32_products
+                                                                            and os.environ.get("MSTTS_PERSIST_FOLD", "1") != "0"))
         if not w.fold_prenet:
-            xw0_product()
-        # ---- decoder loop
+            self._gemm(x, k0, w.xw0, S * B, 4 * H, Pn, Pn, 4 * H, 4 * H, bias=b0, b_off=o0, bias_off=ob0)
         dec = w.dec
         dec.B, dec.S, dec.H, dec.P = B, S, H, Pn
-        lib.lsa_fill(dec.lsa, self.P, B, Te, A, M, d.att_k, d.att_ch, w.keys, w.values, tlen, self.loc_k, self.loc_b, self.loc_kt)
+        lib.lsa_fill(dec.lsa, self.P, B, Te, A, M, d.att_k, d.att_ch, w.keys, w.values, batch["Token_Length"], self.loc_k, self.loc_b, self.loc_kt)
         k1, o1 = self.P(CELL % 1 + "kernel"); b1, ob1 = self.P(CELL % 1 + "bias"); wq, oq = self.P(LSA + "query_layer/kernel")
         dec.xw0, dec.w0f, dec.w1, dec.b1, dec.wq = ptr(w.xw0), ptr(self.w0f), ptr(k1, o1), ptr(b1, ob1), ptr(wq, oq)
         dec.zc0, dec.zh0, dec.zc1, dec.zh1 = ptr(mk["dec_zc_0"]), ptr(mk["dec_zh_0"]), ptr(mk["dec_zc_1"]), ptr(mk["dec_zh_1"])
@@ -642,48 +646,54 @@ class TrainEngine(Engine):
         dec.energy_ws_floats = w.energy_ws_floats if self.fuse_query else 0
         for nm in ("in0", "in1", "pj", "c0", "c1", "acts0", "acts1", "craw0", "craw1", "q_hist", "align_hist", "cum_hist", "gates_ws", "energy_ws", "q_ws"):
             setattr(dec, nm, ptr(getattr(w, nm)))
-        dec_ticket = None
-        if w.persist_now:
-            # ONE launch for all S steps; the launch-per-step loop below is the fallback when the 256 workgroups were not co-resident
-            # or a bounded wait expired (ctrl words, checked after the rest of the forward pass is enqueued - no bubble on the device)
-            pd = w.pdesc
-            pd.w0pk, pd.w1pk, pd.wqpk, pd.xch, pd.ctrl = ptr(self.pk[0]), ptr(self.pk[1]), ptr(self.pk[2]), ptr(w.xch), ptr(w.pctrl)
-            pd.stamps = ptr(self.persist_stamps) if self.persist_stamps is not None else None
-            pd.opk = ptr(w.opk) if w.persist_bwd_now else None
-            w.opk_valid = pd.opk is not None
-            pd.selftest_fail_step = int(self.persist_selftest)
-            pd.near_xcd = near_xcd()
-            pd.recurrent_bf16 = int(self.persist_bf16)
-            pd.pre, pd.b0 = (ptr(x), ptr(b0, ob0)) if w.fold_prenet else (None, None)
-            call("mstts_decoder_train_fwd_persistent", C.byref(dec), C.byref(pd))
-            # the launch's control words -> page-locked memory, ON THIS STREAM right behind the launch, then an event the host waits for at the
-            # end of the pass.  (Until round 6 a side stream did the copy behind a wait for the launch.  A stream's wait is a barrier packet in its
-            # hardware queue, and HIP maps streams onto a few hardware queues: in a process with more streams - an RCCL group - the side stream
-            # shared the main stream's queue, and every kernel enqueued behind such a barrier waited with it: profiles/r06_one_rank_rccl_timeline_before.txt,
-            # the decoder's weight-gradient products sat out the encoder's BPTT launch, +1.0 ms per step.)
-            dec_ticket = Ticket(w.pctrl, w.pctrl_host, decoder_workgroups()).enqueue(torch.cuda.Event())
-        else:
-            w.opk_valid = False
+
+    def _fill_persist_desc(self, desc, packs, xch, ctrl, stamps, opk, selftest):
+        """The launch descriptor (mstts_persist_desc) of a persistent decoder launch, forward or BPTT."""
+        desc.w0pk, desc.w1pk, desc.wqpk, desc.xch, desc.ctrl = ptr(packs[0]), ptr(packs[1]), ptr(packs[2]), ptr(xch), ptr(ctrl)
+        desc.stamps, desc.opk = ptr(stamps), ptr(opk)
+        desc.selftest_fail_step = int(selftest)
+        desc.near_xcd = near_xcd()
+        desc.recurrent_bf16 = int(self.persist_bf16)
+        return desc
+
+    def _decoder_loop(self, w, p, x):
+        """All S steps of the decoder: the persistent launch (returns its ticket) or the launch-per-step loop (None)."""
+        if not p.decoder:
             self._ensure_fallback_packs()
-            call("mstts_decoder_train_fwd", C.byref(dec))
-        self._forward_tail(w, overlap_vocoder=overlap_vocoder and VOC_OVERLAP and self.device.type == "cuda")
+            call("mstts_decoder_train_fwd", C.byref(w.dec))
+            return None
+        # ONE launch for all S steps; the launch-per-step loop is the fallback when the 256 workgroups were not co-resident
+        # or a bounded wait expired (ctrl words, checked after the rest of the forward pass is enqueued - no bubble on the device)
+        pd = self._fill_persist_desc(w.pdesc, self.pk, w.xch, w.pctrl, self.persist_stamps, w.opk if p.packed_bptt else None, self.persist_selftest)
+        b0, ob0 = self.P(CELL % 0 + "bias")
+        pd.pre, pd.b0 = (ptr(x), ptr(b0, ob0)) if w.fold_prenet else (None, None)
+        call("mstts_decoder_train_fwd_persistent", C.byref(w.dec), C.byref(pd))
+        # the launch's control words -> page-locked memory, ON THIS STREAM right behind the launch, then an event the host waits for at the
+        # end of the pass.  (Until round 6 a side stream did the copy behind a wait for the launch.  A stream's wait is a barrier packet in its
+        # hardware queue, and HIP maps streams onto a few hardware queues: in a process with more streams - an RCCL group - the side stream
+        # shared the main stream's queue, and every kernel enqueued behind such a barrier waited with it: profiles/r06_one_rank_rccl_timeline_before.txt,
+        # the decoder's weight-gradient products sat out the encoder's BPTT launch, +1.0 ms per step.)
+        return Ticket(w.pctrl, w.pctrl_host, decoder_workgroups()).enqueue(torch.cuda.Event())
+
+    def _forward_verdict(self, w, batch, dec_ticket, enc_ticket, spk_ticket):
+        """The forward pass's one host sync: redeems the tickets of its persistent launches (and of the speaker stack's in front of it).  False: a
+        launch gave up - the step is marked, the device drained, the moving statistics are back at the state the pass started from: run it again."""
         dec_ok = dec_ticket is None or self._ticket_ok(dec_ticket, "persist_fallbacks")
         enc_ok = enc_ticket is None or self._ticket_ok(enc_ticket, "persist_enc_fallbacks", keep_status=False)
-        spk_ticket = None if _redo else batch.pop("_speaker_ticket", None)
         if spk_ticket is not None and not spk_ticket.ok():
             # the frozen speaker stack in front of this pass (MSTTS_SV.py:49-56) ran as persistent launches whose words are read only now:
             # one of them gave up, the embedding this pass consumed is junk - recompute it launch by launch, then run the pass again
             batch["Speaker_Embedding"].copy_(spk_ticket.redo())
             self.speaker_ticket_redos += 1
             enc_ok = False
-        if not (dec_ok and enc_ok):
-            self._step_fell_back = True
-            torch.cuda.current_stream().synchronize()
-            if w.voc_done is not None:                   # (the side chain writes moving statistics too)
-                w.voc_done.synchronize()
-            self.params.frozen[:self.params.n_moving].copy_(self._moving_snapshot)
-            return self.forward(batch, w, seed=seed, masks=masks, _redo=True, overlap_vocoder=overlap_vocoder)
-        return w
+        if dec_ok and enc_ok:
+            return True
+        self._step_fell_back = True
+        torch.cuda.current_stream().synchronize()
+        if w.voc_done is not None:                       # (the side chain writes moving statistics too)
+            w.voc_done.synchronize()
+        self.params.frozen[:self.params.n_moving].copy_(self._moving_snapshot)
+        return False
 
     def _enc_persistent(self, w, entry, seqs, which):
         """One persistent launch for all steps of both encoder directions (forward: which = 0, BPTT: 1).  Nothing waits here: the launch's
@@ -691,7 +701,7 @@ class TrainEngine(Engine):
         end of the pass."""
         extra = (ptr(w.enc_hist),) if which == 0 else (ptr(w.enc_hist), ptr(w.enc_bws))
         call(entry, C.byref(seqs[0]), C.byref(seqs[1]), ptr(self.enc_pk["fw"][which]), ptr(self.enc_pk["bw"][which]), ptr(w.enc_xch), ptr(w.enc_ctrl), *extra)
-        if getattr(self, "persist_enc_selftest", 0):              # tests: this encoder launch "gave up" - on the DEVICE, where the job-wide verdict reads it too
+        if self.persist_enc_selftest:              # tests: this encoder launch "gave up" - on the DEVICE, where the job-wide verdict reads it too
             self.persist_enc_selftest -= 1
             w.enc_ctrl[1:2].fill_(3)
         n_wg = lstm_fwd_workgroups(w.B, self.d.enc_lstm, 2) if which == 0 else lstm_bwd_workgroups(w.B, 2)
@@ -713,13 +723,13 @@ class TrainEngine(Engine):
         """Adaptive fallback policy, called once per OPTIMIZER STEP (train_step; a forward pass driven on its own calls it itself): closes the books on the previous step (a step in which any persistent
         launch gave up is a strike; PERSIST_STRIKES in a row start a cool-down) and says whether this step may use the persistent
         launches."""
-        if getattr(self, "_step_fell_back", False):
+        if self._step_fell_back:
             if self._persist_cool.strike(PERSIST_STRIKES, PERSIST_COOLDOWN) and not self._persist_warned:
                 self._persist_warned = True
                 warnings.warn("multi_speaker_tts_amd: %d consecutive steps fell back from the persistent launches (status %r: something "
                               "else holds compute units); running the launch-per-step loops for %d steps before probing again"
-                              % (PERSIST_STRIKES, getattr(self, "persist_last_status", None), PERSIST_COOLDOWN), RuntimeWarning, stacklevel=4)
-        elif getattr(self, "_step_was_persistent", False):
+                              % (PERSIST_STRIKES, self.persist_last_status, PERSIST_COOLDOWN), RuntimeWarning, stacklevel=4)
+        elif self._step_was_persistent:
             self._persist_cool.clear()
         self._step_fell_back = False
         if not self._persist_cool.admit():
@@ -732,15 +742,12 @@ class TrainEngine(Engine):
     def unpack_history(self, w):
         """Packed cell-update operands of the persistent forward -> the row-major histories acts0/1, craw0/1, c0/1 (what the
         launch-per-step BPTT and the tests read)."""
-        if getattr(w, "opk_valid", False):
+        if w.opk_valid:
             call("mstts_persist_unpack_history", ptr(w.opk), C.byref(w.dec))
 
     def _forward_tail(self, w, overlap_vocoder=False):
         """Everything behind the decoder loop: projection, postnet, residual, the vocoder's statistics side effect."""
-        d = self.d
-        B, S = w.B, w.S
-        H, M = d.dec_lstm, d.mem
-        mk = w.masks
+        d, mk, B, S, H, M = self.d, w.masks, w.B, w.S, self.d.dec_lstm, self.d.mem
         # ---- projection (Modules.py:309-321) on all steps at once, then batch-major linear/stop
         self._gemm(w.pj, self.wp_pad, w.proj, S * B, self.proj_ld, H + M, H + M, self.proj_ld, self.proj_ld, bias=self.bp_pad)
         call("mstts_unpack_proj", ptr(w.proj), self.proj_ld, ptr(w.linear), ptr(w.stop), B, S, d.n_mel)
@@ -755,26 +762,22 @@ class TrainEngine(Engine):
             x, cin = w.post_y[i], cout
         call("mstts_add", ptr(w.linear), ptr(x), ptr(w.mel_out), B * S * d.n_mel)
         if self.update_vocoder_bn and overlap_vocoder:
-            ready = torch.cuda.Event()
-            ready.record()
-            with torch.cuda.stream(self._voc_stream):
-                self._voc_stream.wait_event(ready)
+            with lib.fork(self._voc_stream) as side:
                 self._vocoder_bn_update(w)
-                w.voc_done = torch.cuda.Event()
-                w.voc_done.record()
+            w.voc_done = side.done
         elif self.update_vocoder_bn:
             self._vocoder_bn_update(w)
 
     def _join_vocoder(self, w):
         """The caller's stream waits for the side chains of this pass that run on the encoder's stream (if any): the vocoder's statistics side effect of
         the forward pass, the postnet's weight-gradient products."""
-        if getattr(w, "voc_done", None) is not None:
-            torch.cuda.current_stream().wait_event(w.voc_done)
+        if w.voc_done is not None:
+            lib.join(w.voc_done)
             w.voc_done = None
-        if getattr(w, "side_wgrads", False):
+        if w.side_wgrads:                    # (conv_bn_bwd records no event of its own: ONE, behind the last product)
             done = torch.cuda.Event()
             done.record(self._enc_stream)
-            torch.cuda.current_stream().wait_event(done)
+            lib.join(done)
             w.side_wgrads = False
 
     def _ensure_bank_pack(self):
@@ -805,11 +808,15 @@ class TrainEngine(Engine):
         """Quirk Q20: the train op also runs the vocoder conv-bank's BN update ops on the predicted mel.  Only the ten layers' moving statistics
         come out of it.  Fused form (VOC_FUSED, dims the packed bank takes): the bank as two window products that write the concatenation
         directly, one segmented batch norm over it with the max-pool on its way out, the two projections, the last layer's statistics alone."""
-        d = self.d
-        B, S = w.B, w.S
-        rows = B * S
+        d, B, S = self.d, w.B, w.S
+        rows, C1 = B * S, d.bank_k * d.bank_ch
+
+        def projection(n, x, y, cout, K, cin, act):
+            kk, ok = self.P(VOC + "convbank_0/conv1d_%d/kernel" % n); b, ob = self.P(VOC + "convbank_0/conv1d_%d/bias" % n)
+            self._gemm(x, kk, y, rows, cout, K * cin, cin, cout, cout, bias=b, act=act, win=(S, cin, (K - 1) // 2), b_off=ok, bias_off=ob, exact=True)
+        proj1 = lambda: projection(8, w.v_pool, w.v_p1, d.proj1_ch, d.proj1_k, C1, ACT_RELU)
+        proj2 = lambda: projection(9, w.v_p1y, w.v_p2, d.n_mel, d.proj2_k, d.proj1_ch, ACT_NONE)
         if w.voc_fused:
-            C1 = d.bank_k * d.bank_ch
             vb = self.voc_bank
             self._ensure_bank_pack()
             t_bank, t_p1, t_p2 = vb["tables"]
@@ -822,63 +829,114 @@ class TrainEngine(Engine):
             bn_seg = lambda tab, nseg, x, y, cols, pool: call("mstts_bn_train_fwd_seg", ptr(x), cols, C.byref(tab), nseg, ptr(y), ptr(w.v_stat),
                                                               ptr(w.v_stat, cols), BN_MOM, BN_EPS, rows, cols, pool, ptr(w.v_bn_ws))
             bn_seg(t_bank, d.bank_k, w.v_cat, w.v_pool, C1, S)
-            kk, ok = self.P(VOC + "convbank_0/conv1d_8/kernel"); b, ob = self.P(VOC + "convbank_0/conv1d_8/bias")
-            self._gemm(w.v_pool, kk, w.v_p1, rows, d.proj1_ch, d.proj1_k * C1, C1, d.proj1_ch, d.proj1_ch, bias=b, act=ACT_RELU,
-                 win=(S, C1, (d.proj1_k - 1) // 2), b_off=ok, bias_off=ob, exact=True)
+            proj1()
             bn_seg(t_p1, 1, w.v_p1, w.v_p1y, d.proj1_ch, 0)
-            kk, ok = self.P(VOC + "convbank_0/conv1d_9/kernel"); b, ob = self.P(VOC + "convbank_0/conv1d_9/bias")
-            self._gemm(w.v_p1y, kk, w.v_p2, rows, d.n_mel, d.proj2_k * d.proj1_ch, d.proj1_ch, d.n_mel, d.n_mel, bias=b,
-                 win=(S, d.proj1_ch, (d.proj2_k - 1) // 2), b_off=ok, bias_off=ob, exact=True)
+            proj2()
             bn_seg(t_p2, 1, w.v_p2, None, d.n_mel, 0)
             return
+        bn = lambda scope, x, y, cols: bn_train_fwd(self, VOC + "convbank_0/batch_normalization%s/" % scope, x, y, w.v_stat, w.v_stat[cols:], None, 1.0,
+                                                    rows, cols, w.v_bn_ws)
         for k in range(1, d.bank_k + 1):
             sfx = bank_suffix(k)
             kk, ok = self.P(VOC + "convbank_0/conv1d%s/kernel" % sfx); b, ob = self.P(VOC + "convbank_0/conv1d%s/bias" % sfx)
             self._gemm(w.mel_out, kk, w.v_tmp, rows, d.bank_ch, k * d.n_mel, d.n_mel, d.bank_ch, d.bank_ch, bias=b, act=ACT_RELU,
                  win=(S, d.n_mel, (k - 1) // 2), b_off=ok, bias_off=ob, exact=True)
-            bn_train_fwd(self, VOC + "convbank_0/batch_normalization%s/" % sfx, w.v_tmp, w.v_tmp2, w.v_stat, w.v_stat[d.bank_ch:], None, 1.0, rows, d.bank_ch, w.v_bn_ws)
+            bn(sfx, w.v_tmp, w.v_tmp2, d.bank_ch)
             call("mstts_copy2d", ptr(w.v_tmp2), d.bank_ch, ptr(w.v_cat, (k - 1) * d.bank_ch), d.bank_k * d.bank_ch, rows, d.bank_ch, 0)
-        C1 = d.bank_k * d.bank_ch
         call("mstts_maxpool2_same", ptr(w.v_cat), ptr(w.v_pool), B, S, C1)
-        kk, ok = self.P(VOC + "convbank_0/conv1d_8/kernel"); b, ob = self.P(VOC + "convbank_0/conv1d_8/bias")
-        self._gemm(w.v_pool, kk, w.v_p1, rows, d.proj1_ch, d.proj1_k * C1, C1, d.proj1_ch, d.proj1_ch, bias=b, act=ACT_RELU,
-             win=(S, C1, (d.proj1_k - 1) // 2), b_off=ok, bias_off=ob, exact=True)
-        bn_train_fwd(self, VOC + "convbank_0/batch_normalization_8/", w.v_p1, w.v_p1y, w.v_stat, w.v_stat[d.proj1_ch:], None, 1.0, rows, d.proj1_ch, w.v_bn_ws)
-        kk, ok = self.P(VOC + "convbank_0/conv1d_9/kernel"); b, ob = self.P(VOC + "convbank_0/conv1d_9/bias")
-        self._gemm(w.v_p1y, kk, w.v_p2, rows, d.n_mel, d.proj2_k * d.proj1_ch, d.proj1_ch, d.n_mel, d.n_mel, bias=b,
-             win=(S, d.proj1_ch, (d.proj2_k - 1) // 2), b_off=ok, bias_off=ob, exact=True)
-        bn_train_fwd(self, VOC + "convbank_0/batch_normalization_9/", w.v_p2, w.v_p2y, w.v_stat, w.v_stat[d.n_mel:], None, 1.0, rows, d.n_mel, w.v_bn_ws)
+        proj1()
+        bn("_8", w.v_p1, w.v_p1y, d.proj1_ch)
+        proj2()
+        bn("_9", w.v_p2, w.v_p2y, d.n_mel)
 
     # ------------------------------------------------------------------ loss + backward
+    def _backward_plan(self, w, on_ready, agree_async, redo):
+        """What this backward pass will use, decided once from what the forward pass left (w.persist_bwd_now: this step's policy decision,
+        taken in forward(); w.persist_bwd: the plan's flag, which tests clear between two backward passes).  A re-run: nothing speculative."""
+        first = not redo
+        bptt = first and w.persist_bwd_now and bool(w.persist_bwd)
+        encoder = first and w.enc_hist_valid             # (the persistent BPTT reads the packed history of a persistent forward)
+        return types.SimpleNamespace(
+            speculative=first,                           # a pass that may be re-run: it asks the job for the verdict (agree / agree_async)
+            decoder=bptt and w.opk_valid,                # the decoder's BPTT as ONE persistent launch, on the forward launch's packed operands
+            encoder=encoder, encoder_forked=encoder and ENC_OVERLAP, tail_forked=ENC_TAIL_OVERLAP,
+            side_wgrads=first and POSTNET_WGRAD_OVERLAP and w.voc_done is not None,
+            # every postnet gradient is final behind the postnet's backward pass: its all-reduce overlaps the decoder BPTT - unless that is the
+            # persistent launch, which needs every CU of the chip for itself: a collective kernel holding CUs at that moment and the 256
+            # workgroups waiting for each other's CUs would sit out the launch's start window (0.2 s) and end in the fallback.  Then the range
+            # is announced BEHIND the launch (the collective is ordered after what is enqueued) and runs under the hoisted products instead.
+            ready_deferred=bptt and on_ready is not None,
+            job_flag=first and agree_async is not None)
+
     def loss_and_backward(self, w, grad_scale=1.0, on_ready=None, on_abort=None, agree=None, agree_async=None, _redo=False):
         """Loss and backward pass.  Like forward(): the persistent launches (decoder BPTT, encoder BPTT) are enqueued without waiting for their
-        control words, which are read once at the end of the pass; if either gave up the whole pass is run again with the launch-per-step
-        loops (it starts by clearing the gradient slab).  on_abort: called before that re-run (train_step: wait for the collectives that the
-        abandoned pass has already started on the slab).
+        control words, which _backward_verdict reads once at the end of the pass; if either gave up the whole pass is run again with the
+        launch-per-step loops (it starts by clearing the gradient slab).  on_ready(lo, hi): that range of the gradient slab is
+        final.  on_abort: called before a re-run (train_step: wait for the collectives the abandoned pass has started on the slab).
         agree: data-parallel runs - callable(passed) -> bool, the MINIMUM of `passed` over the ranks (GradAllReduce.agree).  The collectives
         on_ready started have already mixed this pass's gradients into every rank's slab, so keeping or re-running the pass must be ONE
-        decision of the whole job: either every rank keeps its pass, or every rank drains (on_abort) and runs the pass again - each rank
-        then issues the same sequence of collectives, and a rank whose own launches were healthy throws away the junk a peer contributed
-        (`collective_redos` counts the passes re-run because a PEER's launch gave up).
+        decision of the whole job (`collective_redos` counts the passes re-run because a PEER's launch gave up).
         agree_async: the same decision without a host round trip (GradAllReduce.agree_async, RCCL only): callable(flag) that turns the int32
-        device word `flag` into its minimum over the ranks, in place, on the current stream.  The word is formed on the side stream from the
-        launches' control words (mstts_persist_status) right behind them, exchanged on its own communicator and read - with the control
-        words - at the pass's one host sync, which therefore still falls while the hoisted products run.  Takes precedence over `agree`."""
-        d, ps = self.d, self.params
-        B, Te, L, S = w.B, w.Te, w.L, w.S
-        H, M, A, Pn, He = d.dec_lstm, d.mem, d.att, d.prenet, d.enc_lstm
-        mk, batch = w.masks, w.batch
-        tok, tlen, mel, mlen = batch["Token"], batch["Token_Length"], batch["Mel"], batch["Mel_Length"]
+        device word `flag` into its minimum over the ranks, in place, on the current stream.  Takes precedence over `agree`."""
+        p = self._backward_plan(w, on_ready, agree_async, _redo)
+        self._losses(w, grad_scale)
+        dy = self._postnet_backward(w, p)
+        if on_ready is not None and not p.ready_deferred:
+            self._join_vocoder(w)                # (the weight gradients on the side stream are part of the range)
+            on_ready(*self._grad_range("decoder/conv_"))
+        self._projection_backward(w, dy)
+        bwd_ticket, parts = self._decoder_bptt(w, p)
+        if p.ready_deferred:
+            on_ready(*self._grad_range("decoder/conv_"))
+        if p.encoder_forked:
+            # The encoder's persistent BPTT occupies 32 of the 256 CUs for 0.65 ms: it runs on its own stream UNDER the decoder's hoisted weight-gradient
+            # products instead of in front of the encoder's.  What it waits for - the attention parameter gradients' d_keys, the memory gradient -
+            # is computed first; its launch is enqueued before the products, so its 32 workgroups are resident when the products' tiles arrive.
+            self._recurrent_wgrads(w, 0, w.S, part="attention")
+            self._memory_gradient(w, parts)
+            with lib.fork(self._enc_stream) as side:
+                enc_ticket = self._encoder_bptt(w, p)
+                if p.tail_forked:
+                    # ... and the rest of the encoder's backward pass (weight gradients, convolution blocks, embedding: ~45 launches, 1.1 ms, none of
+                    # it read by the decoder's products) stays on this stream, behind the launch and beside those products
+                    self._encoder_tail(w)
+            self._decoder_products(w)
+            if on_ready is not None:         # decoder + attention gradients are final: overlaps the encoder backward
+                on_ready(*self._grad_range("attention/", "decoder/decoder"))
+            lib.join(side.done)
+            if not p.tail_forked:
+                self._encoder_tail(w)
+        else:
+            self._recurrent_wgrads(w, 0, w.S, part="attention")
+            self._decoder_products(w)
+            self._memory_gradient(w, parts)
+            if on_ready is not None:
+                on_ready(*self._grad_range("attention/", "decoder/decoder"))
+            enc_ticket = self._encoder_bptt(w, p)
+            self._encoder_tail(w)
+        if on_ready is not None:
+            on_ready(*self._grad_range("encoder/"))
+        if not self._backward_verdict(w, p, bwd_ticket, enc_ticket, agree, agree_async):
+            if on_abort is not None:
+                on_abort()
+            torch.cuda.current_stream().synchronize()
+            return self.loss_and_backward(w, grad_scale=grad_scale, on_ready=on_ready, on_abort=on_abort, agree=agree, agree_async=agree_async, _redo=True)
+
+    def _losses(self, w, grad_scale):
+        """The gradient slab cleared; the loss words and the gradients of the three outputs; the l2 regulariser's word."""
+        d, ps, batch = self.d, self.params, w.batch
         ps.grad.zero_()
         w.scalars.zero_()
-        call("mstts_tts_loss_fwd_bwd", ptr(w.linear), ptr(w.mel_out), ptr(mel), ptr(w.stop), ptr(mlen), B, S, d.n_mel,
+        call("mstts_tts_loss_fwd_bwd", ptr(w.linear), ptr(w.mel_out), ptr(batch["Mel"]), ptr(w.stop), ptr(batch["Mel_Length"]), w.B, w.S, d.n_mel,
              int(self.use_l1), float(grad_scale), ptr(w.scalars), ptr(w.d_linear), ptr(w.d_post), ptr(w.d_stop))
         call("mstts_l2_loss_acc", ptr(ps.train), ptr(ps.wd_mask), ps.n_train, ptr(w.scalars, 3))
-        # ---- postnet backward.  In a train step (a vocoder side chain is running) the five weight-gradient products go to the encoder's stream as well, behind
-        # that chain: the ≈1 ms of small launches between this stream's data-gradient products (BN backward, column sums, kernel flips) then run beside a
-        # product instead of alone on the chip.  Joined with the chain in front of the BPTT launch.
-        wg_stream = self._enc_stream if (POSTNET_WGRAD_OVERLAP and getattr(w, "voc_done", None) is not None and not _redo) else None
-        w.side_wgrads = wg_stream is not None
+
+    def _postnet_backward(self, w, p):
+        """Postnet backward; returns its input gradient.  In a train step (a vocoder side chain is running) the five weight-gradient products go to the
+        encoder's stream as well, behind that chain: the ≈1 ms of small launches between this stream's data-gradient products (BN backward, column
+        sums, kernel flips) then run beside a product instead of alone on the chip.  Joined with the chain in front of the BPTT launch."""
+        d, mk, B, S = self.d, w.masks, w.B, w.S
+        w.side_wgrads = p.side_wgrads
         chans = [d.post_ch] * (d.post_n - 1) + [d.n_mel]
         dy = w.d_post
         for i in range(d.post_n - 1, -1, -1):
@@ -887,22 +945,17 @@ class TrainEngine(Engine):
             dx = w.post_dx if (i % 2 == 0) else w.post_dx2
             pre = "decoder/conv_%d/" % i
             conv_bn_bwd(self, self._gemm, pre + "conv1d", pre + "batch_normalization/", dy, x_in, w.post_a[i], w.post_mean[i], w.post_rstd[i],
-                        mk["post_drop_%d" % i], 1 - d.conv_drop, ACT_TANH, B * S, S, cin, chans[i], d.post_k, w.post_dz[i], dx, self._bnws,
-                        wgrad_stream=wg_stream)
+                        mk["post_drop_%d" % i], 1 - d.conv_drop, ACT_TANH, B * S, S, cin, chans[i], d.post_k, w.post_dz[i], dx, w.bn_ws,
+                        wgrad_stream=self._enc_stream if p.side_wgrads else None)
             dy = dx
-        # every postnet gradient is final: its all-reduce overlaps the decoder BPTT - unless that is the persistent launch, which needs
-        # every CU of the chip for itself: a collective kernel holding CUs at that moment and the 256 workgroups waiting for each
-        # other's CUs would sit out the launch's start window (0.2 s) and end in the fallback.  Then the range is announced BEHIND the
-        # launch (the collective is ordered after what is enqueued) and runs under the hoisted weight-gradient products instead.
-        postnet_ready_deferred = on_ready is not None and bool(getattr(w, "persist_bwd_now", False)) and bool(getattr(w, "persist_bwd", False)) and not _redo
-        if on_ready is not None and not postnet_ready_deferred:
-            self._join_vocoder(w)                # (the weight gradients on the side stream are part of the range)
-            on_ready(*self._grad_range("decoder/conv_"))
-        # d_linear(total) = loss part + residual (d_post) + postnet input grad
+        return dy
+
+    def _projection_backward(self, w, dy):
+        """d_linear(total) = loss part + residual (d_post) + postnet input grad (dy); the projection's parameter gradients and d_pj."""
+        d, B, S, H, M = self.d, w.B, w.S, self.d.dec_lstm, self.d.mem
         n = B * S * d.n_mel
         call("mstts_add", ptr(w.d_linear), ptr(w.d_post), ptr(w.d_linear), n)
         call("mstts_add", ptr(w.d_linear), ptr(dy), ptr(w.d_linear), n)
-        # ---- projection backward
         call("mstts_pack_dproj", ptr(w.d_linear), ptr(w.d_stop), ptr(w.d_proj), self.proj_ld, B, S, d.n_mel)
         self.dwp_pad.zero_()
         self._gemm(w.pj, w.d_proj, self.dwp_pad, H + M, self.proj_ld, S * B, H + M, self.proj_ld, self.proj_ld, trans_a=True,
@@ -913,155 +966,116 @@ class TrainEngine(Engine):
         call("mstts_colsum", ptr(w.d_proj), S * B, d.n_mel + 1, self.proj_ld, ptr(gbp, ogbp), 1)
         Ml = M - self.ctx_dead      # the live context columns: nobody reads the gradient of the speaker columns (mstts_decoder_train_bwd_desc.ctx_dead)
         self._gemm(w.d_proj, self.wp_pad, w.d_pj, S * B, H + Ml, self.proj_ld, self.proj_ld, self.proj_ld, H + M, trans_b=True)
-        # ---- decoder loop backward (its persistent launch needs every CU: the vocoder side chain of the forward pass, which ran under the
-        # loss and the postnet's backward pass, has to be off the chip)
+
+    def _decoder_bptt(self, w, p):
+        """Decoder loop backward.  Its persistent launch needs every CU: the vocoder side chain of the forward pass, which ran under the loss and
+        the postnet's backward pass, has to be off the chip.  Returns (the launch's ticket or None, the slabs of d_in0 that hold the context
+        gradient)."""
         self._join_vocoder(w)
         w.dq_hist.zero_()
         db = w.dec_b
         db.fwd = C.pointer(w.dec)
         db.d_pj, db.dg0, db.dg1, db.dq_hist, db.de_hist, db.d_in0, db.ws = (ptr(w.d_pj), ptr(w.dg0), ptr(w.dg1), ptr(w.dq_hist),
                                                                              ptr(w.de_hist), ptr(w.d_in0), ptr(w.dec_bwd_ws))
-        SB = S * B
         self.dw0f.zero_()
         w.d_keys.zero_()
         self.d_loc_k.zero_()
-        parts = w.d_in0_parts
-        # (persist_bwd_now: this step's policy decision, taken in forward(); persist_bwd: the plan's flag, which tests clear between two backward passes)
-        use_pbwd = bool(getattr(w, "persist_bwd_now", False)) and bool(getattr(w, "persist_bwd", False)) and bool(getattr(w, "opk_valid", False)) and not _redo
-        bwd_ticket = None
-        if getattr(w, "opk_valid", False) and not use_pbwd:
-            self.unpack_history(w)            # the persistent forward packed the cell operands; the launch-per-step BPTT reads the histories
-        if use_pbwd:
-            # ONE launch for the whole BPTT; its status words are read while the hoisted weight-gradient products run (no bubble); the
-            # launch-per-step loop is the fallback
-            pb = w.pdesc_b
-            pb.w0pk, pb.w1pk, pb.wqpk, pb.xch, pb.ctrl = ptr(self.pkb[0]), ptr(self.pkb[1]), ptr(self.pkb[2]), ptr(w.xch_b), ptr(w.pctrl_b)
-            pb.stamps = ptr(self.persist_bwd_stamps) if self.persist_bwd_stamps is not None else None
-            pb.opk = ptr(w.opk)
-            pb.selftest_fail_step = int(self.persist_bwd_selftest)
-            pb.near_xcd = near_xcd()
-            pb.recurrent_bf16 = int(self.persist_bf16)
-            call("mstts_decoder_train_bwd_persistent", C.byref(db), C.byref(pb))
-            ev = torch.cuda.Event(enable_timing=self.trace_events)
-            ev.record()
-            self.bptt_end_event = ev             # (bench.py --gpus N: where the first gradient collective starts relative to this)
-            bwd_ticket = Ticket(w.pctrl_b, w.pctrl_b_host, decoder_workgroups()).enqueue(torch.cuda.Event())
-            parts = 1                        # (on success d_in0 slab 0 holds the complete context gradient; a failed launch re-runs the pass)
-        else:
+        if not p.decoder:
+            self.unpack_history(w)            # (where the persistent forward packed the cell operands: the launch-per-step BPTT reads the histories)
             self._ensure_fallback_packs()
             call("mstts_decoder_train_bwd", C.byref(db))
-        if postnet_ready_deferred:
-            on_ready(*self._grad_range("decoder/conv_"))
-        def decoder_products():
-            # hoisted weight gradients of the loop.  (Running them chunk by chunk on a second stream under BPTT was measured: the
-            # GEMMs' MFMA traffic slows every latency-bound loop kernel by 25-35 %, 105.4 vs 102.2 ms per step - not kept.)
-            self._recurrent_wgrads(w, 0, S, part="products")
-            g0, og0 = self.G(CELL % 0 + "kernel")
-            call("mstts_copy2d", ptr(self.dw0f), 4 * H, ptr(g0, og0 + Pn * 4 * H), 4 * H, M, 4 * H, 1)
-            call("mstts_copy2d", ptr(self.dw0f), 4 * H, ptr(g0, og0 + (Pn + M) * 4 * H), 4 * H, M, 4 * H, 1)
-            call("mstts_copy2d", ptr(self.dw0f, M * 4 * H), 4 * H, ptr(g0, og0 + (Pn + 2 * M) * 4 * H), 4 * H, H, 4 * H, 1)
-            # prenet backward (d_pre = dg0 . W0[:P]^T was produced per chunk above)
-            dcur, dnxt = w.d_pre, w.d_pre2
-            for i in range(d.prenet_n - 1, -1, -1):
-                cin = d.n_mel if i == 0 else Pn
-                x_in = w.frames if i == 0 else w.pre_d[i - 1]
-                call("mstts_relu_dropout_bwd", ptr(dcur), ptr(w.pre_d[i]), ptr(mk["prenet_drop_%d" % i]), 1 - d.prenet_drop, ptr(dcur), SB * Pn)
-                gk, ogk = self.G("decoder/decoder/prenet_%d/dense/kernel" % i); gb, ogb = self.G("decoder/decoder/prenet_%d/dense/bias" % i)
-                self._gemm(x_in, dcur, gk, cin, Pn, SB, cin, Pn, Pn, trans_a=True, split_k=max(2, _split_k(cin, Pn, SB)), c_off=ogk)
-                call("mstts_colsum", ptr(dcur), SB, Pn, Pn, ptr(gb, ogb), 1)
-                if i > 0:
-                    k, ok = self.P("decoder/decoder/prenet_%d/dense/kernel" % i)
-                    self._gemm(dcur, k, dnxt, SB, cin, Pn, Pn, Pn, cin, trans_b=True, b_off=ok)
-                    dcur, dnxt = dnxt, dcur
-            gs = {field: ptr(*self.G(name)) for field, name in LSA_VARS}
-            ls = w.dec.lsa
-            call("mstts_lsa_unfold_location_grad", ls.conv_k, ls.conv_b, ls.dense_k, ptr(self.d_loc_k), gs["score_b"],
-                 gs["conv_k"], gs["conv_b"], gs["dense_k"], d.att_k, d.att_ch, d.att)
+            return None, w.d_in0_parts
+        # ONE launch for the whole BPTT; its status words are read while the hoisted weight-gradient products run (no bubble); the
+        # launch-per-step loop is the fallback
+        pb = self._fill_persist_desc(w.pdesc_b, self.pkb, w.xch_b, w.pctrl_b, self.persist_bwd_stamps, w.opk, self.persist_bwd_selftest)
+        call("mstts_decoder_train_bwd_persistent", C.byref(db), C.byref(pb))
+        ev = torch.cuda.Event(enable_timing=self.trace_events)
+        ev.record()
+        self.bptt_end_event = ev             # (bench.py --gpus N: where the first gradient collective starts relative to this)
+        ticket = Ticket(w.pctrl_b, w.pctrl_b_host, decoder_workgroups()).enqueue(torch.cuda.Event())
+        return ticket, 1                     # (on success d_in0 slab 0 holds the complete context gradient; a failed launch re-runs the pass)
 
-        def memory_gradient():
-            # d_values[b] = sum_s align[s,b,:]^T (d_ctx from projection + d_ctx from next step's cell 0)
-            self._gemm(w.align_hist, w.d_pj, w.d_values, Te, Ml, S, B * Te, B * (H + M), M, trans_a=True, batch=B,
-                       strides=(Te, H + M, Te * M), b_off=H, exact=True)
-            if S > 1:
-                for part in range(parts):
-                    self._gemm(w.align_hist, w.d_in0, w.d_values, Te, Ml, S - 1, B * Te, B * (M + H), M, trans_a=True, batch=B,
-                               strides=(Te, M + H, Te * M), b_off=(part * S + 1) * B * (M + H), accumulate=True, exact=True)
-            # memory layer
-            wm, owm = self.P("attention/memory_layer/kernel"); gwm, ogwm = self.G("attention/memory_layer/kernel")
-            self._gemm(w.values, w.d_keys, gwm, M, A, B * Te, M, A, A, trans_a=True, split_k=max(2, _split_k(M, A, B * Te)), c_off=ogwm)
-            self._gemm(w.d_keys, wm, w.d_values, B * Te, Ml, A, A, A, M, trans_b=True, accumulate=True, b_off=owm)
+    def _decoder_products(self, w):
+        """Hoisted weight gradients of the loop, the prenet's backward pass, the location filter's gradient unfolded.  (Running the products chunk by
+        chunk on a second stream under BPTT was measured: the GEMMs' MFMA traffic slows every latency-bound loop kernel by 25-35 %, 105.4 vs
+        102.2 ms per step - not kept.)"""
+        d, mk = self.d, w.masks
+        H, M, Pn, SB = d.dec_lstm, d.mem, d.prenet, w.S * w.B
+        self._recurrent_wgrads(w, 0, w.S, part="products")
+        g0, og0 = self.G(CELL % 0 + "kernel")
+        for src, dst, rows in ((0, Pn, M), (0, Pn + M, M), (M, Pn + 2 * M, H)):         # (the folded context rows appear twice in the kernel)
+            call("mstts_copy2d", ptr(self.dw0f, src * 4 * H), 4 * H, ptr(g0, og0 + dst * 4 * H), 4 * H, rows, 4 * H, 1)
+        # prenet backward (d_pre = dg0 . W0[:P]^T was produced with the products above)
+        dcur, dnxt = w.d_pre, w.d_pre2
+        for i in range(d.prenet_n - 1, -1, -1):
+            cin = d.n_mel if i == 0 else Pn
+            x_in = w.frames if i == 0 else w.pre_d[i - 1]
+            call("mstts_relu_dropout_bwd", ptr(dcur), ptr(w.pre_d[i]), ptr(mk["prenet_drop_%d" % i]), 1 - d.prenet_drop, ptr(dcur), SB * Pn)
+            gk, ogk = self.G("decoder/decoder/prenet_%d/dense/kernel" % i); gb, ogb = self.G("decoder/decoder/prenet_%d/dense/bias" % i)
+            self._gemm(x_in, dcur, gk, cin, Pn, SB, cin, Pn, Pn, trans_a=True, split_k=max(2, _split_k(cin, Pn, SB)), c_off=ogk)
+            call("mstts_colsum", ptr(dcur), SB, Pn, Pn, ptr(gb, ogb), 1)
+            if i > 0:
+                k, ok = self.P("decoder/decoder/prenet_%d/dense/kernel" % i)
+                self._gemm(dcur, k, dnxt, SB, cin, Pn, Pn, Pn, cin, trans_b=True, b_off=ok)
+                dcur, dnxt = dnxt, dcur
+        gs = {field: ptr(*self.G(name)) for field, name in LSA_VARS}
+        ls = w.dec.lsa
+        call("mstts_lsa_unfold_location_grad", ls.conv_k, ls.conv_b, ls.dense_k, ptr(self.d_loc_k), gs["score_b"],
+             gs["conv_k"], gs["conv_b"], gs["dense_k"], d.att_k, d.att_ch, d.att)
 
-        # ---- encoder BiLSTM backward: descriptors
-        x_in, cin = w.enc_y[-1], d.enc_conv_ch
+    def _memory_gradient(self, w, parts):
+        """d_values[b] = sum_s align[s,b,:]^T (d_ctx from projection + d_ctx from next step's cell 0), then the memory layer."""
+        d, B, Te, S = self.d, w.B, w.Te, w.S
+        H, M, A, Ml = d.dec_lstm, d.mem, d.att, d.mem - self.ctx_dead      # (Ml: the live context columns)
+        self._gemm(w.align_hist, w.d_pj, w.d_values, Te, Ml, S, B * Te, B * (H + M), M, trans_a=True, batch=B,
+                   strides=(Te, H + M, Te * M), b_off=H, exact=True)
+        if S > 1:
+            for part in range(parts):
+                self._gemm(w.align_hist, w.d_in0, w.d_values, Te, Ml, S - 1, B * Te, B * (M + H), M, trans_a=True, batch=B,
+                           strides=(Te, M + H, Te * M), b_off=(part * S + 1) * B * (M + H), accumulate=True, exact=True)
+        wm, owm = self.P("attention/memory_layer/kernel"); gwm, ogwm = self.G("attention/memory_layer/kernel")
+        self._gemm(w.values, w.d_keys, gwm, M, A, B * Te, M, A, A, trans_a=True, split_k=max(2, _split_k(M, A, B * Te)), c_off=ogwm)
+        self._gemm(w.d_keys, wm, w.d_values, B * Te, Ml, A, A, A, M, trans_b=True, accumulate=True, b_off=owm)
+
+    def _encoder_bptt(self, w, p):
+        """BPTT of both encoder directions: the persistent launch (returns its ticket) or the launch-per-step pair driver (None)."""
+        d, mk, B, Te, M, He, cin = self.d, w.masks, w.B, w.Te, self.d.mem, self.d.enc_lstm, self.d.enc_conv_ch
         bseqs = []
         for di, dr in enumerate(("fw", "bw")):
             k, ok = self.P(ENC_CELL % dr + "kernel")
-            bseqs.append(lstm_seq_bwd(B, Te, He, (k, ok + cin * 4 * He), tlen, di, d.zoneout, mk["enc_zc_" + dr], mk["enc_zh_" + dr],
+            bseqs.append(lstm_seq_bwd(B, Te, He, (k, ok + cin * 4 * He), w.batch["Token_Length"], di, d.zoneout, mk["enc_zc_" + dr], mk["enc_zh_" + dr],
                                       (w.d_values, di * He), Te * M, M, w.enc_c[dr], w.enc_acts[dr], w.enc_craw[dr], w.enc_dgs[dr], w.enc_dgp[dr],
                                       w.enc_bwd_ws[dr]))
-        def encoder_tail():
-            """Everything behind the encoder's BPTT: the BiLSTM's weight gradients and input gradient, the convolution blocks, the embedding."""
-            x_in, cin = w.enc_y[-1], d.enc_conv_ch
-            for di, dr in enumerate(("fw", "bw")):
-                lstm_layer_grads(self, self._gemm, ENC_CELL % dr, x_in, w.enc_h[dr], w.enc_dgp[dr], w.enc_dgs[dr], w.enc_dy, B * Te, cin, He,
-                                 dx_accumulate=di == 1)
-            # ---- encoder conv backward
-            dy = w.enc_dy
-            bufs = [w.enc_dx, w.enc_dy]
-            for i in range(d.enc_conv_n - 1, -1, -1):
-                cin = d.emb if i == 0 else d.enc_conv_ch
-                x_in = w.emb if i == 0 else w.enc_y[i - 1]
-                dx = bufs[(d.enc_conv_n - 1 - i) % 2]
-                pre = "encoder/conv_%d/" % i
-                conv_bn_bwd(self, self._gemm, pre + "conv1d", pre + "batch_normalization/", dy, x_in, w.enc_a[i], w.enc_mean[i], w.enc_rstd[i],
-                            mk["enc_conv_drop_%d" % i], 1 - d.conv_drop, ACT_RELU, B * Te, Te, cin, d.enc_conv_ch, d.enc_conv_k, w.enc_dz, dx, self._bnws)
-                dy = dx
-            ge, oge = self.G("encoder/embedding_variable")
-            call("mstts_embedding_bwd", ptr(tok), ptr(dy), ptr(ge, oge), B * Te, d.n_tok, d.emb)
+        if p.encoder:
+            return self._enc_persistent(w, "mstts_lstm_seq_bwd_pair_persistent", bseqs, 1)
+        self._ensure_fallback_packs()
+        call("mstts_lstm_seq_bwd_pair", C.byref(bseqs[0]), C.byref(bseqs[1]))    # two launches per step
 
-        # (the persistent BPTT reads the packed history of a persistent forward)
-        enc_ticket = None
-        enc_persistent = bool(getattr(w, "enc_hist_valid", False)) and not _redo
-        if enc_persistent and ENC_OVERLAP:
-            # The encoder's persistent BPTT occupies 32 of the 256 CUs for 0.65 ms: it runs on its own stream UNDER the decoder's hoisted weight-gradient
-            # products instead of in front of the encoder's.  What it waits for - the attention parameter gradients' d_keys, the memory gradient -
-            # is computed first; its launch is enqueued before the products, so its 32 workgroups are resident when the products' tiles arrive.
-            self._recurrent_wgrads(w, 0, S, part="attention")
-            memory_gradient()
-            ready = torch.cuda.Event()
-            ready.record()
-            with torch.cuda.stream(self._enc_stream):
-                self._enc_stream.wait_event(ready)
-                enc_ticket = self._enc_persistent(w, "mstts_lstm_seq_bwd_pair_persistent", bseqs, 1)
-                if ENC_TAIL_OVERLAP:
-                    # ... and the rest of the encoder's backward pass (weight gradients, convolution blocks, embedding: ~45 launches, 1.1 ms, none of
-                    # it read by the decoder's products) stays on this stream, behind the launch and beside those products
-                    encoder_tail()
-                enc_done = torch.cuda.Event()
-                enc_done.record()
-            decoder_products()
-            if on_ready is not None:         # decoder + attention gradients are final: overlaps the encoder backward
-                on_ready(*self._grad_range("attention/", "decoder/decoder"))
-            torch.cuda.current_stream().wait_event(enc_done)
-            if not ENC_TAIL_OVERLAP:
-                encoder_tail()
-        else:
-            self._recurrent_wgrads(w, 0, S, part="attention")
-            decoder_products()
-            memory_gradient()
-            if on_ready is not None:
-                on_ready(*self._grad_range("attention/", "decoder/decoder"))
-            if enc_persistent:
-                enc_ticket = self._enc_persistent(w, "mstts_lstm_seq_bwd_pair_persistent", bseqs, 1)
-            else:
-                self._ensure_fallback_packs()
-                call("mstts_lstm_seq_bwd_pair", C.byref(bseqs[0]), C.byref(bseqs[1]))    # BPTT of both directions: two launches per step
-            encoder_tail()
-        if on_ready is not None:
-            on_ready(*self._grad_range("encoder/"))
-        # ---- the status words of this pass's persistent launches: ONE host sync (the side stream runs in order)
+    def _encoder_tail(self, w):
+        """Everything behind the encoder's BPTT: the BiLSTM's weight gradients and input gradient, the convolution blocks, the embedding."""
+        d, mk, B, Te, He = self.d, w.masks, w.B, w.Te, self.d.enc_lstm
+        x_in, cin = w.enc_y[-1], d.enc_conv_ch
+        for di, dr in enumerate(("fw", "bw")):
+            lstm_layer_grads(self, self._gemm, ENC_CELL % dr, x_in, w.enc_h[dr], w.enc_dgp[dr], w.enc_dgs[dr], w.enc_dy, B * Te, cin, He,
+                             dx_accumulate=di == 1)
+        dy = w.enc_dy
+        bufs = [w.enc_dx, w.enc_dy]
+        for i in range(d.enc_conv_n - 1, -1, -1):
+            cin = d.emb if i == 0 else d.enc_conv_ch
+            x_in = w.emb if i == 0 else w.enc_y[i - 1]
+            dx = bufs[(d.enc_conv_n - 1 - i) % 2]
+            pre = "encoder/conv_%d/" % i
+            conv_bn_bwd(self, self._gemm, pre + "conv1d", pre + "batch_normalization/", dy, x_in, w.enc_a[i], w.enc_mean[i], w.enc_rstd[i],
+                        mk["enc_conv_drop_%d" % i], 1 - d.conv_drop, ACT_RELU, B * Te, Te, cin, d.enc_conv_ch, d.enc_conv_k, w.enc_dz, dx, w.bn_ws)
+            dy = dx
+        ge, oge = self.G("encoder/embedding_variable")
+        call("mstts_embedding_bwd", ptr(w.batch["Token"]), ptr(dy), ptr(ge, oge), B * Te, d.n_tok, d.emb)
+
+    def _backward_verdict(self, w, p, bwd_ticket, enc_ticket, agree, agree_async):
+        """The backward pass's ONE host sync: the status words of its persistent launches, then - data parallel - the job's decision
+        (agree_async: formed on the device and read here too; else _pass_verdict).  True: keep the pass."""
         job_flag = None
-        if agree_async is not None and not _redo:
+        if p.job_flag:
             # every rank, every pass (also one that launched nothing persistent: its word is 1) - the ranks' collective sequences stay in step
             with torch.cuda.stream(self._side):
                 # behind both launches: each ended before its ticket's event - two waits for events that have (long) fired when the side
@@ -1077,22 +1091,16 @@ class TrainEngine(Engine):
                 w.job_flag_host.copy_(w.job_flag, non_blocking=True)
                 job_flag = torch.cuda.Event()
                 job_flag.record()
-        passed = enc_ticket is None or self._ticket_ok(enc_ticket, "persist_enc_fallbacks", keep_status=False)
+        mine = enc_ticket is None or self._ticket_ok(enc_ticket, "persist_enc_fallbacks", keep_status=False)
         if bwd_ticket is not None and not self._ticket_ok(bwd_ticket, "persist_bwd_fallbacks"):
-            passed = False
-        if job_flag is not None:
-            job_flag.synchronize()
-            job_ok = int(w.job_flag_host[0]) == 1            # MIN over the ranks of what mstts_persist_status saw on each
-            if passed and not job_ok:
-                self.collective_redos += 1
-            passed = passed and job_ok
-        else:
-            passed = self._pass_verdict(passed, agree, _redo)
-        if not passed:
-            if on_abort is not None:
-                on_abort()
-            torch.cuda.current_stream().synchronize()
-            return self.loss_and_backward(w, grad_scale=grad_scale, on_ready=on_ready, on_abort=on_abort, agree=agree, agree_async=agree_async, _redo=True)
+            mine = False
+        if job_flag is None:
+            return self._pass_verdict(mine, agree, not p.speculative)
+        job_flag.synchronize()
+        job_ok = int(w.job_flag_host[0]) == 1                    # MIN over the ranks of what mstts_persist_status saw on each
+        if mine and not job_ok:
+            self.collective_redos += 1
+        return mine and job_ok
 
     def _pass_verdict(self, passed, agree, redo):
         """Keep this backward pass or run it again?  With `agree` (data parallel) the answer is the job's, not the rank's: the minimum of
@@ -1109,8 +1117,7 @@ class TrainEngine(Engine):
         dW1, db1, dw0f (folded cell-0 rows), cell-0 prenet rows, db0, dWq, the attention parameter gradients and d_keys; also
         that range of d_pre = dg0 . W0[:P]^T for the prenet backward.  part: "attention" = the attention parameter gradients and d_keys only
         (what the encoder's gradient path waits for), "products" = everything else, "all"."""
-        d = self.d
-        B, Te = w.B, w.Te
+        d, B, Te = self.d, w.B, w.Te
         H, M, A, Pn = d.dec_lstm, d.mem, d.att, d.prenet
         n = (hi - lo) * B
         r = lo * B                                           # first row of the range in the step-major histories
@@ -1179,26 +1186,19 @@ class TrainEngine(Engine):
 
     def scalars(self, w, average=False, group=None):
         """Loss scalars of the last step on `w`; average=True: mean over the data-parallel ranks."""
+        s = w.scalars.clone() if average else w.scalars.detach()
         if average:
             from .dist import average_
-            avg = w.scalars.clone()
-            average_([avg], group=group)
-            s = avg.cpu().numpy()
-        else:
-            s = w.scalars.detach().cpu().numpy()
-        wr = float(s[3]) * self.wr_rate
-        return {"Linear_Loss": float(s[0]), "Postnet_Loss": float(s[1]), "Stop_Loss": float(s[2]),
-                "Weight_Regularization_Loss": wr, "Loss": float(s[0] + s[1] + s[2]) + wr}
+            average_([s], group=group)
+        return _loss_dict(s.cpu().numpy(), self.wr_rate)
 
     def scalars_async(self, w, average=False, group=None):
         """The same, without waiting for the step: the four loss words are copied to a page-locked slot (four slots in rotation) behind
         everything enqueued so far and a handle is returned; handle.get() waits for THAT copy only.  Tacotron2.Train reads a step's losses
         while the next step runs, so the host never drains the device between two steps (MSTTS_SV.py:270-273 fetches them with the step)."""
-        if getattr(self, "_scalar_ring", None) is None:
+        if self._scalar_ring is None:
             self._scalar_ring = torch.zeros(4, 4, dtype=torch.float32).pin_memory()
-            self._scalar_next = 0
             self._scalar_avg = torch.zeros(4, dtype=torch.float32, device=self.device)
-            self._scalar_handles = [None] * 4
         old = self._scalar_handles[self._scalar_next]
         if old is not None:
             old.get()                        # a handle nobody has read yet takes its words out of the slot before the slot is used again (its copy ended steps ago)
@@ -1237,9 +1237,7 @@ class TrainEngine(Engine):
         if self.deterministic and not getattr(lib.deterministic_gemm._depth, "n", 0):
             with lib.deterministic_gemm():
                 return self.train_step(batch, masks=masks, all_reduce=all_reduce)
-        B, Te = batch["Token"].shape
-        L = batch["Mel"].shape[1]
-        w = self.plan(B, Te, L)
+        w = self.plan(*batch["Token"].shape, batch["Mel"].shape[1])
         self.forward(batch, w, masks=masks, allowed=self._persist_begin_step(), overlap_vocoder=True)      # the fallback policy advances once per optimizer step
         if all_reduce is not None:           # bucketed in the order gradients become final (postnet -> decoder/attention -> encoder),
             g = self.params.grad             # each bucket's all-reduce running under the rest of the backward pass

@@ -600,13 +600,9 @@ class InferEngine:
                 # the pass, self._keep; the control words of its launches are copied behind the join.)
                 if self._spk_stream is None:
                     self._spk_stream = torch.cuda.Stream(device=dev)
-                ready = torch.cuda.Event()
-                ready.record()
-                with torch.cuda.stream(self._spk_stream):
-                    self._spk_stream.wait_event(ready)
+                with lib.fork(self._spk_stream) as side:
                     spk = self._speaker_embedding(spk_mel)
-                    spk_done = torch.cuda.Event()
-                    spk_done.record()
+                spk_done = side.done
             else:
                 spk = self._speaker_embedding(spk_mel)
         mark("uploads + speaker encoder")

@@ -418,6 +418,34 @@ def stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+class fork:
+    """Context manager: work enqueued inside goes to `stream`, behind everything enqueued on the current stream so far (an event recorded
+    here, `stream` made current and told to wait for it).  done=True: an event recorded on `stream` behind that work is left in `.done`
+    for join(); done=False records none (`.done` stays None) - whoever needs the work orders itself behind the stream some other way."""
+
+    def __init__(self, stream, done=True):
+        self.stream, self.done, self._want_done = stream, None, done
+
+    def __enter__(self):
+        ready = torch.cuda.Event()
+        ready.record()
+        self._ctx = torch.cuda.stream(self.stream)
+        self._ctx.__enter__()
+        self.stream.wait_event(ready)
+        return self
+
+    def __exit__(self, *exc):
+        if self._want_done and exc[0] is None:
+            self.done = torch.cuda.Event()
+            self.done.record()
+        return self._ctx.__exit__(*exc)
+
+
+def join(event):
+    """The current stream waits for `event` (a fork's `.done`)."""
+    torch.cuda.current_stream().wait_event(event)
+
+
 def ptr(t, offset=0):
     """Device pointer of a tensor (None -> NULL), advanced by ``offset`` elements."""
     if t is None:

@@ -189,10 +189,7 @@ def conv_bn_bwd(eng, gemm, conv, bn, dy, x_in, a, mean, rstd, mask, keep, act, r
     if wgrad_stream is None:
         wgrad()
     else:
-        ev = torch.cuda.Event()
-        ev.record()
-        with torch.cuda.stream(wgrad_stream):
-            wgrad_stream.wait_event(ev)
+        with lib.fork(wgrad_stream, done=False):         # (the caller joins the stream once, behind the last block)
             wgrad()
     if dx is not None:
         k, ok = eng.P(conv + "/kernel")

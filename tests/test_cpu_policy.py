@@ -13,7 +13,8 @@ from helpers import dims_pair
 
 def _policy_obj():
     from multi_speaker_tts_amd import engine as E
-    o = types.SimpleNamespace(_persist_cool=E.CoolDown(), _persist_warned=False, persist_disabled_steps=0, persist_last_status=(256, 1, 0))
+    o = types.SimpleNamespace(_persist_cool=E.CoolDown(), _persist_warned=False, persist_disabled_steps=0, persist_last_status=(256, 1, 0),
+                              _step_fell_back=False, _step_was_persistent=False)
     o.begin = types.MethodType(E.TrainEngine._persist_begin_step, o)
     return E, o
 
