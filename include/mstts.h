@@ -865,7 +865,8 @@ int mstts_decoder_train_fwd(const mstts_decoder_train_desc* d, mstts_stream_t s)
  * runs behind either.  Reference widths only: mstts_persist_fwd_supported(B <= 32, H == 1024, M == 768, A == 128, T <= 128, KS == 31)
  * and a device that admits all 256 workgroups at once (occupancy query, >= 256 CUs).
  *   w0pk / w1pk / wqpk: mstts_persist_pack(w0f, w1, wq) copies (mstts_persist_pack_floats(0 / 1 / 2) floats), refreshed when the
- *                       variables change;  xch: mstts_persist_fwd_ws_bytes() bytes, 16-byte aligned;  ctrl: 272 uint32.
+ *                       variables change;  xch: mstts_persist_fwd_ws_bytes() bytes, 16-byte aligned (the rings, then the [32, 4H] constant
+ *                       gate term of a launch with ctx_dead = 256);  ctrl: 272 uint32.
  * After the launch: ctrl[1] == 0 and ctrl[2] == 256  <=>  the sequence ran to its end.  Anything else (the workgroups were not
  * co-resident within the start window, e.g. because another kernel held CUs; or a bounded wait expired) means the outputs are
  * incomplete: the caller re-runs mstts_decoder_train_fwd, which recomputes every step (abort codes: 1 = start rendezvous timed out,
@@ -907,9 +908,21 @@ typedef struct {
                                      therefore rounds the other way than bf(stored value).  tests/test_gpu_decoder_bf16_ref.py holds both launches to
                                      this statement stage by stage.
                                      (Round 4 had a software-pipelined schedule selector in this slot: removed, tools/persist_pipe.inc.) */
-    int32_t ctx_dead;             /* BPTT launch only (the forward launch ignores it): 0 or 256 = the value of mstts_decoder_train_bwd_desc.ctx_dead, see
-                                     there; w0pk must then be the mstts_persist_bwd_pack_live(..., ctx_dead) copy.  (It takes the place of the struct's
-                                     tail padding: sizeof is unchanged, a zero-initialised descriptor is the earlier behaviour.) */
+    int32_t ctx_dead;             /* 0 or 256, anything else MSTTS_ERR_SHAPE (nothing is launched).  (It takes the place of the struct's tail padding:
+                                     sizeof is unchanged, a zero-initialised descriptor is the earlier behaviour.)
+                                     BPTT launch: the value of mstts_decoder_train_bwd_desc.ctx_dead, see there; w0pk must then be the
+                                     mstts_persist_bwd_pack_live(..., ctx_dead) copy.
+                                     Forward launch: 256 is the caller's PROMISE about the last 256 columns of lsa.values - per row they hold one
+                                     constant spk[b] at every position t < lengths[b] and zero past it (memory = [encoder | tiled speaker
+                                     embedding]).  The context's last 256 columns are then spk[b] at every step, and the fp32 launch with pre / b0 and
+                                     at most 128 encoder positions neither forms nor exchanges nor multiplies them: the entry point forms their share of
+                                     the cell-0 gates once per launch (spk[b] . w0f[rows 512..767], read from mstts_decoder_train_desc.w0f, which
+                                     must be given; spk[b] = values[b, 0, 512..767], values 16-byte aligned; the term is added from step 1 on, step 0
+                                     having no incoming context) and fills columns 512..767 of in0[1..S] and the same context columns of pj[0..S-1]
+                                     with spk[b], so that in0 and pj are completely written as with 0.  Same w0pk (the mstts_persist_pack copy).
+                                     Every other forward call (recurrent_bf16, pre == NULL, more than 128 positions) computes all 768 columns
+                                     whatever this field says, which is always correct.  With values that break the promise the results are wrong
+                                     without any error.  0: every column is computed by the loop, bit for bit the earlier behaviour. */
 } mstts_persist_desc;
 int32_t mstts_persist_fwd_supported(int64_t B, int64_t H, int64_t M, int64_t A, int64_t T, int64_t KS);
 int64_t mstts_persist_fwd_ws_bytes(void);

@@ -67,8 +67,10 @@ namespace mstts {
 #define H1_REQ_EARLY 1          // SPLIT_H1: the request for the h1 slice (published a step ago) leaves in front of the P0 publication instead of behind it
 #endif
 #ifndef P0_EARLY
-#define P0_EARLY 0              // SPLIT_H1: the request for the cell-0 partials leaves in front of the h1 product instead of behind it
+#define P0_EARLY 2              // SPLIT_H1, live-width instantiation only (the full-width one spills 16 registers with it): the request for the cell-0 partials leaves in front of the h1 product instead of behind it; 2 = and is spread over all eight waves (ISSUE_PARTIALS8)
 #endif
+// The live-width instantiation (MC = 512 below) stands on the split on-chain products and on the owners' query projection (whose LDS corner holds its constant gate term)
+constexpr bool FWD_LIVE_BUILT = FWD_QOWN && SPLIT_C0 && SPLIT_M0;
 
 // ring sizes in floats per slot
 constexpr long XCTX = 8L * 128 * 24, XACT = 8L * 128 * 32, XPART = 256L * 8 * 2 * 256, XM1 = 32L * PH, XEN = 32L * 8 * PTMAX;
@@ -99,6 +101,7 @@ struct PersistFwd {
     const float* pre; const float* b0;           // FOLD: prenet output [S, B, 256] and the cell-0 bias - the hoisted product xw0 is then formed inside the loop
     const uint8_t* zc0; const uint8_t* zh0; const uint8_t* zc1; const uint8_t* zh1; float keep;
     const float* keys; const float* values; const int32_t* lengths;
+    const float* cst;                            // live-width instantiation: [B, 4H] share of the constant context columns in the cell-0 gates (persist_ctx_const_kernel)
     const float* loc_k; const float* loc_b; const float* score_w; const float* score_b;
     int B, S, T;
     float* in0; float* in1; float* pj; float* c0; float* c1; float* acts0; float* acts1; float* craw0; float* craw1;
@@ -116,9 +119,18 @@ struct PersistFwd {
 // bf16 - the kernels once, when they are loaded into registers, the activations when they are staged - and run on
 // v_mfma_f32_16x16x32_bf16 with fp32 accumulators (persist_fwd_parts.h); cell states, gates, softmax, cumulative alignments, the history
 // written for BPTT and everything exchanged between workgroups stay fp32.  Same geometry, same hand-offs, half the kernel registers.
-template <bool PROF, bool FOLD, int TT, bool BF16 = false>
+// MC: the live context width, PM or PM - ctx_dead (mstts_persist_desc.ctx_dead).  memory = [encoder 512 | speaker embedding 256, tiled over the
+// row's positions, zero past its length] and the alignments of a row sum to one over its length, so context columns 512 .. 767 are spk[b] at every step: a
+// constant.  With MC = 512 (fp32 / folded / 128 positions only) the loop neither forms nor ships nor multiplies them: an attention workgroup holds 64 value
+// columns and publishes a 64-column context slice, a product workgroup stages 16 context k-steps and keeps two context octets per bf16 plane, and the cell-0
+// owners add the constant columns' share of their gates, cst = spk[b] . w0f[rows 512 .. 767] (persist_ctx_const_kernel, once per launch), from LDS - from step
+// 1 on: step 0 has no incoming context.  The dead columns of in0 / pj are filled by the entry point (persist_fill_dead_kernel).  MC = PM is the earlier kernel.
+template <bool PROF, bool FOLD, int TT, bool BF16 = false, int MC = PM>
 __global__ __launch_bounds__(PTH) void persist_fwd_kernel(PersistFwd d) {
     static_assert(!BF16 || FOLD, "the bf16 instantiation forms the prenet rows' product itself");
+    constexpr bool LIVE = MC != PM;
+    constexpr int CW = MC / 8, K4C = CW / 16;            // context columns per slice (96 | 64) and 16-byte pieces per staging row (6 | 4)
+    static_assert(MC == PM || (MC == PM - 256 && FWD_LIVE_BUILT && !BF16 && FOLD && TT == 128), "live width: the fp32 / folded / 128-position instantiation only");
     // SM0: the on-chain cell-1 product m0 . W1[m0 rows] as the exact three-way bf16 split of BOTH operands (six products on
     // v_mfma_f32_16x16x32_bf16, fp32 accumulate: fp32 accuracy at 6/16 of the f32-input MFMA's matrix-core time, as gemm_split.inc) - the one
     // product of the loop whose kernel half fits as three planes (32 -> 48 registers per lane)
@@ -132,10 +144,13 @@ __global__ __launch_bounds__(PTH) void persist_fwd_kernel(PersistFwd d) {
     // the 256 partials of its 16 units in a fixed order.  The 64 KB the query-kernel slice took hold the `lo` planes of the recurrent kernel halves
     // ([octet][thread], 32 KB each), whose hi / mid planes take the registers of the fp32 halves: SH1 / SH0 run them as six-product splits.
     constexpr bool QO = FWD_QOWN && SC0, SH1 = SPLIT_H1 && QO, SH0 = SPLIT_H0 && QO;
+    constexpr bool P0E = P0_EARLY && SH1 && LIVE, P0E8 = P0E && P0_EARLY == 2;
     constexpr int S_BIA = FL<TT>::S_Q + 128;          // [2 cells][4 gates][4 units] biases, [16] score bias + location bias, [16] score weights (S_Q itself uses 128 of its 512 floats)
     typedef FL<TT> Y;
     constexpr int S_STG = Y::S_STG, S_RED = Y::S_RED, S_TR = Y::S_TR, S_M1 = Y::S_M1, S_EN = Y::S_EN, S_CUM = Y::S_CUM, S_A = Y::S_A, S_Q = Y::S_Q,
                   S_CO = Y::S_CO, S_LK = Y::S_LK, S_FLAG = Y::S_FLAG, S_STAMP = Y::S_STAMP, S_VAL = Y::S_VAL, S_WQ = Y::S_WQ;
+    constexpr int S_KEY = S_VAL + PT * CW;            // LIVE: the row's key slice [512 threads][4 positions] in the value columns' freed room, read where it is used (4 registers)
+    constexpr int S_CST = S_M1 + 512;             // LIVE: this owner's constant gate term [4 gates][4 units][32 rows], in the half of S_M1 that S_WQO leaves
     constexpr int S_WQO = S_M1, S_W1LO = S_WQ, S_W0LO = S_WQ + 4 * 512 * 4;      // QO: query-kernel rows [4 units][128]; lo planes [4 octets][512 threads] x 16 B
     constexpr int NH = TT / 128;                  // halves of 128 encoder positions
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -192,7 +207,11 @@ __global__ __launch_bounds__(PTH) void persist_fwd_kernel(PersistFwd d) {
                 w1s[0][r >> 3][r & 7] = hi; w1s[1][r >> 3][r & 7] = mid; w1s[2][r >> 3][r & 7] = (__bf16)r2;
             }
             if constexpr (SC0) {
-                const float x = p0[r * 64];
+                // LIVE: k-steps 0 .. 15 are context rows 64 gi + 16 q + r, read out of the full-width pack (where row 96 i + 24 q' + k is k-step k of
+                // workgroup (i, gj), lane quad q'; once per launch); k-steps 16 .. 23 do not exist (octet 2 of the planes is never read)
+                const int crow = 64 * gi + 16 * (lane >> 4) + r, ci = crow / 96, cq = (crow - 96 * ci) / 24, ck = crow - 96 * ci - 24 * cq;
+                const float x = (!LIVE || r >= 24) ? p0[r * 64] : r >= 16 ? 0.f
+                              : d.w0pk[((long)((gj * 8 + ci) * 8 + wave) * 64 + ck) * 64 + 16 * cq + (lane & 15)];
                 const __bf16 hi = (__bf16)x; const float r1 = x - (float)hi;
                 const __bf16 mid = (__bf16)r1; const float r2 = r1 - (float)mid;
                 w0s[0][r >> 3][r & 7] = hi; w0s[1][r >> 3][r & 7] = mid; w0s[2][r >> 3][r & 7] = (__bf16)r2;
@@ -239,6 +258,7 @@ __global__ __launch_bounds__(PTH) void persist_fwd_kernel(PersistFwd d) {
             const int t = 128 * (m >> 2) + 4 * atg + (m & 3);
             kreg[m] = (arow && t < T) ? d.keys[((long)ab * T + t) * PA + 16 * gi + ak] : 0.f;
         }
+        if constexpr (LIVE) *reinterpret_cast<pf32x4*>(sm + S_KEY + 4 * tid) = (pf32x4){kreg[0], kreg[1], kreg[2], kreg[3]};
         asb = d.score_b[16 * gi + ak] + d.loc_b[16 * gi + ak];
         awk = d.score_w[16 * gi + ak];
         if constexpr (SC0) {
@@ -249,9 +269,13 @@ __global__ __launch_bounds__(PTH) void persist_fwd_kernel(PersistFwd d) {
             }
         }
         for (int x = tid; x < 32 * 16; x += PTH) sm[S_LK + x] = (x < PKS * 16) ? d.loc_k[(x >> 4) * PA + 16 * gi + (x & 15)] : 0.f;
-        for (int x = tid; x < PT * 96; x += PTH) {
-            const int t = x / 96, c = x - t * 96;
-            sm[S_VAL + x] = (arow && t < alen && t < T) ? d.values[((long)ab * T + t) * PM + 96 * gi + c] : 0.f;
+        for (int x = tid; x < PT * CW; x += PTH) {
+            const int t = x / CW, c = x - t * CW;
+            sm[S_VAL + x] = (arow && t < alen && t < T) ? d.values[((long)ab * T + t) * PM + CW * gi + c] : 0.f;
+        }
+        if constexpr (LIVE) {       // gate tid >> 7, unit 4 g + ((tid >> 5) & 3), row tid & 31
+            const int r = tid & 31;
+            sm[S_CST + tid] = r < B ? d.cst[(long)r * 4 * PH + (tid >> 7) * PH + 4 * g + ((tid >> 5) & 3)] : 0.f;
         }
         for (int x = tid; x < TT + 48; x += PTH) sm[S_CUM + x] = 0.f;
         if constexpr (QO) {
@@ -319,6 +343,22 @@ __global__ __launch_bounds__(PTH) void persist_fwd_kernel(PersistFwd d) {
 #define SUM_PARTIALS()                                                                                                          \
     ((*reinterpret_cast<const pf32x4*>(sm + S_RED + ((0 * 2 + et) * 64 + lane) * 4) + *reinterpret_cast<const pf32x4*>(sm + S_RED + ((1 * 2 + et) * 64 + lane) * 4)) + \
      (*reinterpret_cast<const pf32x4*>(sm + S_RED + ((2 * 2 + et) * 64 + lane) * 4) + *reinterpret_cast<const pf32x4*>(sm + S_RED + ((3 * 2 + et) * 64 + lane) * 4)))
+    // P0_EARLY == 2 (live width), cell-0 partials only: EVERY wave fetches the two tiles of ONE source (8 registers in flight across the h1 product instead
+    // of 16 in four waves), in the slice request's registers, which are free between the h1 slice's completion and stage C; no pre-added pair, so S_RED
+    // is 16 KB: waves 0 .. 3 in S_RED, waves 4 .. 7 in the last 8 KB of the room the value columns left.  The sum's tree is the four-wave form's.
+#define S_RED8(W) ((W) < 4 ? S_RED + (W) * 512 : S_KEY + 2048 + ((W) - 4) * 512)
+#define ISSUE_PARTIALS8(OFFP) do {                                                                                              \
+        _Pragma("unroll") for (int m = 0; m < 2; ++m)                                                                           \
+            soff[m] = (unsigned)(((OFFP) + slot * XPART + (((long)g * 8 + wave) * 2 + m) * 256) * 4 + 16 * lane);               \
+        issue<2>(xr, soff, sv); } while (0)
+#define COMPLETE_PARTIALS8() do {                                                                                               \
+        const unsigned gens__[2] = {gen, gen};                                                                                  \
+        if (!complete<2>(xr, soff, sv, d.ctrl, gens__)) PFAIL();                                                                \
+        float* red__ = sm + (wave < 4 ? S_RED + wave * 512 : S_KEY + 2048 + (wave - 4) * 512);                                  \
+        *reinterpret_cast<pf32x4*>(red__ + lane * 4) = sv[0];                                                                   \
+        *reinterpret_cast<pf32x4*>(red__ + (64 + lane) * 4) = sv[1]; } while (0)
+#define RED8(W) (*reinterpret_cast<const pf32x4*>(sm + S_RED8(W) + (et * 64 + lane) * 4))
+#define SUM_PARTIALS8() (((RED8(0) + RED8(1)) + (RED8(2) + RED8(3))) + ((RED8(4) + RED8(5)) + (RED8(6) + RED8(7))))
     __syncthreads();
     if (PROF && tid == 0) sflag[2] = (unsigned)wall_clock64();
 
@@ -395,13 +435,16 @@ __global__ __launch_bounds__(PTH) void persist_fwd_kernel(PersistFwd d) {
             }
             if (s > 0) {
                 PSTAMP(0);
-                slice_issue<6>(xr, OFF_CTX + pslot * XCTX + gi * 3072L, tid, soff, sv);
+                if constexpr (LIVE) slice_issue_k4(xr, OFF_CTX + pslot * XCTX + gi * (128L * CW / 4), tid, soff, sv);
+                else slice_issue<6>(xr, OFF_CTX + pslot * XCTX + gi * 3072L, tid, soff, sv);
                 if constexpr (BF16) { if (!slice_complete_bf16<6>(xr, stg16, tid, soff, sv, d.ctrl, pgen)) PFAIL(); }
+                else if constexpr (LIVE) { if (!slice_complete_split3_k4(xr, stg16, tid, soff, sv, d.ctrl, pgen)) PFAIL(); }
                 else if constexpr (SC0) { if (!slice_complete_split3_k6(xr, stg16, tid, soff, sv, d.ctrl, pgen)) PFAIL(); }
                 else { if (!slice_complete<6, LA>(xr, stg, tid, soff, sv, d.ctrl, pgen)) PFAIL(); }
                 PABORT_CHECK();
                 PSTAMP(1);
                 if constexpr (BF16) mfma_part_bf16<0, 3, 0>(wb0, stg16, lane, acc0);
+                else if constexpr (LIVE) mfma_part_split3<0, 2>(w0s, stg16, lane, acc0);
                 else if constexpr (SC0) mfma_part_split3<0, 3>(w0s, stg16, lane, acc0);
                 else mfma_part<0, 6, LA, 0, 64>(w0, stg, lane, acc0);
             }
@@ -426,22 +469,34 @@ __global__ __launch_bounds__(PTH) void persist_fwd_kernel(PersistFwd d) {
             else if constexpr (SH1) { if (!slice_complete_split3(xr, stg16, tid, soff, sv, d.ctrl, pgen)) PFAIL(); }
             else { if (!slice_complete<8, LA>(xr, stg, tid, soff, sv, d.ctrl, pgen)) PFAIL(); }
             PABORT_CHECK();
-            if constexpr (SH1 && P0_EARLY) { ISSUE_PARTIALS(OFF_P0) }
+            if constexpr (P0E8) ISSUE_PARTIALS8(OFF_P0);
+            else if constexpr (P0E) { ISSUE_PARTIALS(OFF_P0) }
             if constexpr (BF16) mfma_part_bf16<0, 4, 4>(wb1, stg16, lane, acc1);
             else if constexpr (SH1) mfma_part_split3_lds<0, 4>(w1h, sm + S_W1LO + 4 * tid, stg16, lane, acc1);
             else mfma_part<0, 8, LA, 32, 64>(w1, stg, lane, acc1);
         }
         PSTAMP(13);
         // ================= B: sum of the eight partials, cell-0 update
-        if (!(SH1 && P0_EARLY) || s == 0) { ISSUE_PARTIALS(OFF_P0) }
-        COMPLETE_PARTIALS()
+        if constexpr (P0E8) {
+            if (s == 0) ISSUE_PARTIALS8(OFF_P0);
+            COMPLETE_PARTIALS8();
+        } else {
+            if (!P0E || s == 0) { ISSUE_PARTIALS(OFF_P0) }
+            COMPLETE_PARTIALS()
+        }
         PABORT_CHECK();
         PSTAMP(3);
         {
-            const pf32x4 gs = SUM_PARTIALS();
+            const pf32x4 gs = P0E8 ? SUM_PARTIALS8() : SUM_PARTIALS();
             float add0[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) add0[q] = SC0 ? sm[S_BIA + q * 4 + ee] : FOLD ? b0v[q] : (rowok ? xwv[q] : 0.f);
+            if constexpr (LIVE) {
+                if (s > 0) {        // (step 0 has no incoming context: in0[0] is zero in all 768 columns)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) add0[q] += sm[S_CST + (q * 4 + ee) * 32 + er];
+                }
+            }
             const float cprev0 = c0s;
             const CellOut o = cell_update(gs, add0, c0s, h0s, (zc0v || !rowok) ? d.keep : 0.f, (zh0v || !rowok) ? d.keep : 0.f);
             if (ew) {
@@ -652,7 +707,7 @@ __global__ __launch_bounds__(PTH) void persist_fwd_kernel(PersistFwd d) {
                     const pf32x4 loc = locv[hh];
                     float pre[4];
 #pragma unroll
-                    for (int m = 0; m < 4; ++m) pre[m] = kreg[4 * hh + m] + qk + loc[m];
+                    for (int m = 0; m < 4; ++m) pre[m] = (LIVE ? sm[S_KEY + 4 * tid + m] : kreg[4 * hh + m]) + qk + loc[m];
                     pf32x4 e4;
 #pragma unroll
                     for (int m = 0; m < 4; ++m) {
@@ -719,40 +774,40 @@ __global__ __launch_bounds__(PTH) void persist_fwd_kernel(PersistFwd d) {
                 }
             }
             __syncthreads();
-            if (tid < 384) {
-                const int c = tid % 96, th = tid / 96;
+            if (tid < 4 * CW) {
+                const int c = tid % CW, th = tid / CW;
                 float acc = 0.f;
 #pragma unroll
                 for (int t4 = 0; t4 < 8; ++t4) {                     // (the four alignment weights of a group in one 16-byte LDS read)
                     const pf32x4 a4 = *reinterpret_cast<const pf32x4*>(sm + S_A + 32 * th + 4 * t4);
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) acc += a4[e] * sm[S_VAL + (32 * th + 4 * t4 + e) * 96 + c];
+                    for (int e = 0; e < 4; ++e) acc += a4[e] * sm[S_VAL + (32 * th + 4 * t4 + e) * CW + c];
                 }
                 if (NH > 1) {       // positions 128 + 32 th ..: the values from memory (zero past the row's length there, Modules.py:87-93), L2 hits after the first step
-                    const float* vg = d.values + ((long)ab * T + 128 + 32 * th) * PM + 96 * gi + c;
+                    const float* vg = d.values + ((long)ab * T + 128 + 32 * th) * PM + CW * gi + c;
                     const int nt = T - (128 + 32 * th) < 32 ? (T - (128 + 32 * th) > 0 ? T - (128 + 32 * th) : 0) : 32;
 #pragma unroll 16
                     for (int t = 0; t < 32; ++t) acc += sm[S_A + 128 + 32 * th + t] * (t < nt ? vg[(long)t * PM] : 0.f);
                 }
-                sm[S_CO + th * 96 + c] = acc;
+                sm[S_CO + th * CW + c] = acc;
             }
             __syncthreads();
-            if (tid < 24) {
-                const pf32x4 val = (*reinterpret_cast<const pf32x4*>(sm + S_CO + 4 * tid) + *reinterpret_cast<const pf32x4*>(sm + S_CO + 96 + 4 * tid)) +
-                                   (*reinterpret_cast<const pf32x4*>(sm + S_CO + 192 + 4 * tid) + *reinterpret_cast<const pf32x4*>(sm + S_CO + 288 + 4 * tid));
-                const int qq = tid / 6, k4 = tid - qq * 6;
+            if (tid < CW / 4) {     // (LIVE: the entry point has filled the dead columns 512 .. 767 of in0 / pj with spk[b])
+                const pf32x4 val = (*reinterpret_cast<const pf32x4*>(sm + S_CO + 4 * tid) + *reinterpret_cast<const pf32x4*>(sm + S_CO + CW + 4 * tid)) +
+                                   (*reinterpret_cast<const pf32x4*>(sm + S_CO + 2 * CW + 4 * tid) + *reinterpret_cast<const pf32x4*>(sm + S_CO + 3 * CW + 4 * tid));
+                const int qq = tid / K4C, k4 = tid - qq * K4C;
                 const int rho = ((qq * 2 + (ab >> 4)) * 16) + (ab & 15);
-                const long o = gi * 3072L + rho * 24 + 4 * k4;
+                const long o = gi * (128L * CW / 4) + rho * (CW / 4) + 4 * k4;
                 xpublish_near(xr, (unsigned)((OFF_CTX + slot * XCTX + o) * 4), val, gen, near);
-                reinterpret_cast<pf32x4*>(d.in0 + (sB1 + ab) * (PM + PH) + 96 * gi)[tid] = val;
-                reinterpret_cast<pf32x4*>(d.pj + (sB + ab) * (PH + PM) + PH + 96 * gi)[tid] = val;
+                reinterpret_cast<pf32x4*>(d.in0 + (sB1 + ab) * (PM + PH) + CW * gi)[tid] = val;
+                reinterpret_cast<pf32x4*>(d.pj + (sB + ab) * (PH + PM) + PH + CW * gi)[tid] = val;
             }
         } else {
             PSTAMP(14);
-            if (tid < 24) {         // rows past the batch: zero context, so that the cells' waits complete
-                const int qq = tid / 6, k4 = tid - qq * 6;
+            if (tid < CW / 4) {     // rows past the batch: zero context, so that the cells' waits complete
+                const int qq = tid / K4C, k4 = tid - qq * K4C;
                 const int rho = ((qq * 2 + (ab >> 4)) * 16) + (ab & 15);
-                const long o = gi * 3072L + rho * 24 + 4 * k4;
+                const long o = gi * (128L * CW / 4) + rho * (CW / 4) + 4 * k4;
                 xpublish_near(xr, (unsigned)((OFF_CTX + slot * XCTX + o) * 4), (pf32x4){0.f, 0.f, 0.f, 0.f}, gen, near);
             }
         }
@@ -778,6 +833,11 @@ __global__ __launch_bounds__(PTH) void persist_fwd_kernel(PersistFwd d) {
 #undef ISSUE_PARTIALS
 #undef COMPLETE_PARTIALS
 #undef SUM_PARTIALS
+#undef S_RED8
+#undef ISSUE_PARTIALS8
+#undef COMPLETE_PARTIALS8
+#undef RED8
+#undef SUM_PARTIALS8
 }
 
 // ---- packers: the kernels in the order the lanes keep them (see the header comment)
@@ -812,22 +872,64 @@ __global__ void persist_pack_wq_kernel(const float* __restrict__ wq, float* __re
     wqpk[p] = wq[(long)(32 * (tid >> 4) + 4 * x4 + e) * PA + 16 * gi + (tid & 15)];
 }
 
+// ---- the constant context columns of a live-width launch (mstts_persist_desc.ctx_dead == 256): spk[b] = values[b, 0, 512 .. 767] (position 0 is below every length)
+constexpr int PDEAD = 256, PLIVE = PM - PDEAD;
+constexpr int CST_ROWS = 4;                       // batch rows per thread of persist_ctx_const_kernel
+// cst[b, col] = sum_k spk[b, k] w0f[512 + k, col]: one gate column per thread, FMAs over k = 0 .. 255 in that order (deterministic), accumulated in fp64 and
+// rounded once - a chain of 256 fp32 roundings would be the largest error term of the cell-0 gates (the matrix cores round once per 32 terms)
+__global__ __launch_bounds__(256) void persist_ctx_const_kernel(const float* __restrict__ values, const float* __restrict__ w0f, float* __restrict__ cst, int B, int T) {
+    __shared__ float spk[CST_ROWS][PDEAD];
+    const int b0 = blockIdx.y * CST_ROWS, col = blockIdx.x * 256 + threadIdx.x;
+#pragma unroll
+    for (int r = 0; r < CST_ROWS; ++r) spk[r][threadIdx.x] = b0 + r < B ? values[(long)(b0 + r) * T * PM + PLIVE + threadIdx.x] : 0.f;
+    __syncthreads();
+    double acc[CST_ROWS] = {0., 0., 0., 0.};
+    const float* w = w0f + (long)PLIVE * 4 * PH + col;
+#pragma unroll 8
+    for (int k = 0; k < PDEAD; ++k) {
+        const double x = (double)w[(long)k * 4 * PH];
+#pragma unroll
+        for (int r = 0; r < CST_ROWS; ++r) acc[r] = fma((double)spk[r][k], x, acc[r]);
+    }
+#pragma unroll
+    for (int r = 0; r < CST_ROWS; ++r)
+        if (b0 + r < B) cst[(long)(b0 + r) * 4 * PH + col] = (float)acc[r];
+}
+// the dead columns of what the loop leaves for the hoisted products: in0[s + 1, b, 512 .. 767] = pj[s, b, H + 512 .. H + 767] = spk[b], s = 0 .. S - 1
+__global__ void persist_fill_dead_kernel(const float* __restrict__ values, float* __restrict__ in0, float* __restrict__ pj, int B, int S, int T) {
+    const long n = (long)S * B * (PDEAD / 4);
+    for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < n; p += (long)gridDim.x * blockDim.x) {
+        const int c4 = (int)(p % (PDEAD / 4));
+        const long sb = p / (PDEAD / 4);
+        const int b = (int)(sb % B);
+        const pf32x4 v = *reinterpret_cast<const pf32x4*>(values + (long)b * T * PM + PLIVE + 4 * c4);
+        *reinterpret_cast<pf32x4*>(in0 + (sb + B) * (PM + PH) + PLIVE + 4 * c4) = v;
+        *reinterpret_cast<pf32x4*>(pj + sb * (PH + PM) + PH + PLIVE + 4 * c4) = v;
+    }
+}
+
 }  // namespace mstts
 using namespace mstts;
 
 // Every instantiation, once: 128 or 256 encoder positions (the 128-position one keeps the whole value slice in LDS); form 0 plain, 1 folded
 // prenet product, 2 bf16 recurrent products (folded); with or without the stage stamps.  fwd_index() is the row's place in the table.
+// Behind them the live-width pair (fp32, folded, 128 positions: FWD_LIVE + stamps); a build without the split products has the full width there.
 #define PFW_INST(P_, F_, T_, B16_) {persist_fwd_kernel<P_, F_, T_, B16_>, (int)(FL<T_>::S_FLOATS * 4)}
+#define PFW_LIVE(P_) {persist_fwd_kernel<P_, true, 128, false, FWD_LIVE_BUILT ? PLIVE : PM>, (int)(FL<128>::S_FLOATS * 4)}
 #define PFW_FORMS(T_)                                                                                                                  \
     PFW_INST(false, false, T_, false), PFW_INST(true, false, T_, false), PFW_INST(false, true, T_, false), PFW_INST(true, true, T_, false), \
     PFW_INST(false, true, T_, true), PFW_INST(true, true, T_, true)
-static const PersistInst<PersistFwd> FWD_TABLE[] = {PFW_FORMS(128), PFW_FORMS(256)};
+static const PersistInst<PersistFwd> FWD_TABLE[] = {PFW_FORMS(128), PFW_FORMS(256), PFW_LIVE(false), PFW_LIVE(true)};
 #undef PFW_FORMS
+#undef PFW_LIVE
 #undef PFW_INST
 constexpr int fwd_index(bool t256, int form, bool stamps) { return (t256 * 3 + form) * 2 + stamps; }
-static_assert(sizeof(FWD_TABLE) / sizeof(FWD_TABLE[0]) == fwd_index(true, 2, true) + 1, "one table row per (positions, form, stamps)");
+constexpr int FWD_LIVE = fwd_index(true, 2, true) + 1;
+static_assert(sizeof(FWD_TABLE) / sizeof(FWD_TABLE[0]) == FWD_LIVE + 2, "one table row per (positions, form, stamps), then the live-width pair");
 
-extern "C" int64_t mstts_persist_fwd_ws_bytes(void) { return XCH_FLOATS * 4; }
+// (behind the rings: the [32, 4H] constant gate term of a live-width launch)
+constexpr long XCST_FLOATS = (long)PROWS * 4 * PH;
+extern "C" int64_t mstts_persist_fwd_ws_bytes(void) { return (XCH_FLOATS + XCST_FLOATS) * 4; }
 extern "C" int64_t mstts_persist_pack_floats(int32_t which) { return which == 0 ? 256L * 8 * 64 * 64 : which == 1 ? 256L * 8 * 64 * 64 : 8L * 64 * 256; }
 
 /* 1 when the persistent loop can run this shape on the current device: reference widths, at most 32 rows and 256 encoder
@@ -861,6 +963,10 @@ extern "C" int mstts_decoder_train_fwd_persistent(const mstts_decoder_train_desc
     MSTTS_REQUIRE(d->lsa.keys && d->lsa.values && d->lsa.loc_k && d->lsa.loc_b && d->lsa.score_w && d->lsa.score_b, MSTTS_ERR_SHAPE,
                   "decoder_train_fwd_persistent: attention constants missing");
     MSTTS_REQUIRE(aligned16(p->xch) && aligned16(d->in0) && aligned16(d->pj) && (M + H) % 4 == 0, MSTTS_ERR_ALIGN, "decoder_train_fwd_persistent: 16-byte alignment");
+    MSTTS_REQUIRE(p->ctx_dead == 0 || p->ctx_dead == PDEAD, MSTTS_ERR_SHAPE, "decoder_train_fwd_persistent: ctx_dead must be 0 or 256");
+    // the live-width instantiation exists for fp32 / folded / at most 128 positions; every other call computes all 768 columns, which is always correct
+    const bool live = p->ctx_dead == PDEAD && FWD_LIVE_BUILT && fold && !p->recurrent_bf16 && T <= 128;
+    MSTTS_REQUIRE(!live || (d->w0f && aligned16(d->lsa.values)), MSTTS_ERR_SHAPE, "decoder_train_fwd_persistent: ctx_dead needs the folded cell-0 kernel w0f and 16-byte aligned values");
     hipStream_t hs = (hipStream_t)s;
     // step-0 state (zero context / hidden / cell states / cumulative alignment), armed rings, cleared control words
     hipError_t e = hipMemsetAsync(d->in0, 0, B * (M + H) * sizeof(float), hs);
@@ -882,7 +988,16 @@ extern "C" int mstts_decoder_train_fwd_persistent(const mstts_decoder_train_desc
     a.opk = p->opk; a.xch = p->xch; a.ctrl = p->ctrl; a.stamps = (unsigned long long*)p->stamps;
     persist_knobs(a, p->selftest_fail_step, p->near_xcd);
     MSTTS_REQUIRE(!p->recurrent_bf16 || fold, MSTTS_ERR_SHAPE, "decoder_train_fwd_persistent: the bf16 form needs the folded prenet product (pre / b0)");
-    const PersistInst<PersistFwd>& k = FWD_TABLE[fwd_index(T > 128, p->recurrent_bf16 ? 2 : fold ? 1 : 0, p->stamps != nullptr)];
+    a.cst = p->xch + XCH_FLOATS;
+    if (live && S * B > 0) {
+        // in front of the loop, on its stream: the constant columns' share of the cell-0 gates, and the dead columns of in0 / pj that the hoisted
+        // products behind the loop read (the loop itself writes only the 512 live ones)
+        hipLaunchKernelGGL(persist_ctx_const_kernel, dim3(4 * PH / 256, (unsigned)((B + CST_ROWS - 1) / CST_ROWS)), dim3(256), 0, hs, a.values, d->w0f, p->xch + XCH_FLOATS, (int)B, (int)T);
+        MSTTS_CHECK_LAUNCH("persist_ctx_const");
+        hipLaunchKernelGGL(persist_fill_dead_kernel, dim3((unsigned)std::min<long>((S * B * (PDEAD / 4) + 255) / 256, 4096)), dim3(256), 0, hs, a.values, d->in0, d->pj, (int)B, (int)S, (int)T);
+        MSTTS_CHECK_LAUNCH("persist_fill_dead");
+    }
+    const PersistInst<PersistFwd>& k = FWD_TABLE[live ? FWD_LIVE + (p->stamps != nullptr) : fwd_index(T > 128, p->recurrent_bf16 ? 2 : fold ? 1 : 0, p->stamps != nullptr)];
     hipLaunchKernelGGL(k.kernel, dim3(PWG), dim3(PTH), (size_t)k.lds_bytes, hs, a);
     MSTTS_CHECK_LAUNCH("persist_fwd");
     return MSTTS_OK;

@@ -139,6 +139,21 @@ __device__ __forceinline__ bool slice_complete_split3_k6(__amdgpu_buffer_rsrc_t 
     if (tid + PTH < 128 * 6) { const int p = tid + PTH, rho = p / 6; sp3_put_rk(stg, rho, p - rho * 6, v[1]); }
     return ok;
 }
+// a 128 x 16 slice (K4 = 4 pieces per row: the LIVE context rows, persist.hip's MC = 512) into octets 0 .. 1 of the planes: 512 pieces, ONE per thread
+// (the request rides in element 0 of the caller's two-piece arrays)
+__device__ __forceinline__ void slice_issue_k4(__amdgpu_buffer_rsrc_t xr, long slice_float_off, int tid, unsigned (&off)[2], pf32x4 (&v)[2]) {
+    unsigned o1[1] = {(unsigned)(slice_float_off * 4 + 16 * tid)};
+    pf32x4 v1[1];
+    issue<1>(xr, o1, v1);
+    off[0] = o1[0]; v[0] = v1[0];
+}
+__device__ __forceinline__ bool slice_complete_split3_k4(__amdgpu_buffer_rsrc_t xr, __bf16* stg, int tid, const unsigned (&off)[2], pf32x4 (&v)[2], const unsigned* ctrl, unsigned gen) {
+    const unsigned gens[1] = {gen}, o1[1] = {off[0]};
+    pf32x4 v1[1] = {v[0]};
+    const bool ok = complete<1>(xr, o1, v1, ctrl, gens);
+    sp3_put_rk(stg, tid >> 2, tid & 3, v1[0]);
+    return ok;
+}
 // acc[t] += W[k-steps 8 JA .. 8 JB) . X[t] with wsp[plane][octet] and the staged planes: hi.hi + mid.hi + hi.mid + mid.mid + lo.hi + hi.lo
 template <int JA = 0, int JB = 4>
 __device__ __forceinline__ void mfma_part_split3(const pbf16x8 (&wsp)[3][4], const __bf16* sx, int lane, pf32x4 (&acc)[2]) {

@@ -493,6 +493,8 @@ class TrainEngine(Engine):
         w.job_flag, w.job_flag_host = cv.take(1, dtype=torch.int32), self._pin("job_flag_host", 1)
         w.dec, w.dec_b = lib.DecoderTrain(), lib.DecoderTrainBwd()
         w.dec_b.ctx_dead = self.ctx_dead
+        if w.persist:                        # (the forward launch picks its live-width kernel where it has one - fp32, at most 128 tokens - and fills the dead columns itself)
+            w.pdesc.ctx_dead = self.ctx_dead
         if w.persist_bwd:
             w.pdesc_b.ctx_dead = self.ctx_dead
         w.zero_on_activate, w.extent_bytes, w.arena_generation = cv.zero, cv.off, self._arena.generation
