@@ -111,6 +111,27 @@ int mstts_gemm_bf16_autocut(int32_t on);
 /* 1 (default): contractions large enough to fill the chip with 256 x 256 tiles run on the big-tile kernel (csrc/gemm_bf16.hip: half the operand
  * bytes per flop of the 128 x 128 kernel); 0: the 128 x 128 kernel for everything (A/B runs, tests).  Process-wide. */
 int mstts_gemm_bf16_big(int32_t on);
+/* The contraction on operands that already ARE bf16 in memory (csrc/gemm_bf16_res.hip): C[M,N] (+)= A . B^T + bias, fp32 accumulation on
+ * v_mfma_f32_32x32x16_bf16, fp32 C and bias.  Nothing is rounded: every bf16 x bf16 product is exact in fp32, only the accumulation rounds.
+ *   A    : bf16 [M, lda], k-contiguous: A(m,k) = A[m*lda + k];
+ *   B    : bf16 [N, ldb], k-contiguous as well (the weight stored transposed): B(k,n) = B[n*ldb + k];
+ *   C    : fp32 [M, ldc]; bias: fp32 [N] or null; accumulate: C += ...; split_k > 1: the pieces are added with atomics onto C (pre-zeroed, or
+ *          with accumulate the existing values; bias from piece 0) and honoured exactly - the library makes no K-cut of its own;
+ *   win_T, win_C, win_pad, win_dil: as in mstts_gemm_desc at trans_a = 0 (A is the implicit im2col view of X[rows, win_C]; a final sequence
+ *          shorter than win_T reads zero past row M).
+ * No trans_*, no batch, no activation.  An output element is one fixed-order sum over K (per split piece) whatever M, N and the grid are.
+ * Checked before any launch: K, lda, ldb and (with a window) win_C multiples of 8, A and B 16-byte aligned, C / bias 4-byte aligned
+ * (MSTTS_ERR_ALIGN); with a window lda == win_C, else lda >= K; ldb >= K; ldc >= N (MSTTS_ERR_SHAPE).  mstts_gemm_bf16_res_supported is
+ * host-only (callable without a device): 1 when the shape arguments pass those checks, else 0. */
+typedef struct {
+    const void* A; const void* B; float* C; const float* bias;
+    int64_t M, N, K;
+    int64_t lda, ldb, ldc;
+    int32_t accumulate, split_k;
+    int32_t win_T, win_C, win_pad, win_dil;
+} mstts_gemm_res_desc;
+int mstts_gemm_bf16_res(const mstts_gemm_res_desc* d, mstts_stream_t s);
+int mstts_gemm_bf16_res_supported(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int32_t win_T, int32_t win_C);
 
 /* ---- randomness: Philox4x32-10 keep-masks (replaces tf.random_uniform inside
  * tf.layers.dropout, Modules.py:41-45,137-141,248-253, and ZoneoutLSTMCell.py:266-271) ---- */
@@ -591,6 +612,16 @@ int mstts_wg_res_skip(const float* z, const float* rs, float* x, float* out, int
 int mstts_wg_coupling_inv(const float* audio, const float* log_s_b, const float* w_inv, const float* early, float sigma, float* out,
                           int64_t rows, int64_t c, int64_t c_early, mstts_stream_t s);
 int mstts_philox_normal(float* out, int64_t n, uint64_t seed, uint32_t stream_id, float sigma, mstts_stream_t s);
+/* Glue of the vocoder's config-3 mode (WaveGlowEngine.infer(arith="bf16"): bf16 operands in every contraction, everything else fp32).  The
+ * activations that feed a big product are stored as bf16 by the kernel that produces them, so mstts_gemm_bf16_res reads them as they are.
+ * All need 16-byte aligned pointers and the element count / C a multiple of 4 (MSTTS_ERR_ALIGN / MSTTS_ERR_SHAPE before any launch).
+ *  round_bf16       : dst[i] = bf16(src[i]), round-to-nearest-even (dst: n bf16)
+ *  wg_gate_bf16     : z as mstts_wg_gate writes it (one device function: bit-equal on the same input), and zb = bf16(z)
+ *  wg_res_skip_bf16 : out as mstts_wg_res_skip updates it; !last: xb = bf16(z + rs[:, :C]) - the fp32 sum, then rounded; no fp32 x is
+ *                     written (its only reader is the next layer's convolution, which reads xb) */
+int mstts_round_bf16(const float* src, void* dst, int64_t n, mstts_stream_t s);
+int mstts_wg_gate_bf16(const float* a, int64_t lda, float* z, void* zb, int64_t rows, int64_t C, mstts_stream_t s);
+int mstts_wg_res_skip_bf16(const float* z, const float* rs, void* xb, float* out, int64_t rows, int64_t C, int32_t last, int32_t first, mstts_stream_t s);
 
 /* ---- WaveGlow vocoder, training direction (WaveGlow/WaveGlow.py:37-85; Modules.py:9-34,135-175,210-352,373-385; Inv1x1.py:9-41).  The
  * contractions run on mstts_gemm_f32; these are the remaining pieces, fp32, activations [rows, channels] row-major.

@@ -7,6 +7,8 @@
 //   res_skip      : x = z + rs[:, :C] ; out (+)= rs[:, C:]   (last layer: out (+)= rs)   (:293-311; the residual is added to
 //                   the GATED activation - the reference's quirk)
 //   coupling_inv  : a1 = (a1 - b) * exp(-log_s) ; audio = [a0 | a1] . inv(W) ; optional early-noise prepend (:239-249,354-369)
+//   round_bf16 / gate_bf16 / res_skip_bf16 : the glue of the config-3 mode (bf16 operands in every contraction): they also store the bf16 copy
+//                   the next contraction reads (mstts_gemm_bf16_res), rounded to nearest even from the fp32 value
 //   philox_normal : N(0, sigma^2) draws (Box-Muller on Philox4x32-10 words) for tf.random.normal (:189-193,362-366)
 #include "common.h"
 
@@ -32,11 +34,14 @@ __global__ void wg_overlap_add_kernel(const float* __restrict__ Y, const float* 
     }
 }
 
+// the gate of one element: wg_gate_kernel and wg_gate_bf16_kernel both go through this one function, so they agree bit for bit on the same pre-activation
+__device__ __forceinline__ float wg_gate_value(float t, float s) { return tanhf(t) * sigmoid_acc(s); }
+
 __global__ void wg_gate_kernel(const float* __restrict__ a, long lda, float* __restrict__ z, long rows, int C) {
     const long n = rows * C;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
         const long r = i / C; const int c = (int)(i - r * C);
-        z[i] = tanhf(a[r * lda + c]) * sigmoid_acc(a[r * lda + C + c]);
+        z[i] = wg_gate_value(a[r * lda + c], a[r * lda + C + c]);
     }
 }
 
@@ -64,6 +69,47 @@ __global__ void wg_res_skip_kernel(const float* __restrict__ z, const float* __r
         if (last) skip = rs[r * C + c];
         else { x[i] = z[i] + rs[r * 2 * C + c]; skip = rs[r * 2 * C + C + c]; }
         out[i] = first ? skip : out[i] + skip;
+    }
+}
+
+// ---- config-3 mode (bf16 operands in every contraction): the glue kernels also store the bf16 copy the next contraction reads -------------
+typedef __bf16 wg_bf16x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ wg_bf16x4 wg_round4(float4 v) { return (wg_bf16x4){(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w}; }      // RNE
+
+__global__ void round_bf16_kernel(const float* __restrict__ src, __bf16* __restrict__ dst, long n4) {
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x)
+        *reinterpret_cast<wg_bf16x4*>(dst + 4 * i) = wg_round4(*reinterpret_cast<const float4*>(src + 4 * i));
+}
+
+__global__ void wg_gate_bf16_kernel(const float* __restrict__ a, long lda, float* __restrict__ z, __bf16* __restrict__ zb, long rows, int C) {
+    const long n4 = rows * (C >> 2);
+    const int c4n = C >> 2;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const long r = i / c4n; const int c = (int)(i - r * c4n) * 4;
+        const float4 at = *reinterpret_cast<const float4*>(a + r * lda + c), as = *reinterpret_cast<const float4*>(a + r * lda + C + c);
+        float4 o;
+        o.x = wg_gate_value(at.x, as.x); o.y = wg_gate_value(at.y, as.y); o.z = wg_gate_value(at.z, as.z); o.w = wg_gate_value(at.w, as.w);
+        *reinterpret_cast<float4*>(z + r * C + c) = o;
+        *reinterpret_cast<wg_bf16x4*>(zb + r * C + c) = wg_round4(o);
+    }
+}
+
+__global__ void wg_res_skip_bf16_kernel(const float* __restrict__ z, const float* __restrict__ rs, __bf16* __restrict__ xb, float* __restrict__ out,
+                                        long rows, int C, int last, int first) {
+    const long n4 = rows * (C >> 2);
+    const int c4n = C >> 2;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const long r = i / c4n; const int c = (int)(i - r * c4n) * 4;
+        float4 skip;
+        if (last) skip = *reinterpret_cast<const float4*>(rs + r * C + c);
+        else {
+            const float4 zv = *reinterpret_cast<const float4*>(z + r * C + c), res = *reinterpret_cast<const float4*>(rs + r * 2 * C + c);
+            *reinterpret_cast<wg_bf16x4*>(xb + r * C + c) = wg_round4(make_float4(zv.x + res.x, zv.y + res.y, zv.z + res.z, zv.w + res.w));
+            skip = *reinterpret_cast<const float4*>(rs + r * 2 * C + C + c);
+        }
+        float4* o = reinterpret_cast<float4*>(out + r * C + c);
+        if (!first) { const float4 p = *o; skip.x = p.x + skip.x; skip.y = p.y + skip.y; skip.z = p.z + skip.z; skip.w = p.w + skip.w; }
+        *o = skip;
     }
 }
 
@@ -139,6 +185,31 @@ extern "C" int mstts_wg_res_skip(const float* z, const float* rs, float* x, floa
     if (rows == 0) return MSTTS_OK;
     hipLaunchKernelGGL(wg_res_skip_kernel, dim3(wg_grid(rows * C)), dim3(256), 0, ST(s), z, rs, x, out, (long)rows, (int)C, (int)last, (int)first);
     MSTTS_CHECK_LAUNCH("wg_res_skip");
+    return MSTTS_OK;
+}
+extern "C" int mstts_round_bf16(const float* src, void* dst, int64_t n, mstts_stream_t s) {
+    MSTTS_REQUIRE(n >= 0 && n % 4 == 0, MSTTS_ERR_SHAPE, "round_bf16: the element count must be a multiple of 4");
+    if (n == 0) return MSTTS_OK;
+    MSTTS_REQUIRE(src && dst, MSTTS_ERR_SHAPE, "round_bf16: null pointer");
+    MSTTS_REQUIRE(aligned16(src) && aligned16(dst), MSTTS_ERR_ALIGN, "round_bf16: 16-byte aligned operands required");
+    hipLaunchKernelGGL(round_bf16_kernel, dim3(wg_grid(n / 4)), dim3(256), 0, ST(s), src, (__bf16*)dst, (long)(n / 4));
+    MSTTS_CHECK_LAUNCH("round_bf16");
+    return MSTTS_OK;
+}
+extern "C" int mstts_wg_gate_bf16(const float* a, int64_t lda, float* z, void* zb, int64_t rows, int64_t C, mstts_stream_t s) {
+    MSTTS_REQUIRE(a && z && zb && rows >= 0 && C >= 4 && C % 4 == 0 && lda >= 2 * C && lda % 4 == 0, MSTTS_ERR_SHAPE, "wg_gate_bf16: bad arguments (C and lda multiples of 4)");
+    MSTTS_REQUIRE(aligned16(a) && aligned16(z) && aligned16(zb), MSTTS_ERR_ALIGN, "wg_gate_bf16: 16-byte aligned operands required");
+    if (rows == 0) return MSTTS_OK;
+    hipLaunchKernelGGL(wg_gate_bf16_kernel, dim3(wg_grid(rows * C / 4)), dim3(256), 0, ST(s), a, (long)lda, z, (__bf16*)zb, (long)rows, (int)C);
+    MSTTS_CHECK_LAUNCH("wg_gate_bf16");
+    return MSTTS_OK;
+}
+extern "C" int mstts_wg_res_skip_bf16(const float* z, const float* rs, void* xb, float* out, int64_t rows, int64_t C, int32_t last, int32_t first, mstts_stream_t s) {
+    MSTTS_REQUIRE(z && rs && out && (last || xb) && rows >= 0 && C >= 4 && C % 4 == 0, MSTTS_ERR_SHAPE, "wg_res_skip_bf16: bad arguments (C a multiple of 4)");
+    MSTTS_REQUIRE(aligned16(z) && aligned16(rs) && aligned16(out) && aligned16(xb), MSTTS_ERR_ALIGN, "wg_res_skip_bf16: 16-byte aligned operands required");
+    if (rows == 0) return MSTTS_OK;
+    hipLaunchKernelGGL(wg_res_skip_bf16_kernel, dim3(wg_grid(rows * C / 4)), dim3(256), 0, ST(s), z, rs, (__bf16*)xb, out, (long)rows, (int)C, (int)last, (int)first);
+    MSTTS_CHECK_LAUNCH("wg_res_skip_bf16");
     return MSTTS_OK;
 }
 extern "C" int mstts_wg_coupling_inv(const float* audio, const float* log_s_b, const float* w_inv, const float* early, float sigma, float* out,

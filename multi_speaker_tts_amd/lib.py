@@ -29,6 +29,12 @@ class GemmDesc(C.Structure):
                 ("batch", i64), ("stride_a", i64), ("stride_b", i64), ("stride_c", i64), ("alpha", f32), ("win_dil", i32)]
 
 
+class GemmResDesc(C.Structure):
+    _fields_ = [("A", vp), ("B", vp), ("C", vp), ("bias", vp),
+                ("M", i64), ("N", i64), ("K", i64), ("lda", i64), ("ldb", i64), ("ldc", i64),
+                ("accumulate", i32), ("split_k", i32), ("win_T", i32), ("win_C", i32), ("win_pad", i32), ("win_dil", i32)]
+
+
 class LstmPointFwd(C.Structure):
     _fields_ = [("B", i64), ("H", i64), ("gates_h", vp), ("gates_parts", i32), ("gates_pstride", i64), ("xw", vp), ("xw_sb", i64), ("xw_st", i64), ("bias", vp),
                 ("c_prev", vp), ("h_prev", vp), ("h_prev_ld", i64), ("zc", vp), ("zh", vp), ("zoneout", f32),
@@ -152,6 +158,8 @@ SIGNATURES = {
     "mstts_persist_status": (i32, [vp, i32, vp, i32, vp, vp]),
     "mstts_gemm_bf16": (i32, [P(GemmDesc), vp]),
     "mstts_gemm_bf16_big": (i32, [i32]),
+    "mstts_gemm_bf16_res": (i32, [P(GemmResDesc), vp]),
+    "mstts_gemm_bf16_res_supported": (i32, [i64, i64, i64, i64, i64, i32, i32]),
     "mstts_philox_keep_mask": (i32, [vp, i64, u64, u32, f32, vp]),
     "mstts_philox_keep_mask_rows": (i32, [vp, i64, i64, i64, u64, u32, u64, f32, vp]),
     "mstts_embedding_fwd": (i32, [vp, vp, vp, i64, i64, i64, vp]),
@@ -254,6 +262,9 @@ SIGNATURES = {
     "mstts_wg_res_skip": (i32, [vp, vp, vp, vp, i64, i64, i32, i32, vp]),
     "mstts_wg_coupling_inv": (i32, [vp, vp, vp, vp, f32, vp, i64, i64, i64, vp]),
     "mstts_philox_normal": (i32, [vp, i64, u64, u32, f32, vp]),
+    "mstts_round_bf16": (i32, [vp, vp, i64, vp]),
+    "mstts_wg_gate_bf16": (i32, [vp, i64, vp, vp, i64, i64, vp]),
+    "mstts_wg_res_skip_bf16": (i32, [vp, vp, vp, vp, i64, i64, i32, i32, vp]),
     "mstts_wg_weight_norm_fwd": (i32, [vp, i64, i64, vp]),
     "mstts_wg_weight_norm_bwd": (i32, [vp, i64, i64, vp]),
     "mstts_wg_coupling_fwd": (i32, [vp, vp, vp, vp, i64, i64, i64, vp, i64, i64, vp]),
@@ -494,3 +505,20 @@ def gemm(A, B, Cm, M, N, K, lda, ldb, ldc, bias=None, trans_a=False, trans_b=Fal
     d.batch, d.stride_a, d.stride_b, d.stride_c = batch, strides[0], strides[1], strides[2]
     d.alpha = alpha
     call("mstts_gemm_bf16" if bf16 else "mstts_gemm_f32", C.byref(d))
+
+
+def gemm_res_supported(M, N, K, lda, ldb, win=None):
+    """Whether mstts_gemm_bf16_res takes the shape (host-only: needs no device)."""
+    return bool(load().mstts_gemm_bf16_res_supported(M, N, K, lda, ldb, win[0] if win else 0, win[1] if win else 0))
+
+
+def gemm_res(A, B, Cm, M, N, K, lda, ldb, ldc, bias=None, accumulate=False, split_k=1, win=None, a_off=0, b_off=0, c_off=0, bias_off=0):
+    """Thin wrapper over mstts_gemm_bf16_res: A bf16 [M, lda] and B bf16 [N, ldb], both k-contiguous; Cm / bias fp32.  win = (T, C, pad, dil)."""
+    d = GemmResDesc()
+    d.A, d.B, d.C, d.bias = ptr(A, a_off), ptr(B, b_off), ptr(Cm, c_off), ptr(bias, bias_off)
+    d.M, d.N, d.K, d.lda, d.ldb, d.ldc = M, N, K, lda, ldb, ldc
+    d.accumulate, d.split_k = int(accumulate), split_k
+    if win is not None:
+        d.win_T, d.win_C, d.win_pad = win[:3]
+        d.win_dil = win[3] if len(win) > 3 else 1
+    call("mstts_gemm_bf16_res", C.byref(d))

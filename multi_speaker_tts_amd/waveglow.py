@@ -8,6 +8,8 @@ Python owns buffers and the schedule; every arithmetic step is a libmstts_hip.so
     mstts_wg_gate, the res/skip 1x1 GEMM, mstts_wg_res_skip; the zero-initialised output conv; mstts_wg_coupling_inv
     (affine inverse + inverse 1x1 conv + early-latent re-injection),
   * tf.random.normal -> mstts_philox_normal (or injected arrays, which is what the parity tests use).
+infer(arith="bf16") is the same schedule in BASELINE config 3 arithmetic: bf16 operands in every contraction, fp32 accumulate, the three big
+products on operands that are bf16 in memory (mstts_gemm_bf16_res; WaveGlowEngine._infer_bf16).  The default, "f32", is the path above.
 Weight normalisation (g * v / ||v||, WaveGlow/Modules.py:9-34) and the matrix inverses of the 1x1 kernels are
 constants of a checkpoint and are folded once at load time on the host.
 """
@@ -21,9 +23,20 @@ import numpy as np
 import torch
 
 from . import lib
-from .lib import call, gemm, ptr
+from .lib import call, gemm, gemm_res, gemm_res_supported, ptr
 
 P_WG = "waveglow/"
+ARITHS = ("f32", "bf16")
+
+
+def resolve_arith(arith, default=None):
+    """The vocoder's arithmetic: the argument, else the engine's default, else MSTTS_WG_ARITH, else "f32"."""
+    for a in (arith, default, os.environ.get("MSTTS_WG_ARITH") or None):
+        if a is not None:
+            if a not in ARITHS:
+                raise ValueError("WaveGlow arithmetic must be one of %s, not %r" % (ARITHS, a))
+            return a
+    return "f32"
 
 
 @dataclass
@@ -124,8 +137,11 @@ def _conv_two_pieces(rows, n_out):
 
 
 class WaveGlowEngine:
-    def __init__(self, dims: WGDims = None, device="cuda", values=None, seed=1234):
+    def __init__(self, dims: WGDims = None, device="cuda", values=None, seed=1234, arith=None):
         self.d = dims or WGDims()
+        if arith is not None:
+            resolve_arith(arith)
+        self.arith = arith         # default of infer(arith=None): "f32" | "bf16" (config 3: bf16 operands in every contraction) | None = MSTTS_WG_ARITH, else "f32"
         self.device = torch.device(device)
         self.seed = seed
         lib.load()
@@ -144,6 +160,7 @@ class WaveGlowEngine:
 
     def load(self, v):
         d = self.d
+        self._packed = None
         # conv2d_transpose kernel [1,K,Cout,Cin] -> [Cin, K*Cout]: one GEMM gives every tap product of a frame
         wt = np.asarray(v[P_WG + "conv2d_transpose/kernel"], np.float64)[0]
         self.up_w = self._dev(wt.transpose(2, 0, 1).reshape(d.n_mel, d.up_k * d.n_mel))
@@ -166,6 +183,19 @@ class WaveGlowEngine:
             F["w_inv"] = self._dev(np.linalg.inv(np.asarray(v[P_WG + "affine_coupling_layer_%d/invertible_1x1/kernel" % f], np.float64)))
             self.flow.append(F)
 
+    def packed(self):
+        """The bf16 mode's resident weights: the folded fp32 tensors rounded once (round-to-nearest-even) and stored transposed, [N, K]
+        k-contiguous, as mstts_gemm_bf16_res reads them.  Built on first use, cached per load()."""
+        if self._packed is None:
+            t = lambda w: w.t().contiguous().to(torch.bfloat16)
+            self._packed = [{"w_cond": t(F["w_cond"]), "w_in": [t(w) for w in F["w_in"]], "w_res": [t(w) for w in F["w_res"]]} for F in self.flow]
+        return self._packed
+
+    def _b(self, *shape):
+        t = torch.empty(shape, dtype=torch.bfloat16, device=self.device)
+        self._keep.append(t)
+        return t
+
     def _f(self, *shape):
         n = int(np.prod(shape))
         t = torch.empty((n + 3) // 4 * 4, dtype=torch.float32, device=self.device)[:n].view(shape)
@@ -173,10 +203,8 @@ class WaveGlowEngine:
         return t
 
     # ------------------------------------------------------------------ Glow_Inference
-    @lib.deterministic_gemm()          # bit-reproducible per latent seed: no K-cuts with atomics inside the flow's contractions
-    def infer(self, mel, noise=None, seed=None, sigma=1.0):
-        """mel [N, T, n_mel] (tensor or array) -> wav tensor [N, (T-1)*stride + kernel].  noise: {"z": [N,L/G,z_channels],
-        "early_<flow>": [N,L/G,early_size]} to inject the latents, else Philox normals of `seed`."""
+    def _begin(self, mel):
+        """Start of a call: drops the previous call's buffers; mel as a contiguous fp32 device tensor [N, T, n_mel] and the upsampled length."""
         d = self.d
         self._keep = []
         mel = (mel if torch.is_tensor(mel) else torch.from_numpy(np.asarray(mel))).to(self.device, torch.float32).contiguous()
@@ -185,6 +213,27 @@ class WaveGlowEngine:
         L = (T - 1) * d.up_stride + d.up_k
         if L % d.groups:
             raise ValueError("upsampled length %d is not a multiple of Groups=%d" % (L, d.groups))
+        return mel, N, T, C, L
+
+    def _latent(self, noise, seed, rows, key, width, stream, scale):
+        """[rows, width] latent: the injected noise[key], else Philox normals of (seed, stream)."""
+        t = self._f(rows, width)
+        if noise is not None:
+            t.copy_((noise[key] if torch.is_tensor(noise[key]) else torch.from_numpy(np.asarray(noise[key]))).to(self.device, torch.float32).reshape(rows, width))
+        else:
+            call("mstts_philox_normal", ptr(t), rows * width, seed, stream, scale)
+        return t
+
+    @lib.deterministic_gemm()          # bit-reproducible per latent seed: no K-cuts with atomics inside the flow's contractions
+    def infer(self, mel, noise=None, seed=None, sigma=1.0, arith=None, stages=None):
+        """mel [N, T, n_mel] (tensor or array) -> wav tensor [N, (T-1)*stride + kernel].  noise: {"z": [N,L/G,z_channels],
+        "early_<flow>": [N,L/G,early_size]} to inject the latents, else Philox normals of `seed`.
+        arith: "f32" | "bf16" (see _infer_bf16; resolution: resolve_arith).  stages: a dict the bf16 mode fills with clones of its
+        intermediate tensors (a test hook, see _infer_bf16)."""
+        if resolve_arith(arith, self.arith) == "bf16":
+            return self._infer_bf16(mel, noise, seed, sigma, stages)
+        d = self.d
+        mel, N, T, C, L = self._begin(mel)
         Lg, rows, cm, ch = L // d.groups, N * (L // d.groups), d.groups * C, d.ch
         # Upsample_Mel: every tap product of every frame, then overlap-add (+ bias)
         Y = self._f(N * T, d.up_k * C)
@@ -193,14 +242,7 @@ class WaveGlowEngine:
         call("mstts_wg_overlap_add", ptr(Y), ptr(self.up_b), ptr(up), N, T, d.up_k, d.up_stride, C)
         melg = up                                     # viewed as [rows, G*C]: contiguous regrouping (:180-187)
         seed = self.seed if seed is None else seed
-
-        def latent(key, width, stream, scale):
-            t = self._f(rows, width)
-            if noise is not None:
-                t.copy_((noise[key] if torch.is_tensor(noise[key]) else torch.from_numpy(np.asarray(noise[key]))).to(self.device, torch.float32).reshape(rows, width))
-            else:
-                call("mstts_philox_normal", ptr(t), rows * width, seed, stream, scale)
-            return t
+        latent = lambda key, width, stream, scale: self._latent(noise, seed, rows, key, width, stream, scale)
         audio = latent("z", d.z_channels, 70, 1.0)
         x, z, out = self._f(rows, ch), self._f(rows, ch), self._f(rows, ch)
         cond, rs = self._f(rows, d.layers * 2 * ch), self._f(rows, 2 * ch)
@@ -246,6 +288,97 @@ class WaveGlowEngine:
         return audio.view(N, Lg * d.groups)
 
 
+    def _infer_bf16(self, mel, noise, seed, sigma, stages):
+        """BASELINE config 3 for the vocoder: every contraction multiplies operands rounded to bf16 (round-to-nearest-even) and accumulates in
+        fp32; biases, the gate, the residual stream, the skip sum, the coupling inverse (with w_inv), latents and overlap-add stay fp32.
+        The rounded activations are STORED tensors - melg_b = bf(melg), zb = bf(z), xb_{i+1} = bf(fl32(z_i + res_i)), xb_0 = bf(x) - written
+        by the glue kernels (mstts_round_bf16, mstts_wg_gate_bf16, mstts_wg_res_skip_bf16), and the three big products (conditioning, dilated
+        convolution, res/skip: 204 of a call's launches) read them and the packed weights as they are (mstts_gemm_bf16_res).  The dilated
+        convolution is always one piece accumulated onto its band of `cond`; conv_two_pieces and split_in are fp32-mode features.  The
+        upsampler, the initial conv (K <= 4) and the output conv (N <= 8) have fp32 operands anyway and run on mstts_gemm_bf16.
+        A product mstts_gemm_bf16_res does not take (ch % 8 != 0), and all three with MSTTS_WG_BF16_RESIDENT=0 (the A/B leg), falls back to
+        mstts_gemm_bf16 on the fp32 buffers: same rounding sites (the kernel rounds the same fp32 values), same contract.  One call is
+        bit-reproducible per seed.  `stages`, when given, receives "resident" (which products ran resident), per flow f a dict stages[f]
+        of melg_b, audio (the flow's input), x (the initial conv's output), out (the skip sum), ls_b and next (the coupling inverse's
+        output), and per layer stages[(f, i)] = pre (the layer's band of cond after the conv accumulated), z, zb, rs, xb (as consumed)."""
+        d = self.d
+        mel, N, T, C, L = self._begin(mel)
+        Lg, rows, cm, ch = L // d.groups, N * (L // d.groups), d.groups * C, d.ch
+        ldc, pad = d.layers * 2 * ch, (d.k - 1) // 2
+        resident = os.environ.get("MSTTS_WG_BF16_RESIDENT", "1") != "0"
+        res_cond = resident and gemm_res_supported(rows, ldc, cm, cm, cm)
+        res_conv = resident and gemm_res_supported(rows, 2 * ch, d.k * ch, ch, d.k * ch, win=(Lg, ch))
+        res_rs = resident and gemm_res_supported(rows, 2 * ch, ch, ch, ch)
+        Wp = self.packed() if (res_cond or res_conv or res_rs) else None
+        bf = lambda t: t.to(torch.bfloat16)
+        keep = stages is not None
+        if keep:
+            stages["resident"] = {"cond": res_cond, "conv": res_conv, "res_skip": res_rs}
+        Y = self._f(N * T, d.up_k * C)
+        gemm(mel, self.up_w, Y, N * T, d.up_k * C, C, C, d.up_k * C, d.up_k * C, bf16=True)
+        melg = self._f(N, L, C)                         # viewed as [rows, G*C]
+        call("mstts_wg_overlap_add", ptr(Y), ptr(self.up_b), ptr(melg), N, T, d.up_k, d.up_stride, C)
+        melg_b = None
+        if res_cond:
+            melg_b = self._b(rows, cm)
+            call("mstts_round_bf16", ptr(melg), ptr(melg_b), rows * cm)
+        seed = self.seed if seed is None else seed
+        latent = lambda key, width, stream, scale: self._latent(noise, seed, rows, key, width, stream, scale)
+        audio = latent("z", d.z_channels, 70, 1.0)
+        x, z, out = self._f(rows, ch), self._f(rows, ch), self._f(rows, ch)
+        cond, rs = self._f(rows, ldc), self._f(rows, 2 * ch)
+        xb = self._b(rows, ch) if res_conv else None
+        zb = self._b(rows, ch) if res_rs else None
+        for f in reversed(range(d.flows)):
+            F = self.flow[f]
+            c = F["c"]
+            h = c // 2
+            gemm(audio, F["w_init"], x, rows, ch, h, c, ch, ch, bias=F["b_init"], bf16=True)
+            if res_conv:
+                call("mstts_round_bf16", ptr(x), ptr(xb), rows * ch)
+            if res_cond:
+                gemm_res(melg_b, Wp[f]["w_cond"], cond, rows, ldc, cm, cm, cm, ldc, bias=F["b_cond"])
+            else:
+                gemm(melg, F["w_cond"], cond, rows, ldc, cm, cm, ldc, ldc, bias=F["b_cond"], bf16=True)
+            if keep:
+                stages[f] = {"melg_b": melg_b.clone() if res_cond else bf(melg.view(rows, cm)), "audio": audio.clone(), "x": x.clone()}
+            for i in range(d.layers):
+                last = i == d.layers - 1
+                if keep:
+                    st = stages[(f, i)] = {"xb": xb.clone() if res_conv else bf(x)}
+                if res_conv:
+                    gemm_res(xb, Wp[f]["w_in"][i], cond, rows, 2 * ch, d.k * ch, ch, d.k * ch, ldc, accumulate=True, win=(Lg, ch, pad, 2 ** i), c_off=i * 2 * ch)
+                else:
+                    gemm(x, F["w_in"][i], cond, rows, 2 * ch, d.k * ch, ch, 2 * ch, ldc, accumulate=True, win=(Lg, ch, pad, 2 ** i), c_off=i * 2 * ch, bf16=True)
+                if res_rs:
+                    call("mstts_wg_gate_bf16", ptr(cond, i * 2 * ch), ldc, ptr(z), ptr(zb), rows, ch)
+                else:
+                    call("mstts_wg_gate", ptr(cond, i * 2 * ch), ldc, ptr(z), rows, ch)
+                nres = ch if last else 2 * ch
+                if res_rs:
+                    gemm_res(zb, Wp[f]["w_res"][i], rs, rows, nres, ch, ch, ch, nres, bias=F["b_res"][i])
+                else:
+                    gemm(z, F["w_res"][i], rs, rows, nres, ch, ch, nres, nres, bias=F["b_res"][i], bf16=True)
+                if keep:
+                    st.update(pre=cond[:, i * 2 * ch:(i + 1) * 2 * ch].clone(), z=z.clone(), zb=zb.clone() if res_rs else bf(z),
+                              rs=rs.view(-1)[:rows * nres].view(rows, nres).clone())
+                if res_conv:
+                    call("mstts_wg_res_skip_bf16", ptr(z), ptr(rs), ptr(xb), ptr(out), rows, ch, int(last), int(i == 0))
+                else:
+                    call("mstts_wg_res_skip", ptr(z), ptr(rs), ptr(x), ptr(out), rows, ch, int(last), int(i == 0))
+            ls_b = self._f(rows, c)
+            gemm(out, F["w_out"], ls_b, rows, c, ch, ch, c, c, bias=F["b_out"], bf16=True)
+            early = f % d.early_every == 0 and f > 0
+            ce = d.early_size if early else 0
+            e = latent("early_%d" % f, ce, 71 + f, 1.0) if early else None
+            nxt = self._f(rows, c + ce)
+            call("mstts_wg_coupling_inv", ptr(audio), ptr(ls_b), ptr(F["w_inv"]), ptr(e) if early else None, float(sigma), ptr(nxt), rows, c, ce)
+            if keep:
+                stages[f].update(out=out.clone(), ls_b=ls_b.clone(), next=nxt.clone())
+            audio = nxt
+        return audio.view(N, Lg * d.groups)
+
+
 # ---- MSTTS_SV.Inference_WaveGlow host logic (MSTTS_SV.py:335-375,452-458) ----------------------------------------------
 def split_mels(mels, split):
     """Every mel cut into `split`-frame chunks; index[i] = (first, last+1) chunk of utterance i."""
@@ -258,7 +391,7 @@ def split_mels(mels, split):
     return chunks, index
 
 
-def vocode(engine: WaveGlowEngine, mels, split, batch, noise_seed=None):
+def vocode(engine: WaveGlowEngine, mels, split, batch, noise_seed=None, arith=None):
     """Chunk, zero-pad to the longest chunk, run `batch` chunks at a time, stitch (the per-chunk tail of kernel - stride
     samples is NOT trimmed, as in the reference: WaveGlow/Modules.py:179 is commented out)."""
     chunks, index = split_mels(mels, split)
@@ -269,7 +402,7 @@ def vocode(engine: WaveGlowEngine, mels, split, batch, noise_seed=None):
     wavs = []
     for b0 in range(0, len(chunks), batch):
         seed = None if noise_seed is None else noise_seed + b0
-        wavs.append(engine.infer(pat[b0:b0 + batch], seed=seed).cpu().numpy())
+        wavs.append(engine.infer(pat[b0:b0 + batch], seed=seed, arith=arith).cpu().numpy())
     allw = np.concatenate(wavs, axis=0)
     return [allw[a:b].reshape(-1) for a, b in index]
 
