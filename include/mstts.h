@@ -44,6 +44,9 @@ int mstts_debug_park_cus(int32_t n_workgroups, int64_t microseconds, uint32_t* d
 
 /* ---- dense contraction (tf.matmul / tf.layers.dense / tf.layers.conv1d and their gradients) ---
  * C[M,N] = act(alpha * op(A) . op(B) + bias)   (accumulate: C += ...; split_k > 1: atomic add)
+ * K == 0 is the empty sum, in every kernel of both entry points: C = act(bias), with accumulate C += act(bias) (A and B are not read but must
+ * not be null); M == 0 or N == 0 is MSTTS_OK and touches nothing (tests/test_gpu_gemm_plain_ref.py: the cases k0_nn and k0_acc_nn, and
+ * its test of refusals and empty products).
  * trans_a = 0: A(m,k) = A[m*lda + k]; 1: A(m,k) = A[k*lda + m]
  * trans_b = 0: B(k,n) = B[k*ldb + n]; 1: B(k,n) = B[n*ldb + k]
  * win_T > 0 turns A into the implicit im2col view of X[rows, win_C] (conv1d 'same', NWC):

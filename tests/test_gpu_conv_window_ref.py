@@ -122,26 +122,16 @@ No form of any case needs more than 4.0 x e32 (y of proj1 on the f32-input MFMA,
 worst error / bound is 0.50.  Where a figure equals its e32 the fallback kernel's fmaf chain and the CPU's float32 product add the terms in
 the same order.  Every output stayed NaN outside its M x N elements, none of them kept a NaN, no operand changed.
 """
-import contextlib
-
 import numpy as np
 import pytest
 import torch
 
 from multi_speaker_tts_amd import lib
 from tests import conv_window_ref as R
+from tests.gemm_forms import FORMS, _defaults, _form        # the six forms, shared with tests/test_gpu_gemm_plain_ref.py
 
 pytestmark = pytest.mark.gpu
 SLACK, EDGE = 8, 2            # NaN columns right of every output row, NaN rows before and after every output
-# split3, split_big, bf16_big, lowered minimums, deterministic, entry point
-FORMS = {
-    "f32_mfma": dict(split3=0, split_big=1, bf16_big=1, low_min=False, det=False, bf16=False),
-    "split_128": dict(split3=1, split_big=0, bf16_big=1, low_min=False, det=False, bf16=False),
-    "split_big": dict(split3=1, split_big=1, bf16_big=1, low_min=True, det=False, bf16=False),
-    "default_det": dict(split3=1, split_big=1, bf16_big=1, low_min=False, det=True, bf16=False),
-    "bf16_128": dict(split3=1, split_big=1, bf16_big=0, low_min=False, det=False, bf16=True),
-    "bf16_big": dict(split3=1, split_big=1, bf16_big=1, low_min=True, det=False, bf16=True),
-}
 
 
 @pytest.fixture(scope="module")
@@ -154,29 +144,6 @@ def uploads():
     cache = {}
     yield cache
     cache.clear()
-
-
-def _defaults(L):
-    L.mstts_gemm_split3(1)
-    L.mstts_gemm_split_big(1)
-    L.mstts_gemm_bf16_big(1)
-    L.mstts_gemm_big_min_workgroups(160, 160)
-    L.mstts_gemm_deterministic(0)
-
-
-@contextlib.contextmanager
-def _form(form):
-    f, L = FORMS[form], lib.load()
-    try:
-        L.mstts_gemm_split3(f["split3"])
-        L.mstts_gemm_split_big(f["split_big"])
-        L.mstts_gemm_bf16_big(f["bf16_big"])
-        if f["low_min"]:
-            L.mstts_gemm_big_min_workgroups(1, 1)
-        with (lib.deterministic_gemm() if f["det"] else contextlib.nullcontext()):
-            yield f
-    finally:
-        _defaults(L)
 
 
 def _t(dev, a):
