@@ -4,22 +4,16 @@
 // way into LDS.  Inputs and outputs stay fp32 in memory - master weights, activations, gradients and the accumulators never
 // leave fp32; only the multiplicands are 8-bit-mantissa.  16x the fp32 MFMA rate, so these launches become memory/LDS-bound.
 //
-// Tile 128 x 128 x 64 per 256-thread workgroup (4 wave64 as 2 x 2, each 64 x 64 = 2 x 2 MFMA tiles).  LDS image of an operand:
-// [128 rows][64 k] bf16, row stride 144 B, i.e. k CONTIGUOUS per row whatever the operand's memory layout - an MFMA fragment
-// (lane l: row l & 31, k = 8 (l >> 5) .. + 7) is then one conflict-free ds_read_b128.  The transposition this needs for operands
-// that are contiguous along their M/N index is done in registers: a thread loads a 4 (k) x 4 (rows) block as four float4 and
-// writes four 8-byte k-runs.  The next K-tile is prefetched into registers while the current one is multiplied.
+// The 128 x 128 x 64 tile is gemm_tile128_kernel (gemm_tile.h); here are its loaders for fp32 operands.  The LDS image is k CONTIGUOUS
+// per row whatever the operand's memory layout; the transposition this needs for operands that are contiguous along their M/N index is
+// done in registers: a thread loads a 4 (k) x 4 (rows) block as four float4 and writes four 8-byte k-runs.
 #include "gemm_tile.h"
 #include <type_traits>
 #include <cstdlib>
 
 namespace mstts {
 
-typedef __bf16 gb_bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 gb_bf16x4 __attribute__((ext_vector_type(4)));
-
-constexpr int GB_BK = 64, GB_BM = 128, GB_BN = 128;
-constexpr int GB_LD = 72;                 // LDS row stride in bf16 elements (144 B = 36 words, 36 mod 32 = 4): 16-byte aligned rows, b128 reads conflict-free
 
 __device__ __forceinline__ gb_bf16x4 gb_round4(float a, float b, float c, float d) {
     return (gb_bf16x4){(__bf16)a, (__bf16)b, (__bf16)c, (__bf16)d};
@@ -33,7 +27,7 @@ struct RoundPlane {
 
 // operand contiguous along k in memory (A row-major, or B given as [N,K]): thread (k4 = tid & 15, r = tid >> 4) takes the float4
 // k-run k4 of rows r, r + 16, .., r + 112.  Window arithmetic is hoisted like in gemm.hip: prepare() once, then load() for
-// k0, k0 + GB_BK, ... (a thread's rows are fixed, its k advances by GB_BK per call).
+// k0, k0 + GT_BK, ... (a thread's rows are fixed, its k advances by GT_BK per call).
 template <bool VEC>
 struct GbLoaderKC {
     float4 reg[8];
@@ -75,7 +69,7 @@ struct GbLoaderKC {
             reg[i] = v;
         }
         if (wT > 0) {
-            kc += GB_BK;
+            kc += GT_BK;
             while (kc >= wC) { kc -= wC; ++tap; }
         }
     }
@@ -83,7 +77,7 @@ struct GbLoaderKC {
         const int k4 = threadIdx.x & 15, r = threadIdx.x >> 4;
 #pragma unroll
         for (int i = 0; i < 8; ++i)
-            *reinterpret_cast<gb_bf16x4*>(s + (r + i * 16) * GB_LD + k4 * 4) = gb_round4(reg[i].x, reg[i].y, reg[i].z, reg[i].w);
+            *reinterpret_cast<gb_bf16x4*>(s + (r + i * 16) * GT_LD + k4 * 4) = gb_round4(reg[i].x, reg[i].y, reg[i].z, reg[i].w);
     }
 };
 
@@ -117,7 +111,7 @@ struct GbLoaderMC {
                 const int t = t_k[i] + sh;
                 ok = ok && t >= 0 && t < wT;
                 off = ((long)k + sh) * ld + cm;
-                t_k[i] += GB_BK;
+                t_k[i] += GT_BK;
                 while (t_k[i] >= wT) t_k[i] -= wT;
             }
             if (ok) {
@@ -136,86 +130,44 @@ struct GbLoaderMC {
         const int c4 = threadIdx.x & 31, kq = threadIdx.x >> 5;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            __bf16* p = s + (c4 * 4) * GB_LD + h * 32 + kq * 4;
+            __bf16* p = s + (c4 * 4) * GT_LD + h * 32 + kq * 4;
             const float4 *q = reg + 4 * h;
             *reinterpret_cast<gb_bf16x4*>(p) = gb_round4(q[0].x, q[1].x, q[2].x, q[3].x);
-            *reinterpret_cast<gb_bf16x4*>(p + GB_LD) = gb_round4(q[0].y, q[1].y, q[2].y, q[3].y);
-            *reinterpret_cast<gb_bf16x4*>(p + 2 * GB_LD) = gb_round4(q[0].z, q[1].z, q[2].z, q[3].z);
-            *reinterpret_cast<gb_bf16x4*>(p + 3 * GB_LD) = gb_round4(q[0].w, q[1].w, q[2].w, q[3].w);
+            *reinterpret_cast<gb_bf16x4*>(p + GT_LD) = gb_round4(q[0].y, q[1].y, q[2].y, q[3].y);
+            *reinterpret_cast<gb_bf16x4*>(p + 2 * GT_LD) = gb_round4(q[0].z, q[1].z, q[2].z, q[3].z);
+            *reinterpret_cast<gb_bf16x4*>(p + 3 * GT_LD) = gb_round4(q[0].w, q[1].w, q[2].w, q[3].w);
         }
     }
 };
 
+// the loader pair of gemm_tile128_kernel (gemm_tile.h) for fp32 operands in any of the four layouts
 template <bool TA, bool TB, bool VEC>
-__global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmTileArgs g) {
-    __shared__ __attribute__((aligned(16))) __bf16 As[GB_BM * GB_LD];
-    __shared__ __attribute__((aligned(16))) __bf16 Bs[GB_BN * GB_LD];
-
-    const int tiles_n = (g.N + GB_BN - 1) / GB_BN;
-    const int tile = gemm_xcd_tile(blockIdx.x, gridDim.x);
-    const int tile_m = tile / tiles_n, tile_n = tile % tiles_n;
-    const int batch = blockIdx.z / g.split_k, split = blockIdx.z % g.split_k;
-    const float* A = g.A + (long)batch * g.stride_a;
-    const float* B = g.B + (long)batch * g.stride_b;
-    float* C = g.C + (long)batch * g.stride_c;
-    const int m0 = tile_m * GB_BM, n0 = tile_n * GB_BN;
-    const int kbeg = split * g.k_per_split;
-    const int kend = min(g.K, kbeg + g.k_per_split);
-
+struct GbLoaders {
+    using Args = GemmTileArgs;
     using LA = typename std::conditional<TA, GbLoaderMC<VEC>, GbLoaderKC<VEC>>::type;
     using LB = typename std::conditional<TB, GbLoaderKC<VEC>, GbLoaderMC<VEC>>::type;
-    LA la; LB lb;
-
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wrow = (wave >> 1) * 64, wcol = (wave & 1) * 64;
-    const int l31 = lane & 31, kg = lane >> 5;
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    if constexpr (TA) la.prepare(m0, kbeg, g.win_T, g.win_C, g.win_pad, g.win_dil);
-    else la.prepare(m0, kbeg, g.win_T, g.win_C);
-    if (kbeg < kend) {
-        la.load(A, g.lda, m0, kbeg, g.M, kend, g.win_T, g.win_C, g.win_pad, g.win_dil);
-        lb.load(B, g.ldb, n0, kbeg, g.N, kend, 0, 1, 0, 1);
+    static constexpr bool BATCHED = true;
+    static __device__ __forceinline__ const GemmTileArgs& tile(const Args& g) { return g; }
+    static __device__ __forceinline__ const float* a(const Args& g) { return g.A; }
+    static __device__ __forceinline__ const float* b(const Args& g) { return g.B; }
+    static __device__ __forceinline__ void prepare(const GemmTileArgs& g, LA& la, LB&, int m0, int, int kbeg) {
+        if constexpr (TA) la.prepare(m0, kbeg, g.win_T, g.win_C, g.win_pad, g.win_dil);
+        else la.prepare(m0, kbeg, g.win_T, g.win_C);
     }
-    for (int k0 = kbeg; k0 < kend; k0 += GB_BK) {
-        __syncthreads();                       // previous tile fully consumed
-        la.store(As);
-        lb.store(Bs);
-        __syncthreads();
-        if (k0 + GB_BK < kend) {               // prefetch next tile while this one is multiplied
-            la.load(A, g.lda, m0, k0 + GB_BK, g.M, kend, g.win_T, g.win_C, g.win_pad, g.win_dil);
-            lb.load(B, g.ldb, n0, k0 + GB_BK, g.N, kend, 0, 1, 0, 1);
-        }
-#pragma unroll
-        for (int ks = 0; ks < GB_BK / 16; ++ks) {
-            gb_bf16x8 a[2], b[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) a[i] = *reinterpret_cast<const gb_bf16x8*>(As + (wrow + i * 32 + l31) * GB_LD + ks * 16 + kg * 8);
-#pragma unroll
-            for (int j = 0; j < 2; ++j) b[j] = *reinterpret_cast<const gb_bf16x8*>(Bs + (wcol + j * 32 + l31) * GB_LD + ks * 16 + kg * 8);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
-        }
+    static __device__ __forceinline__ void load(const GemmTileArgs& g, LA& la, LB& lb, const float* A, const float* B, int m0, int n0, int k0, int kend) {
+        la.load(A, g.lda, m0, k0, g.M, kend, g.win_T, g.win_C, g.win_pad, g.win_dil);
+        lb.load(B, g.ldb, n0, k0, g.N, kend, 0, 1, 0, 1);
     }
+};
 
-    gemm_store_tile<2, 2>(g, acc, C, m0 + wrow, n0 + wcol, lane, split == 0, g.split_k > 1);
-}
+// (in a profile: gemm_tile128_kernel<GbLoaders<TA, TB, VEC>>)
+template <bool TA, bool TB, bool VEC> constexpr auto gemm_bf16_kernel = &gemm_tile128_kernel<GbLoaders<TA, TB, VEC>>;
 
 struct GemmBf16 {                 // no WIN flag (run-time window), static LDS
     using Args = GemmTileArgs;
     static constexpr int THREADS = 256;
     static constexpr size_t LDS_BYTES = 0;
-    template <bool TA, bool TB, bool VEC, bool WIN> static constexpr auto kernel() { return &gemm_bf16_kernel<TA, TB, VEC>; }
+    template <bool TA, bool TB, bool VEC, bool WIN> static constexpr auto kernel() { return gemm_bf16_kernel<TA, TB, VEC>; }
 };
 
 
@@ -279,11 +231,11 @@ __global__ __launch_bounds__(GX_THREADS) void gemm_bf16_big_kernel(GemmTileArgs 
 
     const int aoff = (wrow + l31) * GX_LD + kg * 8, boff = GX_PLANE + (wcol + l31) * GX_LD + kg * 8;
     auto kstep = [&](const __bf16* buf, int ks) {
-        gb_bf16x8 a[4], b[2];
+        gemm_bf16x8 a[4], b[2];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) a[i] = *reinterpret_cast<const gb_bf16x8*>(buf + aoff + i * 32 * GX_LD + ks * 16);
+        for (int i = 0; i < 4; ++i) a[i] = *reinterpret_cast<const gemm_bf16x8*>(buf + aoff + i * 32 * GX_LD + ks * 16);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) b[j] = *reinterpret_cast<const gb_bf16x8*>(buf + boff + j * 32 * GX_LD + ks * 16);
+        for (int j = 0; j < 2; ++j) b[j] = *reinterpret_cast<const gemm_bf16x8*>(buf + boff + j * 32 * GX_LD + ks * 16);
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -335,7 +287,7 @@ namespace mstts { int gemm_deterministic_now(); }
 extern "C" int mstts_gemm_bf16(const mstts_gemm_desc* d, mstts_stream_t stream) {
     GemmTileArgs g;
     bool vec;
-    const int rc = gemm_args_from(d, "gemm_bf16", GB_BK, 0, &g, &vec);
+    const int rc = gemm_args_from(d, "gemm_bf16", GT_BK, 0, &g, &vec);
     if (rc != MSTTS_OK || g.M == 0 || g.N == 0) return rc;
     const int batch = d->batch > 0 ? (int)d->batch : 1;
     int split = g.split_k;
@@ -361,7 +313,7 @@ extern "C" int mstts_gemm_bf16(const mstts_gemm_desc* d, mstts_stream_t stream) 
     // `accumulate` the output's N columns (not its row pitch: C may be a column band of a wider matrix) are cleared here first.  A caller's own
     // split_k > 1 is honoured exactly - as mstts_gemm_f32 does - so a caller that reasons about the number of pieces (0 + p + q) gets that number.
     if (g_bf16_autocut && split == 1 && d->act == MSTTS_ACT_NONE && batch == 1 && !gemm_deterministic_now()) {
-        const long tiles = (long)cdiv(d->M, GB_BM) * cdiv(d->N, GB_BN);
+        const long tiles = (long)cdiv(d->M, GT_BM) * cdiv(d->N, GT_BN);
         int best = 1;
         double best_cost = 0.0;
         for (int sk = 1; sk <= 64; ++sk) {
@@ -376,10 +328,10 @@ extern "C" int mstts_gemm_bf16(const mstts_gemm_desc* d, mstts_stream_t stream) 
             }
             split = best;
             g.split_k = split;
-            g.k_per_split = gemm_k_per_split(g.K, split, GB_BK);
+            g.k_per_split = gemm_k_per_split(g.K, split, GT_BK);
         }
     }
-    dim3 grid(cdiv(d->M, GB_BM) * cdiv(d->N, GB_BN), 1, batch * split);
+    dim3 grid(cdiv(d->M, GT_BM) * cdiv(d->N, GT_BN), 1, batch * split);
     gemm_launch<GemmBf16>(g, ta, tb, vec, win, grid, st);
     MSTTS_CHECK_LAUNCH("gemm_bf16");
     return MSTTS_OK;

@@ -1,7 +1,9 @@
 // What the GEMM kernels of gemm.hip (+ gemm_split.inc) and gemm_bf16.hip share: the kernel-argument block, the tile loaders of the
 // LDS-staged bf16 kernels, the epilogue, the XCD-aware tile order, and on the host the descriptor check and the launch path.
 // Each kernel keeps its own K loop and fragment schedule; a kernel family says how a float4 is staged (its `Stage` policy) and with
-// which geometry, everything about addressing and the conv window lives here once.
+// which geometry, everything about addressing and the conv window lives here once.  The two 128 x 128 x 64 bf16 forms (gemm_bf16.hip:
+// fp32 operands rounded on the way into LDS; gemm_bf16_res.hip: operands that are bf16 in memory) differ in their loaders only and are one
+// kernel template, gemm_tile128_kernel.
 #pragma once
 #include "common.h"
 #include <utility>
@@ -238,6 +240,78 @@ __device__ __forceinline__ void gemm_store_tile(const GemmTileArgs& g, const f32
         }
 }
 
+// ---- the 128 x 128 x 64 bf16 tile (gemm_bf16.hip, gemm_bf16_res.hip) ------------------------
+// 256 threads = 4 wave64 as 2 x 2, each 64 x 64 = 2 x 2 MFMA tiles.  LDS image of an operand: [128 rows][64 k] bf16, k contiguous per row
+// at a row stride of 144 B = 36 words (36 mod 32 = 4): 16-byte aligned rows, an MFMA fragment (lane l: row l & 31, k = 8 (l >> 5) .. + 7)
+// is one conflict-free ds_read_b128.
+typedef __bf16 gemm_bf16x8 __attribute__((ext_vector_type(8)));
+constexpr int GT_BM = 128, GT_BN = 128, GT_BK = 64, GT_LD = 72;
+
+// The kernel, for a loader pair L (GbLoaders: fp32 operands rounded on the way into LDS, gemm_bf16.hip; GrLoaders: operands that are bf16
+// in memory, gemm_bf16_res.hip).  L names the kernel's argument (L::Args; L::tile(args) = its GemmTileArgs, L::a / L::b(args) = the operands),
+// whether blockIdx.z also counts batches (L::BATCHED), the two loader types (L::LA, L::LB: their registers are the kernel's own locals) and
+// how they are called: prepare(g, la, lb, m0, n0, kbeg) once, load(g, la, lb, A, B, m0, n0, k0, kend) = fetch the K-tile at k0 of both
+// operands into the loaders' registers; la.store(As) / lb.store(Bs) write those registers to LDS as bf16.  The next K-tile is loaded under the
+// current one's MFMAs.  An output element is ONE sum over the K-tiles of its split in ascending order, whatever M, N or the grid are.
+// One __global__ template and not a shared __device__ body called from two kernels: behind a function boundary, however it is inlined, the
+// same statements get another schedule and register allocation (profiles/waveglow_refactor_codegen.txt), and these kernels are tuned.
+template <class L>
+__global__ __launch_bounds__(256) void gemm_tile128_kernel(typename L::Args args) {
+    __shared__ __attribute__((aligned(16))) __bf16 As[GT_BM * GT_LD];
+    __shared__ __attribute__((aligned(16))) __bf16 Bs[GT_BN * GT_LD];
+    const GemmTileArgs& g = L::tile(args);
+
+    const int tiles_n = (g.N + GT_BN - 1) / GT_BN;
+    const int tile = gemm_xcd_tile(blockIdx.x, gridDim.x);
+    const int tile_m = tile / tiles_n, tile_n = tile % tiles_n;
+    const int batch = L::BATCHED ? blockIdx.z / g.split_k : 0, split = L::BATCHED ? blockIdx.z % g.split_k : blockIdx.z;
+    const auto* A = L::a(args) + (long)batch * g.stride_a;
+    const auto* B = L::b(args) + (long)batch * g.stride_b;
+    float* C = g.C + (long)batch * g.stride_c;
+    const int m0 = tile_m * GT_BM, n0 = tile_n * GT_BN;
+    const int kbeg = split * g.k_per_split;
+    const int kend = min(g.K, kbeg + g.k_per_split);
+
+    typename L::LA la; typename L::LB lb;
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wrow = (wave >> 1) * 64, wcol = (wave & 1) * 64;
+    const int l31 = lane & 31, kg = lane >> 5;
+
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    L::prepare(g, la, lb, m0, n0, kbeg);
+    if (kbeg < kend) L::load(g, la, lb, A, B, m0, n0, kbeg, kend);
+    for (int k0 = kbeg; k0 < kend; k0 += GT_BK) {
+        __syncthreads();                       // previous tile fully consumed
+        la.store(As);
+        lb.store(Bs);
+        __syncthreads();
+        if (k0 + GT_BK < kend) L::load(g, la, lb, A, B, m0, n0, k0 + GT_BK, kend);      // prefetch next tile while this one is multiplied
+#pragma unroll
+        for (int ks = 0; ks < GT_BK / 16; ++ks) {
+            gemm_bf16x8 a[2], b[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) a[i] = *reinterpret_cast<const gemm_bf16x8*>(As + (wrow + i * 32 + l31) * GT_LD + ks * 16 + kg * 8);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) b[j] = *reinterpret_cast<const gemm_bf16x8*>(Bs + (wcol + j * 32 + l31) * GT_LD + ks * 16 + kg * 8);
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
+        }
+    }
+
+    gemm_store_tile<2, 2>(g, acc, C, m0 + wrow, n0 + wcol, lane, split == 0, g.split_k > 1);
+}
+
 // ---- host side ----------------------------------------------------------------------------
 // K range of one of `split` pieces: whole K-tiles of depth bk, at least one
 static inline int gemm_k_per_split(int K, int split, int bk) {
@@ -245,16 +319,27 @@ static inline int gemm_k_per_split(int K, int split, int bk) {
     return kps < bk ? bk : kps;
 }
 
-// Validates a descriptor for the entry point `who` ("gemm" / "gemm_bf16": the prefix of its error texts) and fills the common argument block
-// (k_per_split for K-tiles of depth bk).  max_ld > 0: the entry point's kernels address rows with 32-bit tile-relative offsets.  An empty
-// product (M or N zero) returns MSTTS_OK with g->M = g->N = 0 and nothing else filled: the caller returns.
-// *vec: every float4 the loaders form is 16-byte aligned and does not straddle a conv tap or the end of a row.
-static inline int gemm_args_from(const mstts_gemm_desc* d, const char* who, int bk, long max_ld, GemmTileArgs* g, bool* vec) {
+// What every descriptor (mstts_gemm_desc, mstts_gemm_res_desc) is checked for first, for the entry point `who` (the prefix of its error
+// texts): it is there, its dims are non-negative and fit an int, its operands are there.  Fills g->M, N, K; an empty product (M or N zero)
+// returns MSTTS_OK with g->M = g->N = 0 and nothing else filled: the caller returns.
+template <class Desc>
+static inline int gemm_desc_dims(const Desc* d, const char* who, GemmTileArgs* g) {
     MSTTS_REQUIRE(d != nullptr, MSTTS_ERR_SHAPE, "%s: null descriptor", who);
     MSTTS_REQUIRE(d->M >= 0 && d->N >= 0 && d->K >= 0, MSTTS_ERR_SHAPE, "%s: negative dims", who);
     if (d->M == 0 || d->N == 0) { g->M = g->N = 0; return MSTTS_OK; }
     MSTTS_REQUIRE(d->A && d->B && d->C, MSTTS_ERR_SHAPE, "%s: null operand", who);
     MSTTS_REQUIRE(d->M < (1LL << 31) && d->N < (1LL << 31) && d->K < (1LL << 31), MSTTS_ERR_SHAPE, "%s: dims exceed int32", who);
+    g->M = (int)d->M; g->N = (int)d->N; g->K = (int)d->K;
+    return MSTTS_OK;
+}
+
+// Validates a descriptor for the entry point `who` ("gemm" / "gemm_bf16": the prefix of its error texts) and fills the common argument block
+// (k_per_split for K-tiles of depth bk).  max_ld > 0: the entry point's kernels address rows with 32-bit tile-relative offsets.  An empty
+// product is gemm_desc_dims's.
+// *vec: every float4 the loaders form is 16-byte aligned and does not straddle a conv tap or the end of a row.
+static inline int gemm_args_from(const mstts_gemm_desc* d, const char* who, int bk, long max_ld, GemmTileArgs* g, bool* vec) {
+    const int rc = gemm_desc_dims(d, who, g);
+    if (rc != MSTTS_OK || g->M == 0 || g->N == 0) return rc;
     MSTTS_REQUIRE(max_ld <= 0 || (d->lda >= 0 && d->ldb >= 0 && d->lda < max_ld && d->ldb < max_ld), MSTTS_ERR_SHAPE,
                   "%s: row strides must be below 2^24 elements (tile-relative offsets are 32-bit)", who);
     const int split = d->split_k > 1 ? d->split_k : 1;
@@ -265,7 +350,6 @@ static inline int gemm_args_from(const mstts_gemm_desc* d, const char* who, int 
         MSTTS_REQUIRE(d->win_C % 4 == 0, MSTTS_ERR_SHAPE, "%s: window mode needs win_C %% 4 == 0", who);
     }
     g->A = d->A; g->B = d->B; g->C = d->C; g->bias = d->bias;
-    g->M = (int)d->M; g->N = (int)d->N; g->K = (int)d->K;
     g->lda = d->lda; g->ldb = d->ldb; g->ldc = d->ldc;
     g->win_T = d->win_T; g->win_C = d->win_C > 0 ? d->win_C : 1; g->win_pad = d->win_pad; g->win_dil = d->win_dil > 0 ? d->win_dil : 1;
     g->act = d->act; g->accumulate = d->accumulate; g->split_k = split;

@@ -34,7 +34,7 @@ __global__ void wg_overlap_add_kernel(const float* __restrict__ Y, const float* 
     }
 }
 
-// the gate of one element: wg_gate_kernel and wg_gate_bf16_kernel both go through this one function, so they agree bit for bit on the same pre-activation
+// the gate of one element: every gate kernel goes through this one function, so they agree bit for bit on the same pre-activation
 __device__ __forceinline__ float wg_gate_value(float t, float s) { return tanhf(t) * sigmoid_acc(s); }
 
 __global__ void wg_gate_kernel(const float* __restrict__ a, long lda, float* __restrict__ z, long rows, int C) {
@@ -45,18 +45,28 @@ __global__ void wg_gate_kernel(const float* __restrict__ a, long lda, float* __r
     }
 }
 
-// ... with the dilated convolution's output in its own buffer b [rows, 2C] (see mstts_wg_gate_add): pre-activation = a + b
-__global__ void wg_gate_add_kernel(const float* __restrict__ a, long lda, const float* __restrict__ b, float* __restrict__ z, long rows, int C) {
+typedef __bf16 wg_bf16x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ wg_bf16x4 wg_round4(float4 v) { return (wg_bf16x4){(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w}; }      // RNE
+__device__ __forceinline__ float4 wg_add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+
+// ... four channels per thread (C % 4 == 0, 16-byte aligned operands), with two options.  ADD: the dilated convolution's output is in its
+// own buffer b [rows, 2C] (see mstts_wg_gate_add), pre-activation = a + b.  BF16: the config-3 mode's glue, it also stores zb, the bf16 copy
+// of z the res/skip contraction reads (mstts_gemm_bf16_res), rounded to nearest even from the fp32 value.
+template <bool ADD, bool BF16>
+__global__ void wg_gate4_kernel(const float* __restrict__ a, long lda, const float* __restrict__ b, float* __restrict__ z, __bf16* __restrict__ zb,
+                                long rows, int C) {
     const long n4 = rows * (C >> 2);
     const int c4n = C >> 2;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
         const long r = i / c4n; const int c = (int)(i - r * c4n) * 4;
-        const float4 at = *reinterpret_cast<const float4*>(a + r * lda + c), as = *reinterpret_cast<const float4*>(a + r * lda + C + c);
-        const float4 bt = *reinterpret_cast<const float4*>(b + r * 2 * C + c), bs = *reinterpret_cast<const float4*>(b + r * 2 * C + C + c);
-        float4 o;
-        o.x = tanhf(at.x + bt.x) * sigmoid_acc(as.x + bs.x); o.y = tanhf(at.y + bt.y) * sigmoid_acc(as.y + bs.y);
-        o.z = tanhf(at.z + bt.z) * sigmoid_acc(as.z + bs.z); o.w = tanhf(at.w + bt.w) * sigmoid_acc(as.w + bs.w);
+        float4 t = *reinterpret_cast<const float4*>(a + r * lda + c), s = *reinterpret_cast<const float4*>(a + r * lda + C + c);
+        if (ADD) {
+            t = wg_add4(t, *reinterpret_cast<const float4*>(b + r * 2 * C + c));
+            s = wg_add4(s, *reinterpret_cast<const float4*>(b + r * 2 * C + C + c));
+        }
+        const float4 o = make_float4(wg_gate_value(t.x, s.x), wg_gate_value(t.y, s.y), wg_gate_value(t.z, s.z), wg_gate_value(t.w, s.w));
         *reinterpret_cast<float4*>(z + r * C + c) = o;
+        if (BF16) *reinterpret_cast<wg_bf16x4*>(zb + r * C + c) = wg_round4(o);
     }
 }
 
@@ -73,25 +83,9 @@ __global__ void wg_res_skip_kernel(const float* __restrict__ z, const float* __r
 }
 
 // ---- config-3 mode (bf16 operands in every contraction): the glue kernels also store the bf16 copy the next contraction reads -------------
-typedef __bf16 wg_bf16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ wg_bf16x4 wg_round4(float4 v) { return (wg_bf16x4){(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w}; }      // RNE
-
 __global__ void round_bf16_kernel(const float* __restrict__ src, __bf16* __restrict__ dst, long n4) {
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x)
         *reinterpret_cast<wg_bf16x4*>(dst + 4 * i) = wg_round4(*reinterpret_cast<const float4*>(src + 4 * i));
-}
-
-__global__ void wg_gate_bf16_kernel(const float* __restrict__ a, long lda, float* __restrict__ z, __bf16* __restrict__ zb, long rows, int C) {
-    const long n4 = rows * (C >> 2);
-    const int c4n = C >> 2;
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-        const long r = i / c4n; const int c = (int)(i - r * c4n) * 4;
-        const float4 at = *reinterpret_cast<const float4*>(a + r * lda + c), as = *reinterpret_cast<const float4*>(a + r * lda + C + c);
-        float4 o;
-        o.x = wg_gate_value(at.x, as.x); o.y = wg_gate_value(at.y, as.y); o.z = wg_gate_value(at.z, as.z); o.w = wg_gate_value(at.w, as.w);
-        *reinterpret_cast<float4*>(z + r * C + c) = o;
-        *reinterpret_cast<wg_bf16x4*>(zb + r * C + c) = wg_round4(o);
-    }
 }
 
 __global__ void wg_res_skip_bf16_kernel(const float* __restrict__ z, const float* __restrict__ rs, __bf16* __restrict__ xb, float* __restrict__ out,
@@ -104,11 +98,11 @@ __global__ void wg_res_skip_bf16_kernel(const float* __restrict__ z, const float
         if (last) skip = *reinterpret_cast<const float4*>(rs + r * C + c);
         else {
             const float4 zv = *reinterpret_cast<const float4*>(z + r * C + c), res = *reinterpret_cast<const float4*>(rs + r * 2 * C + c);
-            *reinterpret_cast<wg_bf16x4*>(xb + r * C + c) = wg_round4(make_float4(zv.x + res.x, zv.y + res.y, zv.z + res.z, zv.w + res.w));
+            *reinterpret_cast<wg_bf16x4*>(xb + r * C + c) = wg_round4(wg_add4(zv, res));
             skip = *reinterpret_cast<const float4*>(rs + r * 2 * C + C + c);
         }
         float4* o = reinterpret_cast<float4*>(out + r * C + c);
-        if (!first) { const float4 p = *o; skip.x = p.x + skip.x; skip.y = p.y + skip.y; skip.z = p.z + skip.z; skip.w = p.w + skip.w; }
+        if (!first) skip = wg_add4(*o, skip);
         *o = skip;
     }
 }
@@ -176,7 +170,7 @@ extern "C" int mstts_wg_gate_add(const float* a, int64_t lda, const float* b, fl
     MSTTS_REQUIRE(a && b && z && rows >= 0 && C >= 4 && C % 4 == 0 && lda >= 2 * C && lda % 4 == 0, MSTTS_ERR_SHAPE, "wg_gate_add: bad arguments");
     MSTTS_REQUIRE(aligned16(a) && aligned16(b) && aligned16(z), MSTTS_ERR_ALIGN, "wg_gate_add: 16-byte aligned operands required");
     if (rows == 0) return MSTTS_OK;
-    hipLaunchKernelGGL(wg_gate_add_kernel, dim3(wg_grid(rows * C / 4)), dim3(256), 0, ST(s), a, (long)lda, b, z, (long)rows, (int)C);
+    hipLaunchKernelGGL((wg_gate4_kernel<true, false>), dim3(wg_grid(rows * C / 4)), dim3(256), 0, ST(s), a, (long)lda, b, z, (__bf16*)nullptr, (long)rows, (int)C);
     MSTTS_CHECK_LAUNCH("wg_gate_add");
     return MSTTS_OK;
 }
@@ -200,7 +194,7 @@ extern "C" int mstts_wg_gate_bf16(const float* a, int64_t lda, float* z, void* z
     MSTTS_REQUIRE(a && z && zb && rows >= 0 && C >= 4 && C % 4 == 0 && lda >= 2 * C && lda % 4 == 0, MSTTS_ERR_SHAPE, "wg_gate_bf16: bad arguments (C and lda multiples of 4)");
     MSTTS_REQUIRE(aligned16(a) && aligned16(z) && aligned16(zb), MSTTS_ERR_ALIGN, "wg_gate_bf16: 16-byte aligned operands required");
     if (rows == 0) return MSTTS_OK;
-    hipLaunchKernelGGL(wg_gate_bf16_kernel, dim3(wg_grid(rows * C / 4)), dim3(256), 0, ST(s), a, (long)lda, z, (__bf16*)zb, (long)rows, (int)C);
+    hipLaunchKernelGGL((wg_gate4_kernel<false, true>), dim3(wg_grid(rows * C / 4)), dim3(256), 0, ST(s), a, (long)lda, (const float*)nullptr, z, (__bf16*)zb, (long)rows, (int)C);
     MSTTS_CHECK_LAUNCH("wg_gate_bf16");
     return MSTTS_OK;
 }

@@ -9,7 +9,8 @@ Python owns buffers and the schedule; every arithmetic step is a libmstts_hip.so
     (affine inverse + inverse 1x1 conv + early-latent re-injection),
   * tf.random.normal -> mstts_philox_normal (or injected arrays, which is what the parity tests use).
 infer(arith="bf16") is the same schedule in BASELINE config 3 arithmetic: bf16 operands in every contraction, fp32 accumulate, the three big
-products on operands that are bf16 in memory (mstts_gemm_bf16_res; WaveGlowEngine._infer_bf16).  The default, "f32", is the path above.
+products on operands that are bf16 in memory (mstts_gemm_bf16_res).  The schedule is written once: `wavenet` runs the network inside a
+coupling for inference and for the training forward (waveglow_trainer.py), `WaveNetOps` holds what depends on the arithmetic.
 Weight normalisation (g * v / ||v||, WaveGlow/Modules.py:9-34) and the matrix inverses of the 1x1 kernels are
 constants of a checkpoint and are folded once at load time on the host.
 """
@@ -121,7 +122,7 @@ def _weight_norm(g, v):
 
 
 def _conv_two_pieces(rows, n_out):
-    """Whether the dilated convolution [rows, k ch] x [k ch, n_out] runs as two reduction pieces onto a zeroed buffer (see WaveGlowEngine.infer).
+    """Whether the dilated convolution [rows, k ch] x [k ch, n_out] runs as two reduction pieces onto a zeroed buffer (see WaveNetOps).
     Fitted to tools/wg_conv_ab.py at the reference widths (per-layer microseconds, one piece | two pieces: batch 1: 92 | 64, 2: 99 | 118,
     4: 185 | 164, 5: 187 | 174, 6: 277 | 322, 8: 268 | 330, 12: 534 | 501, 16: 571 | 518, 24: 838 | 853, 32: 923 | 1050): the 128 x 128-tile kernel's
     time steps at 256, 512 and then every 1 024 tiles, the 256 x 256-tile kernel's at every 256 workgroups; in units of the latter's round."""
@@ -134,6 +135,86 @@ def _conv_two_pieces(rows, n_out):
         return False
     one = 0.58 if t128 <= 256 else 1.12 if t128 <= 512 else 1.65 * -(-t128 // 1024)
     return -(-w256 // 256) < one
+
+
+_at = lambda w: w if isinstance(w, tuple) else (w, 0)     # (tensor, element offset) of a weight or bias given as that pair or as a bare tensor
+
+
+class WaveNetOps:
+    """The part of the schedule that depends on the arithmetic, resolved once per call: which entry point each product goes to, the dilated
+    convolution's form, the gate and the res/skip kernel.  The default is the plain fp32 schedule (the training forward's).
+    bf16: operands rounded to bf16 in every contraction; res_cond / res_conv / res_rs: that product reads the STORED bf16 copy of its
+    activation and the packed weight (mstts_gemm_bf16_res).  The convolution (fp32 forms): one piece accumulated onto its band of cond
+    (mstts_gemm_f32 takes 64-row tiles for such shapes, 688 at batch 4 x 40 frames: no atomics; split_in > 1 splits its reduction), or
+    `two`: exactly two reduction pieces (split_k = 2) onto a ZEROED buffer of its own, which the gate adds.  0 + p + q is the same float
+    whichever piece's atomic lands first (three pieces would not be order-free), so the flow stays bit-reproducible per latent seed, and
+    at batch 4 x 40 frames 22 x 4 tiles x 2 pieces = 176 workgroups reach the 256 x 256-tile kernel (csrc/gemm_split.inc) where the
+    128 x 128 one runs 344 tiles as a round and a third: 185 -> 164 us per layer.  _conv_two_pieces decides, a fixed function of the shape."""
+
+    def __init__(self, bf16=False, res_cond=False, res_conv=False, res_rs=False, two=False, split_in=1):
+        assert not (two and (bf16 or split_in != 1)) and (bf16 or not (res_cond or res_conv or res_rs))
+        self.bf16, self.res_cond, self.res_conv, self.res_rs, self.two, self.split_in = bf16, res_cond, res_conv, res_rs, two, split_in
+
+    def product(self, resident, A, Ab, W, Wb, Cm, M, N, K, lda, ldc, bias=None, **kw):
+        """Cm [M, N] (pitch ldc) = A . W + bias.  A: the fp32 operand [M, K], Ab its stored bf16 copy, both at pitch lda; W: the fp32 weight
+        [K, N] (ldb = N), Wb the packed one, TRANSPOSED [N, K] (ldb = K).  resident picks the bf16 pair.  kw: accumulate, split_k, win, c_off."""
+        (W, b_off), (bias, bias_off) = _at(Wb if resident else W), _at(bias)
+        if resident:
+            gemm_res(Ab, W, Cm, M, N, K, lda, K, ldc, bias=bias, b_off=b_off, bias_off=bias_off, **kw)
+        else:
+            gemm(A, W, Cm, M, N, K, lda, N, ldc, bias=bias, b_off=b_off, bias_off=bias_off, bf16=self.bf16, **kw)
+
+    def gate(self, cond, band, ldc, conv, z, zb, rows, ch):
+        if self.two:
+            call("mstts_wg_gate_add", ptr(cond, band), ldc, ptr(conv), ptr(z), rows, ch)
+        elif self.res_rs:
+            call("mstts_wg_gate_bf16", ptr(cond, band), ldc, ptr(z), ptr(zb), rows, ch)
+        else:
+            call("mstts_wg_gate", ptr(cond, band), ldc, ptr(z), rows, ch)
+
+    def res_skip(self, z, rs, x, xb, out, rows, ch, last, first):
+        if self.res_conv:
+            call("mstts_wg_res_skip_bf16", ptr(z), ptr(rs), ptr(xb), ptr(out), rows, ch, int(last), int(first))
+        else:
+            call("mstts_wg_res_skip", ptr(z), ptr(rs), ptr(x), ptr(out), rows, ch, int(last), int(first))
+
+
+def wavenet(ops, d, rows, Lg, W, Wp, a, lda, melg, cond, xs, zs, rs, out, ls_b, melg_b=None, xb=None, zb=None, conv=None, stages=None, f=None):
+    """The network inside one coupling (WaveGlow/Modules.py:251-327), inference and training forward alike: initial conv of a[:, :c/2]
+    (read in place at pitch lda), ONE product for the conditioning convs of all layers, per layer the dilated conv accumulated onto its
+    conditioning band / gate / res-skip product / res-skip glue, the output conv into ls_b.  2 + 3 layers + 1 launches (+ 1 rounding of x
+    when the convolution is resident).
+    W: the coupling's c, w_init, b_init, w_cond, b_cond, w_in[i], w_res[i], b_res[i], w_out, b_out as (tensor, element offset) pairs or
+    bare tensors; Wp: its packed bf16 weights (w_cond, w_in[i], w_res[i]) where a product is resident.  xs[i] / zs[i]: layer i's input and
+    gated activation ([rows, ch]; xs[layers] is the last layer's unused residual output and may be None); cond [rows, layers 2 ch], rs
+    [rows, 2 ch], out = the skip sum; melg_b, xb, zb: the stored bf16 copies (resident products only); conv: the two-piece convolution's
+    buffer.  stages, f: the bf16 mode's test hook (WaveGlowEngine.infer)."""
+    ch, cm, ldc, c = d.ch, d.groups * d.n_mel, d.layers * 2 * d.ch, W["c"]
+    bf = lambda t: t.to(torch.bfloat16)
+    ops.product(False, a, None, W["w_init"], None, xs[0], rows, ch, c // 2, lda, ch, bias=W["b_init"])
+    if ops.res_conv:
+        call("mstts_round_bf16", ptr(xs[0]), ptr(xb), rows * ch)
+    ops.product(ops.res_cond, melg, melg_b, W["w_cond"], Wp and Wp["w_cond"], cond, rows, ldc, cm, cm, ldc, bias=W["b_cond"])
+    if stages is not None:
+        stages[f] = {"melg_b": melg_b.clone() if ops.res_cond else bf(melg.view(rows, cm)), "x": xs[0].clone()}
+    for i in range(d.layers):
+        last, band, win = i == d.layers - 1, i * 2 * ch, (Lg, ch, (d.k - 1) // 2, 2 ** i)
+        if stages is not None:
+            st = stages[(f, i)] = {"xb": xb.clone() if ops.res_conv else bf(xs[i])}
+        if ops.two:
+            conv.zero_()
+            ops.product(False, xs[i], None, W["w_in"][i], None, conv, rows, 2 * ch, d.k * ch, ch, 2 * ch, split_k=2, win=win)
+        else:
+            ops.product(ops.res_conv, xs[i], xb, W["w_in"][i], Wp and Wp["w_in"][i], cond, rows, 2 * ch, d.k * ch, ch, ldc, accumulate=True,
+                        split_k=ops.split_in, win=win, c_off=band)
+        ops.gate(cond, band, ldc, conv, zs[i], zb, rows, ch)
+        nres = ch if last else 2 * ch
+        ops.product(ops.res_rs, zs[i], zb, W["w_res"][i], Wp and Wp["w_res"][i], rs, rows, nres, ch, ch, nres, bias=W["b_res"][i])
+        if stages is not None:
+            st.update(pre=cond[:, band:band + 2 * ch].clone(), z=zs[i].clone(), zb=zb.clone() if ops.res_rs else bf(zs[i]),
+                      rs=rs.view(-1)[:rows * nres].view(rows, nres).clone())
+        ops.res_skip(zs[i], rs, xs[i + 1], xb, out, rows, ch, last, i == 0)
+    ops.product(False, out, None, W["w_out"], None, ls_b, rows, c, ch, ch, c, bias=W["b_out"])
 
 
 class WaveGlowEngine:
@@ -151,8 +232,8 @@ class WaveGlowEngine:
             raise ValueError("WaveGlow variables missing: %s ..." % missing[:3])
         self.load(vals)
         self._keep = []
-        self.split_in = 0          # > 1: split the dilated-conv GEMM's reduction (atomic accumulation); 0 / 1 = off (see infer)
-        self.conv_two_pieces = os.environ.get("MSTTS_WG_TWO_PIECES", "1") != "0"     # the dilated convolution as two reduction pieces onto a zeroed buffer (see infer)
+        self.split_in = 0          # > 1: split the dilated-conv GEMM's reduction (atomic accumulation); 0 / 1 = off (see WaveNetOps)
+        self.conv_two_pieces = os.environ.get("MSTTS_WG_TWO_PIECES", "1") != "0"     # the dilated convolution as two reduction pieces onto a zeroed buffer (see WaveNetOps)
 
     # ------------------------------------------------------------------ checkpoint constants, folded on the host once
     def _dev(self, a):
@@ -227,99 +308,45 @@ class WaveGlowEngine:
     @lib.deterministic_gemm()          # bit-reproducible per latent seed: no K-cuts with atomics inside the flow's contractions
     def infer(self, mel, noise=None, seed=None, sigma=1.0, arith=None, stages=None):
         """mel [N, T, n_mel] (tensor or array) -> wav tensor [N, (T-1)*stride + kernel].  noise: {"z": [N,L/G,z_channels],
-        "early_<flow>": [N,L/G,early_size]} to inject the latents, else Philox normals of `seed`.
-        arith: "f32" | "bf16" (see _infer_bf16; resolution: resolve_arith).  stages: a dict the bf16 mode fills with clones of its
-        intermediate tensors (a test hook, see _infer_bf16)."""
-        if resolve_arith(arith, self.arith) == "bf16":
-            return self._infer_bf16(mel, noise, seed, sigma, stages)
+        "early_<flow>": [N,L/G,early_size]} to inject the latents, else Philox normals of `seed`.  arith: "f32" | "bf16" (resolve_arith).
+
+        "bf16" is BASELINE config 3 for the vocoder: every contraction multiplies operands rounded to bf16 (round-to-nearest-even) and
+        accumulates in fp32; biases, the gate, the residual stream, the skip sum, the coupling inverse (with w_inv), latents and overlap-add
+        stay fp32.  The rounded activations are STORED tensors - melg_b = bf(melg), zb = bf(z), xb_{i+1} = bf(fl32(z_i + res_i)), xb_0 = bf(x) -
+        written by the glue kernels (mstts_round_bf16, mstts_wg_gate_bf16, mstts_wg_res_skip_bf16), and the three big products (conditioning,
+        dilated convolution, res/skip: 204 of a call's launches) read them and the packed weights as they are (mstts_gemm_bf16_res).  The
+        dilated convolution is always one piece accumulated onto its band of `cond`; conv_two_pieces and split_in are fp32-mode features.  The
+        upsampler, the initial conv (K <= 4) and the output conv (N <= 8) have fp32 operands anyway and run on mstts_gemm_bf16.  A product
+        mstts_gemm_bf16_res does not take (ch % 8 != 0), and all three with MSTTS_WG_BF16_RESIDENT=0 (the A/B leg), falls back to
+        mstts_gemm_bf16 on the fp32 buffers: same rounding sites (the kernel rounds the same fp32 values), same contract.
+
+        stages: a test hook of the bf16 mode (the fp32 mode leaves it alone: its parity tests compare the waveform).  It receives "resident"
+        (which products ran resident), per flow f a dict stages[f] of melg_b, audio (the flow's input), x (the initial conv's output), out (the
+        skip sum), ls_b and next (the coupling inverse's output), and per layer stages[(f, i)] = pre (the layer's band of cond after the conv
+        accumulated), z, zb, rs, xb (as consumed)."""
         d = self.d
         mel, N, T, C, L = self._begin(mel)
-        Lg, rows, cm, ch = L // d.groups, N * (L // d.groups), d.groups * C, d.ch
+        Lg, rows, cm, ch, ldc = L // d.groups, N * (L // d.groups), d.groups * C, d.ch, d.layers * 2 * d.ch
+        # everything the schedule depends on, once
+        bf16 = resolve_arith(arith, self.arith) == "bf16"
+        resident = bf16 and os.environ.get("MSTTS_WG_BF16_RESIDENT", "1") != "0"
+        split_in = 1 if bf16 else self.split_in or 1
+        ops = WaveNetOps(bf16=bf16, split_in=split_in,
+                         res_cond=resident and gemm_res_supported(rows, ldc, cm, cm, cm),
+                         res_conv=resident and gemm_res_supported(rows, 2 * ch, d.k * ch, ch, d.k * ch, win=(Lg, ch)),
+                         res_rs=resident and gemm_res_supported(rows, 2 * ch, ch, ch, ch),
+                         two=not bf16 and self.conv_two_pieces and split_in == 1 and ch % 4 == 0 and _conv_two_pieces(rows, 2 * ch))
+        Wp = self.packed() if (ops.res_cond or ops.res_conv or ops.res_rs) else None
+        keep = stages if bf16 else None
+        if keep is not None:
+            keep["resident"] = {"cond": ops.res_cond, "conv": ops.res_conv, "res_skip": ops.res_rs}
         # Upsample_Mel: every tap product of every frame, then overlap-add (+ bias)
         Y = self._f(N * T, d.up_k * C)
-        gemm(mel, self.up_w, Y, N * T, d.up_k * C, C, C, d.up_k * C, d.up_k * C)
-        up = self._f(N, L, C)
-        call("mstts_wg_overlap_add", ptr(Y), ptr(self.up_b), ptr(up), N, T, d.up_k, d.up_stride, C)
-        melg = up                                     # viewed as [rows, G*C]: contiguous regrouping (:180-187)
-        seed = self.seed if seed is None else seed
-        latent = lambda key, width, stream, scale: self._latent(noise, seed, rows, key, width, stream, scale)
-        audio = latent("z", d.z_channels, 70, 1.0)
-        x, z, out = self._f(rows, ch), self._f(rows, ch), self._f(rows, ch)
-        cond, rs = self._f(rows, d.layers * 2 * ch), self._f(rows, 2 * ch)
-        ldc = d.layers * 2 * ch
-        # The [rows, 3*ch] x [3*ch, 2*ch] conv GEMM has only ceil(rows/128) * (2*ch/128) = 344 output tiles of 128 rows at batch 4 x 40
-        # frames on 256 CUs; mstts_gemm_f32 switches to 64-row tiles for such shapes (688 tiles), which beats the split-K form
-        # used before (33.0 vs 33.6 ms per batch) and keeps the launch free of atomics - results are bit-reproducible run to run.
-        # Round 5: where it pays, the convolution's output goes to its own ZEROED buffer as exactly two reduction pieces (split_k = 2).  0 + p + q is
-        # the same float whichever piece's atomic lands first (fp addition commutes; three pieces would not be order-free), so the flow is still
-        # bit-reproducible per latent seed - and at batch 4 x 40 frames 22 x 4 tiles x 2 pieces = 176 workgroups reach the 256 x 256-tile kernel
-        # (csrc/gemm_split.inc), where the 128 x 128 one runs 344 tiles as a round and a third: 185 -> 164 us per layer, gate included (it adds the
-        # two buffers).  _conv_two_pieces: a fixed function of the shape (tools/wg_conv_ab.py), so a seed gives the same samples in every process.
-        split_in = self.split_in or 1
-        two = self.conv_two_pieces and split_in == 1 and ch % 4 == 0 and _conv_two_pieces(rows, 2 * ch)
-        conv = self._f(rows, 2 * ch) if two else None
-        for f in reversed(range(d.flows)):
-            F = self.flow[f]
-            c = F["c"]
-            h = c // 2
-            gemm(audio, F["w_init"], x, rows, ch, h, c, ch, ch, bias=F["b_init"])                       # audio0 = audio[:, :h]
-            gemm(melg, F["w_cond"], cond, rows, ldc, cm, cm, ldc, ldc, bias=F["b_cond"])
-            for i in range(d.layers):
-                last = i == d.layers - 1
-                if two:
-                    conv.zero_()
-                    gemm(x, F["w_in"][i], conv, rows, 2 * ch, d.k * ch, ch, 2 * ch, 2 * ch, split_k=2, win=(Lg, ch, (d.k - 1) // 2, 2 ** i))
-                    call("mstts_wg_gate_add", ptr(cond, i * 2 * ch), ldc, ptr(conv), ptr(z), rows, ch)
-                else:
-                    gemm(x, F["w_in"][i], cond, rows, 2 * ch, d.k * ch, ch, 2 * ch, ldc, accumulate=True, split_k=split_in,
-                         win=(Lg, ch, (d.k - 1) // 2, 2 ** i), c_off=i * 2 * ch)
-                    call("mstts_wg_gate", ptr(cond, i * 2 * ch), ldc, ptr(z), rows, ch)
-                nres = ch if last else 2 * ch
-                gemm(z, F["w_res"][i], rs, rows, nres, ch, ch, nres, nres, bias=F["b_res"][i])
-                call("mstts_wg_res_skip", ptr(z), ptr(rs), ptr(x), ptr(out), rows, ch, int(last), int(i == 0))
-            ls_b = self._f(rows, c)
-            gemm(out, F["w_out"], ls_b, rows, c, ch, ch, c, c, bias=F["b_out"])
-            early = f % d.early_every == 0 and f > 0
-            ce = d.early_size if early else 0
-            e = latent("early_%d" % f, ce, 71 + f, 1.0) if early else None
-            nxt = self._f(rows, c + ce)
-            call("mstts_wg_coupling_inv", ptr(audio), ptr(ls_b), ptr(F["w_inv"]), ptr(e) if early else None, float(sigma), ptr(nxt), rows, c, ce)
-            audio = nxt
-        return audio.view(N, Lg * d.groups)
-
-
-    def _infer_bf16(self, mel, noise, seed, sigma, stages):
-        """BASELINE config 3 for the vocoder: every contraction multiplies operands rounded to bf16 (round-to-nearest-even) and accumulates in
-        fp32; biases, the gate, the residual stream, the skip sum, the coupling inverse (with w_inv), latents and overlap-add stay fp32.
-        The rounded activations are STORED tensors - melg_b = bf(melg), zb = bf(z), xb_{i+1} = bf(fl32(z_i + res_i)), xb_0 = bf(x) - written
-        by the glue kernels (mstts_round_bf16, mstts_wg_gate_bf16, mstts_wg_res_skip_bf16), and the three big products (conditioning, dilated
-        convolution, res/skip: 204 of a call's launches) read them and the packed weights as they are (mstts_gemm_bf16_res).  The dilated
-        convolution is always one piece accumulated onto its band of `cond`; conv_two_pieces and split_in are fp32-mode features.  The
-        upsampler, the initial conv (K <= 4) and the output conv (N <= 8) have fp32 operands anyway and run on mstts_gemm_bf16.
-        A product mstts_gemm_bf16_res does not take (ch % 8 != 0), and all three with MSTTS_WG_BF16_RESIDENT=0 (the A/B leg), falls back to
-        mstts_gemm_bf16 on the fp32 buffers: same rounding sites (the kernel rounds the same fp32 values), same contract.  One call is
-        bit-reproducible per seed.  `stages`, when given, receives "resident" (which products ran resident), per flow f a dict stages[f]
-        of melg_b, audio (the flow's input), x (the initial conv's output), out (the skip sum), ls_b and next (the coupling inverse's
-        output), and per layer stages[(f, i)] = pre (the layer's band of cond after the conv accumulated), z, zb, rs, xb (as consumed)."""
-        d = self.d
-        mel, N, T, C, L = self._begin(mel)
-        Lg, rows, cm, ch = L // d.groups, N * (L // d.groups), d.groups * C, d.ch
-        ldc, pad = d.layers * 2 * ch, (d.k - 1) // 2
-        resident = os.environ.get("MSTTS_WG_BF16_RESIDENT", "1") != "0"
-        res_cond = resident and gemm_res_supported(rows, ldc, cm, cm, cm)
-        res_conv = resident and gemm_res_supported(rows, 2 * ch, d.k * ch, ch, d.k * ch, win=(Lg, ch))
-        res_rs = resident and gemm_res_supported(rows, 2 * ch, ch, ch, ch)
-        Wp = self.packed() if (res_cond or res_conv or res_rs) else None
-        bf = lambda t: t.to(torch.bfloat16)
-        keep = stages is not None
-        if keep:
-            stages["resident"] = {"cond": res_cond, "conv": res_conv, "res_skip": res_rs}
-        Y = self._f(N * T, d.up_k * C)
-        gemm(mel, self.up_w, Y, N * T, d.up_k * C, C, C, d.up_k * C, d.up_k * C, bf16=True)
-        melg = self._f(N, L, C)                         # viewed as [rows, G*C]
+        ops.product(False, mel, None, self.up_w, None, Y, N * T, d.up_k * C, C, C, d.up_k * C)
+        melg = self._f(N, L, C)                       # viewed as [rows, G*C]: contiguous regrouping (:180-187)
         call("mstts_wg_overlap_add", ptr(Y), ptr(self.up_b), ptr(melg), N, T, d.up_k, d.up_stride, C)
         melg_b = None
-        if res_cond:
+        if ops.res_cond:
             melg_b = self._b(rows, cm)
             call("mstts_round_bf16", ptr(melg), ptr(melg_b), rows * cm)
         seed = self.seed if seed is None else seed
@@ -327,54 +354,23 @@ class WaveGlowEngine:
         audio = latent("z", d.z_channels, 70, 1.0)
         x, z, out = self._f(rows, ch), self._f(rows, ch), self._f(rows, ch)
         cond, rs = self._f(rows, ldc), self._f(rows, 2 * ch)
-        xb = self._b(rows, ch) if res_conv else None
-        zb = self._b(rows, ch) if res_rs else None
+        # (rounded copies only where their consumer is resident; the two-piece convolution's own output buffer)
+        xb = self._b(rows, ch) if ops.res_conv else None
+        zb = self._b(rows, ch) if ops.res_rs else None
+        conv = self._f(rows, 2 * ch) if ops.two else None
         for f in reversed(range(d.flows)):
             F = self.flow[f]
             c = F["c"]
-            h = c // 2
-            gemm(audio, F["w_init"], x, rows, ch, h, c, ch, ch, bias=F["b_init"], bf16=True)
-            if res_conv:
-                call("mstts_round_bf16", ptr(x), ptr(xb), rows * ch)
-            if res_cond:
-                gemm_res(melg_b, Wp[f]["w_cond"], cond, rows, ldc, cm, cm, cm, ldc, bias=F["b_cond"])
-            else:
-                gemm(melg, F["w_cond"], cond, rows, ldc, cm, cm, ldc, ldc, bias=F["b_cond"], bf16=True)
-            if keep:
-                stages[f] = {"melg_b": melg_b.clone() if res_cond else bf(melg.view(rows, cm)), "audio": audio.clone(), "x": x.clone()}
-            for i in range(d.layers):
-                last = i == d.layers - 1
-                if keep:
-                    st = stages[(f, i)] = {"xb": xb.clone() if res_conv else bf(x)}
-                if res_conv:
-                    gemm_res(xb, Wp[f]["w_in"][i], cond, rows, 2 * ch, d.k * ch, ch, d.k * ch, ldc, accumulate=True, win=(Lg, ch, pad, 2 ** i), c_off=i * 2 * ch)
-                else:
-                    gemm(x, F["w_in"][i], cond, rows, 2 * ch, d.k * ch, ch, 2 * ch, ldc, accumulate=True, win=(Lg, ch, pad, 2 ** i), c_off=i * 2 * ch, bf16=True)
-                if res_rs:
-                    call("mstts_wg_gate_bf16", ptr(cond, i * 2 * ch), ldc, ptr(z), ptr(zb), rows, ch)
-                else:
-                    call("mstts_wg_gate", ptr(cond, i * 2 * ch), ldc, ptr(z), rows, ch)
-                nres = ch if last else 2 * ch
-                if res_rs:
-                    gemm_res(zb, Wp[f]["w_res"][i], rs, rows, nres, ch, ch, ch, nres, bias=F["b_res"][i])
-                else:
-                    gemm(z, F["w_res"][i], rs, rows, nres, ch, ch, nres, nres, bias=F["b_res"][i], bf16=True)
-                if keep:
-                    st.update(pre=cond[:, i * 2 * ch:(i + 1) * 2 * ch].clone(), z=z.clone(), zb=zb.clone() if res_rs else bf(z),
-                              rs=rs.view(-1)[:rows * nres].view(rows, nres).clone())
-                if res_conv:
-                    call("mstts_wg_res_skip_bf16", ptr(z), ptr(rs), ptr(xb), ptr(out), rows, ch, int(last), int(i == 0))
-                else:
-                    call("mstts_wg_res_skip", ptr(z), ptr(rs), ptr(x), ptr(out), rows, ch, int(last), int(i == 0))
             ls_b = self._f(rows, c)
-            gemm(out, F["w_out"], ls_b, rows, c, ch, ch, c, c, bias=F["b_out"], bf16=True)
+            wavenet(ops, d, rows, Lg, F, Wp and Wp[f], audio, c, melg, cond, [x] * (d.layers + 1), [z] * d.layers, rs, out, ls_b,
+                    melg_b=melg_b, xb=xb, zb=zb, conv=conv, stages=keep, f=f)
             early = f % d.early_every == 0 and f > 0
             ce = d.early_size if early else 0
             e = latent("early_%d" % f, ce, 71 + f, 1.0) if early else None
             nxt = self._f(rows, c + ce)
             call("mstts_wg_coupling_inv", ptr(audio), ptr(ls_b), ptr(F["w_inv"]), ptr(e) if early else None, float(sigma), ptr(nxt), rows, c, ce)
-            if keep:
-                stages[f].update(out=out.clone(), ls_b=ls_b.clone(), next=nxt.clone())
+            if keep is not None:
+                keep[f].update(audio=audio.clone(), out=out.clone(), ls_b=ls_b.clone(), next=nxt.clone())
             audio = nxt
         return audio.view(N, Lg * d.groups)
 

@@ -22,7 +22,7 @@ from . import lib
 from .lib import call, gemm, ptr
 from .params import ParamStore
 from .training import Engine, Workspace, _split_k, exponential_decay
-from .waveglow import P_WG, WGDims, random_values, variable_table
+from .waveglow import P_WG, WGDims, WaveNetOps, random_values, variable_table, wavenet
 
 CLIP_NORM = 0.1          # tf.clip_by_global_norm(gradients, 0.1) (WaveGlow.py:69)
 S_LOG_S, S_LOG_DET, S_AUDIO, S_SUMSQ = 0, 1, 2, 3       # device scalars: sum min(log_s, 8), sum logdet_f, 0.5 sum z^2, 0.5 sum g^2
@@ -142,6 +142,14 @@ class WaveGlowTrainEngine(Engine):
         self.logdet_table = torch.tensor([v for f in range(d.flows) for v in (ps.offset[self._wp(f, "invertible_1x1/kernel")], d.channels(f))],
                                          dtype=torch.int64, device=self.device)
         self.flip = self._f(d.k, 2 * ch, ch)
+        # what `wavenet` reads per flow: (tensor, element offset) of the effective kernels in their slab and of the biases
+        self.wn = []
+        for f in range(d.flows):
+            E, P = self.eff[f], lambda name: ps.p(self._wp(f, "wavenet/" + name))
+            self.wn.append({"c": d.channels(f), "w_init": self._E(self.weff, E["init"]), "b_init": P("audio_initial_conv/bias"),
+                            "w_cond": self._E(self.weff, E["cond"]), "b_cond": (self.b_cond, f * ldc),
+                            "w_in": [self._E(self.weff, e) for e in E["in"]], "w_res": [self._E(self.weff, e) for e in E["res"]],
+                            "b_res": [P("res_%d/bias" % i) for i in range(d.layers)], "w_out": P("conv1d/kernel"), "b_out": P("conv1d/bias")})
 
     def _E(self, slab, idx, off=0):
         """(tensor, element offset) of effective-kernel piece idx."""
@@ -197,29 +205,13 @@ class WaveGlowTrainEngine(Engine):
         call("mstts_copy2d", ptr(w.up), w.up_len * C, ptr(w.melg), L * C, N, L * C, 0)
         call("mstts_copy2d", ptr(audio), audio.shape[1], ptr(w.ain[0]), L, N, L, 0)
         w.scal.zero_()
+        ops = WaveNetOps()                    # the plain fp32 schedule
         for f in range(d.flows):
             c = d.channels(f)
-            h = c // 2
-            E = self.eff[f]
             wt, wo = self.P(self._wp(f, "invertible_1x1/kernel"))
             gemm(w.ain[f], wt, w.y[f], rows, c, c, c, c, c, b_off=wo)
-            p = "wavenet/"
-            sl, so = self._E(self.weff, E["init"]); bt, bo = self.P(self._wp(f, p + "audio_initial_conv/bias"))
-            gemm(w.y[f], sl, w.xs[f][0], rows, ch, h, c, ch, ch, bias=bt, b_off=so, bias_off=bo)          # a0 read in place (lda = c)
-            sl, so = self._E(self.weff, E["cond"])
-            gemm(w.melg, sl, w.cond[f], rows, ldc, cm, cm, ldc, ldc, bias=self.b_cond, b_off=so, bias_off=f * ldc)
-            for i in range(d.layers):
-                last = i == d.layers - 1
-                sl, so = self._E(self.weff, E["in"][i])
-                gemm(w.xs[f][i], sl, w.cond[f], rows, 2 * ch, d.k * ch, ch, 2 * ch, ldc, accumulate=True,
-                     win=(Lg, ch, (d.k - 1) // 2, 2 ** i), b_off=so, c_off=i * 2 * ch)
-                call("mstts_wg_gate", ptr(w.cond[f], i * 2 * ch), ldc, ptr(w.zs[f][i]), rows, ch)
-                nres = ch if last else 2 * ch
-                sl, so = self._E(self.weff, E["res"][i]); bt, bo = self.P(self._wp(f, p + "res_%d/bias" % i))
-                gemm(w.zs[f][i], sl, w.rs, rows, nres, ch, ch, nres, nres, bias=bt, b_off=so, bias_off=bo)
-                call("mstts_wg_res_skip", ptr(w.zs[f][i]), ptr(w.rs), None if last else ptr(w.xs[f][i + 1]), ptr(w.skip[f]), rows, ch, int(last), int(i == 0))
-            kt, ko = self.P(self._wp(f, p + "conv1d/kernel")); bt, bo = self.P(self._wp(f, p + "conv1d/bias"))
-            gemm(w.skip[f], kt, w.lsb[f], rows, c, ch, ch, c, c, bias=bt, b_off=ko, bias_off=bo)
+            # every layer keeps its own input and gated activation for the backward; a0 is read in place (lda = c); the last layer has no residual output
+            wavenet(ops, d, rows, Lg, self.wn[f], None, w.y[f], c, w.melg, w.cond[f], w.xs[f] + [None], w.zs[f], w.rs, w.skip[f], w.lsb[f])
             zc, ce = early_chunk(d, f) or (0, 0)
             nxt = w.ain[f + 1] if f + 1 < d.flows else None
             call("mstts_wg_coupling_fwd", ptr(w.y[f]), ptr(w.lsb[f]), ptr(nxt), ptr(w.z), d.groups, zc, ce, ptr(w.scal, S_LOG_S), rows, c)

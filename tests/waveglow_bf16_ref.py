@@ -1,6 +1,6 @@
 """Stage-wise judge of WaveGlowEngine.infer(arith="bf16") (config 3 for the vocoder) and a float32 torch emulation of the mode.
 
-The mode's contract (multi_speaker_tts_amd/waveglow.py, WaveGlowEngine._infer_bf16): every contraction multiplies operands rounded to bf16
+The mode's contract (multi_speaker_tts_amd/waveglow.py, WaveGlowEngine.infer): every contraction multiplies operands rounded to bf16
 (round-to-nearest-even) and accumulates in fp32; biases, the gate, the residual stream, the skip sum, the coupling inverse, latents and
 overlap-add stay fp32.  The rounded activations are stored tensors: melg_b = bf(melg), zb = bf(z), xb_0 = bf(x), xb_{i+1} = bf(fl32(z_i + res_i)).
 
@@ -104,7 +104,7 @@ def _other_rounding(w):
 
 
 def emulate(eng, mel, noise, sigma=1.0, fault=None, at=(1, 1)):
-    """WaveGlowEngine._infer_bf16 restated in float32 torch on the engine's device-side constants (an engine built with device="cpu" serves):
+    """WaveGlowEngine.infer(arith="bf16") restated in float32 torch on the engine's device-side constants (an engine built with device="cpu" serves):
     same rounding sites, `stages` in the engine's layout.  Returns (wav, stages).  fault: one of FAULTS, planted at (flow, layer) `at`."""
     assert fault is None or fault in FAULTS
     d = eng.d
