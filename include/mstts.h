@@ -518,6 +518,26 @@ int mstts_griffin_lim(const float* spec, const float* phase_u, const uint64_t* s
                       int32_t win, float power, float ref_level_db, float preemph, int32_t iters, float* ws, float* wav_out,
                       mstts_stream_t s);
 
+/* WaveGlow denoiser: bias-spectrum subtraction for nw waveforms at once (csrc/wg_denoise.hip; Audio.spectral_denoise is its fp64
+ * statement).  librosa's stft conventions as mstts_stft_fft has them (center=True, reflect padding by n_fft / 2, window[win] = the periodic
+ * Hann window centred in n_fft, 1 + len_w / hop frames, no pre-emphasis), then per frame and bin
+ *   Y[k] = max(|X[k]| - strength bias[k], 0) X[k] / |X[k]|      (0 where X[k] = 0),   bias[n_fft/2+1] >= 0, strength >= 0,
+ * and istft with length = len_w: the windowed overlap-add of irfft(Y) divided by the summed squared windows of the frames that exist at
+ * each position (where that exceeds float32 tiny), the first n_fft / 2 samples dropped, exactly len_w samples kept.  wav / out = the
+ * waveforms back to back in the same layout (out + wav_off[w] receives waveform w; in place is not supported); wav_off[nw+1] = sample
+ * offsets, once as a HOST array (every waveform is checked before anything is launched) and once as a DEVICE array; frame_off[nw+1] =
+ * DEVICE frame offsets, frame_off[w+1] - frame_off[w] = 1 + len_w / hop; window / twiddle = the tables of mstts_stft_fft.  Two launches:
+ * a workgroup per frame (FFT, subtract, inverse FFT in LDS; the windowed frames go to ws [total_frames, win] =
+ * mstts_wg_denoise_ws_floats floats), then a gather per output sample of the at most four frames that cover it, in frame order - no
+ * atomics, bit-reproducible, the same bits for a waveform alone and in any batch.  fp32; nothing synchronises.  MSTTS_ERR_SHAPE before
+ * any launch, the message naming the waveform: len_w <= n_fft / 2, parameters outside mstts_wg_denoise_supported (n_fft as
+ * mstts_stft_fft_supported accepts it and 2 hop <= win <= 4 hop), a negative strength. */
+int mstts_wg_denoise_supported(int32_t n_fft, int32_t hop, int32_t win);
+int64_t mstts_wg_denoise_ws_floats(int64_t total_frames, int32_t win);
+int mstts_wg_denoise(const float* wav, const int64_t* wav_off_host, const int64_t* wav_off, const int64_t* frame_off, int32_t nw,
+                     const float* bias, float strength, const float* window, const float* twiddle, int32_t n_fft, int32_t hop,
+                     int32_t win, float* ws, float* out, mstts_stream_t s);
+
 /* Waveform front end: what Feeder.load_wav does to decoded samples, for nw waveforms at once (csrc/wav_front_end.hip).  Waveforms lie
  * back to back; every offset array is a DEVICE array of nw + 1 int64 entries, as mstts_stft_fft takes them.  fp32; everything is
  * enqueued on the stream, nothing synchronises; parameters are checked on the host before any launch (MSTTS_ERR_SHAPE).

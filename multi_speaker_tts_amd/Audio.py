@@ -65,16 +65,33 @@ def _constants(num_freq, frame_shift_ms, frame_length_ms, num_mels, sample_rate,
             torch.tensor(fb_t, dtype=torch.float32, device=dev))
 
 
+def _fft_tables(n_fft, win):
+    """The window and twiddle tables of `_fft_constants` for a transform given in samples, float64: the periodic Hann window [win] and
+    (cos, -sin)(2 pi k / n_fft) [n_fft, 2]."""
+    n = np.arange(win)
+    hann = 0.5 - 0.5 * np.cos(2 * np.pi * n / win)
+    k = np.arange(n_fft)
+    tw = np.stack([np.cos(2 * np.pi * k / n_fft), -np.sin(2 * np.pi * k / n_fft)], axis=1)
+    return hann, tw
+
+
+@functools.lru_cache(maxsize=8)
+def _fft_constants_samples(n_fft, win, device):
+    """`_fft_constants` for callers that state the transform in samples (the denoiser: 256 samples at 22 050 Hz is no whole number of
+    milliseconds, `_stft_parameters` would truncate it to 255) -> (hann, twiddle) on the device, the same fp64-built tables."""
+    dev = torch.device(device)
+    hann, tw = _fft_tables(n_fft, win)
+    t = lambda a: torch.tensor(np.ascontiguousarray(a), dtype=torch.float32, device=dev)
+    return t(hann), t(tw)
+
+
 @functools.lru_cache(maxsize=8)
 def _fft_constants(num_freq, frame_shift_ms, frame_length_ms, num_mels, sample_rate, device):
     """Tables of the one-launch FFT path (mstts_stft_fft): periodic Hann window, e^{-2 pi i k / n_fft} twiddles, the mel filterbank
     row-major with each filter's non-zero bin range - all built in float64."""
     n_fft, hop, win = _stft_parameters(num_freq, frame_shift_ms, frame_length_ms, sample_rate)
     dev = torch.device(device)
-    n = np.arange(win)
-    hann = 0.5 - 0.5 * np.cos(2 * np.pi * n / win)
-    k = np.arange(n_fft)
-    tw = np.stack([np.cos(2 * np.pi * k / n_fft), -np.sin(2 * np.pi * k / n_fft)], axis=1)
+    hann, tw = _fft_tables(n_fft, win)
     fb = mel_filterbank(sample_rate, n_fft, num_mels).astype(np.float32)
     rng = np.zeros((num_mels, 2), np.int32)
     for c in range(num_mels):
@@ -228,6 +245,108 @@ def _istft(D, num_freq, frame_shift_ms, frame_length_ms, sample_rate):
     nz = wss > np.finfo(np.float32).tiny
     y[nz] /= wss[nz]
     return y[n_fft // 2:n - n_fft // 2]
+
+
+def _stft_samples(y, n_fft, hop, win):
+    """`_stft` with the transform given in samples -> [n_fft // 2 + 1, 1 + len(y) // hop] (the same arithmetic)."""
+    w = _padded_window(n_fft, win)
+    yp = np.pad(np.asarray(y, np.float64), n_fft // 2, mode="reflect")
+    n_frames = 1 + (len(yp) - n_fft) // hop
+    idx = np.arange(n_fft)[None, :] + hop * np.arange(n_frames)[:, None]
+    return np.fft.rfft(yp[idx] * w[None, :], axis=1).T
+
+
+def _istft_samples(D, n_fft, hop, win, length):
+    """`_istft` with the transform given in samples and torch.istft's `length`: the first n_fft // 2 samples of the normalised overlap-add
+    are dropped and exactly `length` samples kept (not the hop (frames - 1) of `_istft`)."""
+    w = _padded_window(n_fft, win)
+    n_frames = D.shape[1]
+    frames = np.fft.irfft(D.T, n=n_fft, axis=1) * w[None, :]
+    n = n_fft + hop * (n_frames - 1)
+    if length + n_fft // 2 > n:
+        raise ValueError("%d frames do not cover %d samples" % (n_frames, length))
+    y, wss = np.zeros(n), np.zeros(n)
+    for i in range(n_frames):
+        y[i * hop:i * hop + n_fft] += frames[i]
+        wss[i * hop:i * hop + n_fft] += w * w
+    nz = wss > np.finfo(np.float32).tiny
+    y[nz] /= wss[nz]
+    return y[n_fft // 2:n_fft // 2 + length]
+
+
+def spectral_denoise(x, bias, strength, n_fft=1024, hop=256, win=1024):
+    """The WaveGlow denoiser in float64, the checker of `spectral_denoise_batch`: strength * bias [n_fft // 2 + 1] is subtracted from the
+    magnitude of every STFT bin of x (clipped at 0), the phase kept ((1, 0) where a bin is 0), and the result transformed back to
+    len(x) samples.  librosa's conventions as `_stft`; x needs more than n_fft // 2 samples (the reflect padding)."""
+    x = np.asarray(x, np.float64).reshape(-1)
+    bias = np.asarray(bias, np.float64).reshape(-1)
+    if x.shape[0] <= n_fft // 2:
+        raise ValueError("waveform of %d samples is shorter than the STFT's reflect padding (%d samples)" % (x.shape[0], n_fft // 2))
+    if bias.shape[0] != n_fft // 2 + 1 or (bias < 0).any():
+        raise ValueError("bias must hold %d non-negative magnitudes" % (n_fft // 2 + 1))
+    if not strength >= 0:
+        raise ValueError("denoiser strength must not be negative (%r)" % (strength,))
+    X = _stft_samples(x, n_fft, hop, win)
+    mag = np.abs(X)
+    direction = np.where(mag > 0, X / np.where(mag > 0, mag, 1.0), 1.0)
+    Y = np.maximum(mag - float(strength) * bias[:, None], 0.0) * direction
+    return _istft_samples(Y, n_fft, hop, win, x.shape[0])
+
+
+def spectral_denoise_supported(n_fft, hop, win):
+    """Does the device path cover this transform (mstts_wg_denoise_supported: a power-of-two n_fft in [512, 4096], win <= n_fft,
+    2 hop <= win <= 4 hop)?"""
+    return bool(lib.load().mstts_wg_denoise_supported(int(n_fft), int(hop), int(win)))
+
+
+def spectral_denoise_batch(wavs, bias, strength, n_fft=1024, hop=256, win=1024, device="cuda", return_tensor=False):
+    """`spectral_denoise` for several waveforms in ONE device call (mstts_wg_denoise: two launches for the whole batch, fp32).  wavs: list
+    of arrays or device tensors; bias: [n_fft // 2 + 1] array or device tensor (WaveGlowEngine.bias_spectrum) -> list of float32
+    waveforms of the same lengths (NumPy, or device tensors with return_tensor).  A transform outside the device envelope
+    (`spectral_denoise_supported`) goes through the host function waveform by waveform; a waveform of n_fft // 2 samples or fewer and a
+    negative strength are errors on both."""
+    if not len(wavs):
+        return []
+    if not float(strength) >= 0:
+        raise ValueError("denoiser strength must not be negative (%r)" % (strength,))
+    lens = [int(w.numel()) if torch.is_tensor(w) else int(np.asarray(w).size) for w in wavs]
+    for i, n in enumerate(lens):
+        if n <= n_fft // 2:
+            raise ValueError("waveform %d: %d samples, shorter than the STFT's reflect padding (%d samples)" % (i, n, n_fft // 2))
+    if not spectral_denoise_supported(n_fft, hop, win):
+        b = bias.detach().cpu().numpy() if torch.is_tensor(bias) else bias
+        out = []
+        for w in wavs:
+            w = w.detach().cpu().numpy() if torch.is_tensor(w) else w
+            y = spectral_denoise(w, b, strength, n_fft, hop, win).astype(np.float32)
+            out.append(torch.as_tensor(y).to(device) if return_tensor else y)
+        return out
+    hann, tw = _fft_constants_samples(int(n_fft), int(win), str(device))
+    dev = hann.device
+    up = lambda a: (a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a, np.float32))).to(dev, torch.float32).reshape(-1)
+    cat = torch.cat([up(w) for w in wavs]).contiguous()
+    return _denoise_packed(cat, lens, up(bias).contiguous(), strength, n_fft, hop, win, hann, tw, return_tensor)
+
+
+def _denoise_packed(cat, lens, bias, strength, n_fft, hop, win, hann, tw, return_tensor):
+    """The device call of `spectral_denoise_batch` on waveforms of the lengths `lens` that already lie back to back in `cat`."""
+    import ctypes
+    dev, nw = cat.device, len(lens)
+    if bias.numel() != n_fft // 2 + 1:
+        raise ValueError("bias must hold %d magnitudes" % (n_fft // 2 + 1))
+    wav_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    frame_off = np.concatenate([[0], np.cumsum([1 + n // hop for n in lens])]).astype(np.int64)
+    offs = torch.as_tensor(np.stack([wav_off, frame_off])).to(dev)
+    total = int(frame_off[-1])
+    ws = torch.empty(max(int(lib.load().mstts_wg_denoise_ws_floats(total, win)), 1), dtype=torch.float32, device=dev)
+    out = torch.empty_like(cat)
+    host_off = (ctypes.c_int64 * (nw + 1))(*[int(v) for v in wav_off])
+    lib.call("mstts_wg_denoise", lib.ptr(cat), host_off, lib.ptr(offs), lib.ptr(offs, nw + 1), nw, lib.ptr(bias), float(strength),
+             lib.ptr(hann), lib.ptr(tw), int(n_fft), int(hop), int(win), lib.ptr(ws), lib.ptr(out))
+    if return_tensor:
+        return [out[int(a):int(b)] for a, b in zip(wav_off[:-1], wav_off[1:])]
+    host = out.cpu().numpy()                                  # (synchronises: cat, ws may go once this returns)
+    return [host[int(a):int(b)].copy() for a, b in zip(wav_off[:-1], wav_off[1:])]
 
 
 def inv_preemphasis(x, preemphasis=0.97):

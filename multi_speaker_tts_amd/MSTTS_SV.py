@@ -427,18 +427,20 @@ class Tacotron2:
             helper.join()
         return res
 
-    def Inference_WaveGlow(self, path_List, text_List, file_Prefix=None, speaker_Mel_List=None, masks=None, export=True, noise_seed=None, front_end=None, wav_rule=None, wg_arith=None):
+    def Inference_WaveGlow(self, path_List, text_List, file_Prefix=None, speaker_Mel_List=None, masks=None, export=True, noise_seed=None, front_end=None, wav_rule=None, wg_arith=None, denoiser_strength=None):
         """MSTTS_SV.py:325-389 + Export_Inference_WaveGlow :449-466: Tacotron2 forward, the mels cut into
         hp.WaveGlow.Inference.Mel_Split_Length-frame chunks, vocoded hp.WaveGlow.Inference.Batch_Size chunks at a time,
         stitched per utterance, cut at the stop token (in samples of Export_Sample_Rate).  wg_arith: the vocoder's arithmetic, "f32" |
-        "bf16" (bf16 operands in every contraction, fp32 accumulate); None: MSTTS_WG_ARITH, else "f32" (WaveGlowEngine.infer)."""
+        "bf16" (bf16 operands in every contraction, fp32 accumulate); None: MSTTS_WG_ARITH, else "f32" (WaveGlowEngine.infer).
+        denoiser_strength: the WaveGlow denoiser (WaveGlowEngine.denoise: strength times the network's bias spectrum subtracted from every
+        STFT frame, n_fft 1024 / hop 256) on the stitched utterances, before the stop-token cut; None: MSTTS_WG_DENOISE, else off."""
         from . import waveglow as WG
         pattern = self.feeder.Get_Inference_Pattern(path_List, text_List, speaker_Mel_List=speaker_Mel_List, front_end=front_end, rule=wav_rule)
         res = self.infer_engine.forward(pattern, masks=masks, with_vocoder=False)
         res["Global_Step"] = self.global_step
         prefix = file_Prefix or "GS_{}".format(self.global_step)
         wavs = WG.vocode(self.waveglow, list(res["Mel"]), hp.WaveGlow.Inference.Mel_Split_Length, hp.WaveGlow.Inference.Batch_Size,
-                         noise_seed=noise_seed, arith=wg_arith)
+                         noise_seed=noise_seed, arith=wg_arith, denoise=denoiser_strength)
         res["Wav"] = wavs
         cut = []
         for i, text in enumerate(text_List):
@@ -513,15 +515,16 @@ class Tacotron2:
             log(pending)
 
     # ---- inference (MSTTS_SV.py:295-323,391-400)
-    def Inference(self, path_List, text_List, file_Prefix=None, speaker_Mel_List=None, masks=None, export=True, wav=None, griffin_lim_seed=0, front_end=None, wav_rule=None, wg_arith=None):
-        """wg_arith goes to Inference_WaveGlow when hp.Use_Vocoder is WaveGlow (ignored otherwise).  With the Taco1 vocoder the cut spectrograms of the whole call go through ONE batched Griffin-Lim on the GPU
+    def Inference(self, path_List, text_List, file_Prefix=None, speaker_Mel_List=None, masks=None, export=True, wav=None, griffin_lim_seed=0, front_end=None, wav_rule=None, wg_arith=None, denoiser_strength=None):
+        """wg_arith and denoiser_strength go to Inference_WaveGlow when hp.Use_Vocoder is WaveGlow (ignored otherwise).  With the Taco1 vocoder the cut spectrograms of the whole call go through ONE batched Griffin-Lim on the GPU
         (Audio.Griffin_Lim_Batch, initial phases from the device generator seeded by `griffin_lim_seed`): res["Wav"] holds one float32
         waveform per sentence (None where none could be made: a cut of one frame, an export error).  wav: None = with the export;
         True = the waveforms without any file (export=False); False = NPZ files only, as if no vocoder leg existed."""
         if len(text_List) != (len(path_List) if speaker_Mel_List is None else len(speaker_Mel_List)):
             raise ValueError("path_List and text_List must have the same length")
         if hp.Use_Vocoder.upper() == "WaveGlow".upper():          # MSTTS_SV.py:295-299
-            return self.Inference_WaveGlow(path_List, text_List, file_Prefix, speaker_Mel_List=speaker_Mel_List, masks=masks, export=export, front_end=front_end, wav_rule=wav_rule, wg_arith=wg_arith)
+            return self.Inference_WaveGlow(path_List, text_List, file_Prefix, speaker_Mel_List=speaker_Mel_List, masks=masks, export=export, front_end=front_end, wav_rule=wav_rule, wg_arith=wg_arith,
+                                           denoiser_strength=denoiser_strength)
         pattern = self.feeder.Get_Inference_Pattern(path_List, text_List, speaker_Mel_List=speaker_Mel_List, front_end=front_end, rule=wav_rule)
         res = self.infer_engine.forward(pattern, masks=masks)
         res["Global_Step"] = self.global_step

@@ -182,9 +182,11 @@ class WaveGlow(DropIn):
             return WavFeeder(device=self.device)
         return WF.WaveGlowFeeder(bank, seed=self.seed, dims=self.engine.d)
 
-    def Inference(self, path_List, file_Prefix=None, wg_arith=None):
+    def Inference(self, path_List, file_Prefix=None, wg_arith=None, denoiser_strength=None):
         """wav -> mel -> WaveGlowEngine (built from the current values) -> WAV files under hp.WaveGlow.Inference.Path/WAV (WaveGlow.py:144-205).
-        wg_arith: the vocoder's arithmetic, "f32" | "bf16" (None: MSTTS_WG_ARITH, else "f32"; WaveGlowEngine.infer)."""
+        wg_arith: the vocoder's arithmetic, "f32" | "bf16" (None: MSTTS_WG_ARITH, else "f32"; WaveGlowEngine.infer).
+        denoiser_strength: the WaveGlow denoiser (WaveGlowEngine.denoise) on the stitched waveforms, before the peak normalisation; None:
+        MSTTS_WG_DENOISE, else off."""
         from scipy.io.wavfile import write
         from .Feeder import load_wav
         mels = []
@@ -194,7 +196,8 @@ class WaveGlow(DropIn):
             sig = sig / peak * 0.99 if peak > 0 else sig
             mels.append(signal_mel(sig, self.device).astype(np.float32))
         eng = WaveGlowEngine(self.engine.d, device=self.device, values=self.engine.values())
-        wavs = vocode(eng, mels, hp.WaveGlow.Inference.Mel_Split_Length, hp.WaveGlow.Inference.Batch_Size, arith=wg_arith)
+        wavs = vocode(eng, mels, hp.WaveGlow.Inference.Mel_Split_Length, hp.WaveGlow.Inference.Batch_Size, arith=wg_arith,
+                      denoise=denoiser_strength)
         out_dir = os.path.join(hp.WaveGlow.Inference.Path, "WAV").replace("\\", "/")
         os.makedirs(out_dir, exist_ok=True)
         prefix = file_Prefix or "GS_{}".format(self.engine.global_step)

@@ -231,6 +231,9 @@ SIGNATURES = {
     "mstts_griffin_lim_supported": (i32, [i32, i32, i32]),
     "mstts_griffin_lim_ws_floats": (i64, [i64, i32, i32]),
     "mstts_griffin_lim": (i32, [vp, vp, vp, P(i64), vp, i32, vp, vp, i32, i32, i32, f32, f32, f32, i32, vp, vp, vp]),
+    "mstts_wg_denoise_supported": (i32, [i32, i32, i32]),
+    "mstts_wg_denoise_ws_floats": (i64, [i64, i32]),
+    "mstts_wg_denoise": (i32, [vp, P(i64), vp, vp, i32, vp, f32, vp, vp, i32, i32, i32, vp, vp, vp]),
     "mstts_wav_resample_supported": (i32, [i32, i32]),
     "mstts_wav_resample_taps": (i32, [i32, i32]),
     "mstts_wav_resample": (i32, [vp, vp, vp, i32, i64, vp, i32, i32, vp, vp]),

@@ -40,6 +40,21 @@ def resolve_arith(arith, default=None):
     return "f32"
 
 
+def resolve_denoise(strength, default=None):
+    """The denoiser's strength: the argument, else the caller's default, else MSTTS_WG_DENOISE, else 0.0 (off).  Negative or not a
+    number: ValueError."""
+    for v, what in ((strength, "denoiser strength"), (default, "denoiser strength"), (os.environ.get("MSTTS_WG_DENOISE") or None, "MSTTS_WG_DENOISE")):
+        if v is not None:
+            try:
+                f = float(v)
+            except (TypeError, ValueError):
+                raise ValueError("%s must be a number, not %r" % (what, v))
+            if not (0.0 <= f < float("inf")):
+                raise ValueError("%s must be finite and not negative, not %r" % (what, v))
+            return f
+    return 0.0
+
+
 @dataclass
 class WGDims:
     """hp.WaveGlow / hp.Sound.Mel_Dim (Hyper_Parameters.py:196-210)."""
@@ -242,6 +257,7 @@ class WaveGlowEngine:
     def load(self, v):
         d = self.d
         self._packed = None
+        self._bias = {}            # bias_spectrum's cache: a property of the checkpoint
         # conv2d_transpose kernel [1,K,Cout,Cin] -> [Cin, K*Cout]: one GEMM gives every tap product of a frame
         wt = np.asarray(v[P_WG + "conv2d_transpose/kernel"], np.float64)[0]
         self.up_w = self._dev(wt.transpose(2, 0, 1).reshape(d.n_mel, d.up_k * d.n_mel))
@@ -375,6 +391,55 @@ class WaveGlowEngine:
         return audio.view(N, Lg * d.groups)
 
 
+    # ------------------------------------------------------------------ denoiser
+    def bias_spectrum(self, arith=None, n_fft=1024, hop=256, win=1024, frames=88, mel_value=0.0):
+        """The network's stationary bias as a magnitude spectrum, device tensor [n_fft / 2 + 1]: `infer` on a constant mel
+        [1, frames, n_mel] of mel_value with every latent injected as zeros, then |X_0| of that waveform - frame 0 of the STFT only, as the
+        published denoiser takes it - through mstts_stft_fft (raw magnitudes, no pre-emphasis).  Cached per argument tuple and resolved
+        arithmetic; load() drops the cache."""
+        from . import Audio
+        d = self.d
+        key = (resolve_arith(arith, self.arith), int(n_fft), int(hop), int(win), int(frames), float(mel_value))
+        if key in self._bias:
+            return self._bias[key]
+        n_fft, hop, win, frames = key[1:5]
+        L = (frames - 1) * d.up_stride + d.up_k
+        if L <= n_fft // 2:
+            raise ValueError("the bias waveform of %d frames has %d samples, shorter than the STFT's reflect padding (%d samples)" % (frames, L, n_fft // 2))
+        if not lib.load().mstts_stft_fft_supported(n_fft, win) or hop < 1:
+            raise ValueError("bias_spectrum: n_fft must be a power of two in [512, 4096] and win <= n_fft (n_fft %d, hop %d, win %d)" % (n_fft, hop, win))
+        zeros = lambda width: torch.zeros(1, L // d.groups, width, dtype=torch.float32, device=self.device)
+        noise = {"z": zeros(d.z_channels)}
+        noise.update({"early_%d" % f: zeros(d.early_size) for f in range(d.flows) if f % d.early_every == 0 and f > 0})
+        mel = torch.full((1, frames, d.n_mel), key[5], dtype=torch.float32, device=self.device)
+        wav = self.infer(mel, noise=noise, arith=key[0]).reshape(-1).contiguous()
+        hann, tw = Audio._fft_constants_samples(n_fft, win, str(self.device))
+        offs = torch.tensor([0, L, 0, 1], dtype=torch.int64, device=self.device)
+        spec = torch.empty(n_fft // 2 + 1, dtype=torch.float32, device=self.device)
+        call("mstts_stft_fft", ptr(wav), ptr(offs), ptr(offs, 2), 1, 0.0, ptr(hann), ptr(tw), None, None, n_fft, hop, win, 0, 1.0, 0.0, None,
+             ptr(spec), 1, None, None, 0.0, 2)
+        self._bias[key] = spec
+        return spec
+
+    def denoise(self, wavs, strength, arith=None, n_fft=1024, hop=256, win=1024, frames=88, mel_value=0.0, return_tensor=False):
+        """Audio.spectral_denoise_batch with this network's bias spectrum: strength * bias_spectrum(...) subtracted from the magnitude of
+        every STFT bin of every waveform (list of arrays or device tensors), one device call -> list of float32 waveforms of the same lengths."""
+        from . import Audio
+        bias = self.bias_spectrum(arith, n_fft, hop, win, frames, mel_value)
+        return Audio.spectral_denoise_batch(wavs, bias, strength, n_fft, hop, win, device=self.device, return_tensor=return_tensor)
+
+    def _denoise_rows(self, rows, index, strength, arith=None, n_fft=1024, hop=256, win=1024, frames=88, mel_value=0.0):
+        """`denoise` on rows [chunks, L] of a device tensor of which waveform i is the rows index[i][0] .. index[i][1]: consecutive rows
+        are one contiguous range each, which is the packed layout of mstts_wg_denoise as it stands - no copy -> list of host arrays."""
+        from . import Audio
+        if not Audio.spectral_denoise_supported(n_fft, hop, win):
+            return self.denoise([rows[a:b].reshape(-1) for a, b in index], strength, arith, n_fft, hop, win, frames, mel_value)
+        assert rows.is_contiguous() and [a for a, _ in index[1:]] == [b for _, b in index[:-1]] and index[0][0] == 0 and index[-1][1] == rows.shape[0]
+        bias = self.bias_spectrum(arith, n_fft, hop, win, frames, mel_value)
+        hann, tw = Audio._fft_constants_samples(int(n_fft), int(win), str(self.device))
+        return Audio._denoise_packed(rows.reshape(-1), [(b - a) * rows.shape[1] for a, b in index], bias, strength, n_fft, hop, win, hann, tw, False)
+
+
 # ---- MSTTS_SV.Inference_WaveGlow host logic (MSTTS_SV.py:335-375,452-458) ----------------------------------------------
 def split_mels(mels, split):
     """Every mel cut into `split`-frame chunks; index[i] = (first, last+1) chunk of utterance i."""
@@ -387,9 +452,13 @@ def split_mels(mels, split):
     return chunks, index
 
 
-def vocode(engine: WaveGlowEngine, mels, split, batch, noise_seed=None, arith=None):
+def vocode(engine: WaveGlowEngine, mels, split, batch, noise_seed=None, arith=None, denoise=None, denoise_args=None):
     """Chunk, zero-pad to the longest chunk, run `batch` chunks at a time, stitch (the per-chunk tail of kernel - stride
-    samples is NOT trimmed, as in the reference: WaveGlow/Modules.py:179 is commented out)."""
+    samples is NOT trimmed, as in the reference: WaveGlow/Modules.py:179 is commented out).  denoise: the denoiser's strength
+    (`resolve_denoise`: None = MSTTS_WG_DENOISE, else off); when positive the stitched utterances stay on the device, go through
+    WaveGlowEngine.denoise in ONE call (denoise_args: its n_fft / hop / win / frames / mel_value, where not the defaults) and are copied
+    to the host once.  Off, nothing of that runs and the result is what it was without the argument, bit for bit."""
+    strength = resolve_denoise(denoise)
     chunks, index = split_mels(mels, split)
     tmax = max(c.shape[0] for c in chunks)
     pat = np.zeros((len(chunks), tmax, engine.d.n_mel), np.float32)
@@ -398,7 +467,10 @@ def vocode(engine: WaveGlowEngine, mels, split, batch, noise_seed=None, arith=No
     wavs = []
     for b0 in range(0, len(chunks), batch):
         seed = None if noise_seed is None else noise_seed + b0
-        wavs.append(engine.infer(pat[b0:b0 + batch], seed=seed, arith=arith).cpu().numpy())
+        wav = engine.infer(pat[b0:b0 + batch], seed=seed, arith=arith)        # (held by reference: infer drops its own list of buffers at each call)
+        wavs.append(wav if strength > 0 else wav.cpu().numpy())
+    if strength > 0:
+        return engine._denoise_rows(torch.cat(wavs, dim=0), index, strength, arith=arith, **(denoise_args or {}))
     allw = np.concatenate(wavs, axis=0)
     return [allw[a:b].reshape(-1) for a, b in index]
 
