@@ -6,6 +6,7 @@ computation itself is ``mstts_stft_mel`` in libmstts_hip.so.
 """
 from __future__ import annotations
 
+import ctypes
 import functools
 from typing import Callable, NamedTuple
 
@@ -328,25 +329,39 @@ def spectral_denoise_batch(wavs, bias, strength, n_fft=1024, hop=256, win=1024, 
     return _denoise_packed(cat, lens, up(bias).contiguous(), strength, n_fft, hop, win, hann, tw, return_tensor)
 
 
+def _offsets(counts):
+    return np.concatenate([[0], np.cumsum(np.asarray(counts, np.int64).reshape(-1))]).astype(np.int64)
+
+
+def _packed_offsets(lens, frames, dev, host):
+    """Layout of a packed batch, utterance i owning lens[i] samples and frames[i] frames -> (wav_off, frame_off, offs, host_off): the two
+    int64 offset arrays of len(lens) + 1 entries, both on the device in one upload (offs [2, n + 1]: row 0 the samples), and the one named
+    by `host` ("wav" or "frame") as the ctypes array the entry point checks every shape from before it launches anything."""
+    wav_off, frame_off = _offsets(lens), _offsets(frames)
+    return (wav_off, frame_off, torch.as_tensor(np.stack([wav_off, frame_off])).to(dev),
+            (ctypes.c_int64 * (len(lens) + 1))(*(wav_off if host == "wav" else frame_off).tolist()))
+
+
+def _cut_packed(packed, off, return_tensor):
+    """The per-utterance list of a packed device result: views of it with return_tensor, else NumPy copies of one read-back (which
+    synchronises: the call's inputs and workspace may go once it returns)."""
+    if not return_tensor:
+        packed = packed.cpu().numpy()
+    parts = [packed[int(a):int(b)] for a, b in zip(off[:-1], off[1:])]
+    return parts if return_tensor else [p.copy() for p in parts]
+
+
 def _denoise_packed(cat, lens, bias, strength, n_fft, hop, win, hann, tw, return_tensor):
     """The device call of `spectral_denoise_batch` on waveforms of the lengths `lens` that already lie back to back in `cat`."""
-    import ctypes
     dev, nw = cat.device, len(lens)
     if bias.numel() != n_fft // 2 + 1:
         raise ValueError("bias must hold %d magnitudes" % (n_fft // 2 + 1))
-    wav_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-    frame_off = np.concatenate([[0], np.cumsum([1 + n // hop for n in lens])]).astype(np.int64)
-    offs = torch.as_tensor(np.stack([wav_off, frame_off])).to(dev)
-    total = int(frame_off[-1])
-    ws = torch.empty(max(int(lib.load().mstts_wg_denoise_ws_floats(total, win)), 1), dtype=torch.float32, device=dev)
+    wav_off, frame_off, offs, host_off = _packed_offsets(lens, [1 + n // hop for n in lens], dev, "wav")
+    ws = torch.empty(max(int(lib.load().mstts_wg_denoise_ws_floats(int(frame_off[-1]), win)), 1), dtype=torch.float32, device=dev)
     out = torch.empty_like(cat)
-    host_off = (ctypes.c_int64 * (nw + 1))(*[int(v) for v in wav_off])
     lib.call("mstts_wg_denoise", lib.ptr(cat), host_off, lib.ptr(offs), lib.ptr(offs, nw + 1), nw, lib.ptr(bias), float(strength),
              lib.ptr(hann), lib.ptr(tw), int(n_fft), int(hop), int(win), lib.ptr(ws), lib.ptr(out))
-    if return_tensor:
-        return [out[int(a):int(b)] for a, b in zip(wav_off[:-1], wav_off[1:])]
-    host = out.cpu().numpy()                                  # (synchronises: cat, ws may go once this returns)
-    return [host[int(a):int(b)].copy() for a, b in zip(wav_off[:-1], wav_off[1:])]
+    return _cut_packed(out, wav_off, return_tensor)
 
 
 def inv_preemphasis(x, preemphasis=0.97):
@@ -401,9 +416,7 @@ def griffin_lim_offsets(frames, hop):
     frame_off[i] .. frame_off[i + 1] of the concatenated spectrograms and, T_i frames giving hop (T_i - 1) samples (istft with the
     centre padding removed), the samples wav_off[i] .. wav_off[i + 1] of the concatenated waveforms."""
     frames = np.asarray(frames, np.int64).reshape(-1)
-    frame_off = np.concatenate([[0], np.cumsum(frames)]).astype(np.int64)
-    wav_off = np.concatenate([[0], np.cumsum(hop * np.maximum(frames - 1, 0))]).astype(np.int64)
-    return frame_off, wav_off
+    return _offsets(frames), _offsets(hop * np.maximum(frames - 1, 0))
 
 
 def griffin_lim_phases(frames, num_freq, rng):
@@ -474,20 +487,13 @@ def griffin_lim_batch(spectrograms, num_freq, frame_shift_ms, frame_length_ms, s
     up = lambda a: (a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a, np.float32))).to(dev, torch.float32)
     spec = torch.cat([up(s) for s in spectrograms]).contiguous()
     u = torch.cat([up(p).t() for p in phase]).contiguous() if phase is not None else None
-    frame_off, wav_off = griffin_lim_offsets(frames, hop)
-    total = int(frame_off[-1])
-    foff = torch.as_tensor(frame_off).to(dev)
+    wav_off, frame_off, offs, host_off = _packed_offsets([hop * (t - 1) for t in frames], frames, dev, "frame")       # = griffin_lim_offsets
     sd = torch.as_tensor(np.asarray([s % (1 << 64) for s in seeds], np.uint64).view(np.int64)).to(dev) if u is None else None
-    ws = torch.empty(int(lib.load().mstts_griffin_lim_ws_floats(total, n_fft, win)), dtype=torch.float32, device=dev)
+    ws = torch.empty(int(lib.load().mstts_griffin_lim_ws_floats(int(frame_off[-1]), n_fft, win)), dtype=torch.float32, device=dev)
     wav = torch.empty(int(wav_off[-1]), dtype=torch.float32, device=dev)
-    import ctypes
-    host_off = (ctypes.c_int64 * (nu + 1))(*[int(v) for v in frame_off])
-    lib.call("mstts_griffin_lim", lib.ptr(spec), lib.ptr(u), lib.ptr(sd), host_off, lib.ptr(foff), nu, lib.ptr(hann), lib.ptr(tw), n_fft, hop,
-             win, float(power), float(ref_level_db), 0.97, int(griffin_lim_iters), lib.ptr(ws), lib.ptr(wav))
-    if return_tensor:
-        return [wav[int(a):int(b)] for a, b in zip(wav_off[:-1], wav_off[1:])]
-    host = wav.cpu().numpy()                                  # (synchronises: spec, u, ws may go once this returns)
-    return [host[int(a):int(b)].copy() for a, b in zip(wav_off[:-1], wav_off[1:])]
+    lib.call("mstts_griffin_lim", lib.ptr(spec), lib.ptr(u), lib.ptr(sd), host_off, lib.ptr(offs, nu + 1), nu, lib.ptr(hann), lib.ptr(tw), n_fft,
+             hop, win, float(power), float(ref_level_db), 0.97, int(griffin_lim_iters), lib.ptr(ws), lib.ptr(wav))
+    return _cut_packed(wav, wav_off, return_tensor)
 
 
 def Griffin_Lim_Batch(spectrograms, phase=None, rng=None, seed=0, device="cuda", return_tensor=False):

@@ -52,7 +52,7 @@ __global__ __launch_bounds__(256) void stft_fft_kernel(const float* __restrict__
     extern __shared__ __attribute__((aligned(16))) float2 fft_lds[];
     const long g = blockIdx.x;
     int w = 0;
-    for (int lo = 0, hi = nw; hi - lo > 1;) {            // uniform binary search: frame_off[w] <= g
+    for (int lo = 0, hi = nw; hi - lo > 1;) {            // = stft_owner (csrc/stft_parts.h), kept as text: any call moves this kernel's code
         const int mid = (lo + hi) >> 1;
         if (frame_off[mid] <= g) lo = mid; else hi = mid;
         w = lo;

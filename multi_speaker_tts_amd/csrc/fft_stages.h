@@ -1,4 +1,5 @@
-// The in-LDS FFT shared by stft_fft_kernel (csrc/audio.hip) and griffin_lim_kernel (csrc/griffin_lim.hip).
+// The in-LDS FFT of every STFT kernel: stft_frame_body (csrc/stft_frame.h: stft_fft_kernel, stft_bank_batch_kernel, wg_crop_batch_kernel)
+// and the round trips built from csrc/stft_parts.h, griffin_lim_kernel (csrc/griffin_lim.hip) and wg_denoise_frames_kernel (csrc/wg_denoise.hip).
 #pragma once
 #include "common.h"
 

@@ -15,39 +15,13 @@
 // the half-size complex FFT in LDS of stft_fft_kernel (csrc/audio.hip): Stockham radix 4 (+ one radix-2 stage), ping-pong buffers,
 // fp64-built twiddles; the inverse runs the same forward stages on conjugated input.  Bin pairs (k, n_fft/2 - k) stay in one thread
 // from the forward real-FFT split through phase, magnitude and the inverse merge, so the spectrum never leaves registers.
+// A frame is the skeleton wg_denoise_frames_kernel (csrc/wg_denoise.hip) has too, from the pieces of csrc/stft_parts.h: stft_owner,
+// fill the frame (here: stft_ola of the previous frames), fft_stockham_stages, rfft_split / rfft_merge (between them, here: phase
+// times amplitude), stft_frame_tail.  What this file keeps is its own: the periodic reflection, gl_phase, the amplitudes and the initial phase.
 #include "common.h"
-#include "fft_stages.h"
+#include "stft_parts.h"
 
 namespace mstts {
-
-// utterance of frame g: frame_off[w] <= g < frame_off[w + 1] (uniform binary search, as stft_fft_kernel)
-__device__ __forceinline__ int gl_utterance(const long* __restrict__ frame_off, int nu, long g) {
-    int w = 0;
-    for (int lo = 0, hi = nu; hi - lo > 1;) {
-        const int mid = (lo + hi) >> 1;
-        if (frame_off[mid] <= g) lo = mid; else hi = mid;
-        w = lo;
-    }
-    return w;
-}
-
-// Sample of istft's overlap-add at position q = j + pad - off >= 0 (j the index in the trimmed signal) of an utterance with T
-// frames whose windowed frames start at F: entries of the frames fh - 3 .. fh that exist and cover q, summed in frame order,
-// divided by the window-square sum of exactly those frames where that exceeds float32 tiny (Audio._istft).  fh = q / hop.
-__device__ __forceinline__ float gl_ola(const float* __restrict__ F, const float* __restrict__ window, int q, int fh, int T, int hop, int win) {
-    float v[4], ww[4];
-    const int i0 = q - fh * hop;                             // < hop
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const int f = fh - 3 + c, idx = i0 + (3 - c) * hop;
-        const bool ok = f >= 0 && f < T && idx < win;
-        v[c] = ok ? F[(long)f * win + idx] : 0.f;
-        ww[c] = ok ? window[idx] : 0.f;
-    }
-    const float num = ((v[0] + v[1]) + v[2]) + v[3];
-    const float den = ((ww[0] * ww[0] + ww[1] * ww[1]) + ww[2] * ww[2]) + ww[3] * ww[3];
-    return den > 1.17549435e-38f ? num / den : num;
-}
 
 // X / |X| with (1, 0) for X = 0 (exp(i angle(0))); the components are scaled by a power of two first, so tiny and huge bins keep
 // their direction
@@ -91,7 +65,7 @@ __global__ __launch_bounds__(256) void griffin_lim_kernel(const float* __restric
     float2* bufa = gl_lds;
     float2* bufb = gl_lds + N2;
     const long g = blockIdx.x;
-    const int w = gl_utterance(frame_off, nu, g);
+    const int w = stft_owner(frame_off, nu, g);
     const long f0 = frame_off[w];
     const int f = (int)(g - f0), T = (int)(frame_off[w + 1] - f0);
     const int off = (n_fft - win) >> 1, pad = n_fft >> 1;
@@ -107,7 +81,7 @@ __global__ __launch_bounds__(256) void griffin_lim_kernel(const float* __restric
             if (j >= 0 && j < n) {
                 q = j + pad - off;
                 fh = f + (iw >= hop) + (iw >= 2 * hop) + (iw >= 3 * hop);       // (f hop + iw) / hop, iw < win <= 4 hop
-            } else {                                         // np.pad(mode='reflect'): period 2 (n - 1)
+            } else {                                         // np.pad(mode='reflect'): period 2 (n - 1), not stft_reflect_once: n may be 2
                 const int per = 2 * (n - 1);
                 j %= per;
                 if (j < 0) j += per;
@@ -115,7 +89,7 @@ __global__ __launch_bounds__(256) void griffin_lim_kernel(const float* __restric
                 q = j + pad - off;
                 fh = q / hop;
             }
-            return window[iw] * gl_ola(Fu, window, q, fh, T, hop, win);
+            return window[iw] * stft_ola(Fu, window, q, fh, T, hop, win);
         };
         for (int m = tid; m < N2; m += 256) bufa[m] = make_float2(sample(2 * m), sample(2 * m + 1));
         __syncthreads();
@@ -143,50 +117,32 @@ __global__ __launch_bounds__(256) void griffin_lim_kernel(const float* __restric
         sincospif(2.f * u, &s, &c);
         return make_float2(c, s);
     };
-    // bin pairs (k, N2 - k), 1 <= k <= N2 / 2:  X[k] = E + W^k O,  X[N2 - k] = conj(E - W^k O)  with  E = (Z[k] + conj Z[N2-k]) / 2,
-    // O = -i (Z[k] - conj Z[N2-k]) / 2;  then  Y = A X / |X|  and back:  Z'[k] = E' + i O',  Z'[N2-k] = conj E' + i conj O'  with
-    // E' = (Y[k] + conj Y[N2-k]) / 2,  O' = conj(W^k) (Y[k] - conj Y[N2-k]) / 2
-    for (int k = 1 + tid; k <= (N2 >> 1); k += 256) {
+    for (int k = 1 + tid; k <= (N2 >> 1); k += 256) {        // Y = A X / |X| (the prepare launch: A e^{2 pi i u}) on the bin pair (k, N2 - k)
         const int kc = N2 - k;
         const float2 t = tw[k];
-        float2 pk, pc;
+        float2 pk, pc, zk, zc;
         if (FIRST) { pk = initial(k); pc = initial(kc); }
         else {
-            const float2 zk = Z[k], zc = Z[kc];
-            const float er = 0.5f * (zk.x + zc.x), ei = 0.5f * (zk.y - zc.y);
-            const float orr = 0.5f * (zk.y + zc.y), oi = -0.5f * (zk.x - zc.x);
-            const float tr = orr * t.x - oi * t.y, ti = orr * t.y + oi * t.x;
-            pk = gl_phase(er + tr, ei + ti);
-            pc = gl_phase(er - tr, -(ei - ti));
+            float2 xk, xc;
+            rfft_split(Z[k], Z[kc], t, xk, xc);
+            pk = gl_phase(xk.x, xk.y); pc = gl_phase(xc.x, xc.y);
         }
         const float ak = amp(k), ac = amp(kc);
-        const float2 yk = make_float2(ak * pk.x, ak * pk.y), yc = make_float2(ac * pc.x, ac * pc.y);
-        const float e2r = 0.5f * (yk.x + yc.x), e2i = 0.5f * (yk.y - yc.y);
-        const float t2r = 0.5f * (yk.x - yc.x), t2i = 0.5f * (yk.y + yc.y);
-        const float o2r = t2r * t.x + t2i * t.y, o2i = t2i * t.x - t2r * t.y;
-        Y[k] = make_float2(e2r - o2i, -(e2i + o2r));
-        if (kc != k) Y[kc] = make_float2(e2r + o2i, -(o2r - e2i));
+        rfft_merge(make_float2(ak * pk.x, ak * pk.y), make_float2(ac * pc.x, ac * pc.y), t, zk, zc);
+        Y[k] = zk;
+        if (kc != k) Y[kc] = zc;
     }
-    if (tid == 0) {                                          // k = 0 and the Nyquist bin: real, irfft ignores their imaginary parts
+    if (tid == 0) {                                          // k = 0 and the Nyquist bin: real
         float p0, pn;
         if (FIRST) { p0 = initial(0).x; pn = initial(N2).x; }
         else {
-            const float2 z0 = Z[0];
-            p0 = gl_phase(z0.x + z0.y, 0.f).x;
-            pn = gl_phase(z0.x - z0.y, 0.f).x;
+            const float2 x = rfft_split_dc(Z[0]);
+            p0 = gl_phase(x.x, 0.f).x; pn = gl_phase(x.y, 0.f).x;
         }
-        const float y0 = amp(0) * p0, yn = amp(N2) * pn;
-        Y[0] = make_float2(0.5f * (y0 + yn), -0.5f * (y0 - yn));
+        Y[0] = rfft_merge_dc(amp(0) * p0, amp(N2) * pn);
     }
     __syncthreads();
-    float2* R = fft_stockham_stages(Y, Y == bufa ? bufb : bufa, tw, N2, n_fft, tid);       // conj of the packed frame, times N2
-    const float scale = 1.0f / (float)N2;
-    float* out = Fout + g * win;
-    for (int iw = tid; iw < win; iw += 256) {
-        const int i = iw + off;
-        const float2 z = R[i >> 1];
-        out[iw] = window[iw] * (((i & 1) ? -z.y : z.x) * scale);
-    }
+    stft_frame_tail(Y, Y == bufa ? bufb : bufa, tw, N2, n_fft, tid, window, off, win, Fout + g * win);
 }
 
 // istft of the last frames: y[j] for every sample of every utterance
@@ -195,15 +151,10 @@ __global__ __launch_bounds__(256) void gl_overlap_add_kernel(const float* __rest
                                                              float* __restrict__ y) {
     const int off = (n_fft - win) >> 1, pad = n_fft >> 1;
     for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += gridDim.x * 256L) {
-        int w = 0;
-        for (int lo = 0, hi = nu; hi - lo > 1;) {            // sample offset of utterance w = hop (frame_off[w] - w)
-            const int mid = (lo + hi) >> 1;
-            if ((frame_off[mid] - mid) * hop <= i) lo = mid; else hi = mid;
-            w = lo;
-        }
+        const int w = stft_owner_by([&](int m) { return (frame_off[m] - m) * hop; }, nu, i);       // sample offset of utterance m
         const long f0 = frame_off[w];
         const int T = (int)(frame_off[w + 1] - f0), j = (int)(i - (f0 - w) * hop), q = j + pad - off;
-        y[i] = gl_ola(F + f0 * win, window, q, q / hop, T, hop, win);
+        y[i] = stft_ola(F + f0 * win, window, q, q / hop, T, hop, win);
     }
 }
 

@@ -3,7 +3,7 @@
 // how a workgroup finds its waveform, its frame and its output rows; the arithmetic is this one body, so both give the same bits.
 #pragma once
 #include "common.h"
-#include "fft_stages.h"
+#include "stft_parts.h"
 
 namespace mstts {
 
@@ -27,10 +27,7 @@ __device__ __forceinline__ void stft_frame_body(float2* fft_lds, const float* __
     const int off = (n_fft - win) >> 1, pad = n_fft >> 1;
     auto sample = [&](int i) -> float {                  // windowed, pre-emphasised, reflect-padded sample i of this frame
         if (i < off || i >= off + win) return 0.f;
-        long j = f * hop + i - pad;
-        if (j < 0) j = -j;
-        if (j >= n) j = 2 * (n - 1) - j;
-        if (j < 0) j = 0;
+        const long j = stft_reflect_once(f * hop + i - pad, n);
         const float prev = j > 0 ? x[j - 1] : 0.f;
         return window[i - off] * (x[j] - coef * prev);
     };
@@ -55,7 +52,8 @@ __device__ __forceinline__ void stft_frame_body(float2* fft_lds, const float* __
         float2* z = fft_stockham_stages(bufa, bufb, tw, N2, n_fft, tid);
         if (z != bufa) { bufb = bufa; bufa = z; }
     }
-    // real-input post-processing -> magnitudes in LDS (bufb is free)
+    // real-input post-processing -> magnitudes in LDS (bufb is free).  rfft_split's rule (csrc/stft_parts.h has the derivation) in a text
+    // of its own: one bin per thread, and E + W^k O summed left to right, not rfft_split's E + (W^k O) - this body's bits are pinned.
     mag = reinterpret_cast<float*>(bufb);
     for (int k = tid; k < NB; k += 256) {
         const float2 zk = bufa[k & (N2 - 1)], zc = bufa[(N2 - k) & (N2 - 1)];

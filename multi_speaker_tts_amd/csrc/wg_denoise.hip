@@ -5,28 +5,17 @@
 //   y[j]   = sum_t (window * irfft(Y_t))[j + pad - t hop] / sum_t window^2[j + pad - t hop]     the frames that exist there, j < n
 //
 // Two launches.  A: a workgroup per frame, every waveform of the batch in the same grid (frame g belongs to waveform w with
-// frame_off[w] <= g < frame_off[w + 1]): reflect-padded framing as stft_frame_body (csrc/stft_frame.h), the half-size complex FFT in
-// LDS (csrc/fft_stages.h), the real-FFT split with the bin pair (k, n_fft/2 - k) in one thread, magnitude / subtract / clamp / rescale
-// on the pair, the inverse merge and the inverse FFT as griffin_lim_kernel (csrc/griffin_lim.hip) does them - the spectrum never
-// leaves registers and LDS - and the `win` windowed samples stored to the workspace [total_frames, win].  B: y[j] for every sample of
-// every waveform, a gather of the at most four workspace entries that cover it, summed in frame order and divided by the window-square
-// sum of exactly those frames: no atomics, one fixed summation order, so a waveform gives the same bits alone and in any batch.
-// The pieces shared in spirit with audio.hip / griffin_lim.hip are restated here: those two files stay byte-identical.
+// frame_off[w] <= g < frame_off[w + 1]), the skeleton griffin_lim_kernel (csrc/griffin_lim.hip) has too, from the pieces of
+// csrc/stft_parts.h: stft_owner, fill the frame (here: the window times the reflect-padded waveform, stft_reflect_once),
+// fft_stockham_stages, rfft_split / rfft_merge with the bin pair (k, n_fft/2 - k) in one thread (between them, here: magnitude /
+// subtract / clamp / rescale, dn_gain) - the spectrum never leaves registers and LDS - and stft_frame_tail, which stores the `win`
+// windowed samples to the workspace [total_frames, win].  B: y[j] for every sample of every waveform, stft_ola: a gather of the at
+// most four workspace entries that cover it, summed in frame order and divided by the window-square sum of exactly those frames: no
+// atomics, one fixed summation order, so a waveform gives the same bits alone and in any batch.
 #include "common.h"
-#include "fft_stages.h"
+#include "stft_parts.h"
 
 namespace mstts {
-
-// index w with off[w] <= v < off[w + 1] (uniform binary search, as stft_fft_kernel)
-__device__ __forceinline__ int dn_owner(const long* __restrict__ off, int nw, long v) {
-    int w = 0;
-    for (int lo = 0, hi = nw; hi - lo > 1;) {
-        const int mid = (lo + hi) >> 1;
-        if (off[mid] <= v) lo = mid; else hi = mid;
-        w = lo;
-    }
-    return w;
-}
 
 // max(|X| - sb, 0) / |X|, the factor X is scaled by; 0 where |X| = 0 (the direction (1, 0) times max(-sb, 0) = 0)
 __device__ __forceinline__ float dn_gain(float re, float im, float sb) {
@@ -44,61 +33,37 @@ __global__ __launch_bounds__(256) void wg_denoise_frames_kernel(const float* __r
     float2* bufa = dn_lds;
     float2* bufb = dn_lds + N2;
     const long g = blockIdx.x;
-    const int w = dn_owner(frame_off, nw, g);
+    const int w = stft_owner(frame_off, nw, g);
     const long f = g - frame_off[w], n = wav_off[w + 1] - wav_off[w];
     const float* x = wav + wav_off[w];
     const int off = (n_fft - win) >> 1, pad = n_fft >> 1;
     auto sample = [&](int i) -> float {                      // windowed, reflect-padded sample i of this frame (n > pad: one reflection)
         if (i < off || i >= off + win) return 0.f;
-        long j = f * hop + i - pad;
-        if (j < 0) j = -j;
-        if (j >= n) j = 2 * (n - 1) - j;
-        if (j < 0) j = 0;
-        return window[i - off] * x[j];
+        return window[i - off] * x[stft_reflect_once(f * hop + i - pad, n)];
     };
     for (int m = tid; m < N2; m += 256) bufa[m] = make_float2(sample(2 * m), sample(2 * m + 1));
     __syncthreads();
     float2* Z = fft_stockham_stages(bufa, bufb, tw, N2, n_fft, tid);
     float2* Y = Z == bufa ? bufb : bufa;                     // conj of the packed inverse input
-    // bin pairs (k, N2 - k), 1 <= k <= N2 / 2:  X[k] = E + W^k O,  X[N2 - k] = conj(E - W^k O)  with  E = (Z[k] + conj Z[N2-k]) / 2,
-    // O = -i (Z[k] - conj Z[N2-k]) / 2;  Y = gain X  and back:  Z'[k] = E' + i O',  Z'[N2-k] = conj E' + i conj O'  with
-    // E' = (Y[k] + conj Y[N2-k]) / 2,  O' = conj(W^k) (Y[k] - conj Y[N2-k]) / 2
-    for (int k = 1 + tid; k <= (N2 >> 1); k += 256) {
+    for (int k = 1 + tid; k <= (N2 >> 1); k += 256) {        // Y = gain X on the bin pair (k, N2 - k)
         const int kc = N2 - k;
         const float2 t = tw[k];
-        const float2 zk = Z[k], zc = Z[kc];
-        const float er = 0.5f * (zk.x + zc.x), ei = 0.5f * (zk.y - zc.y);
-        const float orr = 0.5f * (zk.y + zc.y), oi = -0.5f * (zk.x - zc.x);
-        const float tr = orr * t.x - oi * t.y, ti = orr * t.y + oi * t.x;
-        const float xkr = er + tr, xki = ei + ti, xcr = er - tr, xci = -(ei - ti);
-        const float gk = dn_gain(xkr, xki, strength * bias[k]), gc = dn_gain(xcr, xci, strength * bias[kc]);
-        const float2 yk = make_float2(gk * xkr, gk * xki), yc = make_float2(gc * xcr, gc * xci);
-        const float e2r = 0.5f * (yk.x + yc.x), e2i = 0.5f * (yk.y - yc.y);
-        const float t2r = 0.5f * (yk.x - yc.x), t2i = 0.5f * (yk.y + yc.y);
-        const float o2r = t2r * t.x + t2i * t.y, o2i = t2i * t.x - t2r * t.y;
-        Y[k] = make_float2(e2r - o2i, -(e2i + o2r));
-        if (kc != k) Y[kc] = make_float2(e2r + o2i, -(o2r - e2i));
+        float2 xk, xc, zk, zc;
+        rfft_split(Z[k], Z[kc], t, xk, xc);
+        const float gk = dn_gain(xk.x, xk.y, strength * bias[k]), gc = dn_gain(xc.x, xc.y, strength * bias[kc]);
+        rfft_merge(make_float2(gk * xk.x, gk * xk.y), make_float2(gc * xc.x, gc * xc.y), t, zk, zc);
+        Y[k] = zk;
+        if (kc != k) Y[kc] = zc;
     }
     if (tid == 0) {                                          // k = 0 and the Nyquist bin: real
-        const float2 z0 = Z[0];
-        const float x0 = z0.x + z0.y, xn = z0.x - z0.y;
-        const float y0 = x0 * dn_gain(x0, 0.f, strength * bias[0]), yn = xn * dn_gain(xn, 0.f, strength * bias[N2]);
-        Y[0] = make_float2(0.5f * (y0 + yn), -0.5f * (y0 - yn));
+        const float2 x = rfft_split_dc(Z[0]);
+        Y[0] = rfft_merge_dc(x.x * dn_gain(x.x, 0.f, strength * bias[0]), x.y * dn_gain(x.y, 0.f, strength * bias[N2]));
     }
     __syncthreads();
-    float2* R = fft_stockham_stages(Y, Y == bufa ? bufb : bufa, tw, N2, n_fft, tid);       // conj of the packed frame, times N2
-    const float scale = 1.0f / (float)N2;
-    float* out = F + g * win;
-    for (int iw = tid; iw < win; iw += 256) {
-        const int i = iw + off;
-        const float2 z = R[i >> 1];
-        out[iw] = window[iw] * (((i & 1) ? -z.y : z.x) * scale);
-    }
+    stft_frame_tail(Y, Y == bufa ? bufb : bufa, tw, N2, n_fft, tid, window, off, win, F + g * win);
 }
 
-// istft with length = n: sample j of waveform w sits at q = j + pad - off of the overlap-add; the frames fh - 3 .. fh (fh = q / hop)
-// that exist and cover q are summed in frame order and divided by the window-square sum of exactly those frames where that exceeds
-// float32 tiny (gl_ola of csrc/griffin_lim.hip, restated).
+// istft with length = n: sample j of waveform w sits at q = j + pad - off of the overlap-add (stft_ola, fh = q / hop)
 __global__ __launch_bounds__(256) void wg_denoise_gather_kernel(const float* __restrict__ F, const long* __restrict__ wav_off,
                                                                 const long* __restrict__ frame_off, int nw,
                                                                 const float* __restrict__ window, int n_fft, int hop, int win, long first,
@@ -106,22 +71,10 @@ __global__ __launch_bounds__(256) void wg_denoise_gather_kernel(const float* __r
     const int off = (n_fft - win) >> 1, pad = n_fft >> 1;
     for (long r = blockIdx.x * 256L + threadIdx.x; r < total; r += gridDim.x * 256L) {
         const long i = first + r;
-        const int w = dn_owner(wav_off, nw, i);
+        const int w = stft_owner(wav_off, nw, i);
         const long f0 = frame_off[w];
-        const int T = (int)(frame_off[w + 1] - f0), q = (int)(i - wav_off[w]) + pad - off, fh = q / hop;
-        const float* Fw = F + f0 * win;
-        const int i0 = q - fh * hop;                         // < hop
-        float v[4], ww[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const int f = fh - 3 + c, idx = i0 + (3 - c) * hop;
-            const bool ok = f >= 0 && f < T && idx < win;
-            v[c] = ok ? Fw[(long)f * win + idx] : 0.f;
-            ww[c] = ok ? window[idx] : 0.f;
-        }
-        const float num = ((v[0] + v[1]) + v[2]) + v[3];
-        const float den = ((ww[0] * ww[0] + ww[1] * ww[1]) + ww[2] * ww[2]) + ww[3] * ww[3];
-        y[i] = den > 1.17549435e-38f ? num / den : num;
+        const int T = (int)(frame_off[w + 1] - f0), q = (int)(i - wav_off[w]) + pad - off;
+        y[i] = stft_ola(F + f0 * win, window, q, q / hop, T, hop, win);
     }
 }
 
