@@ -538,6 +538,37 @@ int mstts_wg_denoise(const float* wav, const int64_t* wav_off_host, const int64_
                      const float* bias, float strength, const float* window, const float* twiddle, int32_t n_fft, int32_t hop,
                      int32_t win, float* ws, float* out, mstts_stream_t s);
 
+/* Exact t-SNE into two dimensions (csrc/tsne.hip; tsne.tsne_host is its fp64 statement, stage by stage).  fp32, plain expf / logf /
+ * division, fixed-order reductions and no floating-point atomics: the same inputs give the same bits.  Everything is enqueued on the
+ * stream, nothing synchronises, no kernel waits on another workgroup; parameters are checked on the host before any launch.
+ * Envelope (mstts_tsne_supported): 4 <= n <= 4096, 1 <= dim <= 1024, 1 <= perplexity < n.
+ *
+ * mstts_tsne_affinities: X [n, dim] with row pitch `pitch` (floats) -> the joint probabilities P [n, n] and the precisions beta [n].
+ *   Squared Euclidean distances; per row the search of scikit-learn's _binary_search_perplexity (beta = 1, doubled or halved until
+ *   bracketed, then bisected, at most 100 evaluations, done at |H - ln perplexity| <= 1e-5, a zero row sum replaced by 1e-8; the row is
+ *   the one of the last evaluated beta; the row's smallest distance is subtracted from all of them first, which changes neither the row nor
+ *   H and keeps float32's exp from underflowing for the nearest neighbour, so the zero-sum case cannot arise); P = max((C + C^T) / sum, 2.220446e-16), symmetric bit for bit, the diagonal at that floor.
+ *   ws = mstts_tsne_affinities_ws_floats(n) floats.  Two launches.
+ * mstts_tsne_iterate: n_iters iterations, numbered first_iter ..., of scikit-learn's gradient descent on the exact KL gradient
+ *   g_i = 4 sum_j (e p_ij - num_ij / Z) num_ij (y_i - y_j), num_ij = 1 / (1 + |y_i - y_j|^2), Z = sum_{i != j} num_ij, on the state
+ *   Y / update / gains [n, 2] in place: gains += 0.2 where update g < 0, else gains *= 0.8, floor 0.01; update = momentum update -
+ *   learning_rate gains g; Y += update.  Iterations below exaggeration_iters use e = early_exaggeration and momentum 0.5, the others
+ *   e = 1 and momentum 0.8; iteration exaggeration_iters itself starts from update = 0, gains = 1 whatever the buffers hold (scikit-learn
+ *   enters its second stage that way).  No recentring, no early stop.  Every iteration it with (it + 1) % 50 == 0, and the last one,
+ *   appends (KL(eP || Q), |g|_2) to history [history_slots, 2]; mstts_tsne_history_slots says how many that will be.  grad [n, 2], where not
+ *   null, receives every iteration's gradient (the last one's remains).  ws =
+ *   mstts_tsne_iterate_ws_floats(n) floats, 16-byte aligned.  Two launches per iteration (row sums per wave; one workgroup that sums Z and
+ *   steps the state): 4 n^2 bytes of P read, 8 n floats written and read back. */
+int mstts_tsne_supported(int64_t n, int64_t dim, double perplexity);
+int64_t mstts_tsne_affinities_ws_floats(int64_t n);
+int64_t mstts_tsne_iterate_ws_floats(int64_t n);
+int32_t mstts_tsne_history_slots(int32_t first_iter, int32_t n_iters);
+int mstts_tsne_affinities(const float* X, int64_t pitch, int32_t n, int32_t dim, float perplexity, float* ws, float* P, float* beta,
+                          mstts_stream_t s);
+int mstts_tsne_iterate(const float* P, int32_t n, float* Y, float* update, float* gains, int32_t first_iter, int32_t n_iters,
+                       int32_t exaggeration_iters, float early_exaggeration, float learning_rate, float* ws, float* history,
+                       int32_t history_slots, float* grad, mstts_stream_t s);
+
 /* Waveform front end: what Feeder.load_wav does to decoded samples, for nw waveforms at once (csrc/wav_front_end.hip).  Waveforms lie
  * back to back; every offset array is a DEVICE array of nw + 1 int64 entries, as mstts_stft_fft takes them.  fp32; everything is
  * enqueued on the stream, nothing synchronises; parameters are checked on the host before any launch (MSTTS_ERR_SHAPE).

@@ -35,6 +35,63 @@ def Embedding_Value(embeddings, labels):
     return np.mean(between) / np.mean(within)
 
 
+TSNE_COLORS = ("r", "g", "b", "c", "m", "y", "k", "w", "orange", "purple")      # one per displayed label: at most ten
+TSNE_PERPLEXITY = 30.0                                                           # scikit-learn's default, what the reference's TSNE() ran with
+
+
+def export_tsne(embedding_Array, label_List, global_Step, out_Dir, file_Name="TSNE", tsne_fn=None):
+    """The part of `Speaker_Embedding.Export_TSNE` that needs no engine: `Embedding_Value` of the embeddings, their 2-D t-SNE map by
+    tsne_fn(X, perplexity=..., seed=0, return_info=True) -> (Y, info) (`tsne.tsne`, or `tsne.tsne_host` where there is no GPU),
+    out_Dir/<file_Name>.npz (Y, labels, value, kl_divergence, global_Step) always and, when matplotlib imports, the reference's picture
+    out_Dir/<file_Name>.PNG: a 10 x 10 inch scatter of the map, the first ten labels in SORTED order (the reference takes the first ten of
+    a set(), an order that changes from process to process) in its colours with black edges, a legend, and the title "Global step: ...
+    t-SNE Result    V: ...".  The perplexity is 30, or min(30, (N - 1) / 3) where 30 >= N (printed; scikit-learn would raise).  Returns
+    {"value", "title", "perplexity", "kl_divergence", "npz", "png"} (png None without matplotlib), or None when the directory or a file
+    cannot be written (an OSError: "export skipped", printed)."""
+    X = np.asarray(embedding_Array, np.float32)
+    labels = [str(x) for x in label_List]
+    n = X.shape[0]
+    if len(labels) != n:
+        raise ValueError("%d labels for %d embeddings" % (len(labels), n))
+    value = float(Embedding_Value(X, labels))
+    perplexity = TSNE_PERPLEXITY
+    if n < 4 or perplexity >= n:
+        perplexity = min(TSNE_PERPLEXITY, (n - 1) / 3.0)
+        print("Export_TSNE: %d embeddings, perplexity %g instead of %g" % (n, perplexity, TSNE_PERPLEXITY))
+    if n >= 2:
+        Y, info = tsne_fn(X, perplexity=perplexity, seed=0, return_info=True)
+        kl = float(info["kl_divergence"])
+    else:
+        Y, kl = np.zeros((n, 2), np.float32), float("nan")
+    title = "Global step: {}    t-SNE Result    V: {:0.5f}".format(global_Step, value)
+    result = {"value": value, "title": title, "perplexity": perplexity, "kl_divergence": kl, "npz": None, "png": None}
+    try:
+        os.makedirs(out_Dir, exist_ok=True)
+        result["npz"] = os.path.join(out_Dir, "{}.npz".format(file_Name)).replace("\\", "/")
+        np.savez(result["npz"], Y=Y, labels=np.asarray(labels), value=value, kl_divergence=kl, global_Step=int(global_Step))
+        try:
+            from matplotlib.backends.backend_agg import FigureCanvasAgg
+            from matplotlib.figure import Figure
+        except ImportError:
+            print("Export_TSNE: matplotlib is not installed, no picture; the map is in %s" % result["npz"])
+            return result
+        fig = Figure(figsize=(10, 10))
+        FigureCanvasAgg(fig)
+        ax = fig.add_subplot(111)
+        for speaker, color in zip(sorted(set(labels)), TSNE_COLORS):
+            mask = np.asarray([x == speaker for x in labels])
+            ax.scatter(Y[mask, 0], Y[mask, 1], c=color, edgecolors="k", label=speaker)
+        ax.set_title(title)
+        fig.tight_layout()
+        ax.legend()
+        result["png"] = os.path.join(out_Dir, "{}.PNG".format(file_Name)).replace("\\", "/")
+        fig.savefig(result["png"], format="png")
+    except OSError as e:
+        print("Export_TSNE: export skipped (%s)" % e)
+        return None
+    return result
+
+
 class Speaker_Embedding(DropIn):
     HP, FILE, SCOPE = "Speaker_Embedding", "speaker_embedding.pt", "speaker_embedding"
     COLUMNS = (("Learning rate: {:0.6f}", "Learning_Rate"), ("Loss: {:0.5f}", "Loss"))
@@ -84,7 +141,7 @@ class Speaker_Embedding(DropIn):
         if (result["Global_Step"] + 1) % hp.Speaker_Embedding.Train.Inference_Timing == 0 and os.path.exists(INFERENCE_IN_TRAIN_FILE):
             with open(INFERENCE_IN_TRAIN_FILE, "r") as f:
                 label_List, path_List = list(zip(*[line.strip().split("\t") for line in f.readlines() if line.strip()]))
-            self.Inference(list(path_List), label_List=list(label_List))
+            self.Inference(list(path_List), export_TSNE=True, label_List=list(label_List))
             print("Global step: {}    Embedding value: {:0.5f}".format(result["Global_Step"] + 1, self.embedding_Value))
 
     def _wav_mels(self, path_List):
@@ -100,8 +157,12 @@ class Speaker_Embedding(DropIn):
         normalisation (Speaker_Embedding/Modules.py:127-137; Feeder.py:105-160).  path_or_mel_List: [T_i, 80] mel arrays - one forward
         for all, as ever - or wav paths (Speaker_Embedding.py:127-150): hp.Speaker_Embedding.Inference.Max_Embedding_per_Batch files per
         forward, each batch normalised as a whole like in the reference, the results stacked.  With a label_List the between / within
-        ratio of the result is left in `embedding_Value` (`Embedding_Value`); export_TSNE is accepted, the t-SNE picture is not drawn."""
+        ratio of the result is left in `embedding_Value` (`Embedding_Value`).  export_TSNE (needs a label_List: ValueError without) also
+        draws the reference's picture of them, `Export_TSNE` with file_Name 'GS_<global step>'; the returned array and `embedding_Value`
+        are the same with and without it."""
         from .inference import InferEngine
+        if export_TSNE and label_List is None:
+            raise ValueError("export_TSNE needs a label_List")
         if self._infer is None:
             self._infer = InferEngine(self.engine.d, device=self.device, params=self.params)
         items = list(path_or_mel_List)
@@ -118,4 +179,19 @@ class Speaker_Embedding(DropIn):
         result = np.vstack(out)
         if label_List is not None:
             self.embedding_Value = Embedding_Value(result, label_List)
+        if export_TSNE:
+            self.Export_TSNE(result, label_List, self.engine.global_step, "GS_{}".format(self.engine.global_step))
+        return result
+
+    def Export_TSNE(self, embedding_Array, label_List, global_Step, file_Name="TSNE"):
+        """The reference's Export_TSNE (Speaker_Embedding.py:152-193): `embedding_Value` of the embeddings and their exact t-SNE map
+        (tsne.tsne on this object's device, seed 0: csrc/tsne.hip) as hp.Speaker_Embedding.Train.Inference_Path/PLOT/<file_Name>.npz and,
+        with matplotlib, .PNG - `export_tsne`, which says what the picture holds.  Synchronous: the reference's thread hid the host's
+        t-SNE, which here is a device call."""
+        from . import tsne as _tsne
+        out_Dir = os.path.join(hp.Speaker_Embedding.Train.Inference_Path, "PLOT").replace("\\", "/")
+        result = export_tsne(embedding_Array, label_List, global_Step, out_Dir, file_Name,
+                             lambda X, **kw: _tsne.tsne(X, device=self.device, **kw))
+        if result is not None:
+            self.embedding_Value = result["value"]
         return result

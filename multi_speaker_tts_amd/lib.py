@@ -234,6 +234,12 @@ SIGNATURES = {
     "mstts_wg_denoise_supported": (i32, [i32, i32, i32]),
     "mstts_wg_denoise_ws_floats": (i64, [i64, i32]),
     "mstts_wg_denoise": (i32, [vp, P(i64), vp, vp, i32, vp, f32, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "mstts_tsne_supported": (i32, [i64, i64, C.c_double]),
+    "mstts_tsne_affinities_ws_floats": (i64, [i64]),
+    "mstts_tsne_iterate_ws_floats": (i64, [i64]),
+    "mstts_tsne_history_slots": (i32, [i32, i32]),
+    "mstts_tsne_affinities": (i32, [vp, i64, i32, i32, f32, vp, vp, vp, vp]),
+    "mstts_tsne_iterate": (i32, [vp, i32, vp, vp, vp, i32, i32, i32, f32, f32, vp, vp, i32, vp, vp]),
     "mstts_wav_resample_supported": (i32, [i32, i32]),
     "mstts_wav_resample_taps": (i32, [i32, i32]),
     "mstts_wav_resample": (i32, [vp, vp, vp, i32, i64, vp, i32, i32, vp, vp]),
