@@ -569,6 +569,32 @@ int mstts_tsne_iterate(const float* P, int32_t n, float* Y, float* update, float
                        int32_t exaggeration_iters, float early_exaggeration, float learning_rate, float* ws, float* history,
                        int32_t history_slots, float* grad, mstts_stream_t s);
 
+/* Batched dynamic time warping and the cepstra of the model's mels (csrc/dtw.hip; dtw.dtw_host and dtw.mel_cepstra_host are the fp64
+ * statements).  fp32, explicit fused multiply-adds, every sum in one fixed order, no atomics: the same inputs give the same bits, for
+ * a pair alone or inside any batch.  Everything is enqueued on the stream, nothing synchronises, the library allocates nothing;
+ * parameters are checked on the host before any launch.  One workgroup owns one pair and synchronises with workgroup barriers only:
+ * no workgroup waits on another, there is no flag and no spin, and every trip count comes from n, m, k or pairs.
+ * Envelope (mstts_dtw_supported, which touches no device): 1 <= n, m <= 1024 frames, 1 <= k <= 128 features; 1 <= pairs <= 65535.
+ *
+ * mstts_dtw_batch: `pairs` pairs of sequences, a packed [sum n, k] and b packed [sum m, k] (rows back to back).  a_off_host and
+ *   b_off_host (pairs + 1 int64 entries each, in frames, starting at 0) are HOST arrays every shape is checked from; offs is the DEVICE
+ *   copy [2, pairs + 1], row 0 a's offsets, row 1 b's.  d[i,j] = sqrt(sum_k (a[i,k] - b[j,k])^2) from the differences, k ascending;
+ *   D[0,0] = d[0,0], D[i,j] = min(D[i-1,j-1] + diag_weight d[i,j], D[i-1,j] + d[i,j], D[i,j-1] + d[i,j]) over the neighbours that exist,
+ *   the first minimum in that order taken; L[i,j] = 1 + L of the neighbour taken, L[0,0] = 1.  cost [pairs] = D[n-1,m-1], length [pairs] =
+ *   L[n-1,m-1].  path, where not null, is int32 [sum (n + m - 1), 2]: pair p owns the n + m - 1 rows from row a_off[p] + b_off[p] - p on and
+ *   receives its length[p] cells (i, j), (0,0) first; the rest of its slot is not written.  Direction bytes are kept only then; the
+ *   backtrack takes at most n + m - 1 steps whatever they hold, its indices clamped to the pair's rectangle.  Rows beyond a pair's own n
+ *   and m are neither read nor written.  k <= 16 is one launch (a row in registers, b in LDS, no distance plane); wider k two (a
+ *   diagonal-major distance plane in ws first).  ws = mstts_dtw_ws_bytes(pairs, largest n, largest m, k, path != null) bytes, 16-byte
+ *   aligned; may be null where that is 0.
+ * mstts_mel_cepstra: out [rows, n_cep] = mel [rows, n_mel] times table^T, table [n_cep, n_mel] (dtw.cepstra_table: built in fp64), the
+ *   sum over the bands ascending.  2 <= n_mel <= 128, 1 <= n_cep <= min(40, n_mel - 1). */
+int mstts_dtw_supported(int64_t n, int64_t m, int64_t k);
+int64_t mstts_dtw_ws_bytes(int64_t pairs, int64_t max_n, int64_t max_m, int64_t k, int32_t want_path);
+int mstts_dtw_batch(const float* a, const float* b, const int64_t* a_off_host, const int64_t* b_off_host, const int64_t* offs, int32_t pairs,
+                    int32_t k, float diag_weight, void* ws, int64_t ws_bytes, float* cost, int32_t* length, int32_t* path, mstts_stream_t s);
+int mstts_mel_cepstra(const float* mel, int64_t rows, int32_t n_mel, int32_t n_cep, const float* table, float* out, mstts_stream_t s);
+
 /* Waveform front end: what Feeder.load_wav does to decoded samples, for nw waveforms at once (csrc/wav_front_end.hip).  Waveforms lie
  * back to back; every offset array is a DEVICE array of nw + 1 int64 entries, as mstts_stft_fft takes them.  fp32; everything is
  * enqueued on the stream, nothing synchronises; parameters are checked on the host before any launch (MSTTS_ERR_SHAPE).

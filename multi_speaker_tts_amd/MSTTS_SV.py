@@ -478,6 +478,79 @@ class Tacotron2:
                 sentences.append(sentence)
         return self.Inference(paths, sentences)
 
+    def Evaluate(self, file_List=None, max_files=64, batch_Size=16, seed=0, n_cep=13, step="symmetric1", pattern_path=None, max_steps=None,
+                 return_mels=False):
+        """How good is this checkpoint: the MCD-DTW figure (dtw.py) of the model running FREE - no teacher forcing - on pattern files whose
+        recorded mels are known.  Not in the reference.  file_List: pattern file names under hp.Train.Pattern_Path (or `pattern_path`); None:
+        the files of Feeder.train_file_order(metadata), thinned by a fixed stride to at most max_files - a deterministic choice.  Keeping those
+        files out of training is the CALLER's business (the hyper-parameter tree is the reference's and has no held-out list).  With no
+        metadata and no file_List one line is printed and None returned, as Run_Inference treats a missing sentence file (rank 0 only).
+
+        The files are sorted by token length and taken batch_Size at a time: tokens wrapped in <S> / <E> and padded with <E> as
+        load_pattern_batch does, the speaker windows of each file's OWN mel as in training, Mel zeros and Mel_Length 0 as in
+        Get_Inference_Pattern; infer_engine.forward(seed=seed + batch index) - prenet dropout is on at inference in this model, so the seed is
+        part of the result; each row cut at Feeder.stop_cut (at least one frame is kept); the post-net Mel against the recorded mel through
+        ONE dtw.mcd_dtw_batch call per decoder batch.  Returns, in the order of the files given: Files, MCD float32 [n] (dB; cepstra of this
+        model's mels - comparable between checkpoints of this model only), Mean_MCD, Frames (predicted, after the cut), Target_Frames,
+        Duration_Ratio, Stopped (the stop token fired before the step limit), Path_Length, Global_Step and, with return_mels, Cut (the cut mels)."""
+        import pickle
+        from . import dtw as _dtw
+        if self.rank != 0:
+            return None
+        _dtw._weight(step)
+        root = (pattern_path or hp.Train.Pattern_Path).replace("\\", "/")
+        if file_List is None:
+            md_file = os.path.join(root, hp.Train.Metadata_File.upper()).replace("\\", "/")
+            if not os.path.exists(md_file):
+                print("'{}' not found and no file_List given: evaluation skipped.".format(md_file))
+                return None
+            with open(md_file, "rb") as f:
+                md = pickle.load(f)
+            _Feeder.check_metadata(md)
+            file_List = _Feeder.train_file_order(md)
+            file_List = file_List[::max(1, -(-len(file_List) // max(1, int(max_files))))]
+        file_List = list(file_List)
+        if not file_List:
+            print("No pattern file to evaluate: evaluation skipped.")
+            return None
+        token_dict = self.feeder.metadata_Dict["Token_Index_Dict"]
+        tokens, mels = [], []
+        for name in file_List:
+            with open(os.path.join(root, name).replace("\\", "/"), "rb") as f:
+                pd = pickle.load(f)
+            tokens.append(np.hstack([token_dict["<S>"], pd["Token"], token_dict["<E>"]]).astype(np.int32))
+            mels.append(np.asarray(pd["Mel"], np.float32))
+        n = len(file_List)
+        order = sorted(range(n), key=lambda i: tokens[i].shape[0])
+        out = {"MCD": np.zeros(n, np.float32), "Frames": np.zeros(n, np.int32), "Stopped": np.zeros(n, bool), "Path_Length": np.zeros(n, np.int32)}
+        cuts = [None] * n
+        for batch_index, at in enumerate(range(0, n, int(batch_Size))):
+            rows = order[at:at + int(batch_Size)]
+            token = np.full((len(rows), max(tokens[i].shape[0] for i in rows)), token_dict["<E>"], np.int32)
+            for r, i in enumerate(rows):
+                token[r, :tokens[i].shape[0]] = tokens[i]
+            pattern = {"Is_Training": False, "Token": token, "Token_Length": np.array([tokens[i].shape[0] for i in rows], np.int32),
+                       "Mel": np.zeros((len(rows), 1, hp.Sound.Mel_Dim), np.float32), "Mel_Length": np.zeros(len(rows), np.int32),
+                       "Speaker_Embedding_Mel": _Feeder.speaker_windows([mels[i] for i in rows])}
+            res = self.infer_engine.forward(pattern, seed=int(seed) + batch_index, max_steps=max_steps, with_vocoder=False)
+            for r, i in enumerate(rows):
+                s = _Feeder.stop_cut(res["Stop"][r])
+                out["Stopped"][i] = s < res["Stop"][r].shape[0]
+                cuts[i] = np.array(res["Mel"][r, :max(s, 1)], np.float32)
+            figure = _dtw.mcd_dtw_batch([cuts[i] for i in rows], [mels[i] for i in rows], n_cep=n_cep, step=step, device=self.device)
+            for r, i in enumerate(rows):
+                out["MCD"][i], out["Path_Length"][i], out["Frames"][i] = figure["mcd"][r], figure["length"][r], cuts[i].shape[0]
+        out["Files"] = file_List
+        out["Target_Frames"] = np.array([m.shape[0] for m in mels], np.int32)
+        out["Duration_Ratio"] = out["Frames"].astype(np.float32) / out["Target_Frames"].astype(np.float32)
+        out["Mean_MCD"] = float(np.mean(out["MCD"], dtype=np.float64))
+        out["Global_Step"] = self.global_step
+        if return_mels:
+            out["Cut"] = cuts
+        print("    ".join(["Global step: {}".format(self.global_step), "Evaluation: {} files".format(n), "MCD-DTW: {:0.4f}".format(out["Mean_MCD"]),
+                           "Duration ratio: {:0.3f}".format(float(np.mean(out["Duration_Ratio"]))), "Not stopped: {}".format(int(n - out["Stopped"].sum()))]))
+        return out
+
     def Train(self, max_steps=None, pattern_fn=None, run_inference=True):
         """MSTTS_SV.py:253-293: an inference pass first, then loop forever (or `max_steps`): pre-train patterns while
         hp.Train.Use_Pre_in_Main_Train and the step is below hp.Train.Pre_Step, the reference's log line, a checkpoint every

@@ -15,7 +15,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmstts_hip.so")
-SOURCES = ["gemm.hip", "gemm_bf16.hip", "gemm_bf16_res.hip", "skinny.hip", "cell.hip", "elementwise.hip", "lsa.hip", "decoder.hip", "audio.hip", "griffin_lim.hip", "wg_denoise.hip", "tsne.hip", "wav_front_end.hip", "waveglow.hip", "waveglow_train.hip", "ge2e.hip", "mel_bank.hip", "stft_bank.hip", "wg_crop.hip", "skinny_bf16.hip", "persist.hip", "persist_bwd.hip", "persist_lstm.hip", "persist_infer.hip"]
+SOURCES = ["gemm.hip", "gemm_bf16.hip", "gemm_bf16_res.hip", "skinny.hip", "cell.hip", "elementwise.hip", "lsa.hip", "decoder.hip", "audio.hip", "griffin_lim.hip", "wg_denoise.hip", "tsne.hip", "dtw.hip", "wav_front_end.hip", "waveglow.hip", "waveglow_train.hip", "ge2e.hip", "mel_bank.hip", "stft_bank.hip", "wg_crop.hip", "skinny_bf16.hip", "persist.hip", "persist_bwd.hip", "persist_lstm.hip", "persist_infer.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + os.environ.get("MSTTS_EXTRA_HIPCC_FLAGS", "").split()     # (extra flags: kernel experiments only)
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "lstm_cell.h"), os.path.join(CSRC, "prenet_body.h"), os.path.join(CSRC, "persist_common.h"), os.path.join(CSRC, "persist_fwd_parts.h"), os.path.join(CSRC, "gemm_split.inc"), os.path.join(CSRC, "gemm_tile.h"), os.path.join(CSRC, "skinny_tile.h"), os.path.join(CSRC, "fft_stages.h"), os.path.join(CSRC, "stft_parts.h"), os.path.join(CSRC, "stft_frame.h"), os.path.join(HERE, "..", "include", "mstts.h")]
 

@@ -240,6 +240,10 @@ SIGNATURES = {
     "mstts_tsne_history_slots": (i32, [i32, i32]),
     "mstts_tsne_affinities": (i32, [vp, i64, i32, i32, f32, vp, vp, vp, vp]),
     "mstts_tsne_iterate": (i32, [vp, i32, vp, vp, vp, i32, i32, i32, f32, f32, vp, vp, i32, vp, vp]),
+    "mstts_dtw_supported": (i32, [i64, i64, i64]),
+    "mstts_dtw_ws_bytes": (i64, [i64, i64, i64, i64, i32]),
+    "mstts_dtw_batch": (i32, [vp, vp, P(i64), P(i64), vp, i32, i32, f32, vp, i64, vp, vp, vp, vp]),
+    "mstts_mel_cepstra": (i32, [vp, i64, i32, i32, vp, vp, vp]),
     "mstts_wav_resample_supported": (i32, [i32, i32]),
     "mstts_wav_resample_taps": (i32, [i32, i32]),
     "mstts_wav_resample": (i32, [vp, vp, vp, i32, i64, vp, i32, i32, vp, vp]),
