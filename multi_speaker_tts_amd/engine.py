@@ -23,8 +23,8 @@ from .lib import ACT_NONE, ACT_RELU, ACT_TANH, gemm, ptr, call
 from .masks import MaskSet, step_seed
 from .params import CELL, ENC_CELL, LSA, LSA_VARS, VOC, Dims, ParamStore, bank_groups, bank_suffix
 from .persist import PERSIST_COOLDOWN, PERSIST_STRIKES, CoolDown, Ticket, decoder_workgroups, lstm_bwd_workgroups, lstm_fwd_workgroups, near_xcd
-from .training import (BN_EPS, BN_MOM, Engine, _split_k, _split_k_big, bn_train_fwd, conv_bn_bwd, conv_fwd, exponential_decay, lstm_layer_grads,
-                       lstm_seq_bwd, lstm_seq_fwd)
+from .training import (BN_EPS, BN_MOM, Engine, _split_k, _split_k_big, bn_train_fwd, conv_bn_bwd, conv_fwd, dense_fwd, exponential_decay,
+                       lstm_layer_fwd, lstm_layer_grads, lstm_seq_bwd)
 
 MAX_PLANS = 64     # cached workspace sets (one per batch shape): views into ONE arena, a set owns no device memory
 
@@ -578,10 +578,9 @@ class TrainEngine(Engine):
         d, mk, tlen, B, Te, M, He = self.d, w.masks, batch["Token_Length"], w.B, w.Te, self.d.mem, self.d.enc_lstm
         seqs = []
         for di, dr in enumerate(("fw", "bw")):
-            k, ok = self.P(ENC_CELL % dr + "kernel"); b, ob = self.P(ENC_CELL % dr + "bias")
-            self._gemm(x, k, w.enc_xw[dr], B * Te, 4 * He, cin, cin, 4 * He, 4 * He, bias=b, b_off=ok, bias_off=ob)
-            q = lstm_seq_fwd(B, Te, He, w.enc_xw[dr], (k, ok + cin * 4 * He), tlen, di, d.zoneout, mk["enc_zc_" + dr], mk["enc_zh_" + dr],
-                             (w.values, di * He), Te * M, M, w.enc_c[dr], w.enc_h[dr], w.enc_acts[dr], w.enc_craw[dr], w.enc_gates[dr])
+            q = lstm_layer_fwd(self, self._gemm, ENC_CELL % dr, x, w.enc_xw[dr], B, Te, cin, He, tlen, di, d.zoneout, mk["enc_zc_" + dr],
+                               mk["enc_zh_" + dr], (w.values, di * He), Te * M, M, w.enc_c[dr], w.enc_h[dr], w.enc_acts[dr], w.enc_craw[dr],
+                               w.enc_gates[dr])
             if self.enc_whp is not None:                 # fused steps: packed recurrent kernel + packed h blocks
                 q.wh_p, q.h_p = ptr(self.enc_whp[dr]), ptr(w.enc_hp[dr])
             seqs.append(q)
@@ -602,8 +601,7 @@ class TrainEngine(Engine):
         call("mstts_shift_frames", ptr(batch["Mel"]), ptr(w.frames), B, w.L, d.n_mel)
         x, cin = w.frames, d.n_mel
         for i in range(d.prenet_n):
-            k, ok = self.P("decoder/decoder/prenet_%d/dense/kernel" % i); b, ob = self.P("decoder/decoder/prenet_%d/dense/bias" % i)
-            self._gemm(x, k, w.pre_a[i], S * B, Pn, cin, cin, Pn, Pn, bias=b, act=ACT_RELU, b_off=ok, bias_off=ob)
+            dense_fwd(self, self._gemm, x, S * B, cin, Pn, "decoder/decoder/prenet_%d/dense" % i, w.pre_a[i], act=ACT_RELU)
             call("mstts_dropout", ptr(w.pre_a[i]), ptr(mk["prenet_drop_%d" % i]), 1 - d.prenet_drop, ptr(w.pre_d[i]), S * B * Pn)
             x, cin = w.pre_d[i], Pn
         return x
@@ -614,8 +612,7 @@ class TrainEngine(Engine):
         if batch.get("_speaker_event") is not None:          # (the product surface forms the embedding on another stream, beside everything above)
             lib.join(batch["_speaker_event"])
         call("mstts_speaker_tile", ptr(batch["Speaker_Embedding"]), ptr(batch["Token_Length"]), ptr(w.values), B, Te, M, 2 * d.enc_lstm, d.spk)
-        wm, owm = self.P("attention/memory_layer/kernel")
-        self._gemm(w.values, wm, w.keys, B * Te, A, M, M, A, A, b_off=owm)
+        dense_fwd(self, self._gemm, w.values, B * Te, M, A, "attention/memory_layer", w.keys, bias=False)
 
     def _fill_decoder(self, w, p, batch, x):
         """The cell-0 input product where it is hoisted, and the decoder loop's descriptor (both forms of the loop read it)."""
@@ -813,11 +810,9 @@ class TrainEngine(Engine):
         d, B, S = self.d, w.B, w.S
         rows, C1 = B * S, d.bank_k * d.bank_ch
 
-        def projection(n, x, y, cout, K, cin, act):
-            kk, ok = self.P(VOC + "convbank_0/conv1d_%d/kernel" % n); b, ob = self.P(VOC + "convbank_0/conv1d_%d/bias" % n)
-            self._gemm(x, kk, y, rows, cout, K * cin, cin, cout, cout, bias=b, act=act, win=(S, cin, (K - 1) // 2), b_off=ok, bias_off=ob, exact=True)
-        proj1 = lambda: projection(8, w.v_pool, w.v_p1, d.proj1_ch, d.proj1_k, C1, ACT_RELU)
-        proj2 = lambda: projection(9, w.v_p1y, w.v_p2, d.n_mel, d.proj2_k, d.proj1_ch, ACT_NONE)
+        exact = lambda *a, **k: self._gemm(*a, exact=True, **k)
+        proj1 = lambda: conv_fwd(self, exact, w.v_pool, rows, S, C1, d.proj1_ch, d.proj1_k, VOC + "convbank_0/conv1d_8", w.v_p1, ACT_RELU)
+        proj2 = lambda: conv_fwd(self, exact, w.v_p1y, rows, S, d.proj1_ch, d.n_mel, d.proj2_k, VOC + "convbank_0/conv1d_9", w.v_p2, ACT_NONE)
         if w.voc_fused:
             vb = self.voc_bank
             self._ensure_bank_pack()
@@ -840,9 +835,7 @@ class TrainEngine(Engine):
                                                     rows, cols, w.v_bn_ws)
         for k in range(1, d.bank_k + 1):
             sfx = bank_suffix(k)
-            kk, ok = self.P(VOC + "convbank_0/conv1d%s/kernel" % sfx); b, ob = self.P(VOC + "convbank_0/conv1d%s/bias" % sfx)
-            self._gemm(w.mel_out, kk, w.v_tmp, rows, d.bank_ch, k * d.n_mel, d.n_mel, d.bank_ch, d.bank_ch, bias=b, act=ACT_RELU,
-                 win=(S, d.n_mel, (k - 1) // 2), b_off=ok, bias_off=ob, exact=True)
+            conv_fwd(self, exact, w.mel_out, rows, S, d.n_mel, d.bank_ch, k, VOC + "convbank_0/conv1d%s" % sfx, w.v_tmp, ACT_RELU)
             bn(sfx, w.v_tmp, w.v_tmp2, d.bank_ch)
             call("mstts_copy2d", ptr(w.v_tmp2), d.bank_ch, ptr(w.v_cat, (k - 1) * d.bank_ch), d.bank_k * d.bank_ch, rows, d.bank_ch, 0)
         call("mstts_maxpool2_same", ptr(w.v_cat), ptr(w.v_pool), B, S, C1)

@@ -23,7 +23,7 @@ from .lib import ACT_NONE, ACT_RELU, ACT_TANH, gemm, ptr, call
 from .masks import MaskSet, step_seed
 from .params import CELL, ENC_CELL, LSA, SPK, SPK_CELL, VOC, VOC_CELL, Dims, ParamStore, bank_suffix
 from .persist import LAST_STEP, PERSIST_COOLDOWN, PERSIST_STRIKES, ROWS_FINISHED, CoolDown, Ticket, decoder_workgroups, lstm_fwd_workgroups, near_xcd
-from .training import BN_EPS, lstm_seq_fwd
+from .training import bn_infer_fwd, conv_fwd, dense_fwd, lstm_seq_fwd
 SPK_OVERLAP = os.environ.get("MSTTS_SPK_OVERLAP", "1") != "0"     # inference forward: the speaker stack on its own stream beside the text encoder
 
 
@@ -69,15 +69,8 @@ class _DeferredCheck:
 
     def redo(self):
         """The sub-graph again, launch by launch (same stream); returns its output."""
-        eng = self.eng
-        eng.persist_lstm_fallbacks += 1
-        eng._lstm_retry = True
-        try:
-            with lib.deterministic_gemm():
-                return self.fn(*self.a, **self.k)
-        finally:
-            eng._lstm_retry = False
-            eng._lstm_pending, eng._lstm_ticket = [], None
+        with lib.deterministic_gemm():
+            return self.eng._launch_by_launch(self.fn, *self.a, **self.k)
 
 
 class InferEngine:
@@ -112,44 +105,38 @@ class InferEngine:
         self._spk_stream = None
         self._lstm_ctrl_host = None
         self._lstm_ticket = None             # read-back of the launches pending so far, once enqueued
-        self._lcache = {}                    # packed recurrent kernels by cell, keyed on ParamStore.version
-        self._dcache = {}                    # ... and those both decoder drivers share
-        self._pcache = {}                    # variable-derived operands of the persistent decoder, keyed on ParamStore.version
+        self._derived = {}                   # operands derived from the variables, by key: (ParamStore.version they were built at, buffers)
 
     # ------------------------------------------------------------------ helpers
-    def _f(self, *shape):
+    def _buf(self, *shape, zero=True):
+        """fp32 buffer of `shape` (whole float4s) that the caller holds; zero=False: uninitialised, for what its first user overwrites."""
         n = int(np.prod(shape))
-        t = torch.zeros((n + 3) // 4 * 4, dtype=torch.float32, device=self.device)[:n].view(shape)
+        return (torch.zeros if zero else torch.empty)((n + 3) // 4 * 4, dtype=torch.float32, device=self.device)[:n].view(shape)
+
+    def _f(self, *shape):
+        t = self._buf(*shape)
         self._keep.append(t)
         return t
 
     def P(self, name):
         return self.params.p(name)
 
-    def _dense(self, x, rows, cin, cout, kname, bname, out, act=ACT_NONE, lda=None):
-        k, ok = self.P(kname)
-        if bname is not None:
-            b, ob = self.P(bname)
-            gemm(x, k, out, rows, cout, cin, lda or cin, cout, cout, bias=b, act=act, b_off=ok, bias_off=ob)
-        else:
-            gemm(x, k, out, rows, cout, cin, lda or cin, cout, cout, act=act, b_off=ok)
-
-    def _conv_bn(self, x, rows, T, cin, cout, K, prefix, act, bn_prefix=None, conv_name="conv1d"):
-        """conv1d 'same' + activation, then inference-mode batch norm (moving statistics)."""
-        k, ok = self.P(prefix + conv_name + "/kernel"); b, ob = self.P(prefix + conv_name + "/bias")
-        a = self._f(rows, cout)
-        gemm(x, k, a, rows, cout, K * cin, cin, cout, cout, bias=b, act=act, win=(T, cin, (K - 1) // 2), b_off=ok, bias_off=ob)
-        bnp = bn_prefix or (prefix + "batch_normalization/")
-        g, og = self.P(bnp + "gamma"); be, obe = self.P(bnp + "beta")
-        mm, omm = self.P(bnp + "moving_mean"); mv, omv = self.P(bnp + "moving_variance")
-        y = self._f(rows, cout)
-        call("mstts_bn_infer_fwd", ptr(a), ptr(g, og), ptr(be, obe), ptr(mm, omm), ptr(mv, omv), ptr(y), BN_EPS, rows, cout)
-        return y
+    def _derived_at_version(self, key, alloc, fill):
+        """The operands derived from the variables kept under `key` (packed, folded, padded kernels): alloc() makes their buffers at the first
+        use, fill(buffers) forms them then and again, into the same buffers, whenever ParamStore.version has moved (a load, an Adam step)."""
+        ent = self._derived.get(key)
+        if ent is None or ent[0] != self.params.version:
+            bufs = alloc() if ent is None else ent[1]
+            fill(bufs)
+            self._derived[key] = ent = (self.params.version, bufs)
+        return ent[1]
 
     def _lstm_seq_desc(self, x, B, T, cin, H, cell_prefix, out, out_sb, out_st, out_off=0, lengths=None, reverse=0, residual=None, zc=None, zh=None, fused=True):
         """Descriptor of one ZoneoutLSTMCell over a sequence: inference mode without masks (0.9*new + 0.1*old), training-mode zoneout
         with keep-masks zc / zh [T, B, H] (ZoneoutLSTMCell.py:259-271).  Where the fused cell step covers the shape (no residual) the
         packed recurrent kernel and packed h blocks are attached, so every step is one launch."""
+        # (not training.lstm_layer_fwd: the scratch below is made BEHIND the gate product, so that its zero fills are enqueued while the product
+        #  runs - the host paces these launch chains, and in front of it they cost the product's ~10 us per layer)
         k, ok = self.P(cell_prefix + "kernel"); b, ob = self.P(cell_prefix + "bias")
         xw = self._f(B * T, 4 * H)
         gemm(x, k, xw, B * T, 4 * H, cin, cin, 4 * H, 4 * H, bias=b, b_off=ok, bias_off=ob)
@@ -157,20 +144,20 @@ class InferEngine:
             lengths = torch.full((B,), T, dtype=torch.int32, device=self.device)
             self._keep.append(lengths)
         L_ = lib.load()
-        q = lstm_seq_fwd(B, T, H, xw, (k, ok + cin * 4 * H), lengths, reverse, self.d.zoneout, zc, zh, (out, out_off), out_sb, out_st,
+        q = lstm_seq_fwd(B, T, H, cin, xw, (k, ok), lengths, reverse, self.d.zoneout, zc, zh, (out, out_off), out_sb, out_st,
                          self._f(T + 1, B, H), self._f(T + 1, B, H), None, None, self._f(int(L_.mstts_lstm_seq_ws_floats(B, H, 0))),
                          residual=residual)
         if fused and residual is None and L_.mstts_cell_fwd_supported(H, H):
             whp = self._f(H * 4 * H)             # (packed per call: the parameters may have been reloaded in between; 1 small launch)
-            call("mstts_pack_cell_fwd", ptr(k, ok + cin * 4 * H), 4 * H, ptr(whp), H, H)
+            call("mstts_pack_cell_fwd", q.wh, 4 * H, ptr(whp), H, H)
             q.wh_p, q.h_p = ptr(whp), ptr(self._f(2 * int(L_.mstts_cell_act_floats(B, H))))
         return q
 
     # ---- persistent recurrent layers
-    def _lstm_persist_args(self, descs, cell_prefixes, cins, B, T, H):
-        """Packed kernels (cached), ring, history scratch and a fresh control-word slot for one persistent LSTM launch over `descs`; None when
-        the shape / device is not covered or this forward pass is a retry without them."""
-        L_, ndir = lib.load(), len(descs)
+    def _lstm_persist_args(self, ndir, B, T, H):
+        """Ring, a fresh control-word slot and history scratch for one persistent LSTM launch over ndir directions; None when the shape /
+        device is not covered or this forward pass is a retry without them."""
+        L_ = lib.load()
         if not self.persist_lstm or self._lstm_retry or not L_.mstts_persist_lstm_fwd_supported_n(B, H, ndir):
             return None
         if self._lstm_ctrl is None:
@@ -178,22 +165,18 @@ class InferEngine:
             self._lstm_ctrl_host = torch.zeros(64, 16, dtype=torch.int32).pin_memory()
         if len(self._lstm_pending) >= 64:
             return None
-        pks = []
-        for prefix, cin in zip(cell_prefixes, cins):
-            ent = self._lcache.get(prefix)
-            if ent is None or ent[0] != self.params.version:
-                k, ok = self.P(prefix + "kernel")
-                pk = ent[1] if ent is not None else torch.empty(H * 4 * H, dtype=torch.float32, device=self.device)
-                call("mstts_persist_lstm_pack_fwd", ptr(k, ok + cin * 4 * H), 4 * H, H, ptr(pk))
-                self._lcache[prefix] = ent = (self.params.version, pk)
-            pks.append(ent[1])
-        empty = lambda n: torch.empty((int(n) + 3) // 4 * 4, dtype=torch.float32, device=self.device)
-        xch, hist = empty(L_.mstts_persist_lstm_ws_bytes_n(B, ndir) // 4), empty(L_.mstts_persist_lstm_hist_floats_n(T, B, ndir))
+        xch = self._buf(L_.mstts_persist_lstm_ws_bytes_n(B, ndir) // 4, zero=False)
+        hist = self._buf(L_.mstts_persist_lstm_hist_floats_n(T, B, ndir), zero=False)
         self._keep.extend((xch, hist))
         slot = len(self._lstm_pending)
         self._lstm_pending.append((slot, lstm_fwd_workgroups(B, H, ndir)))
         self.persist_lstm_launches += 1
-        return pks, ptr(xch), ptr(self._lstm_ctrl, slot * 16), ptr(hist)
+        return ptr(xch), ptr(self._lstm_ctrl, slot * 16), ptr(hist)
+
+    def _lstm_packed(self, cell_prefix, q):
+        """The cell's recurrent kernel q.wh in a persistent LSTM launch's order, kept until the variables change."""
+        return ptr(self._derived_at_version(cell_prefix, lambda: self._buf(q.H * 4 * q.H, zero=False),
+                                            lambda pk: call("mstts_persist_lstm_pack_fwd", q.wh, 4 * q.H, q.H, ptr(pk))))
 
     def _lstm_ctrl_copy(self):
         """Enqueue the read-back of the control words of the persistent LSTM launches so far (call in front of a host sync)."""
@@ -217,11 +200,11 @@ class InferEngine:
         post_add = (residual is not None and out_off == 0 and out_st == H and out_sb == T * H and
                     bool(lib.load().mstts_cell_fwd_supported(H, H)))
         dst = self._f(B, T, H) if post_add else out
-        pa = self._lstm_persist_args([None], [cell_prefix], [cin], B, T, H) if (residual is None or post_add) else None
+        pa = self._lstm_persist_args(1, B, T, H) if (residual is None or post_add) else None
         q = self._lstm_seq_desc(x, B, T, cin, H, cell_prefix, dst, out_sb, out_st, out_off=out_off, residual=None if post_add else residual,
                                 fused=pa is None, **kw)
         if pa is not None:
-            call("mstts_lstm_seq_fwd_persistent", C.byref(q), ptr(pa[0][0]), pa[1], pa[2], pa[3])
+            call("mstts_lstm_seq_fwd_persistent", C.byref(q), self._lstm_packed(cell_prefix, q), *pa)
         else:
             call("mstts_lstm_seq_fwd", C.byref(q))
         if post_add:
@@ -230,11 +213,12 @@ class InferEngine:
     def _bilstm_seq(self, x, B, T, cin, H, cell_fmt, out, out_sb, out_st, lengths=None):
         """Forward and backward direction of a bidirectional layer advancing together: one launch per step where the fused form applies
         (mstts_lstm_seq_fwd_pair falls back to two sequential loops otherwise)."""
-        pa = self._lstm_persist_args([None, None], [cell_fmt % "fw", cell_fmt % "bw"], [cin, cin], B, T, H)
+        pa = self._lstm_persist_args(2, B, T, H)
         qs = [self._lstm_seq_desc(x, B, T, cin, H, cell_fmt % dr, out, out_sb, out_st, out_off=di * H, lengths=lengths, reverse=di, fused=pa is None)
               for di, dr in enumerate(("fw", "bw"))]
         if pa is not None:
-            call("mstts_lstm_seq_fwd_pair_persistent", C.byref(qs[0]), C.byref(qs[1]), ptr(pa[0][0]), ptr(pa[0][1]), pa[1], pa[2], pa[3])
+            call("mstts_lstm_seq_fwd_pair_persistent", C.byref(qs[0]), C.byref(qs[1]), self._lstm_packed(cell_fmt % "fw", qs[0]),
+                 self._lstm_packed(cell_fmt % "bw", qs[1]), *pa)
         else:
             call("mstts_lstm_seq_fwd_pair", C.byref(qs[0]), C.byref(qs[1]))
 
@@ -252,14 +236,18 @@ class InferEngine:
                 self._lstm_verify()
             return out
         except _PersistRetry as e:
-            self.persist_lstm_fallbacks += 1
             warnings.warn("multi_speaker_tts_amd: %s; re-running launch by launch" % (e,), RuntimeWarning, stacklevel=3)
-            self._lstm_retry = True
-            try:
-                return fn(*a, **k)
-            finally:
-                self._lstm_retry = False
-                self._lstm_pending, self._lstm_ticket = [], None
+            return self._launch_by_launch(fn, *a, **k)
+
+    def _launch_by_launch(self, fn, *a, **k):
+        """fn again (same stream) with the launch-per-step LSTM drivers, after a persistent launch of its sub-graph gave up."""
+        self.persist_lstm_fallbacks += 1
+        self._lstm_retry = True
+        try:
+            return fn(*a, **k)
+        finally:
+            self._lstm_retry = False
+            self._lstm_pending, self._lstm_ticket = [], None
 
     def speaker_embedding(self, spk_mel, masks=None, defer=False):
         """defer=True (the TRAIN step's frozen speaker stack, MSTTS_SV.py:49-56,211): no host sync here.  Returns (embedding, ticket);
@@ -296,7 +284,7 @@ class InferEngine:
         NB, T, _ = spk_mel.shape
         B = NB // d.spk_samples
         x = self._f(NB * T, d.spk)
-        self._dense(spk_mel, NB * T, d.n_mel, d.spk, SPK + "dense/kernel", SPK + "dense/bias", x)
+        dense_fwd(self, gemm, spk_mel, NB * T, d.n_mel, d.spk, SPK + "dense", x)
         for i in range(d.spk_lstm_n):
             y = self._f(NB, T, d.spk_lstm)
             self._lstm_seq(x, NB, T, d.spk, d.spk_lstm, SPK_CELL % (i, i), y, T * d.spk_lstm, d.spk_lstm,
@@ -317,7 +305,10 @@ class InferEngine:
         call("mstts_embedding_fwd", ptr(token), ptr(emb, oe), ptr(x), B * T, d.n_tok, d.emb)
         cin = d.emb
         for i in range(d.enc_conv_n):
-            x = self._conv_bn(x, B * T, T, cin, d.enc_conv_ch, d.enc_conv_k, "encoder/conv_%d/" % i, ACT_RELU)
+            a = self._f(B * T, d.enc_conv_ch)
+            conv_fwd(self, gemm, x, B * T, T, cin, d.enc_conv_ch, d.enc_conv_k, "encoder/conv_%d/conv1d" % i, a, ACT_RELU)
+            x = self._f(B * T, d.enc_conv_ch)
+            bn_infer_fwd(self, "encoder/conv_%d/batch_normalization/" % i, a, x, B * T, d.enc_conv_ch)
             cin = d.enc_conv_ch
         values = self._f(B, T, M)
         self._bilstm_seq(x, B, T, cin, He, ENC_CELL, values, T * M, M, lengths=token_length)
@@ -325,8 +316,7 @@ class InferEngine:
             torch.cuda.current_stream().wait_event(spk_done)
         call("mstts_speaker_tile", ptr(spk), ptr(token_length), ptr(values), B, T, M, 2 * He, d.spk)
         keys = self._f(B, T, d.att)
-        wm, owm = self.P("attention/memory_layer/kernel")
-        gemm(values, wm, keys, B * T, d.att, M, M, d.att, d.att, b_off=owm)
+        dense_fwd(self, gemm, values, B * T, M, d.att, "attention/memory_layer", keys, bias=False)
         return values, keys
 
     @lib.deterministic_gemm()
@@ -342,21 +332,19 @@ class InferEngine:
         else:
             mk.draw(seed if seed is not None else step_seed(self.seed, 0))
         self._keep.append(mk)
-        # variable-derived operands shared by both drivers, kept until the variables change: cell-0 kernel with its two context row blocks
-        # folded, the folded location filter
-        c = self._dcache
-        if c.get("version") != self.params.version:
-            k0, o0 = self.P(CELL % 0 + "kernel")
-            if "w0f" not in c:
-                c.update(w0f=torch.zeros((M + H) * 4 * H, dtype=torch.float32, device=self.device).view(M + H, 4 * H),
-                         loc_k=torch.zeros(d.att_k * A, dtype=torch.float32, device=self.device).view(d.att_k, A),
-                         loc_b=torch.zeros(A, dtype=torch.float32, device=self.device),
-                         loc_kt=torch.zeros(A * 36, dtype=torch.float32, device=self.device).view(A, 36) if d.att_k <= 31 else None)
+        k0, o0 = self.P(CELL % 0 + "kernel"); b0, ob0 = self.P(CELL % 0 + "bias")
+        wpj, owpj = self.P("decoder/decoder/linear_projection/dense/kernel")
+        npad = (NM + 1 + 3) // 4 * 4
+        # variable-derived operands shared by both drivers: cell-0 kernel with its two context row blocks folded, the folded
+        # location filter, the projection kernel in rows of whole float4s (the padding zero)
+        def fold(c):
             call("mstts_fold_rows", ptr(k0, o0 + Pn * 4 * H), ptr(c["w0f"]), 2 * M + H, 4 * H, 0, M)
             lib.lsa_fold(self.P, c["loc_k"], c["loc_b"], c["loc_kt"], d.att_k, d.att_ch, A)
-            c["version"] = self.params.version
-        w0f = c["w0f"]
-        k0, o0 = self.P(CELL % 0 + "kernel"); b0, ob0 = self.P(CELL % 0 + "bias")
+            call("mstts_copy2d", ptr(wpj, owpj), NM + 1, ptr(c["wp_pad"]), npad, H + M, NM + 1, 0)
+        c = self._derived_at_version("decoder", lambda: dict(w0f=self._buf(M + H, 4 * H), loc_k=self._buf(d.att_k, A), loc_b=self._buf(A),
+                                                             loc_kt=self._buf(A, 36) if d.att_k <= 31 else None,
+                                                             wp_pad=self._buf(H + M, npad)), fold)
+        w0f, self._dec = c["w0f"], dict(c, vp=None)          # (what the drivers of this call read beside their arguments)
         q = lib.DecoderInfer()
         q.B, q.H, q.P, q.n_mel, q.Smax = B, H, Pn, NM, Smax
         lib.lsa_fill(q.lsa, self.P, B, T, A, M, d.att_k, d.att_ch, keys, values, token_length, c["loc_k"], c["loc_b"], c["loc_kt"])
@@ -370,27 +358,38 @@ class InferEngine:
         q.wx0, q.b0, q.w0f = ptr(k0, o0), ptr(b0, ob0), ptr(w0f)
         q.zoneout = d.zoneout
         # (outputs: every row of the steps that ran is written by whichever driver runs; no clearing pass)
-        empty = lambda *shape: torch.empty(int(np.prod(shape)), dtype=torch.float32, device=self.device).view(shape)
-        linear, stop, align = empty(Smax, B, NM), empty(Smax, B), empty(Smax, B, T)
+        linear, stop, align = self._buf(Smax, B, NM, zero=False), self._buf(Smax, B, zero=False), self._buf(Smax, B, T, zero=False)
         self._keep.extend((linear, stop, align))
         q.linear, q.stop, q.align_hist = ptr(linear), ptr(stop), ptr(align)
-        # ONE launch for the whole loop where the shape and the device allow it ...
+        # ONE launch for the whole loop where the shape and the device allow it, else a launch chain per step
         S = self._decode_persistent(q, values, w0f, mk, B, T, Smax)
-        if S is not None:
-            return linear[:S], stop[:S], align[:S], S
-        # ... else a launch chain per step
+        if S is None:
+            S = self._decode_stepwise(q, values, w0f, stop)
+        return linear[:S], stop[:S], align[:S], S
+
+    def _projected_values(self, values):
+        """vp = values . wp_pad[H:, :], a loop invariant of one decode call like the keys: formed at the call's first request."""
+        dec = self._dec
+        if dec["vp"] is None:
+            (B, T, M), npad = values.shape, dec["wp_pad"].shape[1]
+            dec["vp"] = self._f(B * T, npad)
+            gemm(values, dec["wp_pad"], dec["vp"], B * T, npad, M, M, npad, npad, b_off=self.d.dec_lstm * npad)
+        return dec["vp"]
+
+    def _decode_stepwise(self, q, values, w0f, stop):
+        """The free-running loop as a launch chain per step, self.chunk steps between two stop checks.  Returns the number of steps."""
+        d, L_ = self.d, lib.load()
+        B, T, M = values.shape
+        H, A, Pn, NM, Smax = d.dec_lstm, d.att, d.prenet, d.n_mel, q.Smax
         q.in0, q.in1, q.pj = ptr(self._f(2, B, Pn + M + H)), ptr(self._f(2, B, 2 * H)), ptr(self._f(B, H + M))
-        if lib.load().mstts_decoder_infer_fast(B, H, Pn, M, A, NM):
+        if L_.mstts_decoder_infer_fast(B, H, Pn, M, A, NM):
             # weight-streaming path: cell-0 kernel with the prenet rows stacked on the folded [ctx ; h] rows, padded projection
             w0s = self._f(Pn + M + H, 4 * H)
-            call("mstts_copy2d", ptr(k0, o0), 4 * H, ptr(w0s), 4 * H, Pn, 4 * H, 0)
+            call("mstts_copy2d", q.wx0, 4 * H, ptr(w0s), 4 * H, Pn, 4 * H, 0)
             call("mstts_copy2d", ptr(w0f), 4 * H, ptr(w0s, Pn * 4 * H), 4 * H, M + H, 4 * H, 0)
-            npad = (NM + 1 + 3) // 4 * 4
-            wp_pad = self._f(H + M, npad)
-            wpj, owpj = self.P("decoder/decoder/linear_projection/dense/kernel")
-            call("mstts_copy2d", ptr(wpj, owpj), NM + 1, ptr(wp_pad), npad, H + M, NM + 1, 0)
+            wp_pad = self._dec["wp_pad"]
+            npad = wp_pad.shape[1]
             q.w0s, q.wp_pad = ptr(w0s), ptr(wp_pad)
-            L_ = lib.load()
             if L_.mstts_cell_fwd_supported(H, Pn + M + H) and L_.mstts_cell_fwd_supported(H, 2 * H):
                 # fused cell steps: both cell kernels in the lanes' order + packed activation blocks (csrc/cell.hip)
                 w0sp, w1p = self._f((Pn + M + H) * 4 * H), self._f(2 * H * 4 * H)
@@ -400,14 +399,12 @@ class InferEngine:
                 act_p = self._f(2 * int(L_.mstts_cell_act_floats(B, Pn + M + H) + L_.mstts_cell_act_floats(B, 2 * H)))
                 q.w0sp, q.w1p, q.act_p = ptr(w0sp), ptr(w1p), ptr(act_p)
                 if L_.mstts_lsa_step_qp_supported(T, M, H, npad):
-                    # output projection inside the attention launch: the projected values (loop invariant, like the keys) and the
-                    # m1 rows of the kernel packed by owner slice
-                    wp_own, vp = self._f(int(L_.mstts_lsa_proj_pack_floats())), self._f(B * T, npad)
+                    # output projection inside the attention launch: the m1 rows of the kernel packed by owner slice, and the projected values
+                    wp_own = self._f(int(L_.mstts_lsa_proj_pack_floats()))
                     call("mstts_lsa_proj_pack", ptr(wp_pad), npad, H, npad, ptr(wp_own))
-                    gemm(values, wp_pad, vp, B * T, npad, M, M, npad, npad, b_off=H * npad)
-                    q.wp_own, q.vp = ptr(wp_own), ptr(vp)
+                    q.wp_own, q.vp = ptr(wp_own), ptr(self._projected_values(values))
         q.c0, q.c1, q.cum = ptr(self._f(2, B, H)), ptr(self._f(2, B, H)), ptr(self._f(2, B, T))
-        q.pre_ws = ptr(self._f(int(lib.load().mstts_decoder_infer_ws_floats(B, H, Pn, T, A, NM))))
+        q.pre_ws = ptr(self._f(int(L_.mstts_decoder_infer_ws_floats(B, H, Pn, T, A, NM))))
         # Decoder_Dynamic_Decode stops after the first step at which every row has raised its stop flag
         # (stop_logit >= 0 OR time >= Max_Inference_Length, OR-accumulated; Modules.py:216-219,395,409).
         self._lstm_ctrl_copy()
@@ -425,7 +422,7 @@ class InferEngine:
                     S = t + 1
                     break
             done += n
-        return linear[:S], stop[:S], align[:S], S
+        return S
 
     def _decode_persistent(self, q, values, w0f, mk, B, T, Smax):
         """The whole free-running loop as ONE launch (mstts_decoder_infer_persistent).  Returns the number of steps, or None when the
@@ -464,53 +461,47 @@ class InferEngine:
         """Operands, the launch, the read-back of its control words and the stream's sync behind them; returns the ticket."""
         d, L_ = self.d, lib.load()
         H, A, Pn, NM, M = d.dec_lstm, d.att, d.prenet, d.n_mel, d.mem
-        NP = 84
-        pw0, opw0 = self.P("decoder/decoder/prenet_0/dense/kernel"); pb0, opb0 = self.P("decoder/decoder/prenet_0/dense/bias")
-        pw1, opw1 = self.P("decoder/decoder/prenet_1/dense/kernel"); pb1, opb1 = self.P("decoder/decoder/prenet_1/dense/bias")
-        # what depends on the variables only (padded projection, first prenet layer folded onto its m1 half, kernels in the lanes' order):
-        # kept until the variables change (ParamStore.version)
-        c = self._pcache
-        if c.get("version") != self.params.version:
-            alloc = lambda *shape: torch.zeros(int(np.prod(shape)), dtype=torch.float32, device=self.device).view(shape)
+        prenet0, prenet1 = "decoder/decoder/prenet_0/dense", "decoder/decoder/prenet_1/dense"
+        wp_pad = self._dec["wp_pad"]
+        NP = wp_pad.shape[1]
+
+        def fill(c):
             k0, o0 = self.P(CELL % 0 + "kernel"); k1, o1 = self.P(CELL % 1 + "kernel"); wq, oq = self.P(LSA + "query_layer/kernel")
-            wpj, owpj = self.P("decoder/decoder/linear_projection/dense/kernel"); bpj, obpj = self.P("decoder/decoder/linear_projection/dense/bias")
-            if "wp_pad" not in c:
-                c.update(wp_pad=alloc(H + M, NP), bp_pad=alloc(NP), wfm=alloc(H, Pn), bf=alloc(4, Pn), bp4=alloc(4, NP),
-                         pk=[torch.empty(int(L_.mstts_persist_pack_floats(i)), dtype=torch.float32, device=self.device) for i in range(3)],
-                         wqppk=torch.empty(int(L_.mstts_persist_infer_pack_floats()), dtype=torch.float32, device=self.device),
-                         xch=torch.empty(int(L_.mstts_persist_infer_ws_bytes()) // 4, dtype=torch.float32, device=self.device),
-                         ctrl=torch.zeros(272, dtype=torch.int32, device=self.device), ctrl_host=torch.zeros(272, dtype=torch.int32).pin_memory())
-            call("mstts_copy2d", ptr(wpj, owpj), NM + 1, ptr(c["wp_pad"]), NP, H + M, NM + 1, 0)
+            bpj, obpj = self.P("decoder/decoder/linear_projection/dense/bias")
             call("mstts_copy2d", ptr(bpj, obpj), NM + 1, ptr(c["bp_pad"]), NP, 1, NM + 1, 0)
-            gemm(c["wp_pad"], pw0, c["wfm"], H, Pn, NM, NP, Pn, Pn, b_off=opw0)
+            dense_fwd(self, gemm, wp_pad, H, NM, Pn, prenet0, c["wfm"], lda=NP, bias=False)
             c["bp4"][0].copy_(c["bp_pad"])                # (a 4-row product: row 0 is bp, the other rows are zero)
-            gemm(c["bp4"], pw0, c["bf"], 4, Pn, NM, NP, Pn, Pn, bias=pb0, b_off=opw0, bias_off=opb0)
+            dense_fwd(self, gemm, c["bp4"], 4, NM, Pn, prenet0, c["bf"], lda=NP)
             # (w0f: the caller's folded cell-0 kernel - its values depend on the variables only)
             call("mstts_persist_pack", ptr(w0f), ptr(k1, o1), ptr(wq, oq), ptr(k0, o0), ptr(c["pk"][0]), ptr(c["pk"][1]), ptr(c["pk"][2]))
-            call("mstts_persist_infer_pack", ptr(wq, oq), ptr(c["wp_pad"]), NP, ptr(c["wfm"]), ptr(c["wqppk"]))
-            c["version"] = self.params.version
-        wp_pad, bp_pad, wfm, bf, pk, wqppk, xch, ctrl = (c[k] for k in ("wp_pad", "bp_pad", "wfm", "bf", "pk", "wqppk", "xch", "ctrl"))
+            call("mstts_persist_infer_pack", ptr(wq, oq), ptr(wp_pad), NP, ptr(c["wfm"]), ptr(c["wqppk"]))
+        # what depends on the variables only (padded projection bias, first prenet layer folded onto its m1 half, kernels in the lanes' order),
+        # with the launch's exchange block and control words
+        c = self._derived_at_version("persist_infer", lambda: dict(
+            bp_pad=self._buf(NP), wfm=self._buf(H, Pn), bf=self._buf(4, Pn), bp4=self._buf(4, NP),
+            pk=[self._buf(L_.mstts_persist_pack_floats(i), zero=False) for i in range(3)],
+            wqppk=self._buf(L_.mstts_persist_infer_pack_floats(), zero=False), xch=self._buf(L_.mstts_persist_infer_ws_bytes() // 4, zero=False),
+            ctrl=torch.zeros(272, dtype=torch.int32, device=self.device), ctrl_host=torch.zeros(272, dtype=torch.int32).pin_memory()), fill)
         # loop invariants of this batch (see include/mstts.h): projected values, and the first prenet layer applied to them
-        vp, u = self._f(B * T, NP), self._f(B * T, Pn)
-        gemm(values, wp_pad, vp, B * T, NP, M, M, NP, NP, b_off=H * NP)
-        gemm(vp, pw0, u, B * T, Pn, NM, NP, Pn, Pn, b_off=opw0)
+        vp, u = self._projected_values(values), self._f(B * T, Pn)
+        dense_fwd(self, gemm, vp, B * T, NM, Pn, prenet0, u, lda=NP, bias=False)
         # prenet of the all-zero start frame with the masks of step 0 (Modules.py:178-185)
         zf, pa, pb = self._f(B, NM), self._f(B, Pn), self._f(B, Pn)
-        gemm(zf, pw0, pa, B, Pn, NM, NM, Pn, Pn, bias=pb0, act=ACT_RELU, b_off=opw0, bias_off=opb0)
+        dense_fwd(self, gemm, zf, B, NM, Pn, prenet0, pa, act=ACT_RELU)
         call("mstts_dropout", ptr(pa), ptr(mk["prenet_drop_0"]), 1 - d.prenet_drop, ptr(pb), B * Pn)
-        gemm(pb, pw1, pa, B, Pn, Pn, Pn, Pn, Pn, bias=pb1, act=ACT_RELU, b_off=opw1, bias_off=opb1)
+        dense_fwd(self, gemm, pb, B, Pn, Pn, prenet1, pa, act=ACT_RELU)
         pre0 = self._f(B, Pn)
         call("mstts_dropout", ptr(pa), ptr(mk["prenet_drop_1"]), 1 - d.prenet_drop, ptr(pre0), B * Pn)
         pd = lib.PersistInferDesc()
-        pd.w0pk, pd.w1pk, pd.wqppk = ptr(pk[0]), ptr(pk[1]), ptr(wqppk)
-        pd.pre0, pd.bf, pd.u, pd.vp, pd.bp_pad = ptr(pre0), ptr(bf), ptr(u), ptr(vp), ptr(bp_pad)
-        pd.xch, pd.ctrl = ptr(xch), ptr(ctrl)
+        pd.w0pk, pd.w1pk, pd.wqppk = ptr(c["pk"][0]), ptr(c["pk"][1]), ptr(c["wqppk"])
+        pd.pre0, pd.bf, pd.u, pd.vp, pd.bp_pad = ptr(pre0), ptr(c["bf"]), ptr(u), ptr(vp), ptr(c["bp_pad"])
+        pd.xch, pd.ctrl = ptr(c["xch"]), ptr(c["ctrl"])
         pd.stamps = ptr(self.persist_infer_stamps) if self.persist_infer_stamps is not None else None
         pd.selftest_fail_step = int(self.persist_infer_selftest)
         pd.near_xcd = near_xcd()
         call("mstts_decoder_infer_persistent", C.byref(q), C.byref(pd))
         self._lstm_ctrl_copy()
-        ticket = Ticket(ctrl, c["ctrl_host"], decoder_workgroups()).enqueue()
+        ticket = Ticket(c["ctrl"], c["ctrl_host"], decoder_workgroups()).enqueue()
         torch.cuda.current_stream().synchronize()
         return ticket
 
@@ -519,7 +510,10 @@ class InferEngine:
         x, cin = linear_bsc, d.n_mel
         for i in range(d.post_n):
             cout = d.post_ch if i < d.post_n - 1 else d.n_mel
-            x = self._conv_bn(x, B * S, S, cin, cout, d.post_k, "decoder/conv_%d/" % i, ACT_TANH)
+            a = self._f(B * S, cout)
+            conv_fwd(self, gemm, x, B * S, S, cin, cout, d.post_k, "decoder/conv_%d/conv1d" % i, a, ACT_TANH)
+            x = self._f(B * S, cout)
+            bn_infer_fwd(self, "decoder/conv_%d/batch_normalization/" % i, a, x, B * S, cout)
             cin = cout
         mel = self._f(B, S, d.n_mel)
         call("mstts_add", ptr(linear_bsc), ptr(x), ptr(mel), B * S * d.n_mel)
@@ -529,31 +523,33 @@ class InferEngine:
         """ConvBank -> Highway -> BiRNN -> Projection (MSTTS_SV.py:100-115), inference mode."""
         d = self.d
         rows, C1 = B * S, d.bank_k * d.bank_ch
-        cat = self._f(rows, C1)
+        cat, cb = self._f(rows, C1), VOC + "convbank_0/"
         for k in range(1, d.bank_k + 1):
-            sfx = bank_suffix(k)
-            y = self._conv_bn(mel, rows, S, d.n_mel, d.bank_ch, k, VOC + "convbank_0/", ACT_RELU,
-                              bn_prefix=VOC + "convbank_0/batch_normalization%s/" % sfx, conv_name="conv1d%s" % sfx)
+            a = self._f(rows, d.bank_ch)
+            conv_fwd(self, gemm, mel, rows, S, d.n_mel, d.bank_ch, k, cb + "conv1d" + bank_suffix(k), a, ACT_RELU)
+            y = self._f(rows, d.bank_ch)
+            bn_infer_fwd(self, cb + "batch_normalization%s/" % bank_suffix(k), a, y, rows, d.bank_ch)
             call("mstts_copy2d", ptr(y), d.bank_ch, ptr(cat, (k - 1) * d.bank_ch), C1, rows, d.bank_ch, 0)
-        pool = self._f(rows, C1)
-        call("mstts_maxpool2_same", ptr(cat), ptr(pool), B, S, C1)
-        p1 = self._conv_bn(pool, rows, S, C1, d.proj1_ch, d.proj1_k, VOC + "convbank_0/", ACT_RELU,
-                           bn_prefix=VOC + "convbank_0/batch_normalization_8/", conv_name="conv1d_8")
-        p2 = self._conv_bn(p1, rows, S, d.proj1_ch, d.n_mel, d.proj2_k, VOC + "convbank_0/", ACT_NONE,
-                           bn_prefix=VOC + "convbank_0/batch_normalization_9/", conv_name="conv1d_9")
+        p = self._f(rows, C1)
+        call("mstts_maxpool2_same", ptr(cat), ptr(p), B, S, C1)
+        for sfx, cin, cout, K, act in (("_8", C1, d.proj1_ch, d.proj1_k, ACT_RELU), ("_9", d.proj1_ch, d.n_mel, d.proj2_k, ACT_NONE)):
+            a = self._f(rows, cout)
+            conv_fwd(self, gemm, p, rows, S, cin, cout, K, cb + "conv1d" + sfx, a, act)
+            p = self._f(rows, cout)
+            bn_infer_fwd(self, cb + "batch_normalization%s/" % sfx, a, p, rows, cout)
         x = self._f(rows, d.n_mel)
-        call("mstts_add", ptr(mel), ptr(p2), ptr(x), rows * d.n_mel)
+        call("mstts_add", ptr(mel), ptr(p), ptr(x), rows * d.n_mel)
         for i in range(d.highway_n):
             hp_, tp_ = self._f(rows, d.n_mel), self._f(rows, d.n_mel)
-            self._dense(x, rows, d.n_mel, d.n_mel, VOC + "highway_%d/dense/kernel" % i, VOC + "highway_%d/dense/bias" % i, hp_)
-            self._dense(x, rows, d.n_mel, d.n_mel, VOC + "highway_%d/dense_1/kernel" % i, VOC + "highway_%d/dense_1/bias" % i, tp_)
+            dense_fwd(self, gemm, x, rows, d.n_mel, d.n_mel, VOC + "highway_%d/dense" % i, hp_)
+            dense_fwd(self, gemm, x, rows, d.n_mel, d.n_mel, VOC + "highway_%d/dense_1" % i, tp_)
             y = self._f(rows, d.n_mel)
             call("mstts_highway_combine", ptr(hp_), ptr(tp_), ptr(x), ptr(y), rows * d.n_mel)
             x = y
         rnn = self._f(B, S, 2 * d.birnn)
         self._bilstm_seq(x, B, S, d.n_mel, d.birnn, VOC_CELL, rnn, S * 2 * d.birnn, 2 * d.birnn)
         spec = self._f(rows, d.n_spec)
-        self._dense(rnn, rows, 2 * d.birnn, d.n_spec, VOC + "dense/kernel", VOC + "dense/bias", spec)
+        dense_fwd(self, gemm, rnn, rows, 2 * d.birnn, d.n_spec, VOC + "dense", spec)
         return spec.view(B, S, d.n_spec)
 
     # ------------------------------------------------------------------ whole forward
@@ -564,13 +560,8 @@ class InferEngine:
         try:
             return self._forward(pattern, masks, seed, max_steps, with_vocoder)
         except _PersistRetry as e:
-            self.persist_lstm_fallbacks += 1
             warnings.warn("multi_speaker_tts_amd: %s; re-running the forward pass launch by launch" % (e,), RuntimeWarning, stacklevel=2)
-            self._lstm_retry = True
-            try:
-                return self._forward(pattern, masks, seed, max_steps, with_vocoder)
-            finally:
-                self._lstm_retry = False
+            return self._launch_by_launch(self._forward, pattern, masks, seed, max_steps, with_vocoder)
 
     def _forward(self, pattern, masks=None, seed=None, max_steps=None, with_vocoder=True):
         """pattern: dict with Token [B,T] int32, Token_Length [B] int32 and either Speaker_Embedding_Mel

@@ -19,7 +19,7 @@ from .lib import call, gemm, ptr
 from .masks import step_seed
 from .params import SPK, SPK_CELL, Dims, ParamStore
 from .persist import Ticket, lstm_bwd_workgroups, lstm_fwd_workgroups
-from .training import Engine, Workspace, _split_k, exponential_decay, lstm_layer_grads, lstm_seq_bwd, lstm_seq_fwd
+from .training import Engine, Workspace, _split_k, dense_fwd, exponential_decay, lstm_layer_fwd, lstm_layer_grads, lstm_seq_bwd
 
 
 def is_trainable(name):
@@ -120,23 +120,20 @@ class SpeakerTrainEngine(Engine):
                 sd = seed if seed is not None else step_seed(self.seed, self.global_step)
                 call("mstts_philox_keep_mask", ptr(w.zc[i]), T * N * H, sd, 60 + 2 * i, 1 - d.zoneout)
                 call("mstts_philox_keep_mask", ptr(w.zh[i]), T * N * H, sd, 61 + 2 * i, 1 - d.zoneout)
-        k, ok = self.P(SPK + "dense/kernel"); b, ob = self.P(SPK + "dense/bias")
-        gemm(mel, k, w.x[0], N * T, d.spk, d.n_mel, d.n_mel, d.spk, d.spk, bias=b, b_off=ok, bias_off=ob)
+        dense_fwd(self, gemm, mel, N * T, d.n_mel, d.spk, SPK + "dense", w.x[0])
         for i in range(d.spk_lstm_n):
-            k, ok = self.P(SPK_CELL % (i, i) + "kernel"); b, ob = self.P(SPK_CELL % (i, i) + "bias")
-            gemm(w.x[i], k, w.xw, N * T, 4 * H, d.spk, d.spk, 4 * H, 4 * H, bias=b, b_off=ok, bias_off=ob)
-            res = i < d.spk_lstm_n - 1
-            q = lstm_seq_fwd(N, T, H, w.xw, (k, ok + d.spk * 4 * H), w.lengths, 0, d.zoneout, w.zc[i], w.zh[i],
-                             (w.y if (res and w.fused) else w.x[i + 1], 0), T * H, H, w.c[i], w.h[i], w.acts[i], w.craw[i], w.gates,
-                             residual=w.x[i] if (res and not w.fused) else None)
+            cell, res = SPK_CELL % (i, i), i < d.spk_lstm_n - 1
+            q = lstm_layer_fwd(self, gemm, cell, w.x[i], w.xw, N, T, d.spk, H, w.lengths, 0, d.zoneout, w.zc[i], w.zh[i],
+                               (w.y if (res and w.fused) else w.x[i + 1], 0), T * H, H, w.c[i], w.h[i], w.acts[i], w.craw[i], w.gates,
+                               residual=w.x[i] if (res and not w.fused) else None)
             done = False
             if getattr(w, "persist", False):
-                call("mstts_persist_lstm_pack", ptr(k, ok + d.spk * 4 * H), 4 * H, ptr(w.pk[i][0]), ptr(w.pk[i][1]))
+                call("mstts_persist_lstm_pack", q.wh, 4 * H, ptr(w.pk[i][0]), ptr(w.pk[i][1]))
                 call("mstts_lstm_seq_fwd_persistent", C.byref(q), ptr(w.pk[i][0]), ptr(w.pxch), ptr(w.pctrl), ptr(w.phist[i]))
                 done = w.phist_valid[i] = self._persist_ok(w, lstm_fwd_workgroups(N, H, 1))
             if not done:
                 if w.fused:
-                    call("mstts_pack_cell_fwd", ptr(k, ok + d.spk * 4 * H), 4 * H, ptr(w.whp), H, H)
+                    call("mstts_pack_cell_fwd", q.wh, 4 * H, ptr(w.whp), H, H)
                     q.wh_p, q.h_p = ptr(w.whp), ptr(w.hp)
                 call("mstts_lstm_seq_fwd", C.byref(q))
             if res and w.fused:

@@ -16,8 +16,8 @@ from . import lib
 from .lib import ACT_NONE, ACT_RELU, call, gemm, ptr
 from .masks import step_seed
 from .params import VOC, Dims, ParamStore, bank_suffix
-from .training import (Engine, Workspace, _split_k, bn_train_fwd, conv_bn_bwd, conv_fwd, exponential_decay, lstm_layer_grads, lstm_seq_bwd,
-                       lstm_seq_fwd)
+from .training import (Engine, Workspace, _split_k, bn_train_fwd, conv_bn_bwd, conv_fwd, dense_fwd, exponential_decay, lstm_layer_fwd,
+                       lstm_layer_grads, lstm_seq_bwd)
 
 BIRNN = VOC + "birnn/stack_bidirectional_rnn/cell_0/bidirectional_rnn/%s/zoneout_lstm_cell/"
 
@@ -128,25 +128,20 @@ class Taco1TrainEngine(Engine):
         bn_train_fwd(self, VOC + "convbank_0/batch_normalization_9/", w.p2_a, w.p2_y, w.p2_mean, w.p2_rstd, None, 1.0, rows, d.n_mel, w.bn_ws)
         call("mstts_add", ptr(mel), ptr(w.p2_y), ptr(w.hx[0]), rows * d.n_mel)
         for i in range(d.highway_n):
-            pre = VOC + "highway_%d/" % i
-            for nm, out in (("dense", w.hh[i]), ("dense_1", w.ht[i])):
-                kk, ok = self.P(pre + nm + "/kernel"); b, ob = self.P(pre + nm + "/bias")
-                gemm(w.hx[i], kk, out, rows, d.n_mel, d.n_mel, d.n_mel, d.n_mel, d.n_mel, bias=b, b_off=ok, bias_off=ob)
+            dense_fwd(self, gemm, w.hx[i], rows, d.n_mel, d.n_mel, VOC + "highway_%d/dense" % i, w.hh[i])
+            dense_fwd(self, gemm, w.hx[i], rows, d.n_mel, d.n_mel, VOC + "highway_%d/dense_1" % i, w.ht[i])
             call("mstts_highway_combine", ptr(w.hh[i]), ptr(w.ht[i]), ptr(w.hx[i]), ptr(w.hx[i + 1]), rows * d.n_mel)
         x = w.hx[d.highway_n]
         seqs = []
         for di, dr in enumerate(("fw", "bw")):
-            k, ok = self.P(BIRNN % dr + "kernel"); b, ob = self.P(BIRNN % dr + "bias")
-            gemm(x, k, w.xw[dr], rows, 4 * Hh, d.n_mel, d.n_mel, 4 * Hh, 4 * Hh, bias=b, b_off=ok, bias_off=ob)
-            q = lstm_seq_fwd(B, S, Hh, w.xw[dr], (k, ok + d.n_mel * 4 * Hh), w.lengths, di, d.zoneout, w.zc[dr], w.zh[dr], (w.rnn, di * Hh),
-                             S * 2 * Hh, 2 * Hh, w.c[dr], w.h[dr], w.acts[dr], w.craw[dr], w.gates)
+            q = lstm_layer_fwd(self, gemm, BIRNN % dr, x, w.xw[dr], B, S, d.n_mel, Hh, w.lengths, di, d.zoneout, w.zc[dr], w.zh[dr],
+                               (w.rnn, di * Hh), S * 2 * Hh, 2 * Hh, w.c[dr], w.h[dr], w.acts[dr], w.craw[dr], w.gates)
             if w.fused:
-                call("mstts_pack_cell_fwd", ptr(k, ok + d.n_mel * 4 * Hh), 4 * Hh, ptr(w.whp[dr]), Hh, Hh)
+                call("mstts_pack_cell_fwd", q.wh, 4 * Hh, ptr(w.whp[dr]), Hh, Hh)
                 q.wh_p, q.h_p = ptr(w.whp[dr]), ptr(w.hp[dr])
             seqs.append(q)
         call("mstts_lstm_seq_fwd_pair", C.byref(seqs[0]), C.byref(seqs[1]))     # both directions advance together
-        kk, ok = self.P(VOC + "dense/kernel"); b, ob = self.P(VOC + "dense/bias")
-        gemm(w.rnn, kk, w.pred, rows, d.n_spec, 2 * Hh, 2 * Hh, d.n_spec, d.n_spec, bias=b, b_off=ok, bias_off=ob)
+        dense_fwd(self, gemm, w.rnn, rows, 2 * Hh, d.n_spec, VOC + "dense", w.pred)
         return w.pred
 
     # ------------------------------------------------------------------ loss + backward

@@ -1,7 +1,7 @@
 """Host plumbing shared by the training engines (engine.TrainEngine, taco1_trainer, speaker_trainer, waveglow_trainer) and the drop-in
 trainer classes (Taco1_Mel_to_Spect.Mel_to_Spect, Speaker_Embedding.Speaker_Embedding, WaveGlow.WaveGlow): the weight-gradient split
-heuristics, the batch-norm constants, the learning-rate schedule, the TF-Adam step, the LSTM-sequence descriptors and an LSTM layer's
-gradients, the conv / batch-norm blocks, and a drop-in class's checkpoint file and Train loop.  The engines own their buffers and schedules.
+heuristics, the batch-norm constants, the learning-rate schedule, the TF-Adam step, the layer blocks the engines (inference.InferEngine
+too) write their graphs with, and a drop-in class's checkpoint file and Train loop.  The engines own their buffers and schedules.
 """
 from __future__ import annotations
 
@@ -14,7 +14,7 @@ import torch
 
 from . import Hyper_Parameters as hp
 from . import lib
-from .lib import call, ptr
+from .lib import ACT_NONE, call, ptr
 
 BN_MOM, BN_EPS = 0.99, 1e-3
 
@@ -129,14 +129,15 @@ class Engine:
 
 
 # ---- LSTM layers ----------------------------------------------------------------------------------------------------------------------
-# wh, out and d_out are (tensor, element offset) pairs, every other buffer a tensor or None.  wh is the recurrent part of the cell's
-# kernel [cin + H, 4 H] (row stride 4 H); out / d_out hold [B, T, .] blocks at sb / st floats per batch row / time step.  The caller
-# attaches the fused cell step's packed kernel and h blocks (wh_p, h_p) where it uses them.
-def lstm_seq_fwd(B, T, H, xw, wh, lengths, reverse, zoneout, zc, zh, out, out_sb, out_st, c_hist, h_hist, acts, c_raw, gates_ws, residual=None):
-    """lib.LstmSeqFwd of one LSTM layer over a sequence (xw = x W_x + b; acts / c_raw None: inference mode)."""
-    return lib.LstmSeqFwd(B=B, T=T, H=H, xw=ptr(xw), wh=ptr(*wh), wh_ld=4 * H, lengths=ptr(lengths), reverse=reverse, zoneout=zoneout,
-                          zc=ptr(zc), zh=ptr(zh), residual=ptr(residual), out=ptr(*out), out_sb=out_sb, out_st=out_st,
-                          c_hist=ptr(c_hist), h_hist=ptr(h_hist), acts=ptr(acts), c_raw=ptr(c_raw), gates_ws=ptr(gates_ws))
+# kernel, wh, out and d_out are (tensor, element offset) pairs, every other buffer a tensor or None.  kernel is the cell's stacked kernel
+# [cin + H, 4 H] (row stride 4 H), wh its recurrent rows; out / d_out hold [B, T, .] blocks at sb / st floats per batch row / time step.  The
+# caller attaches the fused cell step's packed kernel and h blocks (wh_p, h_p) where it uses them.
+def lstm_seq_fwd(B, T, H, cin, xw, kernel, lengths, reverse, zoneout, zc, zh, out, out_sb, out_st, c_hist, h_hist, acts, c_raw, gates_ws,
+                 residual=None):
+    """lib.LstmSeqFwd of one LSTM layer over a sequence (xw = x W_x + b over the kernel's cin input rows; acts / c_raw None: inference mode)."""
+    return lib.LstmSeqFwd(B=B, T=T, H=H, xw=ptr(xw), wh=ptr(kernel[0], kernel[1] + cin * 4 * H), wh_ld=4 * H, lengths=ptr(lengths),
+                          reverse=reverse, zoneout=zoneout, zc=ptr(zc), zh=ptr(zh), residual=ptr(residual), out=ptr(*out), out_sb=out_sb,
+                          out_st=out_st, c_hist=ptr(c_hist), h_hist=ptr(h_hist), acts=ptr(acts), c_raw=ptr(c_raw), gates_ws=ptr(gates_ws))
 
 
 def lstm_seq_bwd(B, T, H, wh, lengths, reverse, zoneout, zc, zh, d_out, dout_sb, dout_st, c_hist, acts, c_raw, dgates_step, dgates_pos, ws):
@@ -144,6 +145,14 @@ def lstm_seq_bwd(B, T, H, wh, lengths, reverse, zoneout, zc, zh, d_out, dout_sb,
     return lib.LstmSeqBwd(B=B, T=T, H=H, wh=ptr(*wh), wh_ld=4 * H, lengths=ptr(lengths), reverse=reverse, zoneout=zoneout,
                           zc=ptr(zc), zh=ptr(zh), d_out=ptr(*d_out), dout_sb=dout_sb, dout_st=dout_st, c_hist=ptr(c_hist), acts=ptr(acts),
                           c_raw=ptr(c_raw), dgates_step=ptr(dgates_step), dgates_pos=ptr(dgates_pos), ws=ptr(ws))
+
+
+def lstm_layer_fwd(eng, gemm, cell, x, xw, B, T, cin, H, *seq, **kw):
+    """One LSTM layer of scope `cell` over x [B * T, cin], forward: the gate product x W_x + b into the caller's xw, and the lib.LstmSeqFwd of
+    its steps, which the caller launches (seq, kw: lstm_seq_fwd's arguments from `lengths` on).  gemm: TrainEngine._gemm or lib.gemm."""
+    k, ok = eng.P(cell + "kernel"); b, ob = eng.P(cell + "bias")
+    gemm(x, k, xw, B * T, 4 * H, cin, cin, 4 * H, 4 * H, bias=b, b_off=ok, bias_off=ob)
+    return lstm_seq_fwd(B, T, H, cin, xw, (k, ok), *seq, **kw)
 
 
 def lstm_layer_grads(eng, gemm, cell, x, h, dgp, dgs, dx, rows, cin, H, dx_accumulate=False):
@@ -157,7 +166,14 @@ def lstm_layer_grads(eng, gemm, cell, x, h, dgp, dgs, dx, rows, cin, H, dx_accum
     gemm(dgp, k, dx, rows, cin, 4 * H, 4 * H, 4 * H, cin, trans_b=True, accumulate=dx_accumulate, b_off=ok)
 
 
-# ---- conv + batch-norm blocks ---------------------------------------------------------------------------------------------------------
+# ---- dense, conv and batch-norm blocks ------------------------------------------------------------------------------------------------
+def dense_fwd(eng, gemm, x, rows, cin, cout, scope, out, act=ACT_NONE, lda=None, bias=True):
+    """x [rows, cin] (row pitch lda; None: cin) times the kernel of scope `scope`, + its bias unless bias=False, + activation, into out."""
+    k, ok = eng.P(scope + "/kernel")
+    b, ob = eng.P(scope + "/bias") if bias else (None, 0)
+    gemm(x, k, out, rows, cout, cin, lda or cin, cout, cout, bias=b, act=act, b_off=ok, bias_off=ob)
+
+
 def conv_fwd(eng, gemm, x, rows, T, cin, cout, K, conv, out, act):
     """conv1d 'same' of x [rows = batch x T, cin] with the kernel and bias of scope `conv`, + activation, into out."""
     k, ok = eng.P(conv + "/kernel"); b, ob = eng.P(conv + "/bias")
@@ -171,6 +187,13 @@ def bn_train_fwd(eng, bn, a, y, mean, rstd, mask, keep, rows, C, ws):
     mm, omm = eng.P(bn + "moving_mean"); mv, omv = eng.P(bn + "moving_variance")
     call("mstts_bn_train_fwd", ptr(a), ptr(g, og), ptr(b, ob), ptr(mm, omm), ptr(mv, omv), ptr(y), ptr(mean), ptr(rstd),
          ptr(mask), float(keep), BN_MOM, BN_EPS, rows, C, ptr(ws))
+
+
+def bn_infer_fwd(eng, bn, a, y, rows, C):
+    """Inference-mode batch norm of scope `bn` over a [rows, C] block: the moving statistics, nothing updated."""
+    g, og = eng.P(bn + "gamma"); b, ob = eng.P(bn + "beta")
+    mm, omm = eng.P(bn + "moving_mean"); mv, omv = eng.P(bn + "moving_variance")
+    call("mstts_bn_infer_fwd", ptr(a), ptr(g, og), ptr(b, ob), ptr(mm, omm), ptr(mv, omv), ptr(y), BN_EPS, rows, C)
 
 
 def conv_bn_bwd(eng, gemm, conv, bn, dy, x_in, a, mean, rstd, mask, keep, act, rows, T, cin, cout, K, dz, dx, ws, dx_accumulate=False,

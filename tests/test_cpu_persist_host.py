@@ -155,6 +155,34 @@ def test_inference_engine_warns_at_every_cooldown(monkeypatch):
     assert len(rec) == 2 and o.persist_disabled_decodes == 2 and o.persist_infer_fallbacks == 4
 
 
+def test_derived_operands_follow_the_params_version():
+    """InferEngine._derived_at_version on a bare object: built once per ParamStore.version, refilled after a bump into the same buffers,
+    and one key's refill leaves the others alone."""
+    from multi_speaker_tts_amd.inference import InferEngine
+    o = types.SimpleNamespace(params=types.SimpleNamespace(version=3), _derived={})
+    log = []
+
+    def get(key, value):
+        def alloc():
+            log.append(("alloc", key))
+            return torch.zeros(2)
+
+        def fill(buf):
+            log.append(("fill", key))
+            buf.fill_(value)
+        return InferEngine._derived_at_version(o, key, alloc, fill)
+    a = get("a", 1.0)
+    assert log == [("alloc", "a"), ("fill", "a")] and a.tolist() == [1.0, 1.0]
+    assert get("a", 9.0) is a and a.tolist() == [1.0, 1.0] and len(log) == 2               # same version: neither built nor filled again
+    b = get("b", 2.0)
+    assert b is not a and log[2:] == [("alloc", "b"), ("fill", "b")] and a.tolist() == [1.0, 1.0]
+    o.params.version += 1                                                                  # a load, or a trainer's Adam step on a shared store
+    assert get("a", 5.0) is a and log[4:] == [("fill", "a")] and a.tolist() == [5.0, 5.0]  # refilled in place, no new buffer
+    assert b.tolist() == [2.0, 2.0] and o._derived["b"][0] == 3                            # "b" is still the version-3 build ...
+    assert get("b", 6.0) is b and log[5:] == [("fill", "b")] and b.tolist() == [6.0, 6.0]  # ... until it is asked for
+    assert get("a", 7.0) is a and get("b", 8.0) is b and len(log) == 6
+
+
 def test_near_xcd_is_read_in_one_place(monkeypatch):
     monkeypatch.delenv("MSTTS_PERSIST_NEAR", raising=False)
     assert P.near_xcd() == 1
